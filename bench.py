@@ -14,7 +14,9 @@ resident in HBM before the timed region, as the reference has them resident befo
 After the K timed steps every rank renders its WHOLE frame range once (the "clip" leg: sustained rate over
 3600 / N frames, then the one RCCL gather of the u8 shards to rank 0, timed) - reported as extra keys `sustained`,
 `e2e` (SURVEY 8(d) metric (ii): set-up + render of the whole clip) and `gather_ms`; `value` stays the K-step rate.
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0); `ms_per_step` is the wall time of one timed step.
+``--dump-outputs DIR`` also writes what the last timed step computed (rank 0's u8 frames, a fixed seeded sample as float32
+.npy files, see dump_outputs) - the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -68,7 +70,41 @@ def parse():
                     help="configs[3] leg: also time the secondary model's other arithmetic modes (exact f32, bf16): four more 100-step loops")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the configs[3] (guided-diffusion DDIM) and configs[4] (render -> RealESRGAN x4) legs (extra keys)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's u8 frames, as float32: "
+                         "a fixed, seeded sample, under 64 MB) to DIR/<name>.npy, for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_FRAMES = 3            # whole frames of the last timed step's batch in --dump-outputs (3 x 12 MB as float32)
+DUMP_SAMPLES = 1 << 20     # + this many values drawn over the whole batch (4 MB + 8 MB of float64 indices)
+
+
+def dump_outputs(out_dir, u8, frame0):
+    """--dump-outputs: the last timed step's u8 frames [B, H, W, 3] as float32 .npy files.  The selection depends on the
+    batch shape only (fixed seeds), so two runs with the same arguments write the same elements.
+      frames.npy          [n, H, W, 3]  whole frames (the batch's first, last and one seeded middle frame)
+      frame_index.npy     [n]           their clip frame indices (float64)
+      sample.npy          [k]           values at seeded flat positions over the whole batch
+      sample_index.npy    [k]           those flat positions in [B, H, W, 3] (float64, exact)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    B = u8.shape[0]
+    sel = sorted({0, B - 1, int(np.random.default_rng(1).integers(0, B))})[:DUMP_FRAMES]
+    idx = np.unique(np.random.default_rng(0).integers(0, u8.numel(), size=DUMP_SAMPLES, dtype=np.int64))
+    idx_dev = torch.from_numpy(idx).to(u8.device)
+    arrays = {
+        "frames": u8[sel].float().cpu().numpy(),
+        "frame_index": np.asarray([frame0 + s for s in sel], dtype=np.float64),
+        "sample": u8.reshape(-1)[idx_dev].float().cpu().numpy(),
+        "sample_index": idx.astype(np.float64),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in arrays.items()}
 
 
 def kernel_of(ci, co, res, up):
@@ -754,8 +790,11 @@ def main():
     out_u8 = torch.empty((keep, B, RES, RES, 3), dtype=torch.uint8, device=device)
     scratch_u8 = torch.empty((B, RES, RES, 3), dtype=torch.uint8, device=device)
 
+    def first_frame(k):
+        return lo + (k * B) % max(1, (hi - lo) - B + 1)  # batches walk this rank's frame range
+
     def step(k, u8):
-        i = lo + (k * B) % max(1, (hi - lo) - B + 1)  # batches walk this rank's frame range
+        i = first_frame(k)
         nz = loop_batch(noise, i, B, raw=True)  # 17 Loop modules: the maps in one pass + per-sample factors (two launches)
         net(latents[i:i + B], noise=nz, rgb8_out=u8)
 
@@ -789,6 +828,9 @@ def main():
     ms = (C.c_float * max(1, cnt.value))()
     L.check(lib.maua_synth_get_profile(h, ms, cnt.value, C.byref(cnt)))
     L.check(lib.maua_synth_set_option(h, b"profile", 0))
+    dumped = None
+    if a.dump_outputs and rank == 0:   # (after the timed region: the copies are not part of any number)
+        dumped = dump_outputs(a.dump_outputs, out_u8[(a.steps - 1) % keep], first_frame(a.steps - 1))
 
     if dist is not None:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -878,6 +920,8 @@ def main():
                                 "HIP context, the first import and process_warmup_s (a 16-frame 64^2 clip through the same path)"},
         }
         res["config"]["gather"] = "streamed: finished chunks of frames_per_step frames travel to rank 0 on a side stream during the render"
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         return res
 
     # ---- clip leg: this rank's whole frame range once (3600 / N frames, ceil((hi - lo) / B) steps) into a resident

@@ -1289,6 +1289,27 @@ def golden_grads():
     save("g34_grads", **out)
 
 
+QUANTILE_NS = [1, 2, 3, 10, 1001, 65536]
+QUANTILE_QS = [0.0, 0.01, 0.025, 0.3, 0.5, 0.75, 0.975, 1.0]
+
+
+def golden_quantile():
+    """g35: the reference's compiled efficient_quantile extension (_efficient_quantile(x, q, True, 3)) on randn vectors of
+    QUANTILE_NS lengths drawn in turn from one generator (seed 77); the inputs are regenerated by the test, their first
+    and last values are stored as a check."""
+    ext = sys.modules["maua.audiovisual.audioreactive.selfsupervised.features.efficient_quantile.efficient_quantile"]
+    g = torch.Generator().manual_seed(77)
+    ref, first, last = [], [], []
+    for n in QUANTILE_NS:
+        x = torch.randn(n, generator=g)
+        ref.append([ext._efficient_quantile(x, torch.FloatTensor([q]), True, 3).squeeze().item() for q in QUANTILE_QS])
+        first.append(x[0].item())
+        last.append(x[-1].item())
+    save("g35_quantile", ns=np.asarray(QUANTILE_NS, dtype=np.int64), qs=np.asarray(QUANTILE_QS, dtype=np.float64),
+         ref=np.asarray(ref, dtype=np.float32), x_first=np.asarray(first, dtype=np.float32),
+         x_last=np.asarray(last, dtype=np.float32))
+
+
 if __name__ == "__main__":
     import_reference()
     which = sys.argv[1:] or ["ops", "modules", "audio", "latents", "noise", "io"]
