@@ -499,6 +499,9 @@ int maua_secondary_vjp(maua_secondary* net, const float* g_v, int B, int H, int 
  * QKVAttentionLegacy.forward - qkv [B][T][3 * heads * head_ch] with channel = head * 3 ch + {q | k | v} * ch + c (what
  * `qkv.reshape(bs * n_heads, ch * 3, length).split(ch, dim=1)` sees) -> out [B][T][heads * head_ch]; head_ch 32 or 64 */
 int maua_attention_legacy(maua_ctx* ctx, const void* qkv, void* out, int B, int T, int heads, int head_ch, int dtype);
+/* the same with CLIP's causal mask (build_attention_mask: triu(-inf, 1) - query t attends to keys 0 .. t), the text tower's
+ * attention; same layouts, head_ch 32 or 64; forward only */
+int maua_attention_causal(maua_ctx* ctx, const void* qkv, void* out, int B, int T, int heads, int head_ch, int dtype);
 /* its input gradient (autograd through QKVAttentionLegacy.forward): d_out [B][T][heads * head_ch] -> d_qkv like qkv */
 int maua_attention_legacy_vjp(maua_ctx* ctx, const void* qkv, const void* d_out, void* d_qkv, int B, int T, int heads, int head_ch,
                               int dtype);
@@ -547,8 +550,8 @@ int maua_mse_guide_grad(maua_ctx* ctx, const float* img, const float* target, lo
  * Normalize, clip_model.encode_image (OpenAI CLIP VisionTransformer: un-vendored pip dependency, published architecture restated,
  * parity unpinned), spherical_dist_loss to the target embeddings (maua/loss.py:22-25), weights, mean over cutouts,
  * torch.autograd.grad(loss.sum() * scale, img) / cutout_batches }, clamp_gradient.  The gradient is evaluated on the transposed
- * network inside the library (csrc/clip.hip, cutouts.hip, gemm_dma.hip).  The text tower is NOT here: target embeddings are handed
- * in (TextPrompt embeddings computed once, off the loop - set_targets :117-143); image (style) targets can be embedded with
+ * network inside the library (csrc/clip.hip, cutouts.hip, gemm_dma.hip).  Target embeddings are handed in (set_targets :117-143,
+ * computed once, off the loop): text prompts through the text tower below (maua_clip_text_*), image (style) targets with
  * maua_clip_encode_image.  dtype: MAUA_BF16 (the reference runs the perceptor in fp16) or MAUA_F32 (exact products, parity mode).
  * Parameter names: CLIP's state-dict keys below "visual." (conv1.weight, class_embedding, positional_embedding, ln_pre.*,
  * transformer.resblocks.<i>.{attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.*, ln_1.*, mlp.c_fc.*, mlp.c_proj.*, ln_2.*},
@@ -576,6 +579,20 @@ int maua_clip_guide_grad(maua_clip* net, const float* img, int B, int H, int W, 
                          float scale, float clamp_gradient, float* grad);
 /* sum_p w_p dist_p of the first `count` cutout images of the last pass through the tower (cutout-major; device f32 [count]) */
 int maua_clip_last_image_losses(maua_clip* net, int count, float* out);
+/* CLIP's text tower (clip/model.py CLIP.encode_text: token_embedding + positional_embedding, `layers` pre-LN residual blocks with
+ * the causal mask, ln_final of the EOT row = argmax of the row's token ids, @ text_projection); published architecture restated,
+ * parity unpinned.  Forward only: prompts are constants of the guided loop.  dtype MAUA_BF16 or MAUA_F32 (exact products).
+ * Parameter names: CLIP's top-level text keys (token_embedding.weight [vocab][w], positional_embedding [ctx][w],
+ * transformer.resblocks.<i>.{attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.*, ln_1.*, mlp.c_fc.*, mlp.c_proj.*, ln_2.*},
+ * ln_final.*, text_projection [w][E]), host float32 in the checkpoint's layout.  Workspaces grow on demand. */
+typedef struct maua_clip_text maua_clip_text;
+int maua_clip_text_create(maua_ctx* ctx, int context_length, int vocab_size, int width, int layers, int heads, int embed_dim, int dtype,
+                          maua_clip_text** out);
+void maua_clip_text_destroy(maua_clip_text* net);
+int maua_clip_text_load(maua_clip_text* net, const char* name, const float* host_data, size_t count);
+/* tokens device int32 [N][context_length] (clip.tokenize's ids; every id must lie in [0, vocab_size) - an id outside is clamped,
+ * never read outside the table) -> embeds device f32 [N][embed_dim] */
+int maua_clip_text_encode(maua_clip_text* net, const int* tokens, int N, float* embeds);
 /* the guided loop with THIS grad module: the following maua_ddim_guided_loop calls on `net` (speed "fast": a secondary model, or
  * "regular") evaluate CLIPGrads on the image estimate instead of the image-MSE module (their target / mse_k arguments are ignored);
  * rects: HOST int [n_steps][batches][cutn][3], one draw per step and cutout batch (mult: NULL or [n_steps][batches][cutn], as above),

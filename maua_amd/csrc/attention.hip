@@ -21,6 +21,10 @@
 // bf16: v_mfma_f32_32x32x16_bf16, P rounded to bf16; f32 (parity mode): v_mfma_f32_32x32x2_f32, exact products, expf.
 // Attention is < 1 % of the UNet's FLOPs at 256^2 (T <= 1024, ch = 64): this kernel is built for exactness and for
 // not materialising T x T, not for the MFMA roof.
+//
+// CAUSAL (a template parameter, so the non-causal instantiations the UNet and the image tower run are the code they were):
+// CLIP's text tower, `build_attention_mask()` = triu(-inf, 1) - key j is masked for query i when j > i.  A workgroup's key loop
+// ends at min(T, its first query + 128): the blocks wholly above the diagonal are neither loaded nor multiplied.
 #include "common.h"
 #include "internal.h"
 
@@ -45,7 +49,7 @@ template <> struct AMma<float> {
   }
 };
 
-template <typename T, int D>
+template <typename T, int D, bool CAUSAL>
 __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
   constexpr int SZ = (int)sizeof(T), EPC = 16 / SZ;
   constexpr int KRS = D * SZ + 16;        // K rows: [32 keys][D]
@@ -60,6 +64,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
   const int head = blockIdx.y, b = blockIdx.z;
   const int T_ = a.T;
   const int qrow = blockIdx.x * 128 + wave * 32 + r;
+  const int kend = CAUSAL ? min(T_, (int)blockIdx.x * 128 + 128) : T_;   // keys this workgroup's queries can see
   const T* base = reinterpret_cast<const T*>(a.qkv) + (long)b * T_ * a.ld_qkv + head * 3 * D;
 
   u32x4 qf[QS];
@@ -91,7 +96,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
     }                                                                           \
   }
   MAUA_AT_LOAD(0)
-  for (int kb = 0; kb < T_; kb += 32) {
+  for (int kb = 0; kb < kend; kb += 32) {
     __syncthreads();  // the previous block's fragment reads are done
 #pragma unroll
     for (int it = 0; it < NP; it++) {
@@ -113,7 +118,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
       }
     }
     __syncthreads();
-    if (kb + 32 < T_) MAUA_AT_LOAD(kb + 32)   // (flies during this block's products)
+    if (kb + 32 < kend) MAUA_AT_LOAD(kb + 32)   // (flies during this block's products)
 
     // S^T block: rows = keys, columns = queries
     f32x16 s;
@@ -129,7 +134,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
 #pragma unroll
     for (int e = 0; e < 16; e++) {
       const int key = kb + 8 * (e >> 2) + 4 * h + (e & 3);
-      s[e] = key < T_ ? s[e] * a.scale : -__builtin_huge_valf();
+      s[e] = key < T_ && (!CAUSAL || key <= qrow) ? s[e] * a.scale : -__builtin_huge_valf();
       mx = fmaxf(mx, s[e]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -208,7 +213,11 @@ int launch_attention(hipStream_t stream, int dtype, const AttnArgs& a) {
   MAUA_REQUIRE(a.qkv && a.out && a.T > 0 && a.heads > 0 && a.B <= 65535 && a.heads <= 65535, "attention: bad arguments");
   if (a.B == 0) return MAUA_OK;
   dim3 grid((unsigned)((a.T + 127) / 128), (unsigned)a.heads, (unsigned)a.B);
-#define MAUA_ATTN(TT, DD) hipLaunchKernelGGL((attention_kernel<TT, DD>), grid, dim3(256), 0, stream, a)
+#define MAUA_ATTN(TT, DD)                                                                             \
+  do {                                                                                                \
+    if (a.causal) hipLaunchKernelGGL((attention_kernel<TT, DD, true>), grid, dim3(256), 0, stream, a);  \
+    else hipLaunchKernelGGL((attention_kernel<TT, DD, false>), grid, dim3(256), 0, stream, a);          \
+  } while (0)
   if (dtype == MAUA_BF16) {
     if (a.D == 64) MAUA_ATTN(bf16_t, 64); else MAUA_ATTN(bf16_t, 32);
   } else {

@@ -441,6 +441,19 @@ struct maua_clip {
   unsigned long long uid = 0, epoch = 0;   // identity of this tower / generation of its buffers (a captured graph holds pointers into
 };                                          // them: unet.hip compares both before a replay)
 
+// CLIP's text tower (CLIP.encode_text): forward only - prompts are constants of the guided loop
+struct maua_clip_text {
+  maua_ctx* ctx;
+  int dtype;
+  size_t esize;
+  int ctx_len, vocab, width, layers, heads, E;
+  float *tok_emb = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *proj = nullptr;   // f32 [vocab][w], [ctx][w], [w], [w], [w][E]
+  std::vector<maua::Layer> L;   // weights only (no transposes: no way back)
+  // workspaces for `cap` sequences (at least TEXT_MIN_ROWS rows), shared by the layers
+  long cap = 0;
+  void *xa = nullptr, *xb = nullptr, *lno = nullptr, *qkv = nullptr, *ao = nullptr, *xm = nullptr, *h = nullptr, *act = nullptr;
+};
+
 namespace maua {
 namespace {
 
@@ -644,7 +657,8 @@ int forward_any(maua_clip* n, long N, bool keep) {
 int backward_any(maua_clip* n, long N) { return n->dtype == MAUA_BF16 ? run_backward<bf16_t>(n, N) : run_backward<float>(n, N); }
 
 // host float matrix [R][C] -> device T [R][C] (and optionally its transpose [C][R]); rows permuted by `perm` when given
-int upload_matrix(maua_clip* n, const float* h, int R, int C, const int* perm, void** dev, void** dev_t) {
+template <class Net>
+int upload_matrix(Net* n, const float* h, int R, int C, const int* perm, void** dev, void** dev_t) {
   std::vector<float> a((size_t)R * C);
   for (int r = 0; r < R; r++) memcpy(&a[(size_t)r * C], h + (size_t)(perm ? perm[r] : r) * C, (size_t)C * 4);
   auto put = [&](const std::vector<float>& src, void** d) -> int {
@@ -679,6 +693,202 @@ int upload_vec(const float* h, size_t count, const int* perm, float** dev) {
   if (!*dev)
     if (int rc = dalloc((void**)dev, count * 4)) return rc;
   MAUA_HIP_CHECK(hipMemcpy(*dev, a.data(), count * 4, hipMemcpyHostToDevice));
+  return MAUA_OK;
+}
+
+// the keys of CLIP's residual blocks, "transformer.resblocks.<i>.<par>" (the image tower below "visual.", the text tower at the top
+// level).  with_t: the transposed weights too (the image tower's way back)
+bool is_block_key(const std::string& s) { return s.compare(0, 22, "transformer.resblocks.") == 0; }
+
+template <class Net>
+int load_block(Net* n, const char* who, const std::string& s, const float* host, size_t count, bool with_t) {
+  const size_t p0 = 22;   // strlen("transformer.resblocks.")
+  const int w = n->width;
+  auto need = [&](size_t c) -> int {
+    if (count != c) return fail(std::string(who) + ": " + s + ": wrong size");
+    return MAUA_OK;
+  };
+  const size_t dot = s.find('.', p0);
+  if (dot == std::string::npos) return fail(std::string(who) + ": unknown parameter name: " + s);
+  const int i = atoi(s.substr(p0, dot - p0).c_str());
+  if (i < 0 || i >= n->layers) return fail(std::string(who) + ": no such block: " + s);
+  Layer& l = n->L[i];
+  const std::string par = s.substr(dot + 1);
+  // in_proj rows [q | k | v] x [head][d] -> head-major [head][q | k | v][d]: the layout attention.hip reads
+  const int D = w / n->heads;
+  std::vector<int> perm(3 * w);
+  for (int h = 0; h < n->heads; h++)
+    for (int part = 0; part < 3; part++)
+      for (int d = 0; d < D; d++) perm[(h * 3 + part) * D + d] = part * w + h * D + d;
+  auto t = [&](void** p) { return with_t ? p : nullptr; };
+  if (par == "attn.in_proj_weight") { if (int rc = need((size_t)3 * w * w)) return rc; return upload_matrix(n, host, 3 * w, w, perm.data(), &l.w_qkv, t(&l.w_qkv_t)); }
+  if (par == "attn.in_proj_bias") { if (int rc = need((size_t)3 * w)) return rc; return upload_vec(host, 3 * w, perm.data(), &l.b_qkv); }
+  if (par == "attn.out_proj.weight") { if (int rc = need((size_t)w * w)) return rc; return upload_matrix(n, host, w, w, nullptr, &l.w_out, t(&l.w_out_t)); }
+  if (par == "attn.out_proj.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.b_out); }
+  if (par == "mlp.c_fc.weight") { if (int rc = need((size_t)4 * w * w)) return rc; return upload_matrix(n, host, 4 * w, w, nullptr, &l.w_fc, t(&l.w_fc_t)); }
+  if (par == "mlp.c_fc.bias") { if (int rc = need((size_t)4 * w)) return rc; return upload_vec(host, 4 * w, nullptr, &l.b_fc); }
+  if (par == "mlp.c_proj.weight") { if (int rc = need((size_t)4 * w * w)) return rc; return upload_matrix(n, host, w, 4 * w, nullptr, &l.w_pr, t(&l.w_pr_t)); }
+  if (par == "mlp.c_proj.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.b_pr); }
+  if (par == "ln_1.weight") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln1_g); }
+  if (par == "ln_1.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln1_b); }
+  if (par == "ln_2.weight") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln2_g); }
+  if (par == "ln_2.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln2_b); }
+  return fail(std::string(who) + ": unknown parameter name: " + s);
+}
+
+// ------------------------------------------------------------------------------------------------ the text tower (CLIP.encode_text)
+//   tokens [N][ctx] int32 -> x = token_embedding[tokens] + positional_embedding -> L x { x += out_proj(causal attention(in_proj(ln_1(x))));
+//   x += c_proj(QuickGELU(c_fc(ln_2(x)))) } -> ln_final(x[n, argmax(tokens[n])]) @ text_projection -> [N][E] f32
+// The blocks are the image tower's sequence with the causal mask (build_attention_mask: triu(-inf, 1)) and no kept activations.
+
+// x[n][t][c] = token_embedding[tokens[n][t]][c] + positional_embedding[t][c], rounded to T once
+template <typename T>
+__global__ __launch_bounds__(256) void text_tokens_kernel(const int* __restrict__ tokens, const float* __restrict__ emb, const float* __restrict__ pos,
+                                                          T* __restrict__ x, long N, int Tk, int C, int vocab) {
+  constexpr int E = Pc<T>::N;
+  const int ppr = C / E;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= N * Tk * ppr) return;
+  const int pc = (int)(idx % ppr);
+  const long nt = idx / ppr;
+  const int t = (int)(nt % Tk);
+  const int id = min(max(tokens[nt], 0), vocab - 1);   // (the host validates the ids; this keeps a bad one inside the table)
+  const float* er = emb + (long)id * C + pc * E;
+  const float* pr = pos + (long)t * C + pc * E;
+  float v[E];
+#pragma unroll
+  for (int e = 0; e < E; e++) v[e] = er[e] + pr[e];
+  Pc<T>::store(x + nt * C + (long)pc * E, v);
+}
+
+// per sequence, one workgroup, float32: eot = argmax(tokens[n]) (the first maximum, as torch.argmax), ln_final of that row only (a
+// LayerNorm is per row: the same as CLIP's ln_final over every row followed by the gather), @ text_projection -> embed[n]
+template <typename T>
+__global__ __launch_bounds__(256) void text_head_kernel(const int* __restrict__ tokens, const T* __restrict__ x, const float* __restrict__ g,
+                                                        const float* __restrict__ b, const float* __restrict__ proj, float* __restrict__ embed,
+                                                        int Tk, int w, int E) {
+  extern __shared__ float sm[];
+  float* z = sm;               // [w]
+  float* red = z + w;          // [4]
+  int* eot = (int*)(red + 4);  // [1]
+  const int tid = threadIdx.x;
+  const long n = blockIdx.x;
+  if (tid < 64) {
+    const int* row = tokens + n * Tk;
+    int best = row[0], at = 0;
+    for (int t = tid; t < Tk; t += 64)
+      if (row[t] > best) { best = row[t]; at = t; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int ob = __shfl_xor(best, o), oa = __shfl_xor(at, o);
+      if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
+    }
+    if (tid == 0) *eot = at;
+  }
+  __syncthreads();
+  const T* xr = x + (n * Tk + *eot) * w;
+  float s = 0.f;
+  for (int c = tid; c < w; c += 256) { const float v = Elem<T>::load(xr + c); z[c] = v; s += v; }
+  const float mean = block_sum(s, red) / (float)w;
+  float q = 0.f;
+  for (int c = tid; c < w; c += 256) { const float d = z[c] - mean; q = fmaf(d, d, q); }
+  const float rstd = rsqrtf(block_sum(q, red) / (float)w + 1e-5f);
+  for (int c = tid; c < w; c += 256) z[c] = fmaf((z[c] - mean) * rstd, g[c], b[c]);
+  __syncthreads();
+  for (int j = tid; j < E; j += 256) {
+    float acc = 0.f;
+    for (int c = 0; c < w; c++) acc = fmaf(z[c], proj[(long)c * E + j], acc);
+    embed[n * E + j] = acc;
+  }
+}
+
+void free_text_ws(maua_clip_text* n) {
+  for (void** p : {&n->xa, &n->xb, &n->lno, &n->qkv, &n->ao, &n->xm, &n->h, &n->act}) {
+    dfree(*p);
+    *p = nullptr;
+  }
+  n->cap = 0;
+}
+
+// The text tower's GEMMs run on ONE kernel for every batch size - gemm.hip's 128 x 128 register-staged kernel, never the LDS-direct
+// one (chosen by the row count) nor the small-M one - over at least TEXT_MIN_ROWS rows (the rows past N * ctx are workspace, zeroed
+// at allocation, never read back): a prompt's embedding then does not depend on what else is in the batch, so prompts embedded one by
+// one, in a batch, or from the cache agree bit for bit.  (The tower runs once per prompt set, off the guided loop.)
+constexpr long TEXT_MIN_ROWS = 128;
+
+long text_rows(const maua_clip_text* n, long N) { return std::max<long>(N * n->ctx_len, TEXT_MIN_ROWS); }
+
+int text_gemm(maua_clip_text* n, const void* a, long M, int K, const void* w, int N, const float* bias, const void* res, void* c) {
+  GemmArgs g{};
+  g.a0 = a; g.lda0 = K; g.K0 = K; g.w = w; g.bias = bias; g.res = res; g.ldr = N; g.c = c; g.ldc = N; g.M = M; g.N = N;
+  g.prefer_dma = 0;
+  return launch_gemm_nt(n->ctx->stream, n->dtype, g);
+}
+
+// sequences per pass: 32-bit byte offsets inside the GEMM operands (the MLP's [M][4 w]), <= 65535 (attention's grid)
+long text_chunk(const maua_clip_text* n) {
+  return std::max<long>(1, std::min<long>(65535, ((1L << 32) - 1) / ((long)n->ctx_len * 4 * n->width * (long)n->esize)));
+}
+
+// workspaces for N sequences, all allocated before the first launch of a pass
+int ensure_text_ws(maua_clip_text* n, long N) {
+  if (N <= n->cap) return MAUA_OK;
+  MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
+  free_text_ws(n);
+  const size_t es = n->esize, M = (size_t)text_rows(n, N), w = n->width;
+  int rc = dalloc(&n->xa, M * w * es);
+  if (!rc) rc = dalloc(&n->xb, M * w * es);
+  if (!rc) rc = dalloc(&n->lno, M * w * es);
+  if (!rc) rc = dalloc(&n->qkv, M * 3 * w * es);
+  if (!rc) rc = dalloc(&n->ao, M * w * es);
+  if (!rc) rc = dalloc(&n->xm, M * w * es);
+  if (!rc) rc = dalloc(&n->h, M * 4 * w * es);
+  if (!rc) rc = dalloc(&n->act, M * 4 * w * es);
+  if (rc) { free_text_ws(n); return fail("maua_clip_text: out of device memory for the text tower's activations"); }
+  for (void* p : {n->xa, n->xb, n->lno, n->qkv, n->ao, n->xm, n->h, n->act}) {
+    const size_t mult = (p == n->qkv) ? 3 : (p == n->h || p == n->act) ? 4 : 1;
+    MAUA_HIP_CHECK(hipMemset(p, 0, M * mult * w * es));
+  }
+  n->cap = N;
+  return MAUA_OK;
+}
+
+template <typename T>
+int text_forward(maua_clip_text* n, const int* tokens, long N, float* embeds) {
+  hipStream_t st = n->ctx->stream;
+  const int w = n->width, Tk = n->ctx_len;
+  const long M = N * Tk, Mg = text_rows(n, N);   // Mg: the GEMMs' rows
+  constexpr int E = 16 / (int)sizeof(T);
+  {
+    const long total = M * (w / E);
+    hipLaunchKernelGGL(text_tokens_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, tokens, n->tok_emb, n->pos, (T*)n->xa,
+                       N, Tk, w, n->vocab);
+  }
+  const dim3 lgrid((unsigned)((M + 3) / 4));
+  void* x = n->xa;
+  void* other = n->xb;
+  for (int i = 0; i < n->layers; i++) {
+    Layer& l = n->L[i];
+    // x -> ln_1 -> in_proj -> causal attention -> out_proj (+ x) = xm
+    hipLaunchKernelGGL(layer_norm_kernel<T>, lgrid, dim3(256), 0, st, (const T*)x, l.ln1_g, l.ln1_b, (T*)n->lno, (float*)nullptr, M, w);
+    if (int rc = text_gemm(n, n->lno, Mg, w, l.w_qkv, 3 * w, l.b_qkv, nullptr, n->qkv)) return rc;
+    AttnArgs a{};
+    a.qkv = n->qkv; a.out = n->ao; a.B = (int)N; a.T = Tk; a.heads = n->heads; a.D = w / n->heads; a.ld_qkv = 3 * w; a.ld_out = w;
+    a.scale = 1.f / std::sqrt((float)a.D); a.causal = 1;
+    if (int rc = launch_attention(st, n->dtype, a)) return rc;
+    if (int rc = text_gemm(n, n->ao, Mg, w, l.w_out, w, l.b_out, x, n->xm)) return rc;
+    // xm -> ln_2 -> c_fc -> QuickGELU -> c_proj (+ xm) = next x
+    hipLaunchKernelGGL(layer_norm_kernel<T>, lgrid, dim3(256), 0, st, (const T*)n->xm, l.ln2_g, l.ln2_b, (T*)n->lno, (float*)nullptr, M, w);
+    if (int rc = text_gemm(n, n->lno, Mg, w, l.w_fc, 4 * w, l.b_fc, nullptr, n->h)) return rc;
+    const long pieces = M * 4 * w / E;
+    hipLaunchKernelGGL(quick_gelu_kernel<T>, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, (const T*)n->h, (T*)n->act, pieces);
+    if (int rc = text_gemm(n, n->act, Mg, 4 * w, l.w_pr, w, l.b_pr, n->xm, other)) return rc;
+    std::swap(x, other);
+  }
+  const size_t smem = ((size_t)w + 8) * 4;
+  hipLaunchKernelGGL(text_head_kernel<T>, dim3((unsigned)N), dim3(256), smem, st, tokens, (const T*)x, n->lnf_g, n->lnf_b, n->proj, embeds, Tk,
+                     w, n->E);
+  MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
 
@@ -820,33 +1030,7 @@ int maua_clip_load(maua_clip* n, const char* name, const float* host, size_t cou
   if (s == "ln_post.weight") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &n->lnpost_g); }
   if (s == "ln_post.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &n->lnpost_b); }
   if (s == "proj") { if (int rc = need((size_t)w * n->E)) return rc; return upload_vec(host, (size_t)w * n->E, nullptr, &n->proj); }
-  const std::string pre = "transformer.resblocks.";
-  if (s.compare(0, pre.size(), pre) == 0) {
-    const size_t dot = s.find('.', pre.size());
-    if (dot == std::string::npos) return fail("maua_clip_load: unknown parameter name: " + s);
-    const int i = atoi(s.substr(pre.size(), dot - pre.size()).c_str());
-    if (i < 0 || i >= n->layers) return fail("maua_clip_load: no such block: " + s);
-    Layer& l = n->L[i];
-    const std::string par = s.substr(dot + 1);
-    // in_proj rows [q | k | v] x [head][d] -> head-major [head][q | k | v][d]: the layout attention.hip reads
-    const int D = w / n->heads;
-    std::vector<int> perm(3 * w);
-    for (int h = 0; h < n->heads; h++)
-      for (int part = 0; part < 3; part++)
-        for (int d = 0; d < D; d++) perm[(h * 3 + part) * D + d] = part * w + h * D + d;
-    if (par == "attn.in_proj_weight") { if (int rc = need((size_t)3 * w * w)) return rc; return upload_matrix(n, host, 3 * w, w, perm.data(), &l.w_qkv, &l.w_qkv_t); }
-    if (par == "attn.in_proj_bias") { if (int rc = need((size_t)3 * w)) return rc; return upload_vec(host, 3 * w, perm.data(), &l.b_qkv); }
-    if (par == "attn.out_proj.weight") { if (int rc = need((size_t)w * w)) return rc; return upload_matrix(n, host, w, w, nullptr, &l.w_out, &l.w_out_t); }
-    if (par == "attn.out_proj.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.b_out); }
-    if (par == "mlp.c_fc.weight") { if (int rc = need((size_t)4 * w * w)) return rc; return upload_matrix(n, host, 4 * w, w, nullptr, &l.w_fc, &l.w_fc_t); }
-    if (par == "mlp.c_fc.bias") { if (int rc = need((size_t)4 * w)) return rc; return upload_vec(host, 4 * w, nullptr, &l.b_fc); }
-    if (par == "mlp.c_proj.weight") { if (int rc = need((size_t)4 * w * w)) return rc; return upload_matrix(n, host, w, 4 * w, nullptr, &l.w_pr, &l.w_pr_t); }
-    if (par == "mlp.c_proj.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.b_pr); }
-    if (par == "ln_1.weight") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln1_g); }
-    if (par == "ln_1.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln1_b); }
-    if (par == "ln_2.weight") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln2_g); }
-    if (par == "ln_2.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &l.ln2_b); }
-  }
+  if (is_block_key(s)) return load_block(n, "maua_clip_load", s, host, count, true);
   return fail("maua_clip_load: unknown parameter name: " + s);
 }
 
@@ -1045,6 +1229,77 @@ int maua_layer_norm_vjp(maua_ctx* ctx, const void* x, const float* stats, const 
   else
     hipLaunchKernelGGL(layer_norm_vjp_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)x, stats, gamma, (const float*)dy, (const float*)add, (float*)dx, rows, C, 0);
   MAUA_HIP_CHECK(hipGetLastError());
+  return MAUA_OK;
+}
+
+// ---- the text tower
+int maua_clip_text_create(maua_ctx* ctx, int context_length, int vocab_size, int width, int layers, int heads, int embed_dim, int dtype,
+                          maua_clip_text** out) {
+  MAUA_REQUIRE(ctx && out, "maua_clip_text_create: NULL argument");
+  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "maua_clip_text_create: dtype must be MAUA_BF16 or MAUA_F32");
+  MAUA_REQUIRE(context_length > 0 && vocab_size > 0, "maua_clip_text_create: bad context length / vocabulary size");
+  MAUA_REQUIRE(width > 0 && heads > 0 && width % heads == 0 && attention_supported(width / heads), "maua_clip_text_create: head width must be 32 or 64");
+  const int epc = dtype == MAUA_BF16 ? 8 : 4, kc = dtype == MAUA_BF16 ? 32 : 16;
+  MAUA_REQUIRE(width % 32 == 0 && width % kc == 0 && width / epc <= 64 * LN_MAXP, "maua_clip_text_create: width must be a multiple of 32 (at most 4096 / 2048)");
+  MAUA_REQUIRE(layers > 0 && embed_dim > 0, "maua_clip_text_create: bad layer count / embedding size");
+  maua_clip_text* n = new maua_clip_text();
+  n->ctx = ctx; n->dtype = dtype; n->esize = dtype == MAUA_BF16 ? 2 : 4;
+  n->ctx_len = context_length; n->vocab = vocab_size; n->width = width; n->layers = layers; n->heads = heads; n->E = embed_dim;
+  n->L.resize(layers);
+  *out = n;
+  return MAUA_OK;
+}
+
+void maua_clip_text_destroy(maua_clip_text* n) {
+  if (!n) return;
+  hipStreamSynchronize(n->ctx->stream);
+  free_text_ws(n);
+  for (auto& l : n->L)
+    for (void* p : {l.w_qkv, l.w_out, l.w_fc, l.w_pr, (void*)l.b_qkv, (void*)l.b_out, (void*)l.b_fc, (void*)l.b_pr, (void*)l.ln1_g,
+                    (void*)l.ln1_b, (void*)l.ln2_g, (void*)l.ln2_b})
+      dfree(p);
+  for (void* p : {(void*)n->tok_emb, (void*)n->pos, (void*)n->lnf_g, (void*)n->lnf_b, (void*)n->proj}) dfree(p);
+  delete n;
+}
+
+// name: a text-half key of CLIP's state dict ("token_embedding.weight", "positional_embedding", "transformer.resblocks.<i>.*",
+// "ln_final.weight", "ln_final.bias", "text_projection"); host float32 data in the checkpoint's layout
+int maua_clip_text_load(maua_clip_text* n, const char* name, const float* host, size_t count) {
+  MAUA_REQUIRE(n && name && host, "maua_clip_text_load: NULL argument");
+  MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
+  const std::string s(name);
+  const int w = n->width;
+  auto need = [&](size_t c) -> int {
+    if (count != c) return fail("maua_clip_text_load: " + s + ": wrong size");
+    return MAUA_OK;
+  };
+  if (s == "token_embedding.weight") { if (int rc = need((size_t)n->vocab * w)) return rc; return upload_vec(host, (size_t)n->vocab * w, nullptr, &n->tok_emb); }
+  if (s == "positional_embedding") { if (int rc = need((size_t)n->ctx_len * w)) return rc; return upload_vec(host, (size_t)n->ctx_len * w, nullptr, &n->pos); }
+  if (s == "ln_final.weight") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &n->lnf_g); }
+  if (s == "ln_final.bias") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &n->lnf_b); }
+  if (s == "text_projection") { if (int rc = need((size_t)w * n->E)) return rc; return upload_vec(host, (size_t)w * n->E, nullptr, &n->proj); }
+  if (is_block_key(s)) return load_block(n, "maua_clip_text_load", s, host, count, false);
+  return fail("maua_clip_text_load: unknown parameter name: " + s);
+}
+
+// CLIP.encode_text: tokens device int32 [N][context_length] (ids in [0, vocab_size): out-of-range ids are the caller's error - they are
+// clamped, never read outside the table) -> embeds device f32 [N][embed_dim]
+int maua_clip_text_encode(maua_clip_text* n, const int* tokens, int N, float* embeds) {
+  MAUA_REQUIRE(n && N >= 0, "maua_clip_text_encode: bad arguments");
+  if (N == 0) return MAUA_OK;
+  MAUA_REQUIRE(tokens && embeds, "maua_clip_text_encode: NULL argument");
+  bool ok = n->tok_emb && n->pos && n->lnf_g && n->lnf_b && n->proj;
+  for (auto& l : n->L)
+    ok = ok && l.w_qkv && l.w_out && l.w_fc && l.w_pr && l.b_qkv && l.b_out && l.b_fc && l.b_pr && l.ln1_g && l.ln1_b && l.ln2_g && l.ln2_b;
+  if (!ok) return fail("maua_clip_text: parameters missing (maua_clip_text_load every key of the text tower first)");
+  const long chunk = text_chunk(n);
+  if (int rc = ensure_text_ws(n, std::min<long>(N, chunk))) return rc;
+  for (long n0 = 0; n0 < N; n0 += chunk) {
+    const long nn = std::min<long>(chunk, N - n0);
+    const int* tk = tokens + n0 * n->ctx_len;
+    float* em = embeds + n0 * n->E;
+    if (int rc = n->dtype == MAUA_BF16 ? text_forward<bf16_t>(n, tk, nn, em) : text_forward<float>(n, tk, nn, em)) return rc;
+  }
   return MAUA_OK;
 }
 

@@ -277,6 +277,7 @@ struct AttnArgs {
   long ld_qkv, ld_out;
   float scale;          // 1 / sqrt(D)
   float* lse;           // optional [B][heads][T]: each row's log-sum-exp of the scaled scores (what the input gradient needs)
+  int causal;           // != 0: query i sees keys 0 .. i only (CLIP's text tower); forward only - attention_vjp.hip ignores it
 };
 bool attention_supported(int head_ch);
 int launch_attention(hipStream_t stream, int dtype, const AttnArgs& a);

@@ -1731,6 +1731,15 @@ int maua_attention_legacy(maua_ctx* ctx, const void* qkv, void* out, int B, int 
   return launch_attention(ctx->stream, dtype, a);
 }
 
+// the same with CLIP's causal mask (text tower): query t attends to keys 0 .. t
+int maua_attention_causal(maua_ctx* ctx, const void* qkv, void* out, int B, int T, int heads, int head_ch, int dtype) {
+  MAUA_REQUIRE(ctx, "maua_attention_causal: ctx is NULL");
+  AttnArgs a{};
+  a.qkv = qkv; a.out = out; a.B = B; a.T = T; a.heads = heads; a.D = head_ch; a.ld_qkv = 3L * heads * head_ch;
+  a.ld_out = (long)heads * head_ch; a.scale = 1.f / sqrtf((float)head_ch); a.causal = 1;
+  return launch_attention(ctx->stream, dtype, a);
+}
+
 // conv_nd(1, K, N, 1) / nn.Linear on rows: c[M][N] = a[M][K] x w[N][K]^T + bias (+ res[M][N]); a, w, res, c in dtype
 int maua_linear_nt(maua_ctx* ctx, const void* a, const void* w, const float* bias, const void* res, void* c, long M, int N,
                    int K, int dtype) {

@@ -22,8 +22,9 @@ configs[3]; "p"; "plms": the fork's sampler restated from its published algorith
 Grad modules: ``maua_amd.grad.CLIPGrads`` (round 6: maua/grad.py:96-165 - MauaCutouts, the CLIP image tower forward AND its input
 gradient, spherical distance to the target embeddings - inside the library, also inside the captured guided loop) is what
 configs[3]'s "text prompts" go through; the perceptor itself is an un-vendored pip dependency (published architecture restated,
-**parity unpinned**; no weights in the image: benchmarks run it random-init like the UNet) and the text tower stays outside (target
-embeddings are handed in).  ``MSEGuide`` (image targets) is the module that needs no perceptor.  Any other caller-supplied object with
+**parity unpinned**; no weights in the image: benchmarks run it random-init like the UNet).  A ``TextPrompt`` reaches it through
+CLIP's text tower and tokenizer (maua_amd/clip.py, clip_tokenizer.py: embedded once per ``set_targets``, off the loop; parity
+unpinned) or arrives as a precomputed ``EmbeddingPrompt``.  ``MSEGuide`` (image targets) is the module that needs no perceptor.  Any other caller-supplied object with
 the contract of maua/grad.py:15-25 (``scale``, ``set_targets(prompts)``, ``__call__(img, t) -> d loss / d img`` on the device) works
 step by step; ColorMatch / VGG / LPIPS grads (:48-93, :167-199) are not built.
 """
@@ -1040,16 +1041,19 @@ def get_diffusion_model(diffusion="guided", timesteps: int = 50, sampler: str = 
     """maua/diffusion/image.py:76-125 for the guided-diffusion processor: the grad-module list (CLIPGrads, LPIPSGrads, VGGGrads,
     ColorMatchGrads - each only when its scale is positive, in that order) around ``GuidedDiffusion``.  ``guided_kwargs`` (a dict) reach its
     constructor (``allow_random_init`` / ready ``model`` + ``diffusion`` objects: there are no checkpoints in the image; the perceptors
-    follow ``allow_random_init``).  The latent / stable / glide processors are other networks and not part of this build."""
+    follow ``allow_random_init``), except ``guided_kwargs["clip_kwargs"]``: a dict for ``CLIPGrads`` (``clip_models``, ``perceptors``,
+    ``text_tower``, ``bpe_path``, ``text_encoder``, ...).  The latent / stable / glide processors are other networks and not part of
+    this build."""
     if isinstance(diffusion, GuidedDiffusion):
         return diffusion
     if diffusion != "guided":
         raise NotImplementedError(f'get_diffusion_model("{diffusion}"): only the "guided" processor (maua/diffusion/processors/guided.py) is built')
     from .grad import CLIPGrads, ColorMatchGrads, LPIPSGrads, VGGGrads
     guided_kwargs = dict(guided_kwargs or {})
+    clip_kwargs = dict(guided_kwargs.pop("clip_kwargs", None) or {})
     rnd = dict(allow_random_init=True) if guided_kwargs.get("allow_random_init") else {}
     grad_modules = (
-        ([CLIPGrads(scale=clip_scale, **rnd)] if clip_scale > 0 else [])
+        ([CLIPGrads(scale=clip_scale, **{**rnd, **clip_kwargs})] if clip_scale > 0 else [])
         + ([LPIPSGrads(scale=lpips_scale, **rnd)] if lpips_scale > 0 else [])
         + ([VGGGrads(scale=style_scale, **rnd)] if style_scale > 0 else [])
         + ([ColorMatchGrads(scale=color_match_scale)] if color_match_scale > 0 else [])
