@@ -577,6 +577,11 @@ int maua_clip_set_targets(maua_clip* net, const float* targets, const float* wei
  * mean over cutouts then divides by the sum of a batch's multiplicities.  Same gradient, fewer images. */
 int maua_clip_guide_grad(maua_clip* net, const float* img, int B, int H, int W, const int* rects, const float* mult, int cutn, int batches,
                          float scale, float clamp_gradient, float* grad);
+/* maua_clip_guide_grad with augmented cutouts (no multiplicities: augmented cutouts all differ): augs HOST float [batches][cutn][17]
+ * ("normal", per_call 0: rects of the padded image, no flags) or [batches][17] ("dango", per_call 1), keys HOST [batches] - one noise
+ * key per cutout batch (maua_cutouts_aug's layout) */
+int maua_clip_guide_grad_aug(maua_clip* net, const float* img, int B, int H, int W, const int* rects, int cutn, int batches, const float* augs,
+                             const unsigned long long* keys, int per_call, float scale, float clamp_gradient, float* grad);
 /* sum_p w_p dist_p of the first `count` cutout images of the last pass through the tower (cutout-major; device f32 [count]) */
 int maua_clip_last_image_losses(maua_clip* net, int count, float* out);
 /* CLIP's text tower (clip/model.py CLIP.encode_text: token_embedding + positional_embedding, `layers` pre-LN residual blocks with
@@ -608,6 +613,20 @@ int maua_cutouts(maua_ctx* ctx, const float* img, int B, int H, int W, const int
                  const float* mean3, const float* std3, float* out);
 int maua_cutouts_vjp(maua_ctx* ctx, const float* d_out, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul,
                      const float* std3, float* d_img);
+/* The cutouts with the torchvision augmentation pipeline of "normal" / "dango" cutouts (cutouts.py:59-71 / 133-146, skip_augs=False;
+ * csrc/cutout_augs.hip): flip, noise, nearest RandomAffine, noise, bilinear RandomPerspective, noise, grey, noise.
+ * augs: HOST float records of MAUA_AUG_REC values in the draw order {flip, affine[6] (torchvision's inverse affine matrix), persp_on,
+ * persp[8] (its perspective coefficients; ignored when off), grey} - flags 0 / 1, finite, invertible: anything else is refused.
+ * per_call 0 ("normal"): augs [n_cut], record n augments crop n (no flags in its rectangle) at its own size before the resize;
+ * per_call 1 ("dango"): augs [1] augments every resized cutout.  The noise is the library's Philox normals x 0.01 under `key`, stream
+ * 4 j + stage (stage 0..3 in pipeline order), offset = the row-major element index: "normal": j = n, tensor [B][3][s][s]; "dango":
+ * j = 0, tensor [n_cut * B][3][cut_size][cut_size].  The warps fill 0 in the space img * mul + add.  out as maua_cutouts;
+ * maua_cutouts_aug_vjp: d_out -> d_img (the noise drops out; deterministic: no float atomics). */
+#define MAUA_AUG_REC 17
+int maua_cutouts_aug(maua_ctx* ctx, const float* img, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul, float add,
+                     const float* mean3, const float* std3, const float* augs, unsigned long long key, int per_call, float* out);
+int maua_cutouts_aug_vjp(maua_ctx* ctx, const float* d_out, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul,
+                         const float* std3, const float* augs, int per_call, float* d_img);
 /* nn.LayerNorm over the last dimension of x [rows][C] in dtype (float32 statistics, eps 1e-5; clip/model.py LayerNorm); stats:
  * optional device f32 [rows][2] = (mean, rstd), what maua_layer_norm_vjp needs: dx = d LayerNorm / d x applied to dy (+ add) */
 int maua_layer_norm(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, long rows, int C, int dtype, void* y, float* stats);

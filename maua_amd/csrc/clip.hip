@@ -437,6 +437,10 @@ struct maua_clip {
   void* cut_tables = nullptr; size_t cut_tables_bytes = 0;
   float* cut_th = nullptr; size_t cut_th_bytes = 0;
   int* rects_dev = nullptr; size_t rects_cap = 0;   // + the multiplicities behind the rectangles (floats)
+  // augmented cutouts (cutout_augs.hip): rectangles + slot rectangles, records, and the two [group][B][3][S][S] buffers
+  int* aug_rects = nullptr; size_t aug_rects_cap = 0;
+  void* aug_recs = nullptr; size_t aug_recs_cap = 0;
+  float *aug_x1 = nullptr, *aug_x2 = nullptr; size_t aug_x_bytes = 0;
   double* parts = nullptr;
   unsigned long long uid = 0, epoch = 0;   // identity of this tower / generation of its buffers (a captured graph holds pointers into
 };                                          // them: unet.hip compares both before a replay)
@@ -970,6 +974,52 @@ int clip_guide_grad(maua_clip* n, const float* img, int B, int H, int W, const i
   return MAUA_OK;
 }
 
+// One cutout group of CLIPGrads.forward with augmented cutouts (cutout_augs.hip).  "normal" (per_call 0): the group's n_cut records
+// augment their crops of img into per-cutout slots (aug_x2), the resize reads slot n for cutout n (slot_rects: (size, 0, 0)); back:
+// resize VJP per slot -> augmentation adjoint -> the crops' gradients summed into grad in cutout order.  "dango" (per_call 1): the
+// resize writes planar [n_cut B][3][cs][cs] (aug_x2), the call's one record augments it into the tower's patch rows; back: patch-row
+// gradient -> adjoint -> the existing cutouts VJP.  noise_i0: the group's first image in the call's [N B] noise layout ("dango").
+int clip_grad_group_aug(maua_clip* n, const float* img, int B, int H, int W, const int* rects_dev, const int* slot_rects_dev, const void* recs,
+                        int n_cut, int per_call, int noise_i0, float coef, float* grad, int accumulate) {
+  hipStream_t st = n->ctx->stream;
+  const long N = (long)n_cut * B;
+  const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, sd[3] = {0.26862954f, 0.26130258f, 0.27577711f};   // grad.py:110
+  const float zero3[3] = {0.f, 0.f, 0.f}, one3[3] = {1.f, 1.f, 1.f};
+  CutoutPlan p{};
+  p.B = B; p.n_cut = n_cut; p.cs = n->res;
+  if (!per_call) {
+    const int S = std::min(H, W);
+    if (int rc = aug_forward_src(st, recs, n_cut, B, S, 0, img, H, W, 0.5f, 0.5f, n->aug_x1)) return rc;
+    if (int rc = aug_forward_out(st, MAUA_F32, recs, n_cut, B, S, 0, n->aug_x1, n->aug_x2, 0, zero3, one3)) return rc;
+    p.img = n->aug_x2; p.rects = slot_rects_dev; p.H = S; p.W = S; p.mul = 1.f; p.add = 0.f; p.img_stride = (long)B * 3 * S * S;
+    for (int c = 0; c < 3; c++) { p.mean[c] = mean[c]; p.std[c] = sd[c]; }
+    p.patch = n->patch;
+    if (int rc = launch_cutout_tables(st, p, n->cut_tables)) return rc;
+    if (int rc = launch_cutouts_forward(st, n->dtype, p, n->cut_tables, n->patches)) return rc;
+    if (int rc = forward_any(n, N, true)) return rc;
+    if (int rc = zero_dx(n, N)) return rc;
+    if (int rc = run_head(n, N, true, nullptr, B, coef, true, nullptr)) return rc;
+    if (int rc = backward_any(n, N)) return rc;
+    if (int rc = launch_cutouts_vjp(st, n->dtype, p, n->cut_tables, n->dwide, n->cut_th, n->aug_x2, 0)) return rc;
+    if (int rc = aug_adjoint_out(st, MAUA_F32, recs, n_cut, B, S, n->aug_x2, 0, one3, n->aug_x1)) return rc;
+    return aug_adjoint_src(st, recs, n_cut, B, S, n->aug_x1, H, W, 0.5f, grad, accumulate);
+  }
+  const int cs = n->res;
+  p.img = img; p.rects = rects_dev; p.H = H; p.W = W; p.mul = 0.5f; p.add = 0.5f;
+  for (int c = 0; c < 3; c++) { p.mean[c] = 0.f; p.std[c] = 1.f; }
+  if (int rc = launch_cutout_tables(st, p, n->cut_tables)) return rc;
+  if (int rc = launch_cutouts_forward(st, MAUA_F32, p, n->cut_tables, n->aug_x2)) return rc;
+  if (int rc = aug_forward_src(st, recs, 1, (int)N, cs, noise_i0, n->aug_x2, cs, cs, 1.f, 0.f, n->aug_x1)) return rc;
+  if (int rc = aug_forward_out(st, n->dtype, recs, 1, (int)N, cs, noise_i0, n->aug_x1, n->patches, n->patch, mean, sd)) return rc;
+  if (int rc = forward_any(n, N, true)) return rc;
+  if (int rc = zero_dx(n, N)) return rc;
+  if (int rc = run_head(n, N, true, nullptr, B, coef, true, nullptr)) return rc;
+  if (int rc = backward_any(n, N)) return rc;
+  if (int rc = aug_adjoint_out(st, n->dtype, recs, 1, (int)N, cs, n->dwide, n->patch, sd, n->aug_x2)) return rc;
+  if (int rc = aug_adjoint_src(st, recs, 1, (int)N, cs, n->aug_x2, cs, cs, 1.f, n->aug_x1, 0)) return rc;
+  return launch_cutouts_vjp(st, MAUA_F32, p, n->cut_tables, n->aug_x1, n->cut_th, grad, accumulate);
+}
+
 }  // namespace maua
 
 extern "C" {
@@ -1006,7 +1056,7 @@ void maua_clip_destroy(maua_clip* n) {
       dfree(p);
   for (void* p : {n->w_conv, n->w_conv_t, (void*)n->cls, (void*)n->pos, (void*)n->lnpre_g, (void*)n->lnpre_b, (void*)n->lnpost_g,
                   (void*)n->lnpost_b, (void*)n->proj, (void*)n->tgt, (void*)n->twt, (void*)n->sel, n->cut_tables, (void*)n->cut_th,
-                  (void*)n->rects_dev, (void*)n->parts})
+                  (void*)n->rects_dev, (void*)n->parts, (void*)n->aug_rects, n->aug_recs, (void*)n->aug_x1, (void*)n->aug_x2})
     dfree(p);
   delete n;
 }
@@ -1161,6 +1211,78 @@ int maua_clip_guide_grad(maua_clip* n, const float* img, int B, int H, int W, co
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));   // (the caller's arrays may be temporaries)
   if (int rc = clip_prepare_guide(n, B, H, W, clip_group_size(n, B, cutn))) return rc;
   return clip_guide_grad(n, img, B, H, W, n->rects_dev, mult_dev, cutn, cutn_total, batches, scale, clamp_gradient, grad);
+}
+
+// CLIPGrads.forward with augmented "normal" (per_call 0) / "dango" (per_call 1) cutouts: maua_clip_guide_grad with, per cutout batch,
+// the augmentation records (HOST float [batches][cutn][17] / [batches][17]) and the noise key (HOST [batches])
+int maua_clip_guide_grad_aug(maua_clip* n, const float* img, int B, int H, int W, const int* rects, int cutn, int batches, const float* augs,
+                             const unsigned long long* keys, int per_call, float scale, float clamp_gradient, float* grad) {
+  MAUA_REQUIRE(n && img && rects && augs && keys && grad, "maua_clip_guide_grad_aug: NULL argument");
+  MAUA_REQUIRE(B >= 0 && cutn > 0 && batches > 0, "maua_clip_guide_grad_aug: bad sizes");
+  MAUA_REQUIRE(per_call == 0 || per_call == 1, "maua_clip_guide_grad_aug: per_call is 0 (\"normal\") or 1 (\"dango\")");
+  if (int rc = clip_loaded(n)) return rc;
+  if (B == 0) return MAUA_OK;
+  MAUA_REQUIRE(n->sel_B == 0 || n->sel_B == B, "maua_clip_guide_grad_aug: the per-sample target selection was set for another batch size");
+  const long total = (long)batches * cutn;
+  for (long i = 0; i < total; i++) {
+    const int s = rects[3 * i] & CUT_SIZE_MASK, oy = rects[3 * i + 1], ox = rects[3 * i + 2];
+    MAUA_REQUIRE(s > 0 && oy >= 0 && ox >= 0 && oy + s <= H && ox + s <= W, "maua_clip_guide_grad_aug: a cutout leaves the image");
+    MAUA_REQUIRE(per_call || (rects[3 * i] & ~CUT_SIZE_MASK) == 0, "maua_clip_guide_grad_aug: \"normal\" cutouts carry no grey / flip flags");
+  }
+  MAUA_REQUIRE(per_call || H == W, "maua_clip_guide_grad_aug: \"normal\" cutouts need a square image");
+  const int n_rec = per_call ? batches : (int)total;
+  std::vector<char> recs((size_t)n_rec * aug_record_bytes());
+  if (int rc = aug_records(augs, n_rec, per_call ? nullptr : rects, n->res, keys, per_call ? 1 : cutn, recs.data())) return rc;
+  hipStream_t st = n->ctx->stream;
+  const int grp = clip_group_size(n, B, cutn);
+  const int S = per_call ? n->res : std::min(H, W);
+  const size_t xb = (size_t)grp * B * 3 * S * S * 4;
+  if ((size_t)total * 24 > n->aug_rects_cap || recs.size() > n->aug_recs_cap || xb > n->aug_x_bytes) {
+    MAUA_HIP_CHECK(hipStreamSynchronize(st));
+    if ((size_t)total * 24 > n->aug_rects_cap) {
+      dfree(n->aug_rects); n->aug_rects = nullptr;
+      if (int rc = dalloc((void**)&n->aug_rects, (size_t)total * 24)) return rc;
+      n->aug_rects_cap = (size_t)total * 24;
+    }
+    if (recs.size() > n->aug_recs_cap) {
+      dfree(n->aug_recs); n->aug_recs = nullptr;
+      if (int rc = dalloc(&n->aug_recs, recs.size())) return rc;
+      n->aug_recs_cap = recs.size();
+    }
+    if (xb > n->aug_x_bytes) {
+      dfree(n->aug_x1); dfree(n->aug_x2); n->aug_x1 = n->aug_x2 = nullptr;
+      if (int rc = dalloc((void**)&n->aug_x1, xb)) return rc;
+      if (int rc = dalloc((void**)&n->aug_x2, xb)) return rc;
+      n->aug_x_bytes = xb;
+    }
+    n->epoch++;
+  }
+  std::vector<int> slot((size_t)total * 3);
+  for (long i = 0; i < total; i++) { slot[3 * i] = rects[3 * i] & CUT_SIZE_MASK; slot[3 * i + 1] = 0; slot[3 * i + 2] = 0; }
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_rects, rects, (size_t)total * 12, hipMemcpyHostToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_rects + 3 * total, slot.data(), (size_t)total * 12, hipMemcpyHostToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_recs, recs.data(), recs.size(), hipMemcpyHostToDevice, st));
+  MAUA_HIP_CHECK(hipStreamSynchronize(st));   // (the host vectors die with this call)
+  if (int rc = clip_prepare_guide(n, B, H, W, grp)) return rc;
+  const float coef = 1.f / ((float)cutn * (float)batches);
+  const size_t rb = aug_record_bytes();
+  bool first = true;
+  for (int k = 0; k < batches; k++)
+    for (int c0 = 0; c0 < cutn; c0 += grp) {
+      const int nc = std::min(grp, cutn - c0);
+      const long i0 = (long)k * cutn + c0;
+      const void* rp = (const char*)n->aug_recs + (per_call ? (size_t)k : (size_t)i0) * rb;
+      if (int rc = clip_grad_group_aug(n, img, B, H, W, n->aug_rects + 3 * i0, n->aug_rects + 3 * (total + i0), rp, nc, per_call, c0 * B, coef,
+                                       grad, first ? 0 : 1))
+        return rc;
+      first = false;
+    }
+  const long cnt = (long)B * 3 * H * W;
+  hipLaunchKernelGGL(sq_partial_kernel, dim3(NPARTS), dim3(256), 0, st, grad, cnt, n->parts);
+  hipLaunchKernelGGL(clamp_scale_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, grad, cnt, n->parts, NPARTS, clamp_gradient,
+                     scale);
+  MAUA_HIP_CHECK(hipGetLastError());
+  return MAUA_OK;
 }
 
 // sum_p w_p dist_p of each cutout image of the LAST pass through the tower ([n] floats, device; n <= cutn * B: cutout-major, what

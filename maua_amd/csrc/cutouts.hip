@@ -10,6 +10,9 @@
 // (internal.h CUT_GREY / CUT_FLIP): luma of the three planes in the vertical pass, mirrored store; the adjoints mirror the load and
 // spread the three planes' sum over the luma coefficients.
 //
+// Augmented cutouts (cutout_augs.hip): "normal" crops are augmented at their own size into per-cutout slots first; CutoutPlan's
+// img_stride lets cutout n read slot n (and its gradient go back to slot n) - stride 0 is the plain path.
+//
 // Who draws the rectangles: the host (maua_amd/grad.py restates the reference's draws from torch's generator, pinned by
 // tests/golden/g33_cutouts.npz); this file takes (size, top, left) per cutout in device memory, so a captured sampler loop reads
 // its step's rectangles from a table uploaded before the loop.
@@ -86,6 +89,7 @@ struct CutArgs {
   void* out;             // planar f32 [n_cut * B][3][cs][cs] or patch rows (T) [n_cut * B * (cs / p)^2][3 p p]
   int patch;             // 0: planar f32; p: patch rows
   int smax;              // row stride of the horizontal-adjoint buffer = the largest cutout size
+  long img_stride;       // CutoutPlan::img_stride
 };
 
 template <typename T>
@@ -119,7 +123,7 @@ __global__ __launch_bounds__(256) void cutouts_fwd_kernel(CutArgs a) {
   const int* lt = a.left + (long)n * a.cs;
   const float* wt = a.wts + (long)n * a.cs * CT_MAXT;
   const long plane = (long)a.H * a.W;
-  const float* src = a.img + ((long)b * 3 + (grey ? 0 : c)) * plane + (long)oy * a.W + ox;
+  const float* src = a.img + n * a.img_stride + ((long)b * 3 + (grey ? 0 : c)) * plane + (long)oy * a.W + ox;
   // vertical pass (the reference resizes rows first): band[yl][X] = sum_i w[y][i] * I[left(y) + i][X]; a grey cutout reads the luma
   // of the three planes instead of its own (resize and the luma are both linear: grey before or after the resize is the same image)
   for (int e = threadIdx.x; e < rows * size; e += 256) {
@@ -190,12 +194,14 @@ __global__ __launch_bounds__(256) void cutouts_bwd_h_kernel(CutArgs a, const voi
 }
 
 // vertical adjoint + sum over the cutouts: grad[b][c][Y][X] (+)= mul * sum_n sum_y w_n[y][Y - top_n - left_n(y)] * th[n, b][c][y][X - left_n]
-// grid (ceil(W / 256), H, B * 3)
+// grid (ceil(W / 256), H, B * 3); with an image stride, grid (ceil(W / 256), H, n_cut * B * 3): cutout n's own slot, no sum
 __global__ __launch_bounds__(256) void cutouts_bwd_v_kernel(CutArgs a, const float* __restrict__ th, float* __restrict__ grad, int accumulate) {
   const int X = blockIdx.x * 256 + threadIdx.x, Yg = blockIdx.y;
-  const int bc = blockIdx.z, b = bc / 3, c = bc - b * 3;
+  const int slot = a.img_stride ? (int)(blockIdx.z / (a.B * 3)) : 0;
+  const int bc = blockIdx.z - slot * a.B * 3, b = bc / 3, c = bc - b * 3;
+  const int n_lo = a.img_stride ? slot : 0, n_hi = a.img_stride ? slot + 1 : a.n_cut;
   float acc = 0.f;
-  for (int n = 0; n < a.n_cut; n++) {
+  for (int n = n_lo; n < n_hi; n++) {
     const int rs = a.rects[3 * n], size = rs & CUT_SIZE_MASK, oy = a.rects[3 * n + 1], ox = a.rects[3 * n + 2];
     const bool grey = (rs & CUT_GREY) != 0;
     const int Y = Yg - oy;
@@ -223,7 +229,7 @@ __global__ __launch_bounds__(256) void cutouts_bwd_v_kernel(CutArgs a, const flo
     }
   }
   if (X >= a.W) return;
-  float* g = grad + ((long)bc * a.H + Yg) * a.W + X;
+  float* g = grad + slot * a.img_stride + ((long)bc * a.H + Yg) * a.W + X;
   *g = accumulate ? *g + acc * a.mul : acc * a.mul;
 }
 
@@ -239,7 +245,7 @@ static int fill(CutArgs& a, const CutoutPlan& p, void* tables) {
   MAUA_REQUIRE(std::min(p.H, p.W) <= 4 * p.cs - 1, "cutouts: images of more than 4 x the cut size need more than 16 filter taps");
   a.img = p.img; a.rects = p.rects; a.B = p.B; a.H = p.H; a.W = p.W; a.n_cut = p.n_cut; a.cs = p.cs; a.mul = p.mul; a.add = p.add;
   for (int c = 0; c < 3; c++) { a.mean[c] = p.mean[c]; a.inv_std[c] = 1.f / p.std[c]; }
-  a.patch = p.patch; a.smax = std::min(p.H, p.W);
+  a.patch = p.patch; a.smax = std::min(p.H, p.W); a.img_stride = p.img_stride;
   char* t = (char*)tables;
   a.left = (const int*)t;
   a.wts = (const float*)(t + (size_t)p.n_cut * p.cs * 4);
@@ -289,8 +295,9 @@ int launch_cutouts_vjp(hipStream_t stream, int dtype, const CutoutPlan& p, void*
     MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)cutouts_bwd_h_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipLaunchKernelGGL(cutouts_bwd_h_kernel<float>, grid, dim3(256), smem, stream, a, d_out, th);
   }
-  MAUA_REQUIRE((long)p.B * 3 <= 65535 && p.H <= 65535, "cutouts: image batch / height too large for one launch");
-  hipLaunchKernelGGL(cutouts_bwd_v_kernel, dim3((unsigned)cdiv(p.W, 256), (unsigned)p.H, (unsigned)(p.B * 3)), dim3(256), 0, stream, a, th,
+  const long zs = (long)p.B * 3 * (p.img_stride ? p.n_cut : 1);
+  MAUA_REQUIRE(zs <= 65535 && p.H <= 65535, "cutouts: image batch / height too large for one launch");
+  hipLaunchKernelGGL(cutouts_bwd_v_kernel, dim3((unsigned)cdiv(p.W, 256), (unsigned)p.H, (unsigned)zs), dim3(256), 0, stream, a, th,
                      grad, accumulate);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;

@@ -335,13 +335,29 @@ struct CutoutPlan {
   float mul, add;          // affine applied to the image first ((img + 1) / 2: 0.5, 0.5)
   float mean[3], std[3];   // Normalize applied to the cutouts
   int patch;
-};
+  long img_stride;         // 0: every cutout reads the same image batch; else cutout n reads its own batch at img + n * img_stride
+};                         // (and the gradient goes to its own slot grad + n * img_stride: the augmented crops of cutout_augs.hip)
 size_t cutouts_table_bytes(int n_cut, int cs);
 size_t cutouts_th_bytes(int n_cut, int B, int cs, int smax);
 int launch_cutout_tables(hipStream_t stream, const CutoutPlan& p, void* tables);
 int launch_cutouts_forward(hipStream_t stream, int dtype, const CutoutPlan& p, void* tables, void* out);
 int launch_cutouts_vjp(hipStream_t stream, int dtype, const CutoutPlan& p, void* tables, const void* d_out, float* th, float* grad,
                        int accumulate);
+
+// cutout_augs.hip: the torchvision augmentation pipeline of "normal" / "dango" cutouts (see the file's header).  A record set is
+// prepared on the host (aug_records: checked, inverse warps in double) and uploaded; the four passes run on caller-owned buffers
+// [n_rec][nimg][3][S][S] f32.  noise_i0: index of the first image in the noise layout (a dango call split into groups).
+constexpr int AUG_REC = 17;
+size_t aug_record_bytes();
+int aug_records(const float* augs, int n_rec, const int* rects, int side, const unsigned long long* keys, int recs_per_key, void* host_out);
+int aug_forward_src(hipStream_t st, const void* recs, int n_rec, int nimg, int S, int noise_i0, const float* src, int H, int W, float mul,
+                    float add, float* x1);
+int aug_forward_out(hipStream_t st, int dtype, const void* recs, int n_rec, int nimg, int S, int noise_i0, const float* x1, void* out,
+                    int patch, const float* mean3, const float* std3);
+int aug_adjoint_out(hipStream_t st, int dtype, const void* recs, int n_rec, int nimg, int S, const void* d_out, int patch,
+                    const float* std3, float* d_a);
+int aug_adjoint_src(hipStream_t st, const void* recs, int n_rec, int nimg, int S, const float* d_a, int H, int W, float mul, float* dst,
+                    int accumulate);
 
 // colormatch.hip: ColorMatchGrads.forward on caller-owned workspaces (nothing allocated: capturable), the conditioning's NaN-screened sum
 size_t colormatch_fix_bytes(int B, int nbins);

@@ -26,7 +26,9 @@ configs[3]'s "text prompts" go through; the perceptor itself is an un-vendored p
 CLIP's text tower and tokenizer (maua_amd/clip.py, clip_tokenizer.py: embedded once per ``set_targets``, off the loop; parity
 unpinned) or arrives as a precomputed ``EmbeddingPrompt``.  ``MSEGuide`` (image targets) is the module that needs no perceptor.  Any other caller-supplied object with
 the contract of maua/grad.py:15-25 (``scale``, ``set_targets(prompts)``, ``__call__(img, t) -> d loss / d img`` on the device) works
-step by step; ColorMatch / VGG / LPIPS grads (:48-93, :167-199) are not built.
+step by step; ColorMatch / VGG / LPIPS grads (:48-93, :167-199) are not built.  CLIPGrads with "normal" / "dango" cutouts at
+their default ``skip_augs=False`` (torchvision's augmentation pipeline, csrc/cutout_augs.hip) runs step by step: its ``graph_spec()``
+is None, so the guided loop falls back to the eager path for it.
 """
 import ctypes as C
 import math
