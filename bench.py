@@ -11,10 +11,13 @@ range over the ranks.  One "step" = one batch of B frames through the per-batch 
 selfsupervised/sample.py:90-98 (reference): 17 index-addressed Loop noise maps -> StyleGAN2 synthesis forward ->
 (x+1)/2 -> u8 HWC pack.  Latents (spline-loop schedule blended by the onset envelope) and network weights are
 resident in HBM before the timed region, as the reference has them resident before its render loop.
-After the K timed steps every rank renders its WHOLE frame range once (the "clip" leg: sustained rate over
-3600 / N frames, then the one RCCL gather of the u8 shards to rank 0, timed) - reported as extra keys `sustained`,
-`e2e` (SURVEY 8(d) metric (ii): set-up + render of the whole clip) and `gather_ms`; `value` stays the K-step rate.
-Prints ONE JSON line (rank 0); `ms_per_step` is the wall time of one timed step.
+Prints ONE JSON line (rank 0); `value` is the K-step rate and `ms_per_step` the wall time of one timed step.  A plain run
+does only what that line needs: set-up, W warm-up steps, the K timed steps (per-launch HIP events on: `roofline`,
+`kernels`), --dump-outputs, the line.
+``--full`` adds everything else after the timed steps, as extra keys: every rank renders its WHOLE frame range once (the
+"clip" leg: sustained rate over 3600 / N frames, then the one RCCL gather of the u8 shards to rank 0, timed - `sustained`,
+`e2e` (SURVEY 8(d) metric (ii): set-up + render of the whole clip), `strong` and `gather_ms`), the rocprofv3 counter passes
+behind `roofline.traffic`, the float16 / configs[3] / configs[4] legs (`f16`, `diffusion`, `upscale`) and `cpu_baseline`.
 ``--dump-outputs DIR`` also writes what the last timed step computed (rank 0's u8 frames, a fixed seeded sample as float32
 .npy files, see dump_outputs) - the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
@@ -58,18 +61,24 @@ def parse():
     ap.add_argument("--batch", type=int, default=DEFAULT_BATCH,
                     help="frames per step per GPU (the reference's sample.py defaults to 32 for 8-24 GB cards; 128 frames of "
                          "activations are ~10 GB of the MI355X's 288 GB and amortise the low-resolution layers: +8 %% frames/s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-oracle baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the clip leg (`sustained`, `e2e`, "
+                         "`strong`, `gather_ms`), the live counter passes behind `roofline.traffic`, the float16 / configs[3] / configs[4] "
+                         "legs and the CPU-oracle baseline (a few minutes on one GPU); the options below marked (--full) shape these")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU-oracle baseline leg")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(--full) budget of the CPU-oracle baseline leg")
     ap.add_argument("--gather", choices=("cabi", "torch"), default=None,
-                    help="transport of the clip leg's frame exchange at N > 1: the library's own RCCL communicator (default) or "
+                    help="(--full) transport of the clip leg's frame exchange at N > 1: the library's own RCCL communicator (default) or "
                          "torch.distributed's point-to-point calls on torch's RCCL group (also the automatic fallback)")
     ap.add_argument("--strict", action="store_true",
-                    help="exit with status 3 (after printing the headline line) when the clip leg's exchange fails or hangs at N > 1; "
-                         "by default the status stays 0 and the line carries \"ok\": false")
+                    help="(--full) exit with status 3 (after printing the headline line) when the clip leg's exchange fails or hangs at "
+                         "N > 1; by default the status stays 0 and the line carries \"ok\": false")
     ap.add_argument("--diffusion-arms", action="store_true",
-                    help="configs[3] leg: also time the secondary model's other arithmetic modes (exact f32, bf16): four more 100-step loops")
+                    help="(--full) configs[3] leg: also time the secondary model's other arithmetic modes (exact f32, bf16): four more "
+                         "100-step loops")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the configs[3] (guided-diffusion DDIM) and configs[4] (render -> RealESRGAN x4) legs (extra keys)")
+                    help="(--full) skip the float16, configs[3] (guided-diffusion DDIM) and configs[4] (render -> RealESRGAN x4) legs "
+                         "(extra keys)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0's u8 frames, as float32: "
                          "a fixed, seeded sample, under 64 MB) to DIR/<name>.npy, for comparing two builds output for output")
@@ -873,10 +882,13 @@ def main():
         else:
             roof = {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": f_hbm}
         roof.update({"frac_mfma": f_mfma, "frac_hbm": f_hbm})
-        traffic, traffic_source = (None, "N > 1") if world > 1 else live_traffic(dom, B)
-        if traffic is None:
-            replayed, src = measured_traffic(dom, B)
-            traffic, traffic_source = replayed, src + " [" + traffic_source + "]"
+        if not a.full:
+            traffic, traffic_source = None, "not measured: a plain run takes no counter passes (--full measures it)"
+        else:
+            traffic, traffic_source = (None, "N > 1") if world > 1 else live_traffic(dom, B)
+            if traffic is None:
+                replayed, src = measured_traffic(dom, B)
+                traffic, traffic_source = replayed, src + " [" + traffic_source + "]"
         roof.update({"kernel": dom, "avg_launch_ms": gd["ms"] / gd["launches"], "launches_timed": gd["launches"],
                      "traffic": traffic, "traffic_source": traffic_source})
         # the whole step against both roofs: algorithmic FLOPs / bytes of every launch of the forward (+ the noise maps the
@@ -896,7 +908,7 @@ def main():
                                    "(120 s synthetic audio @30720 Hz), per step: 17 Loop noise maps + synthesis + u8 pack",
                        "frames_per_step_per_gpu": B, "clip_frames": T_FRAMES, "frame_sharding": f"contiguous x{world}",
                        "latents": info},
-            "ok": True,
+            "ok": True, "full": a.full,
             "tolerance": TOLERANCE,
             "roofline": roof, "kernels": roof_all, "fused_into_other_launches": fused_rows, "gather_ms": gather_ms,
             "sustained_sclk_mhz": sclk_mhz,
@@ -919,10 +931,18 @@ def main():
                                 "noise planes, render + u8 pack of every frame, gather (N > 1); excludes what a process pays once: the "
                                 "HIP context, the first import and process_warmup_s (a 16-frame 64^2 clip through the same path)"},
         }
-        res["config"]["gather"] = "streamed: finished chunks of frames_per_step frames travel to rank 0 on a side stream during the render"
+        if a.full:   # (the clip leg's exchange)
+            res["config"]["gather"] = "streamed: finished chunks of frames_per_step frames travel to rank 0 on a side stream during the render"
         if dumped is not None:
             res["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         return res
+
+    if not a.full:   # a plain run ends here: the line of the timed steps
+        if rank == 0:
+            print(("\n" if world > 1 else "") + json.dumps(build_result(None, None)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- clip leg: this rank's whole frame range once (3600 / N frames, ceil((hi - lo) / B) steps) into a resident
     # buffer, the u8 shards travelling to rank 0 CHUNK BY CHUNK on a side stream while the next batch renders (RCCL

@@ -1,7 +1,7 @@
 """Measured HBM traffic per kernel launch from rocprofv3 PMC counters (GPU box).
 
 Two separate passes (FETCH_SIZE needs 3 of the 4 TCC slots, WRITE_SIZE 2: MI355X_MICROARCH.md §rocprofv3 PMC
-slots), each `rocprofv3 --kernel-trace --pmc <counter>` over `bench.py --steps 4 --warmup 1 --no-cpu-baseline`.
+slots), each `rocprofv3 --kernel-trace --pmc <counter>` over `bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-extras`.
 Corrections prescribed by MI355X_MICROARCH.md §HBM: counters are in KiB (x1024); on gfx950 FETCH_SIZE reports
 exactly half of the bytes of a wide (16 B/lane) coalesced streaming read, so it is doubled; WRITE_SIZE is taken
 as reported (uncalibrated).  Infinity-Cache hits are included in both (fabric-side counters).
@@ -24,10 +24,10 @@ BATCH = int(os.environ.get("BATCH", "128"))  # frames per step (bench.py default
 def run(counter, batch=None, steps=4, timeout=None, out=None):
     out = out or OUT
     os.makedirs(out, exist_ok=True)
-    # (the child must not start its own counter passes: bench.py runs these two by itself at the end of a default run)
+    # (the child must not start its own counter passes: bench.py --full runs these two by itself after its timed steps)
     env = dict(os.environ, TMPDIR="/tmp", MAUA_BENCH_NO_LIVE_TRAFFIC="1")
     cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "-o", counter, "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-extras",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-extras",
            "--batch", str(batch or BATCH)]
     subprocess.run(cmd, check=True, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=ROOT, timeout=timeout)
     f = glob.glob(os.path.join(out, "**", f"{counter}_counter_collection.csv"), recursive=True)[0]

@@ -6,9 +6,9 @@ TAG=${TAG:-r03}
 O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -2 $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_prof.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_prof.json 2> $O/prof.err
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); cp "$f" $O/kernel_stats.csv; head -12 $O/kernel_stats.csv | cut -c1-160
 BATCH=128 python scripts/collect_traffic.py > $O/traffic.log 2>&1; cp gpurun_out/traffic.json $O/traffic.json; cat $O/traffic.log
 python scripts/pmc_summary.py 128 $O/pmc_summary.json > $O/pmc_summary.txt 2>&1; head -14 $O/pmc_summary.txt

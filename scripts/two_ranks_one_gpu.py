@@ -55,7 +55,7 @@ def main():
                    HSA_ENABLE_IPC_MODE_LEGACY="0", NCCL_DEBUG="WARN")
         if what == "bench":
             env["MAUA_BENCH_BACKEND"] = "gloo"   # torch's control plane over gloo; the library's RCCL communicator will refuse the shared GPU
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16"]
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16"]
         else:
             cmd = [sys.executable, os.path.join(ROOT, "scripts", "two_ranks_one_gpu.py"), "_worker"]
         procs.append(subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))

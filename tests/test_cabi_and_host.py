@@ -337,6 +337,21 @@ def test_bench_layer_table_matches_the_profile_slots():
         if hasattr(SynthesisNetwork, "layer_shapes_for") else True
 
 
+def test_bench_full_legs_are_opt_in(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` is the lean run; the clip leg, the counter passes, the extra legs and the
+    CPU baseline run only behind --full, which every option shaping them leaves off."""
+    import importlib.util
+    import pathlib
+    spec = importlib.util.spec_from_file_location("maua_bench", pathlib.Path(__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--no-extras", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, None)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--steps", "7"])
+    assert bench.parse().full
+
+
 def test_host_layer_signatures_match_the_reference():
     """The drop-in surface as data: argument names, their order and their defaults of every reference function / method the
     host layer mirrors (tests/golden/g25_signatures.json, read from the reference's source with ast by make_golden.py) against
