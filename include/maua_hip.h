@@ -509,6 +509,32 @@ int maua_attention_legacy_vjp(maua_ctx* ctx, const void* qkv, const void* d_out,
  * c[M][N] = a[M][K] x w[N][K]^T + bias[N] (+ res[M][N]); K % 32 (bf16) / 16 (f32) == 0, N % 32 == 0 */
 int maua_linear_nt(maua_ctx* ctx, const void* a, const void* w, const float* bias, const void* res, void* c, long M, int N,
                    int K, int dtype);
+/* kernel-selection switches of the GEMM behind maua_linear_nt and the UNet / CLIP / perceptor layers, for parity tests (no
+ * reference counterpart).  c[m][n] = sum_k A[m][k] w[n][k] (+ bias[n]) (+ res[m][n]), A's columns [0, K0) from a0 (row stride lda0)
+ * and [K0, K0 + K1) from a1 (lda1); w [N][K0 + K1] dense; res [M][ldr]; c [M][ldc]; strides in elements of dtype (MAUA_BF16 or
+ * MAUA_F32).  epi (bf16, kernels 3 and 4 only): 1 = c2[m][n] <- QuickGELU(c[m][n]) as well (row stride ldc2); 2 = c <- c *
+ * QuickGELU'(aux[m][n]) (ldaux).  batch > 1: that many products of one A source, no bias, no residual, a0 / w / c of product b
+ * at + b * a_bstride / w_bstride / c_bstride elements (batch <= 65535, strides whole 16-byte pieces).  Always checked: K0, K1
+ * whole 64-byte chunks, N % 32 == 0, lda0 / lda1 whole 16-byte pieces, ldc % 4 == 0, a0, a1, w, bias, c, res, c2, aux 16-byte aligned.
+ * Kernels: 1 = 64 x 128 register-staged (any such shape, f32 or bf16, epi 0); 2 = 128 x 128 register-staged (K parts whole
+ * 128-byte chunks, ldc / ldr 16-byte pieces, epi 0); 3 = 256 x 128 LDS-direct (bf16, batch 1, K parts whole 64-channel chunks,
+ * N % 128 == 0, ldc / ldr / ldc2 / ldaux % 8 == 0, M lda0 2, M lda1 2 and N (K0 + K1) 2 below 2^32 bytes); 4 = 256 x 256
+ * LDS-direct (as 3, plus K1 == 0 and N % 256 == 0).  Production routing adds thresholds that are about occupancy only, never
+ * about correctness: kernel 2 needs M >= 128; kernels 3 / 4 need prefer_dma, M >= 256 and at least 256 tiles of 256 x 128 (3) /
+ * 256 x 256 (4) - and take 4 over 3 unless the environment sets MAUA_GEMM_DMA_128.  A forced kernel drops exactly these. */
+typedef struct {
+  const void* a0; long lda0; int K0;   const void* a1; long lda1; int K1;
+  const void* w;  const float* bias;   const void* res; long ldr;
+  void* c; long ldc; long M; int N;
+  int epi; void* c2; long ldc2; const void* aux; long ldaux;
+  int batch; long a_bstride, w_bstride, c_bstride;
+} maua_gemm_desc;
+/* host only, no device needed: the kernel (1 .. 4) the launch would run (force 0: production routing, prefer_dma as the ctx
+ * option "linear_dma" / the CLIP tower set it), *remap_out its XCD remap (kernel 2: the number of N tiles whose M tile is kept on
+ * one XCD, 0 = none; may be NULL); MAUA_ERR + maua_last_error() if refused.  Pointers are only checked, never dereferenced. */
+int maua_gemm_nt_route(const maua_gemm_desc* d, int dtype, int prefer_dma, int* remap_out);
+/* launch: force 0 = production routing, 1 .. 4 = that kernel, refused (no launch) when it cannot take the shape */
+int maua_gemm_nt_ex(maua_ctx* ctx, const maua_gemm_desc* d, int dtype, int prefer_dma, int force);
 /* GroupNorm32(32, C)(x) [* (1 + scale) + shift with scale_shift [B][2C] (ResBlock use_scale_shift_norm)] [-> SiLU];
  * statistics in float64, eps 1e-5.  x, y [B][H][W][C] */
 int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift,

@@ -137,3 +137,13 @@ def dev_tensor(t, dtype=None):
     if t.device.type == "cuda":
         return t.to(dtype=dtype).contiguous()
     return t.to(device="cuda", dtype=dtype).contiguous()
+
+
+class GemmDesc(C.Structure):
+    """maua_gemm_desc (include/maua_hip.h): one GEMM for maua_gemm_nt_route / maua_gemm_nt_ex; pointers as integers."""
+    _fields_ = [("a0", C.c_void_p), ("lda0", C.c_long), ("K0", C.c_int),
+                ("a1", C.c_void_p), ("lda1", C.c_long), ("K1", C.c_int),
+                ("w", C.c_void_p), ("bias", C.c_void_p), ("res", C.c_void_p), ("ldr", C.c_long),
+                ("c", C.c_void_p), ("ldc", C.c_long), ("M", C.c_long), ("N", C.c_int),
+                ("epi", C.c_int), ("c2", C.c_void_p), ("ldc2", C.c_long), ("aux", C.c_void_p), ("ldaux", C.c_long),
+                ("batch", C.c_int), ("a_bstride", C.c_long), ("w_bstride", C.c_long), ("c_bstride", C.c_long)]

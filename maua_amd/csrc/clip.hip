@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "quick_gelu.h"
 
 using namespace maua;
 
@@ -68,7 +69,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__device__ __forceinline__ float sigmoid_f(float x, bool exact) { return 1.f / (1.f + (exact ? expf(-x) : __expf(-x))); }
 
 constexpr int LN_MAXP = 8;   // 16-byte pieces per lane: C <= 64 * 8 * (16 / sizeof(T))
 
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(const T* __restrict__ h
   float v[E];
   Pc<T>::load(h + p * E, v);
 #pragma unroll
-  for (int e = 0; e < E; e++) v[e] = v[e] * sigmoid_f(1.702f * v[e], sizeof(T) == 4);
+  for (int e = 0; e < E; e++) v[e] = quick_gelu_f(v[e], sizeof(T) == 4);
   Pc<T>::store(a + p * E, v);
 }
 template <typename T>
@@ -193,10 +193,7 @@ __global__ __launch_bounds__(256) void quick_gelu_vjp_kernel(const T* __restrict
   Pc<T>::load(h + p * E, v);
   Pc<T>::load(da + p * E, d);
 #pragma unroll
-  for (int e = 0; e < E; e++) {
-    const float s = sigmoid_f(1.702f * v[e], sizeof(T) == 4);
-    d[e] *= s * (1.f + 1.702f * v[e] * (1.f - s));
-  }
+  for (int e = 0; e < E; e++) d[e] *= quick_gelu_grad_f(v[e], sizeof(T) == 4);
   Pc<T>::store(dh + p * E, d);
 }
 

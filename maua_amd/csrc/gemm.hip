@@ -117,7 +117,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs g) {
       if (g.res) {
         const T* rp = reinterpret_cast<const T*>(g.res) + m * g.ldr + n;
 #pragma unroll
-        for (int k = 0; k < 4; k++) v[k] += Elem<T>::load(rp + k);
+        for (int k = 0; k < 4; k++) {
+          // (bf16: the bias-added value is rounded to bf16 before the residual is added, as in the three kernels below)
+          if constexpr (sizeof(T) == 2)
+            if (!g.c_f32) v[k] = bf2f(f2bf(v[k]));
+          v[k] += Elem<T>::load(rp + k);
+        }
       }
       if (g.c_f32) {
         *reinterpret_cast<float4*>(reinterpret_cast<float*>(g.c) + m * g.ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
@@ -287,29 +292,80 @@ __global__ __launch_bounds__(256) void gemm_nt128_kernel(GemmArgs g) {
 
 }  // namespace
 
-int launch_gemm_nt(hipStream_t stream, int dtype, const GemmArgs& g) {
-  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "gemm_nt: unsupported dtype");
-  const int kc = dtype == MAUA_BF16 ? 32 : 16;
-  MAUA_REQUIRE(g.a0 && g.w && g.c && g.K0 > 0 && g.K0 % kc == 0 && g.K1 % kc == 0 && (g.K1 == 0 || g.a1),
-               "gemm_nt: K parts must be multiples of 64 bytes");
-  MAUA_REQUIRE(g.N % 32 == 0 && g.N > 0 && g.lda0 % 4 == 0 && g.ldc % 4 == 0, "gemm_nt: N must be a multiple of 32");
-  if (g.M == 0) return MAUA_OK;
-  const unsigned nb = g.batch > 1 ? (unsigned)g.batch : 1u;
-  MAUA_REQUIRE(nb == 1 || (!g.a1 && g.K1 == 0 && !g.res && !g.bias && nb <= 65535), "gemm_nt: a batched launch takes one A source, no bias, no residual");
-  if (nb == 1 && g.prefer_dma && gemm_dma_supported(dtype, g)) return launch_gemm_dma(stream, g);
-  MAUA_REQUIRE(g.epi == 0, "gemm_nt: the QuickGELU epilogue forms exist on the LDS-direct kernel only (callers check gemm_dma_supported)");
+// the 128 x 128 kernel's conditions: both K parts in whole 128-byte chunks and 16-byte row pieces everywhere (correctness), and
+// M >= 128 (occupancy: below one tile the 64-row kernel wastes less)
+static bool gemm128_takes(int dtype, const GemmArgs& g, bool occupancy) {
   const int kcw = dtype == MAUA_BF16 ? 64 : 32;   // channels per 128-byte chunk
   const int epc = dtype == MAUA_BF16 ? 8 : 4;
-  if (!g.c_f32 && g.K0 % kcw == 0 && g.K1 % kcw == 0 && g.M >= 128 && g.ldc % epc == 0 && (!g.res || g.ldr % epc == 0) &&
-      g.lda0 % epc == 0 && (g.K1 == 0 || g.lda1 % epc == 0)) {
+  return !g.c_f32 && g.epi == 0 && g.K0 % kcw == 0 && g.K1 % kcw == 0 && (!occupancy || g.M >= 128) && g.ldc % epc == 0 &&
+         (!g.res || g.ldr % epc == 0) && g.lda0 % epc == 0 && (g.K1 == 0 || g.lda1 % epc == 0);
+}
+
+GemmRoute gemm_route(int dtype, const GemmArgs& g, int prefer_dma, int force) {
+  GemmRoute r{0, 0};
+  const bool single = g.batch <= 1;
+  if (force == 0) {
+    if (single && prefer_dma && gemm_dma_supported(dtype, g))
+      r.kernel = gemm256_takes(g) && !getenv("MAUA_GEMM_DMA_128") ? 4 : 3;
+    else if (g.epi == 0)
+      r.kernel = gemm128_takes(dtype, g, true) ? 2 : 1;
+  } else if (force == 1) {
+    r.kernel = g.epi == 0 ? 1 : 0;
+  } else if (force == 2) {
+    r.kernel = gemm128_takes(dtype, g, false) ? 2 : 0;
+  } else if (force == 3 || force == 4) {
+    r.kernel = single && gemm_dma_shape_ok(dtype, g) && (force == 3 || gemm256_shape_ok(g)) ? force : 0;
+  }
+  if (r.kernel == 2) {
+    static const bool xcd_off = getenv("MAUA_GEMM_XCD_OFF") != nullptr;
+    const long mt = (g.M + WBM - 1) / WBM, nt = (g.N + WBN - 1) / WBN;
+    if (single && nt >= 2 && nt <= 8 && mt >= 64 && !xcd_off)   // few N tiles over many rows: keep an M tile's N tiles on one XCD
+      r.remap_nt = (int)nt;
+  }
+  return r;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int gemm_plan(int dtype, const GemmArgs& g, int prefer_dma, int force, GemmRoute* out) {
+  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "gemm_nt: unsupported dtype");
+  MAUA_REQUIRE(force >= 0 && force <= 4, "gemm_nt: force must be 0 (production routing) or a kernel id 1 .. 4");
+  const int kc = dtype == MAUA_BF16 ? 32 : 16;    // channels per 64-byte chunk
+  const int epc = dtype == MAUA_BF16 ? 8 : 4;     // channels per 16-byte piece
+  MAUA_REQUIRE(g.a0 && g.w && g.c && g.K0 > 0 && g.K0 % kc == 0 && g.K1 >= 0 && g.K1 % kc == 0 && (g.K1 == 0 || g.a1),
+               "gemm_nt: K parts must be multiples of 64 bytes");
+  MAUA_REQUIRE(g.N % 32 == 0 && g.N > 0 && g.M >= 0, "gemm_nt: N must be a multiple of 32");
+  // every kernel reads A rows in 16-byte pieces and writes C in at least 8-byte ones
+  MAUA_REQUIRE(g.lda0 % epc == 0 && (g.K1 == 0 || g.lda1 % epc == 0) && g.ldc % 4 == 0,
+               "gemm_nt: lda0 / lda1 must be whole 16-byte pieces, ldc a multiple of 4");
+  MAUA_REQUIRE(aligned16(g.a0) && (g.K1 == 0 || aligned16(g.a1)) && aligned16(g.w) && aligned16(g.c) && aligned16(g.res) &&
+                   aligned16(g.bias) && (g.epi != 1 || aligned16(g.c2)) && (g.epi != 2 || aligned16(g.aux)),
+               "gemm_nt: a0, a1, w, bias, c, res, c2 and aux must be 16-byte aligned");
+  MAUA_REQUIRE(g.batch <= 1 || (!g.a1 && g.K1 == 0 && !g.res && !g.bias && g.batch <= 65535),
+               "gemm_nt: a batched launch takes one A source, no bias, no residual");
+  MAUA_REQUIRE(g.batch <= 1 || (g.a_bstride % epc == 0 && g.w_bstride % epc == 0 && g.c_bstride % epc == 0),
+               "gemm_nt: batch strides must be whole 16-byte pieces");
+  const GemmRoute r = gemm_route(dtype, g, prefer_dma, force);
+  if (r.kernel == 0) {
+    MAUA_REQUIRE(g.epi == 0, "gemm_nt: the QuickGELU epilogue forms exist on the LDS-direct kernels only (callers check gemm_dma_supported)");
+    return fail("gemm_nt: the forced kernel cannot take this shape");
+  }
+  // kernels 2 .. 4 read the residual in 16-byte pieces (their routes check it; restated here for the forced ones)
+  MAUA_REQUIRE(r.kernel == 1 || !g.res || g.ldr % epc == 0, "gemm_nt: ldr must be whole 16-byte pieces");
+  *out = r;
+  return MAUA_OK;
+}
+
+int launch_gemm_routed(hipStream_t stream, int dtype, const GemmArgs& g, GemmRoute r) {
+  if (g.M == 0) return MAUA_OK;
+  if (r.kernel == 3 || r.kernel == 4) return launch_gemm_dma(stream, g, r.kernel);
+  const unsigned nb = g.batch > 1 ? (unsigned)g.batch : 1u;
+  if (r.kernel == 2) {
     const size_t smem = std::max<size_t>((size_t)2 * WBM * WRS, (size_t)WBM * (WBN * (dtype == MAUA_BF16 ? 2 : 4) + 16));
     dim3 gridw((unsigned)((g.M + WBM - 1) / WBM), (unsigned)((g.N + WBN - 1) / WBN), nb);
     GemmArgs gr = g;
-    static const bool xcd_off = getenv("MAUA_GEMM_XCD_OFF") != nullptr;
-    if (nb == 1 && gridw.y >= 2 && gridw.y <= 8 && gridw.x >= 64 && !xcd_off) {   // few N tiles over many rows: keep an M tile's N tiles on one XCD
-      gr.remap_nt = (int)gridw.y;
-      gridw = dim3((gridw.x + 7) / 8 * 8 * gridw.y, 1, 1);
-    }
+    gr.remap_nt = r.remap_nt;
+    if (r.remap_nt) gridw = dim3((gridw.x + 7) / 8 * 8 * gridw.y, 1, 1);
     if (dtype == MAUA_BF16) {
       MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_nt128_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
       hipLaunchKernelGGL(gemm_nt128_kernel<bf16_t>, gridw, dim3(256), smem, stream, gr);
@@ -320,6 +376,7 @@ int launch_gemm_nt(hipStream_t stream, int dtype, const GemmArgs& g) {
     MAUA_HIP_CHECK(hipGetLastError());
     return MAUA_OK;
   }
+  MAUA_REQUIRE(r.kernel == 1, "gemm_nt: unknown kernel id");
   dim3 grid((unsigned)((g.M + GBM - 1) / GBM), (unsigned)((g.N + GBN - 1) / GBN), nb);
   if (dtype == MAUA_BF16)
     hipLaunchKernelGGL(gemm_nt_kernel<bf16_t>, grid, dim3(256), 0, stream, g);
@@ -329,4 +386,38 @@ int launch_gemm_nt(hipStream_t stream, int dtype, const GemmArgs& g) {
   return MAUA_OK;
 }
 
+int launch_gemm_nt(hipStream_t stream, int dtype, const GemmArgs& g) {
+  GemmRoute r;
+  if (int rc = gemm_plan(dtype, g, g.prefer_dma, 0, &r)) return rc;
+  return launch_gemm_routed(stream, dtype, g, r);
+}
+
 }  // namespace maua
+
+using namespace maua;
+
+static GemmArgs gemm_args(const maua_gemm_desc* d) {
+  GemmArgs g{};
+  g.a0 = d->a0; g.lda0 = d->lda0; g.K0 = d->K0; g.a1 = d->a1; g.lda1 = d->lda1; g.K1 = d->K1;
+  g.w = d->w; g.bias = d->bias; g.res = d->res; g.ldr = d->ldr; g.c = d->c; g.ldc = d->ldc; g.M = d->M; g.N = d->N;
+  g.epi = d->epi; g.c2 = d->c2; g.ldc2 = d->ldc2; g.aux = d->aux; g.ldaux = d->ldaux;
+  g.batch = d->batch; g.a_bstride = d->a_bstride; g.w_bstride = d->w_bstride; g.c_bstride = d->c_bstride;
+  return g;
+}
+
+int maua_gemm_nt_route(const maua_gemm_desc* d, int dtype, int prefer_dma, int* remap_out) {
+  MAUA_REQUIRE(d, "maua_gemm_nt_route: desc is NULL");
+  GemmRoute r;
+  if (int rc = gemm_plan(dtype, gemm_args(d), prefer_dma, 0, &r)) return rc;
+  if (remap_out) *remap_out = r.remap_nt;
+  return r.kernel;
+}
+
+int maua_gemm_nt_ex(maua_ctx* ctx, const maua_gemm_desc* d, int dtype, int prefer_dma, int force) {
+  MAUA_REQUIRE(ctx && d, "maua_gemm_nt_ex: NULL argument");
+  GemmArgs g = gemm_args(d);
+  g.prefer_dma = prefer_dma;
+  GemmRoute r;
+  if (int rc = gemm_plan(dtype, g, prefer_dma, force, &r)) return rc;
+  return launch_gemm_routed(ctx->stream, dtype, g, r);
+}

@@ -9,7 +9,7 @@
 // stays on gemm.hip's register-staged kernels.
 //
 // Epilogue forms (GemmArgs.epi), both applied to the value as stored (rounded to bf16), so that they equal the separate element-wise
-// kernels of clip.hip bit for bit:  1 = c2 <- QuickGELU(c) stored beside c (mlp.c_fc: the pre-activation is kept for the gradient,
+// kernels of clip.hip bit for bit (both sides evaluate quick_gelu.h's one definition):  1 = c2 <- QuickGELU(c) stored beside c (mlp.c_fc: the pre-activation is kept for the gradient,
 // the activation feeds c_proj);  2 = c <- c * QuickGELU'(aux) (the gradient through the activation on the way back).
 //
 // Why a second kernel: gemm.hip stages a chunk through registers one stage ahead - 16 MFMAs per wave are shorter than an HBM round trip
@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "quick_gelu.h"
 
 namespace maua {
 
@@ -57,12 +58,9 @@ __device__ __forceinline__ void mma(f32x16& acc, const u32x4& w, const u32x4& x)
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
 }
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-// x * sigmoid(1.702 x) (clip/model.py QuickGELU) and its derivative s + 1.702 x s (1 - s)
-__device__ __forceinline__ float qgelu(float x) { return x / (1.f + __expf(-1.702f * x)); }
-__device__ __forceinline__ float qgelu_grad(float x) {
-  const float s = 1.f / (1.f + __expf(-1.702f * x));
-  return s * (1.f + 1.702f * x * (1.f - s));
-}
+// QuickGELU and its derivative: quick_gelu.h's definitions at bf16's precision (__expf), as clip.hip's bf16 element-wise kernels use them
+__device__ __forceinline__ float qgelu(float x) { return quick_gelu_f(x, false); }
+__device__ __forceinline__ float qgelu_grad(float x) { return quick_gelu_grad_f(x, false); }
 
 __global__ __launch_bounds__(DNT) void gemm_dma_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -424,25 +422,30 @@ __global__ __launch_bounds__(QNT) void gemm256_kernel(GemmArgs g) {
 
 }  // namespace
 
-// shapes the LDS-direct kernel takes: bf16, both K parts in whole 64-channel chunks, N in whole 128-column tiles, 32-bit byte offsets
-// into A and W, and enough tiles for the chip
-bool gemm_dma_supported(int dtype, const GemmArgs& g) {
-  if (dtype != MAUA_BF16 || g.c_f32 || g.K0 % 64 || g.K1 % 64 || g.N % DBN || g.M < DBM) return false;
+// shapes the LDS-direct kernels can compute correctly: bf16, both K parts in whole 64-channel chunks, N in whole 128-column tiles,
+// 16-byte row pieces, 32-bit byte offsets into A and W, a known epilogue form with its operand
+bool gemm_dma_shape_ok(int dtype, const GemmArgs& g) {
+  if (dtype != MAUA_BF16 || g.c_f32 || g.K0 % 64 || g.K1 % 64 || g.N % DBN || g.M < 1) return false;
   if (g.lda0 % 8 || (g.K1 && g.lda1 % 8) || g.ldc % 8 || (g.res && g.ldr % 8)) return false;
   if ((g.epi == 1 && (!g.c2 || g.ldc2 % 8)) || (g.epi == 2 && (!g.aux || g.ldaux % 8)) || g.epi < 0 || g.epi > 2) return false;
   const long K = g.K0 + g.K1;
   if (g.M * g.lda0 * 2 >= (1L << 32) || (g.K1 && g.M * g.lda1 * 2 >= (1L << 32)) || (long)g.N * K * 2 >= (1L << 32)) return false;
-  return ((g.M + DBM - 1) / DBM) * (g.N / DBN) >= 256;
+  return true;
 }
 
-// the 256 x 256 form: one K source, N in whole 256-column tiles, at least a chip's worth of tiles
-static bool gemm256_takes(const GemmArgs& g) {
-  return g.K1 == 0 && g.N % QBN == 0 && ((g.M + QBM - 1) / QBM) * (g.N / QBN) >= 256;
+// ... and the shapes production routing sends there: the above, plus enough tiles for the chip (an occupancy threshold only)
+bool gemm_dma_supported(int dtype, const GemmArgs& g) {
+  return gemm_dma_shape_ok(dtype, g) && g.M >= DBM && ((g.M + DBM - 1) / DBM) * (g.N / DBN) >= 256;
 }
 
-int launch_gemm_dma(hipStream_t stream, const GemmArgs& g) {
-  MAUA_REQUIRE(gemm_dma_supported(MAUA_BF16, g), "gemm_dma: unsupported shape");
-  if (gemm256_takes(g) && !getenv("MAUA_GEMM_DMA_128")) {
+// the 256 x 256 form: one K source and N in whole 256-column tiles (correctness); at least a chip's worth of tiles (occupancy)
+bool gemm256_shape_ok(const GemmArgs& g) { return g.K1 == 0 && g.N % QBN == 0; }
+bool gemm256_takes(const GemmArgs& g) { return gemm256_shape_ok(g) && ((g.M + QBM - 1) / QBM) * (g.N / QBN) >= 256; }
+
+// kernel: 4 = gemm256_kernel, 3 = gemm_dma_kernel (launch_gemm_nt has routed and validated)
+int launch_gemm_dma(hipStream_t stream, const GemmArgs& g, int kernel) {
+  MAUA_REQUIRE(gemm_dma_shape_ok(MAUA_BF16, g) && (kernel == 3 || (kernel == 4 && gemm256_shape_ok(g))), "gemm_dma: unsupported shape");
+  if (kernel == 4) {
     const size_t smem = std::max<size_t>((size_t)2 * QSTAGE, (size_t)QBM * QES);
     const long mtiles8 = ((g.M + QBM - 1) / QBM + 7) / 8 * 8;
     const dim3 grid((unsigned)(mtiles8 * (g.N / QBN)));

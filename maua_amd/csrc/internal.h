@@ -264,9 +264,22 @@ struct GemmArgs {
   int remap_nt;
 };
 int launch_gemm_nt(hipStream_t stream, int dtype, const GemmArgs& g);
-// gemm_dma.hip: 256 x 128 tiles on LDS-direct loads (see there); launch_gemm_nt routes when g.prefer_dma
+// launch_gemm_nt in its three steps.  gemm_route (host only, no HIP call): the kernel that takes g - 1 gemm_nt_kernel (64 x 128),
+// 2 gemm_nt128_kernel (128 x 128), 3 gemm_dma_kernel (256 x 128), 4 gemm256_kernel (256 x 256), 0 none - and the remap_nt kernel 2
+// would use; force 0 = production routing (prefer_dma stands for g.prefer_dma), 1 .. 4 = that kernel if it can compute the shape
+// correctly, occupancy thresholds ignored.  gemm_plan: gemm_route plus every check the chosen kernel's loads and stores rely on
+// (MAUA_ERR + last error when refused).  launch_gemm_routed: the launch of a planned route.
+struct GemmRoute { int kernel; int remap_nt; };
+GemmRoute gemm_route(int dtype, const GemmArgs& g, int prefer_dma, int force = 0);
+int gemm_plan(int dtype, const GemmArgs& g, int prefer_dma, int force, GemmRoute* out);
+int launch_gemm_routed(hipStream_t stream, int dtype, const GemmArgs& g, GemmRoute r);
+// gemm_dma.hip: 256 x 128 (kernel 3) and 256 x 256 (kernel 4) tiles on LDS-direct loads (see there).  *_shape_ok: what the kernels
+// compute correctly; gemm_dma_supported / gemm256_takes: that, plus the occupancy thresholds production routing applies
+bool gemm_dma_shape_ok(int dtype, const GemmArgs& g);
 bool gemm_dma_supported(int dtype, const GemmArgs& g);
-int launch_gemm_dma(hipStream_t stream, const GemmArgs& g);
+bool gemm256_shape_ok(const GemmArgs& g);
+bool gemm256_takes(const GemmArgs& g);
+int launch_gemm_dma(hipStream_t stream, const GemmArgs& g, int kernel);
 
 // ---- attention.hip: softmax(Q K^T / sqrt(D)) V per (sample, head); qkv [B][T][ld_qkv] with head-major [q | k | v] channel
 // layout (guided-diffusion's QKVAttentionLegacy), out [B][T][ld_out] with channel = head * D + d
