@@ -116,10 +116,19 @@ int maua_synth_num_ws(const maua_synth* net);      /* SynthesisNetwork.num_ws, i
 int maua_synth_num_layers(const maua_synth* net);  /* synthesis layers in execution order (17 at 1024^2) */
 /* options: "keep_features" (0/1) keeps every layer's activation for maua_synth_get_feature (parity/debug);
  * "profile" (0/1) records HIP events on the ctx stream around every launch of a forward;
+ * kernel routing, for A/B comparisons and parity tests (every value computes the same network, up to rounding):
  * "tconv_up" (default 1) runs up-layers with 32^2..512^2 inputs as the minimal stride-2 transposed convolution + a
  * FIR/epilogue pass (0 = four 3x3 phase kernels everywhere, 4x the MACs; v > 1 = every up-layer with input size <= v);
+ * "tconv_dma" (default 1) runs that transposed convolution on LDS-direct loads (0 = register-staged kernel);
+ * "tconv_fir" (default 256) fuses it with the FIR/epilogue pass from this input size up (0 = never);
+ * "dma_conv" (default 1) runs the conv1 behind such an up-layer on LDS-direct loads, on pre-modulated input;
+ * "dual_store" (default 1) lets a conv1 with a separate toRGB pass also store its output pre-modulated for the next up-layer;
  * "use_hires" (default 1) / "fuse_torgb" (default 1) select the register-stationary high-resolution kernels and
- * the toRGB fusion (0 = generic kernels everywhere, for A/B comparisons and parity tests). */
+ * the toRGB fusion (0 = generic kernels everywhere);
+ * "upwalk" (default 2) runs the 64 -> 32 channel up-layer as a row walk (1: on its own; 2: the last block as one fused
+ * walk; 0 = off);
+ * "walk_segs" (default 0 = cost model) / "walk_narrow" (default 1) shape that fused walk;
+ * "lowres" (default 1) runs the <= 8x8 layers as one batch-wide GEMM. */
 /* ---- arbitrary output sizes (maua/GAN/wrappers/stylegan2.py:104-151 change_output_resolution and
  * :216-340 get_hook).  The feature map is resized at ONE layer and every later layer runs at the scaled size.
  *  layer:  the reference's index into layer_names (0 = pre-hook on bs.0.conv1's input, L >= 1 = forward hook on

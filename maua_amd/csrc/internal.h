@@ -36,7 +36,7 @@ struct ConvArgs {
   float* rgb_out;         // [B][3][H][W]
   float rgb_clamp;
   float fir[16];
-  int variant;            // launch_tconv2: TCONV_EDGES_ONLY restricts the launch to the thin regions (0 = everything)
+  int variant;            // launch_modconv_dma: 128 takes the 128-channel tile although 256 would divide (0 = its own choice)
   // channel-sliced operands (modconv3x3_kernel only; 0 = dense): elements between consecutive pixels of x / y, first
   // output channel inside a y pixel (dense-block buffers of the RRDB network, super.hip)
   int x_pstride, y_pstride, y_coff;
@@ -149,7 +149,6 @@ int launch_f32_split_inplace(hipStream_t stream, void* w, long n_floats);
 // modconv_tconv.hip: up-layer as the minimal stride-2 transposed convolution; writes the raw tensor
 // t [B][2H+1][2W+1][Co] (uses x, x_bstride, w (from launch_prep_tconv_weights), s, y, B, H, W, Ci, Co of ConvArgs)
 int launch_tconv2(hipStream_t stream, int dtype, const ConvArgs& a);
-constexpr int TCONV_EDGES_ONLY = 100;  // ConvArgs.variant: launch_tconv2 covers only the last row / column of positions
 // modconv_tconv_dma.hip: the main H x W block on LDS-direct loads; x already multiplied by the styles (bf16)
 bool tconv_dma_supported(int dtype, int Ci, int Co, int H, int W);
 int launch_tconv_dma(hipStream_t stream, const ConvArgs& a, int dtype = MAUA_BF16);

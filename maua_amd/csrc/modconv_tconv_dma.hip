@@ -302,7 +302,7 @@ bool tconv_dma_supported(int dtype, int Ci, int Co, int H, int W) {
 }
 
 // main H x W block of the position grid; a.x must already carry the styles.  The caller adds the last row / column with
-// launch_tconv2 (variant = TCONV_EDGES_ONLY, unit styles).
+// launch_tconv_edges.
 int launch_tconv_dma(hipStream_t stream, const ConvArgs& a, int dtype) {
   MAUA_REQUIRE(tconv_dma_supported(dtype, a.Ci, a.Co, a.H, a.W), "tconv_dma: unsupported shape");
   if (a.B == 0) return MAUA_OK;

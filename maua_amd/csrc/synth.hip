@@ -76,10 +76,10 @@ struct maua_synth {
                        // 128^2 2.33 -> 2.62, 64^2 1.89 -> 2.65: the 1.42x MACs pay only where the t round trip was HBM-bound.
   const float* nz_scales = nullptr;   // [num_layers][nz_scale_stride] per-sample noise factors (maua_synth_set_noise_scale) or NULL
   long nz_scale_stride = 0;
-  int tconv_min = 32;  // ... from this input size up (below: the phase kernels / the batch-wide low-resolution GEMM)
   int dma_conv = 1;    // conv1 layers behind such an up-layer: LDS-direct-load kernel on pre-modulated input (bf16 / f16)
   int dual_store = 1;  // ... whose toRGB is a separate pass (512 channels): plain + style-scaled output in one epilogue (no premod pass)
-  int tconv_dma = 2;   // the up-layers' transposed conv on LDS-direct loads (main block; pre-modulated input)
+  int tconv_dma = 1;   // the up-layers' transposed conv on LDS-direct loads (main block; pre-modulated input) + the dedicated
+                       // edge kernel for the last row / column (0: the register-staged transposed conv)
   float* ones = nullptr;   // [Bcap][max channels] unit styles (kernels that take already-modulated input)
   void* xm = nullptr;      // [Bcap] pre-modulated copy of an up-layer's input when its producer could not scale it
   void* tbuf = nullptr;  // [Bcap] transposed-conv tensor of the largest up-layer
@@ -98,7 +98,6 @@ struct maua_synth {
   // profile mode: HIP events recorded on the ctx stream around every launch of a forward
   int profile = 0;
   std::vector<hipEvent_t> ev;
-  std::vector<std::string> ev_names;
   size_t ev_used = 0;
   std::vector<size_t> ev_fwd_start;
   // workspace
@@ -109,7 +108,7 @@ struct maua_synth {
   float fir[16];
 };
 
-static void prof_mark(maua_synth* n, const char* name) {
+static void prof_mark(maua_synth* n) {
   if (!n->profile || n->ev_used >= (1u << 16)) return;
   if (n->ev_used == n->ev.size()) {
     hipEvent_t e;
@@ -117,10 +116,17 @@ static void prof_mark(maua_synth* n, const char* name) {
     n->ev.push_back(e);
   }
   hipEventRecord(n->ev[n->ev_used++], n->ctx->stream);
-  n->ev_names.push_back(name);
 }
 
 static int channels_for(int res, int base, int maxc) { return std::min(base / res, maxc); }
+
+// kernels a layer fits at its current grid (the forward's plan and the workspace sizing ask the same question)
+static bool lowres_fits(const maua_synth* n, const ConvLayer& c) {
+  return lowres_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw);
+}
+static bool tconv_dma_fits(const maua_synth* n, const ConvLayer& c) {
+  return c.up == 2 && tconv_dma_supported(n->dtype, c.Ci, c.Co, c.ih, c.iw);
+}
 
 // per-layer grids: native power-of-two sizes, scaled from the resized layer on
 static void compute_dims(maua_synth* n) {
@@ -142,43 +148,24 @@ static void compute_dims(maua_synth* n) {
   n->out_h = h; n->out_w = w;
 }
 
+template <typename T>
+static void release(T*& p) {  // (hipFree(NULL) is a no-op)
+  hipFree(p);
+  p = nullptr;
+}
+
 static int free_workspace(maua_synth* n) {
   for (auto& c : n->convs) {
-    if (c.s) hipFree(c.s);
-    if (c.d) hipFree(c.d);
-    if (c.feat) hipFree(c.feat);
-    c.s = c.d = nullptr;
-    c.feat = nullptr;
+    release(c.s); release(c.d); release(c.feat);
   }
   for (auto& r : n->rgbs) {
-    if (r.s) hipFree(r.s);
-    if (r.wmod) hipFree(r.wmod);
-    r.s = r.wmod = nullptr;
+    release(r.s); release(r.wmod);
   }
   for (int i = 0; i < 2; i++) {
-    if (n->act[i]) hipFree(n->act[i]);
-    if (n->img[i]) hipFree(n->img[i]);
-    n->act[i] = nullptr;
-    n->img[i] = nullptr;
+    release(n->act[i]); release(n->img[i]); release(n->rgb_tmp[i]);
   }
-  if (n->style_table_dev) hipFree(n->style_table_dev);
-  n->style_table_dev = nullptr;
-  if (n->tbuf) hipFree(n->tbuf);
-  n->tbuf = nullptr;
-  if (n->ones) hipFree(n->ones);
-  if (n->xm) hipFree(n->xm);
-  n->ones = nullptr;
-  n->xm = nullptr;
-  if (n->lowres_xm) hipFree(n->lowres_xm);
-  if (n->lowres_ws) hipFree(n->lowres_ws);
-  n->lowres_xm = nullptr;
-  n->lowres_ws = nullptr;
-  if (n->const_rs) hipFree(n->const_rs);
-  n->const_rs = nullptr;
-  for (int i = 0; i < 2; i++) {
-    if (n->rgb_tmp[i]) hipFree(n->rgb_tmp[i]);
-    n->rgb_tmp[i] = nullptr;
-  }
+  release(n->style_table_dev); release(n->tbuf); release(n->ones); release(n->xm);
+  release(n->lowres_xm); release(n->lowres_ws); release(n->const_rs);
   n->bcap = 0;
   return MAUA_OK;
 }
@@ -214,7 +201,7 @@ static int ensure_workspace(maua_synth* n, int B) {
   if (max_t) MAUA_HIP_CHECK(hipMalloc(&n->tbuf, (size_t)B * max_t * n->esize));
   size_t lx = 0, lw = 0;
   for (auto& c : n->convs)
-    if (lowres_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw)) {
+    if (lowres_fits(n, c)) {
       size_t x1, w1;
       lowres_workspace(n->dtype, B, c.ih, c.iw, c.Ci, c.Co, c.up, &x1, &w1);
       lx = std::max(lx, x1); lw = std::max(lw, w1);
@@ -226,7 +213,7 @@ static int ensure_workspace(maua_synth* n, int B) {
       maxc = std::max(maxc, std::max(c.Ci, c.Co));
       // (only the up-layers whose producer has no fused toRGB need the copy: inputs up to 64^2 at 1024^2 networks;
       //  sized for any up-layer so that hooks / options can fall back to it)
-      if (c.up == 2 && tconv_dma_supported(n->dtype, c.Ci, c.Co, c.ih, c.iw)) xm_elems = std::max(xm_elems, (size_t)c.ih * c.iw * c.Ci);
+      if (tconv_dma_fits(n, c)) xm_elems = std::max(xm_elems, (size_t)c.ih * c.iw * c.Ci);
     }
     std::vector<float> h1((size_t)B * maxc, 1.f);
     MAUA_HIP_CHECK(hipMalloc((void**)&n->ones, h1.size() * sizeof(float)));
@@ -257,6 +244,162 @@ static int ensure_workspace(maua_synth* n, int B) {
   MAUA_HIP_CHECK(hipMemcpy(n->style_table_dev, tab.data(), tab.size() * sizeof(StyleLayer), hipMemcpyHostToDevice));
   n->bcap = B;
   return MAUA_OK;
+}
+
+// ---- one forward: a plan (which kernel each layer takes; host only), then a launch loop that executes it
+
+// up-layers from this input size up run as a transposed conv (tconv_up = 1).  Measured: pays off from 32^2 inputs up; below, the
+// extra launch costs more than the MACs it saves (the phase kernels / the batch-wide low-resolution GEMM take those layers)
+constexpr int TCONV_MIN = 32;
+
+enum class Route : uint8_t {
+  Lowres,     // <= 8x8 inputs: one batch-wide split-K GEMM (modconv_lowres.hip)
+  Generic,    // modconv3x3 (up-layers: the four 3x3 phase kernels)
+  DmaConv1,   // conv1 on input its producer already multiplied by the styles, LDS-direct loads (modconv_dma.hip)
+  Hires,      // weights in registers (modconv_hires.hip; up-layers: the FIR-folded phase form)
+  Upwalk,     // the 64 -> 32 channel up-layer on the half-folded row walk (modconv_upwalk.hip)
+  FusedWalk,  // ... the whole last block as ONE walk: conv0 up -> conv1 -> toRGB + skip (-> u8)
+  WalkDone,   // conv1 of that block: nothing to launch
+  TconvFir,   // transposed conv + FIR + epilogue in one kernel, t stays in LDS (modconv_tconv_fir.hip)
+  TconvDma,   // transposed conv: edge kernel + main block on LDS-direct loads, then the FIR / epilogue pass (t through HBM)
+  Tconv2,     // transposed conv on the register-staged kernel, then the FIR / epilogue pass
+};
+// who multiplies a layer's input by its styles: its own kernel, the producing layer's epilogue, the producer's second store
+// into the premod buffer (dual store), or a premod pass in front of the layer
+enum class Src : uint8_t { Kernel, Producer, Xm, PremodPass };
+enum class RgbRoute : uint8_t { Separate, Fused, Hook };  // a block's toRGB: own launch, in a conv epilogue, around a resize
+
+struct Step {
+  Route route = Route::Generic;
+  Src src = Src::Kernel;
+  bool scale_next = false;  // the epilogue stores the output multiplied by the next layer's styles ...
+  bool dual = false;        // ... into the premod buffer, next to the plain output (dual store)
+  bool rgb = false;         // the block's toRGB + skip ride on the epilogue
+  bool rgb8 = false;        // ... and so does the u8 pack of the final frame
+  bool skip_store = false;  // the features are not stored (nothing but the fused toRGB reads them)
+};
+struct Plan {
+  std::vector<Step> conv;     // per conv layer
+  std::vector<RgbRoute> rgb;  // per block
+  bool pack = false;          // the u8 frame is packed by its own launch
+};
+
+// does a warp hook replace the output of layer k (1-based, as in maua_synth_set_warp)?
+static bool layer_warped(const maua_synth* n, int k) {
+  for (int s = 0; s < 3; s++)
+    if (n->warp_layer[s] == k && n->warp_minv[s]) return true;
+  return false;
+}
+
+// the route of a layer whose producer did not multiply its input by its styles
+static Route base_route(const maua_synth* n, const ConvLayer& c) {
+  const bool hires_ok = n->use_hires && hires_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw);
+  if (c.up == 2 && n->tconv_up) {
+    // minimal up-layer: t = conv_transpose2d(x*s, W, stride 2) on the matrix cores, then FIR + epilogue.  tconv_up = 1: inputs
+    // TCONV_MIN^2 .. 512^2, except where the register-stationary kernel exists (bf16 64 -> 32 channels, the 1024^2 layer): its
+    // FIR-folded phase form beats tconv + upfir, whose t round trip is HBM-bound there (1.33 vs 1.56 ms at B = 32);
+    // tconv_up = v > 1: every up-layer with inputs up to v
+    const int hin = std::min(c.ih, c.iw), hmax = std::max(c.ih, c.iw);
+    const bool dflt = n->tconv_up == 1;
+    if (!(dflt && hires_ok) && hin >= (dflt ? TCONV_MIN : 1) && hmax <= (dflt ? 512 : n->tconv_up)) {
+      if (!dflt || !n->tconv_dma || !tconv_dma_fits(n, c)) return Route::Tconv2;
+      return n->tconv_fir > 0 && hin >= n->tconv_fir && tconv_fir_supported(n->dtype, c.Ci, c.Co, c.ih, c.iw) ? Route::TconvFir
+                                                                                                           : Route::TconvDma;
+    }
+  }
+  if (hires_ok) return Route::Hires;
+  return n->lowres && lowres_fits(n, c) ? Route::Lowres : Route::Generic;
+}
+static bool reads_premod(Route r) { return r == Route::TconvFir || r == Route::TconvDma; }  // x must carry the styles
+
+// Every launch of the next forward, decided from the net's state alone (shapes, dtype, options, hooks, feature capture, the
+// premod buffer) and from whether the caller wants u8 frames.  No HIP calls.
+static Plan plan_forward(const maua_synth* n, bool want_u8) {
+  const size_t L = n->convs.size();
+  Plan p;
+  p.conv.resize(L);
+  p.rgb.assign(n->nblocks, RgbRoute::Separate);
+  p.pack = want_u8;
+  for (size_t li = 0; li < L; li++) {
+    const ConvLayer& c = n->convs[li];
+    Step& s = p.conv[li];
+    const int k = (int)li + 1;  // hook index of this layer's output
+    const bool last = c.block == n->nblocks - 1;
+    const bool hooked = n->rs_layer == k;
+    const bool warped = layer_warped(n, k);  // a translate / zoom / rotate hook replaces the output before toRGB reads it
+    const bool rs_block = n->rs_layer >= 1 && n->convs[n->rs_layer - 1].block == c.block;  // toRGB takes the hook path
+    const bool fuse_rgb_ok = c.which == 1 && n->fuse_torgb && !rs_block && !warped;
+    // only the next layer reads this output, unchanged (its input grid is then this layer's output grid)
+    const bool private_out = !hooked && !warped && !n->keep_features && li + 1 < L;
+    const bool next_replaced = n->rs_layer == k + 1 || layer_warped(n, k + 1);
+    const ConvLayer* nx = private_out ? &n->convs[li + 1] : nullptr;
+    s.route = base_route(n, c);
+    if (c.up == 1 && s.src == Src::Producer) s.route = Route::DmaConv1;
+    if (li > 0 && p.conv[li - 1].route == Route::FusedWalk) s.route = Route::WalkDone;  // (a Hires conv1)
+    switch (s.route) {
+      case Route::DmaConv1:
+        s.rgb = fuse_rgb_ok && dma_rgb_fusable(c.Co) && c.ih % 2 == 0 && c.iw % 2 == 0;
+        // the up-layer that follows takes pre-modulated input: with the block's toRGB fused here nothing else reads these
+        // features, so they are stored already multiplied by its styles; (round 5) the 512-channel conv1 layers keep a separate
+        // toRGB pass, which reads the PLAIN features: stored twice - plain to y, scaled into the premod buffer
+        if (nx && reads_premod(base_route(n, *nx))) {
+          if (s.rgb) {
+            s.scale_next = true;
+            p.conv[li + 1].src = Src::Producer;
+          } else if (n->dual_store && n->xm && !next_replaced) {
+            s.scale_next = s.dual = true;
+            p.conv[li + 1].src = Src::Xm;
+          }
+        }
+        break;
+      case Route::Hires:
+      case Route::WalkDone:
+        if (fuse_rgb_ok) {  // conv1: the block's toRGB + skip ride on the epilogue tile, in the last block the u8 pack too
+          s.rgb = true;
+          s.rgb8 = last && want_u8;
+          s.skip_store = last && !n->keep_features && !hooked;  // the last block's features have no other reader
+        }
+        // the 64 -> 32 up-layer: half the matrix work of the phase form; the last block as one walk when nothing else reads
+        // its features (no hooks, no feature capture): they never reach HBM
+        if (s.route == Route::Hires && c.up == 2 && n->upwalk && c.wt_h &&
+            upwalk_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw)) {
+          s.route = Route::Upwalk;
+          if (n->upwalk >= 2 && last && nx && n->fuse_torgb && !rs_block && !next_replaced &&
+              upwalk_fused_supported(n->dtype, c.Ci, c.Co, c.ih, c.iw)) {
+            s.route = Route::FusedWalk;
+            s.skip_store = true;
+          }
+        }
+        break;
+      case Route::Generic:
+        s.rgb = fuse_rgb_ok && modconv_rgb_fusable(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw);
+        [[fallthrough]];
+      case Route::TconvFir:
+      case Route::TconvDma:
+      case Route::Tconv2:
+        if (reads_premod(s.route) && s.src == Src::Kernel) s.src = Src::PremodPass;
+        // an up-layer whose conv1 takes pre-modulated input (modconv_dma.hip) multiplies its output by that layer's styles
+        if (c.up == 2 && n->dma_conv && nx && dma_conv_supported(n->dtype, nx->Ci, nx->Co, nx->up, nx->ih, nx->iw)) {
+          s.scale_next = true;
+          p.conv[li + 1].src = Src::Producer;
+        }
+        break;
+      default:
+        break;
+    }
+    if (s.rgb) p.rgb[c.block] = RgbRoute::Fused;
+    if (rs_block) p.rgb[c.block] = RgbRoute::Hook;
+    if (s.rgb8) p.pack = false;
+  }
+  return p;
+}
+
+template <typename A>  // ConvArgs / HiresArgs / UpfirArgs
+static void lrelu_epilogue(A& a) {
+  a.act = MAUA_ACT_LRELU;
+  a.alpha = 0.2f;
+  a.gain = std::sqrt(2.0f);
+  a.clamp = 256.f;
 }
 
 extern "C" {
@@ -430,56 +573,7 @@ int maua_synth_set_option(maua_synth* n, const char* key, int value) {
   if (!strcmp(key, "profile")) {
     n->profile = value;
     n->ev_used = 0;
-    n->ev_names.clear();
     n->ev_fwd_start.clear();
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "lowres")) {
-    n->lowres = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "use_hires")) {
-    n->use_hires = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "upwalk")) {
-    n->upwalk = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "dual_store")) {
-    n->dual_store = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "walk_segs")) {
-    n->walk_segs = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "walk_narrow")) {
-    n->walk_narrow = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "tconv_min")) {
-    n->tconv_min = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "tconv_fir")) {
-    n->tconv_fir = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "tconv_up")) {
-    n->tconv_up = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "tconv_dma")) {
-    n->tconv_dma = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "dma_conv")) {
-    n->dma_conv = value;
-    return MAUA_OK;
-  }
-  if (!strcmp(key, "fuse_torgb")) {
-    n->fuse_torgb = value;
     return MAUA_OK;
   }
   if (!strcmp(key, "keep_features")) {
@@ -490,6 +584,17 @@ int maua_synth_set_option(maua_synth* n, const char* key, int value) {
     }
     return MAUA_OK;
   }
+  // kernel routing (read by the next forward's plan)
+  static const std::pair<const char*, int maua_synth::*> routing[] = {
+      {"lowres", &maua_synth::lowres},         {"use_hires", &maua_synth::use_hires}, {"upwalk", &maua_synth::upwalk},
+      {"walk_segs", &maua_synth::walk_segs},   {"walk_narrow", &maua_synth::walk_narrow},
+      {"fuse_torgb", &maua_synth::fuse_torgb}, {"tconv_up", &maua_synth::tconv_up},   {"tconv_fir", &maua_synth::tconv_fir},
+      {"tconv_dma", &maua_synth::tconv_dma},   {"dma_conv", &maua_synth::dma_conv},   {"dual_store", &maua_synth::dual_store}};
+  for (const auto& o : routing)
+    if (!strcmp(key, o.first)) {
+      n->*o.second = value;
+      return MAUA_OK;
+    }
   return fail(std::string("maua_synth_set_option: unknown option ") + key);
 }
 
@@ -599,14 +704,6 @@ int maua_synth_load_device(maua_synth* n, const char* name, const float* dev, si
   return rc;
 }
 
-// does this up-layer run the LDS-direct transposed-conv kernel?  (same routing conditions as in the forward below)
-static bool up_uses_tconv_dma(const maua_synth* n, const ConvLayer& c) {
-  if (!n->tconv_dma || n->tconv_up != 1 || c.up != 2) return false;
-  const bool hires_up = n->use_hires && hires_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw);
-  const int hin = std::min(c.ih, c.iw), hmax = std::max(c.ih, c.iw);
-  return !hires_up && hin >= n->tconv_min && hmax <= 512 && tconv_dma_supported(n->dtype, c.Ci, c.Co, c.ih, c.iw);
-}
-
 int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* noise, const long* noise_bstride, int B,
                            float* img_out, uint8_t* rgb8_out) {
   MAUA_REQUIRE(n && ws, "maua_synth_forward: NULL argument");
@@ -617,16 +714,18 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
   MAUA_REQUIRE(img_out || rgb8_out, "maua_synth_forward: no output buffer");
   if (B == 0) return MAUA_OK;
   if (int rc = ensure_workspace(n, B)) return rc;
+  const Plan plan = plan_forward(n, rgb8_out != nullptr);
   hipStream_t st = n->ctx->stream;
   const int ntab = (int)(n->convs.size() + n->rgbs.size());
   int max_c = 0;
   for (auto& c : n->convs) max_c = std::max(max_c, std::max(c.Ci, c.Co));
-  // events accumulate across forwards until maua_synth_get_profile() reads and resets them
+  // events accumulate across forwards until maua_synth_get_profile() reads and resets them.  Slots: styles, one per conv layer
+  // (two for the transposed-conv routes), toRGB per block, the u8 pack; a hook's launches land in the slot that follows
   if (n->profile) n->ev_fwd_start.push_back(n->ev_used);
-  prof_mark(n, "begin");
+  prof_mark(n);
   if (int rc = launch_styles(st, n->style_table_dev, ntab, ws, n->num_ws, n->w_dim, B, max_c, n->dtype == MAUA_F16)) return rc;
 
-  prof_mark(n, "styles");
+  prof_mark(n);
   const void* x = n->const_x;
   long x_bstride = 0;
   int cur = 0;
@@ -641,240 +740,116 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
     if (int rc = resize_feat(n->const_x, 0, 1, 4, 4, n->convs[0].Ci, n->const_rs)) return rc;
     x = n->const_rs;
   }
+  auto set_noise = [&](auto& a, size_t li) {  // (ConvArgs / HiresArgs / UpfirArgs)
+    const ConvLayer& c = n->convs[li];
+    const bool given = noise && noise[li];
+    a.noise = given ? noise[li] : c.noise_const;
+    a.noise_bstride = given ? (noise_bstride ? noise_bstride[li] : (long)c.oh * c.ow) : 0;
+    a.noise_strength = (n->nv_compat & 2) ? c.noise_strength : 1.f;
+    // (un-normalised Loop maps: the factor 1 / (rms + eps) of each sample rides on the noise strength; only with caller-supplied maps)
+    a.noise_scale = (n->nz_scales && given) ? n->nz_scales + (long)li * n->nz_scale_stride : nullptr;
+  };
+  auto layer_args = [&](auto a, size_t li, const void* in, void* out) {  // what every modulated 3x3 launch shares (ConvArgs / HiresArgs)
+    const ConvLayer& c = n->convs[li];
+    a.x = in; a.w = c.wt; a.s = c.s; a.d = c.d; a.bias = c.bias; a.y = out;
+    a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = c.up;
+    set_noise(a, li);
+    lrelu_epilogue(a);
+    return a;
+  };
+  auto pack_u8 = [&](HiresArgs& a) {  // the final frame packed to u8 in the same epilogue
+    a.rgb8_out = rgb8_out;
+    a.rgb_skip_f32 = img_out == nullptr;  // (nobody reads the f32 image)
+  };
   const float* prev_img = nullptr;
   int img_cur = 0;
   size_t li = 0;
-  bool rgb8_done = false;
-  bool walk_skip = false;      // the previous up-layer ran the whole block (modconv_upwalk.hip): its conv1 is done
-  bool x_premod = false;       // the current x already carries the styles of the conv1 that reads it (modconv_dma.hip)
-  bool premod_for_up = false;  // ... of the up-layer that reads it (modconv_tconv_dma.hip)
-  bool premod_in_xm = false;   // ... or the premod buffer already holds x times that up-layer's styles (dual store of the conv1 before it)
   for (int blk = 0; blk < n->nblocks; blk++) {
     const int nconv = blk == 0 ? 1 : 2;
-    RgbLayer& g = n->rgbs[blk];
-    const bool last = blk == n->nblocks - 1;
-    float* rgb_out = (last && img_out) ? img_out : n->img[img_cur];
-    bool rgb_fused = false;
+    const RgbLayer& g = n->rgbs[blk];
+    float* rgb_out = (blk == n->nblocks - 1 && img_out) ? img_out : n->img[img_cur];
+    auto fuse_torgb = [&](auto& a) {  // the block's toRGB + skip in the epilogue (ConvArgs / HiresArgs)
+      a.rgb_wmod = g.wmod; a.rgb_bias = g.bias; a.rgb_prev = prev_img; a.rgb_out = rgb_out; a.rgb_clamp = 256.f;
+      memcpy(a.fir, n->fir, sizeof(a.fir));
+    };
     for (int k = 0; k < nconv; k++, li++) {
-      ConvLayer& c = n->convs[li];
-      const float* nz = (noise && noise[li]) ? noise[li] : c.noise_const;
-      const long nz_stride = (noise && noise[li]) ? (noise_bstride ? noise_bstride[li] : (long)c.oh * c.ow) : 0;
-      const float nz_strength = (n->nv_compat & 2) ? c.noise_strength : 1.f;
-      // (un-normalised Loop maps: the factor 1 / (rms + eps) of each sample rides on the noise strength; only with caller-supplied maps)
-      const float* nz_scale = (n->nz_scales && noise && noise[li]) ? n->nz_scales + (long)li * n->nz_scale_stride : nullptr;
+      const ConvLayer& c = n->convs[li];
+      const Step& s = plan.conv[li];
       const bool hooked = n->rs_layer == (int)li + 1;  // this layer's output is resized before anything reads it
-      void* y = hooked ? n->act[cur] : n->keep_features ? c.feat : n->act[cur];
-      const int hin = std::min(c.ih, c.iw), hin_max = std::max(c.ih, c.iw);
-      const int tconv_max = n->tconv_up == 1 ? 512 : n->tconv_up;  // option value > 1 = largest input size routed
-      // (default routing: where the register-stationary kernel exists (bf16 64 -> 32 channels, the 1024^2 layer) its
-      //  FIR-folded phase form beats tconv + upfir, whose t round trip is HBM-bound there: 1.33 vs 1.56 ms at B = 32)
-      const bool hires_up = c.up == 2 && n->tconv_up == 1 && n->use_hires &&
-                            hires_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw);
-      const bool via_tconv = c.up == 2 && n->tconv_up && !hires_up && hin >= (n->tconv_up == 1 ? n->tconv_min : 1) &&
-                             hin_max <= tconv_max;
-      const bool rs_block = n->rs_layer >= 1 && n->convs[n->rs_layer - 1].block == blk;  // toRGB needs the hook path
-      // a translate / zoom / rotate hook on this layer replaces its output before toRGB reads it: no fused toRGB then
-      bool warped = false;
-      for (int wsl = 0; wsl < 3; wsl++) warped = warped || (n->warp_layer[wsl] == (int)li + 1 && n->warp_minv[wsl]);
-      const bool fuse_rgb_ok = c.which == 1 && n->fuse_torgb && !rs_block && !warped;
-      // does the conv1 that follows this up-layer take pre-modulated input?  (then the epilogue below multiplies the
-      // output by that layer's styles; nothing else reads an up-layer's output)
-      const bool premod_in = x_premod;
-      x_premod = false;
-      const bool premod_up_in = premod_for_up;   // x carries this up-layer's styles (set by the conv1 that produced it)
-      premod_for_up = false;
-      const bool xm_ready = premod_in_xm;        // ... or that conv1 wrote the scaled copy into the premod buffer
-      premod_in_xm = false;
-      bool premod_out = false;
-      // (producers that can scale their output: the FIR pass of a tconv up-layer, the generic kernel's epilogue)
-      const bool generic_up = c.up == 2 && !via_tconv && !hires_up &&
-                              !(n->lowres && lowres_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw));
-      if ((via_tconv || generic_up) && n->dma_conv && !hooked && !warped && !n->keep_features && c.which == 0 &&
-          li + 1 < n->convs.size()) {
-        const ConvLayer& nx = n->convs[li + 1];
-        premod_out = nx.block == blk && dma_conv_supported(n->dtype, nx.Ci, nx.Co, nx.up, nx.ih, nx.iw);
-      }
-      if (premod_in) {
-        ConvArgs a{};
-        a.x = x; a.x_bstride = x_bstride; a.w = c.wt; a.s = nullptr; a.d = c.d;
-        a.noise = nz; a.noise_bstride = nz_stride; a.noise_strength = nz_strength; a.noise_scale = nz_scale;
-        a.bias = c.bias; a.y = y;
-        a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = 1;
-        a.act = MAUA_ACT_LRELU; a.alpha = 0.2f; a.gain = std::sqrt(2.0f); a.clamp = 256.f;
-        if (fuse_rgb_ok && dma_rgb_fusable(c.Co) && (c.ih % 2) == 0 && (c.iw % 2) == 0) {
-          a.rgb_wmod = g.wmod; a.rgb_bias = g.bias; a.rgb_prev = prev_img; a.rgb_out = rgb_out; a.rgb_clamp = 256.f;
-          memcpy(a.fir, n->fir, sizeof(a.fir));
-          rgb_fused = true;
+      void* y = n->keep_features && !hooked ? c.feat : n->act[cur];
+      const float* next_s = s.scale_next ? n->convs[li + 1].s : nullptr;
+      switch (s.route) {
+        case Route::Lowres:
+        case Route::Generic:
+        case Route::DmaConv1: {
+          ConvArgs a = layer_args(ConvArgs{}, li, x, y);
+          a.x_bstride = x_bstride;
+          a.out_scale = next_s;
+          if (s.dual) a.y_scaled = n->xm;
+          if (s.rgb) fuse_torgb(a);
+          if (s.route == Route::DmaConv1) a.s = nullptr;  // (the input carries the styles)
+          if (int rc = s.route == Route::Lowres    ? launch_modconv_lowres(st, n->dtype, a, n->lowres_xm, n->lowres_ws)
+                       : s.route == Route::Generic ? launch_modconv3x3(st, n->dtype, a)
+                                                   : launch_modconv_dma(st, a, n->dtype))
+            return rc;
+          break;
         }
-        // the up-layer that follows reads only these features (the block's toRGB is fused right here): store them
-        // already multiplied by its styles when it runs the LDS-direct transposed-conv kernel
-        if (rgb_fused && !hooked && !warped && !n->keep_features && li + 1 < n->convs.size()) {
-          const ConvLayer& nx = n->convs[li + 1];
-          if (nx.up == 2 && up_uses_tconv_dma(n, nx)) {
-            a.out_scale = nx.s;
-            premod_for_up = true;
+        case Route::Hires:
+        case Route::Upwalk:
+        case Route::FusedWalk: {
+          HiresArgs a = layer_args(HiresArgs{}, li, x, s.skip_store ? nullptr : y);
+          if (s.rgb) fuse_torgb(a);
+          if (s.rgb8) pack_u8(a);
+          if (s.route != Route::Hires) a.w = c.wt_h;  // (the half-folded weights)
+          if (s.route != Route::FusedWalk) {
+            if (int rc = s.route == Route::Hires ? launch_modconv_hires(st, a, n->dtype) : launch_upwalk(st, a, n->dtype)) return rc;
+            break;
           }
-        } else if (!rgb_fused && n->dual_store && n->xm && !hooked && !warped && !n->keep_features && li + 1 < n->convs.size()) {
-          // (round 5) the 512-channel conv1 layers keep a separate toRGB pass, which reads the PLAIN features: they are stored
-          // twice - plain to y, multiplied by the next up-layer's styles into the premod buffer - instead of a pass over y later
-          const ConvLayer& nx = n->convs[li + 1];
-          bool warped_nx = n->rs_layer == (int)li + 2;
-          for (int wsl = 0; wsl < 3; wsl++) warped_nx = warped_nx || (n->warp_layer[wsl] == (int)li + 2 && n->warp_minv[wsl]);
-          if (nx.up == 2 && up_uses_tconv_dma(n, nx) && nx.ih == c.oh && nx.iw == c.ow && !warped_nx && n->rs_layer != (int)li + 1) {
-            a.out_scale = nx.s;
-            a.y_scaled = n->xm;
-            premod_in_xm = true;
-          }
+          HiresArgs f = layer_args(HiresArgs{}, li + 1, nullptr, nullptr);  // the block's conv1 + toRGB (+ u8)
+          fuse_torgb(f);
+          if (plan.conv[li + 1].rgb8) pack_u8(f);
+          if (int rc = launch_upwalk_fused(st, a, f, n->walk_segs, n->walk_narrow, n->dtype)) return rc;
+          break;
         }
-        if (int rc = launch_modconv_dma(st, a, n->dtype)) return rc;
-      } else if (!via_tconv && n->use_hires && hires_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw)) {
-        HiresArgs a{};
-        a.x = x; a.w = c.wt; a.s = c.s; a.d = c.d; a.noise = nz; a.noise_bstride = nz_stride;
-        a.noise_strength = nz_strength; a.noise_scale = nz_scale; a.bias = c.bias; a.y = y;
-        a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = c.up;
-        a.act = MAUA_ACT_LRELU; a.alpha = 0.2f; a.gain = std::sqrt(2.0f); a.clamp = 256.f;
-        if (fuse_rgb_ok) {  // conv1: the block's toRGB + skip rides on the epilogue tile
-          a.rgb_wmod = g.wmod; a.rgb_bias = g.bias; a.rgb_prev = prev_img; a.rgb_out = rgb_out; a.rgb_clamp = 256.f;
-          memcpy(a.fir, n->fir, sizeof(a.fir));
-          rgb_fused = true;
-          if (last && rgb8_out) {  // the u8 frame is packed in the same epilogue
-            a.rgb8_out = rgb8_out;
-            a.rgb_skip_f32 = img_out == nullptr;
-            rgb8_done = true;
-          }
-          // the last block's features have no reader besides the toRGB fused here: skip their HBM store
-          if (last && !n->keep_features && !hooked) a.y = nullptr;
-        }
-        if (walk_skip) {
-          // (conv1 of a block that ran as one fused walk: nothing left to launch)
-          rgb_fused = true;
-          rgb8_done = rgb8_done || (last && rgb8_out);
-          walk_skip = false;
-        } else if (c.up == 2 && n->upwalk && c.wt_h && !fuse_rgb_ok &&
-                   upwalk_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw)) {  // half the matrix work of the phase form
-          a.w = c.wt_h;
-          // the last block as ONE walk (conv0 up -> conv1 -> toRGB + skip -> image / u8): when nothing else reads its
-          // features (no hooks, no feature capture) they never reach HBM
-          bool fused_walk = false;
-          if (n->upwalk >= 2 && last && li + 1 < n->convs.size() && !hooked && !warped && !n->keep_features &&
-              n->fuse_torgb && !rs_block) {
-            ConvLayer& c1 = n->convs[li + 1];
-            bool warped1 = n->rs_layer == (int)li + 2;
-            for (int wsl = 0; wsl < 3; wsl++) warped1 = warped1 || (n->warp_layer[wsl] == (int)li + 2 && n->warp_minv[wsl]);
-            if (c1.block == blk && c1.up == 1 && c1.Ci == c.Co && c1.Co == c.Co && c1.ih == c.oh && c1.iw == c.ow &&
-                !warped1 && upwalk_fused_supported(n->dtype, c.Ci, c.Co, c.ih, c.iw)) {
-              const float* nz1 = (noise && noise[li + 1]) ? noise[li + 1] : c1.noise_const;
-              HiresArgs f{};
-              f.x = nullptr; f.w = c1.wt; f.s = c1.s; f.d = c1.d; f.noise = nz1;
-              f.noise_bstride = (noise && noise[li + 1]) ? (noise_bstride ? noise_bstride[li + 1] : (long)c1.oh * c1.ow) : 0;
-              f.noise_strength = (n->nv_compat & 2) ? c1.noise_strength : 1.f;
-              f.noise_scale = (n->nz_scales && noise && noise[li + 1]) ? n->nz_scales + (long)(li + 1) * n->nz_scale_stride : nullptr;
-              f.bias = c1.bias; f.y = nullptr;
-              f.B = B; f.H = c1.ih; f.W = c1.iw; f.Ci = c1.Ci; f.Co = c1.Co; f.up = 1;
-              f.act = MAUA_ACT_LRELU; f.alpha = 0.2f; f.gain = std::sqrt(2.0f); f.clamp = 256.f;
-              f.rgb_wmod = g.wmod; f.rgb_bias = g.bias; f.rgb_prev = prev_img; f.rgb_out = rgb_out; f.rgb_clamp = 256.f;
-              memcpy(f.fir, n->fir, sizeof(f.fir));
-              if (rgb8_out) {
-                f.rgb8_out = rgb8_out;
-                f.rgb_skip_f32 = img_out == nullptr;
-              }
-              a.y = nullptr;
-              if (int rc = launch_upwalk_fused(st, a, f, n->walk_segs, n->walk_narrow, n->dtype)) return rc;
-              fused_walk = true;
-              walk_skip = true;
-            }
-          }
-          if (!fused_walk)
-            if (int rc = launch_upwalk(st, a, n->dtype)) return rc;
-        } else if (int rc = launch_modconv_hires(st, a, n->dtype)) {
-          return rc;
-        }
-      } else if (via_tconv) {
-        // (measured: pays off from 32^2 inputs up; below, the extra launch costs more than the MACs it saves,
-        //  a tconv_up value > 1 sets the largest routed input size)
-        // minimal up-layer: t = conv_transpose2d(x*s, W, stride 2) on the matrix cores, then FIR + epilogue
-        ConvArgs a{};
-        a.x = x; a.x_bstride = x_bstride; a.w = c.wt_t; a.s = c.s; a.d = nullptr; a.noise = nullptr; a.bias = nullptr;
-        a.y = n->tbuf; a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = 2;
-        bool up_fused = false;
-        if (up_uses_tconv_dma(n, c)) {
-          // main block on the LDS-direct kernel (input already multiplied by the styles: by the producing conv1, or by
-          // a pass over the - small - input here), last row / column of positions on the register-staged kernel
-          if (xm_ready) {          // the producing conv1 left the scaled copy in the premod buffer
-            a.x = n->xm;
-            a.x_bstride = (long)c.ih * c.iw * c.Ci;
-          } else if (!premod_up_in) {
+        case Route::WalkDone:
+          break;
+        case Route::TconvFir:
+        case Route::TconvDma:
+        case Route::Tconv2: {
+          ConvArgs a{};
+          a.x = x; a.x_bstride = x_bstride; a.w = c.wt_t; a.s = c.s; a.y = n->tbuf;
+          a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = 2;
+          UpfirArgs u{};
+          u.y = y; u.d = c.d; u.bias = c.bias; u.out_scale = next_s; u.B = B; u.H = c.ih; u.W = c.iw; u.Co = c.Co;
+          set_noise(u, li);
+          lrelu_epilogue(u);
+          if (s.src == Src::PremodPass)  // (the input is small: inputs up to 64^2 at 1024^2 networks)
             if (int rc = launch_premod_nhwc(st, x, x_bstride, c.s, n->xm, B, (long)c.ih * c.iw, c.Ci, n->dtype)) return rc;
+          if (s.src == Src::PremodPass || s.src == Src::Xm) {
             a.x = n->xm;
             a.x_bstride = (long)c.ih * c.iw * c.Ci;
           }
-          a.s = n->ones;
-          if (n->tconv_fir > 0 && hin >= n->tconv_fir && tconv_fir_supported(n->dtype, c.Ci, c.Co, c.ih, c.iw)) {
-            // the whole layer in one kernel: t never leaves LDS (bit-identical output)
-            UpfirArgs u{};
-            u.y = y; u.d = c.d; u.noise = nz; u.noise_bstride = nz_stride; u.noise_strength = nz_strength; u.noise_scale = nz_scale;
-            u.bias = c.bias; u.B = B; u.H = c.ih; u.W = c.iw; u.Co = c.Co;
-            if (premod_out) {
-              u.out_scale = n->convs[li + 1].s;
-              x_premod = true;
-            }
-            u.act = MAUA_ACT_LRELU; u.alpha = 0.2f; u.gain = std::sqrt(2.0f); u.clamp = 256.f;
+          if (reads_premod(s.route)) a.s = n->ones;
+          if (s.route == Route::TconvFir) {  // the whole layer in one kernel: t never leaves LDS (bit-identical output)
             if (int rc = launch_tconv_fir(st, a, u, n->dtype)) return rc;
-            prof_mark(n, "conv0_tconv");   // (two profile slots like the two-launch path: the second measures ~0)
-            up_fused = true;
+            prof_mark(n);  // (two profile slots like the two-launch path: the second measures ~0)
+            break;
           }
-          // (the thin edges first, the main block behind them; running the edges on a side stream beside the main block
-          //  measured no different: 8.06 vs 8.08 ms per forward)
-          if (up_fused) {
-          } else if (n->tconv_dma >= 2) {          // dedicated edge kernel (3 of 9 weight blocks, no tile waste)
+          if (s.route == Route::TconvDma) {
+            // the thin edges first (3 of 9 weight blocks, no tile waste), the main block behind them; running the edges on a
+            // side stream beside the main block measured no different: 8.06 vs 8.08 ms per forward
             if (int rc = launch_tconv_edges(st, a, n->dtype)) return rc;
-          } else {
-            ConvArgs e = a;
-            e.variant = TCONV_EDGES_ONLY;
-            if (int rc = launch_tconv2(st, n->dtype, e)) return rc;
-          }
-          a.variant = 0;
-          if (!up_fused)
             if (int rc = launch_tconv_dma(st, a, n->dtype)) return rc;
-        } else if (int rc = launch_tconv2(st, n->dtype, a)) {
-          return rc;
-        }
-        if (!up_fused) {
-        prof_mark(n, "conv0_tconv");  // (profile mode: this up-layer occupies two slots)
-        UpfirArgs u{};
-        u.t = n->tbuf; u.y = y; u.d = c.d; u.noise = nz; u.noise_bstride = nz_stride; u.noise_strength = nz_strength; u.noise_scale = nz_scale;
-        u.bias = c.bias; u.B = B; u.H = c.ih; u.W = c.iw; u.Co = c.Co;
-        if (premod_out) {
-          u.out_scale = n->convs[li + 1].s;
-          x_premod = true;
-        }
-        u.act = MAUA_ACT_LRELU; u.alpha = 0.2f; u.gain = std::sqrt(2.0f); u.clamp = 256.f;
-        if (int rc = launch_upfir_epilogue(st, n->dtype, u)) return rc;
-        }
-      } else {
-        ConvArgs a{};
-        a.x = x; a.x_bstride = x_bstride; a.w = c.wt; a.s = c.s; a.d = c.d;
-        a.noise = nz; a.noise_bstride = nz_stride; a.noise_strength = nz_strength; a.noise_scale = nz_scale;
-        a.bias = c.bias; a.y = y;
-        a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = c.up;
-        a.act = MAUA_ACT_LRELU; a.alpha = 0.2f; a.gain = std::sqrt(2.0f); a.clamp = 256.f;
-        if (n->lowres && lowres_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw)) {
-          // <= 8x8 input pixels: one GEMM over all samples, split-K (modconv_lowres.hip)
-          if (int rc = launch_modconv_lowres(st, n->dtype, a, n->lowres_xm, n->lowres_ws)) return rc;
-        } else {
-        if (premod_out) {
-          a.out_scale = n->convs[li + 1].s;
-          x_premod = true;
-        }
-        if (fuse_rgb_ok && modconv_rgb_fusable(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw)) {  // the block's toRGB + skip in the epilogue
-          a.rgb_wmod = g.wmod; a.rgb_bias = g.bias; a.rgb_prev = prev_img; a.rgb_out = rgb_out; a.rgb_clamp = 256.f;
-          memcpy(a.fir, n->fir, sizeof(a.fir));
-          rgb_fused = true;
-        }
-        if (int rc = launch_modconv3x3(st, n->dtype, a)) return rc;
+          } else if (int rc = launch_tconv2(st, n->dtype, a)) {
+            return rc;
+          }
+          prof_mark(n);  // (profile mode: this up-layer occupies two slots)
+          u.t = n->tbuf;
+          if (int rc = launch_upfir_epilogue(st, n->dtype, u)) return rc;
+          break;
         }
       }
-      prof_mark(n, c.which == 0 ? "conv0" : "conv1");
+      prof_mark(n);
       x = y;
       x_bstride = (long)c.oh * c.ow * c.Co;
       cur ^= 1;
@@ -898,48 +873,44 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
         }
       }
     }
-    const bool rs_here = n->rs_layer >= 1 && n->convs[n->rs_layer - 1].block == blk;
-    if (rs_here) {
-      // the reference's rgb_hook / img_hook around the resized block (get_hook :325-338): toRGB runs on the resized
+    if (plan.rgb[blk] != RgbRoute::Fused) {
+      // around the resized block, the reference's rgb_hook / img_hook (get_hook :325-338): toRGB runs on the resized
       // features, its output goes back to the layer's native grid (bicubic back / crop), joins the skip image there,
       // and the block's image is resized forward again (no fill noise on images)
-      const ConvLayer& hc = n->convs[n->rs_layer - 1];
-      const int nh = hc.oh, nw = hc.ow;  // native grid of the block
+      const bool hook = plan.rgb[blk] == RgbRoute::Hook;
       RgbArgs r{};
-      r.x = x; r.wmod = g.wmod; r.bias = g.bias; r.prev = nullptr;
-      r.out = n->rgb_tmp[0]; r.B = B; r.H = g.h; r.W = g.w; r.C = g.C; r.clamp = 256.f;
+      r.x = x; r.wmod = g.wmod; r.bias = g.bias; r.prev = hook ? nullptr : prev_img;
+      r.out = hook ? n->rgb_tmp[0] : rgb_out; r.B = B; r.H = g.h; r.W = g.w; r.C = g.C; r.clamp = 256.f;
       memcpy(r.fir, n->fir, sizeof(r.fir));
       if (int rc = launch_torgb(st, n->dtype, r)) return rc;
-      ResizeArgs inv{};
-      inv.x = n->rgb_tmp[0]; inv.x_bstride = 3L * g.h * g.w; inv.y = n->rgb_tmp[1]; inv.B = B; inv.H = g.h; inv.W = g.w;
-      inv.C = 3; inv.oh = nh; inv.ow = nw; inv.mode = n->rs_mode; inv.pl = -n->rs_pl; inv.pt = -n->rs_pt;
-      inv.how = MAUA_PAD_CONSTANT; inv.value = 0.f; inv.noise = nullptr;
-      if (int rc = launch_resize2d(st, MAUA_F32, false, inv)) return rc;
-      const float* native = n->rgb_tmp[1];
-      if (prev_img) {
-        if (int rc = launch_skip_add(st, n->rgb_tmp[1], prev_img, n->rgb_tmp[0], B, nh, nw, n->fir)) return rc;
-        native = n->rgb_tmp[0];
+      if (hook) {
+        const ConvLayer& hc = n->convs[n->rs_layer - 1];
+        const int nh = hc.oh, nw = hc.ow;  // native grid of the block
+        ResizeArgs inv{};
+        inv.x = n->rgb_tmp[0]; inv.x_bstride = 3L * g.h * g.w; inv.y = n->rgb_tmp[1]; inv.B = B; inv.H = g.h; inv.W = g.w;
+        inv.C = 3; inv.oh = nh; inv.ow = nw; inv.mode = n->rs_mode; inv.pl = -n->rs_pl; inv.pt = -n->rs_pt;
+        inv.how = MAUA_PAD_CONSTANT; inv.value = 0.f; inv.noise = nullptr;
+        if (int rc = launch_resize2d(st, MAUA_F32, false, inv)) return rc;
+        const float* native = n->rgb_tmp[1];
+        if (prev_img) {
+          if (int rc = launch_skip_add(st, n->rgb_tmp[1], prev_img, n->rgb_tmp[0], B, nh, nw, n->fir)) return rc;
+          native = n->rgb_tmp[0];
+        }
+        ResizeArgs fwd{};
+        fwd.x = native; fwd.x_bstride = 3L * nh * nw; fwd.y = rgb_out; fwd.B = B; fwd.H = nh; fwd.W = nw; fwd.C = 3;
+        fwd.oh = g.h; fwd.ow = g.w; fwd.mode = n->rs_mode; fwd.pl = n->rs_pl; fwd.pt = n->rs_pt; fwd.how = n->rs_how;
+        fwd.value = n->rs_value; fwd.noise = nullptr;
+        if (int rc = launch_resize2d(st, MAUA_F32, false, fwd)) return rc;
       }
-      ResizeArgs fwd{};
-      fwd.x = native; fwd.x_bstride = 3L * nh * nw; fwd.y = rgb_out; fwd.B = B; fwd.H = nh; fwd.W = nw; fwd.C = 3;
-      fwd.oh = g.h; fwd.ow = g.w; fwd.mode = n->rs_mode; fwd.pl = n->rs_pl; fwd.pt = n->rs_pt; fwd.how = n->rs_how;
-      fwd.value = n->rs_value; fwd.noise = nullptr;
-      if (int rc = launch_resize2d(st, MAUA_F32, false, fwd)) return rc;
-    } else if (!rgb_fused) {
-      RgbArgs r{};
-      r.x = x; r.wmod = g.wmod; r.bias = g.bias; r.prev = prev_img;
-      r.out = rgb_out; r.B = B; r.H = g.h; r.W = g.w; r.C = g.C; r.clamp = 256.f;
-      memcpy(r.fir, n->fir, sizeof(r.fir));
-      if (int rc = launch_torgb(st, n->dtype, r)) return rc;
     }
-    prof_mark(n, "torgb");  // zero-length when fused into conv1
+    prof_mark(n);  // zero-length when fused into conv1
     prev_img = rgb_out;
     img_cur ^= 1;
   }
   if (rgb8_out) {
-    if (!rgb8_done)
+    if (plan.pack)
       if (int rc = launch_pack_rgb8(st, prev_img, rgb8_out, B, n->out_h, n->out_w)) return rc;
-    prof_mark(n, "pack_rgb8");  // zero-length when the last block's epilogue packed the frame
+    prof_mark(n);  // zero-length when the last block's epilogue packed the frame
   }
   return MAUA_OK;
 }
@@ -965,7 +936,6 @@ int maua_synth_get_profile(maua_synth* n, float* ms_out, int capacity, int* coun
   *count = k;
   if (ms_out) {  // reading resets the recording
     n->ev_used = 0;
-    n->ev_names.clear();
     n->ev_fwd_start.clear();
   }
   return MAUA_OK;
