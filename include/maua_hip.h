@@ -544,6 +544,48 @@ typedef struct {
 int maua_gemm_nt_route(const maua_gemm_desc* d, int dtype, int prefer_dma, int* remap_out);
 /* launch: force 0 = production routing, 1 .. 4 = that kernel, refused (no launch) when it cannot take the shape */
 int maua_gemm_nt_ex(maua_ctx* ctx, const maua_gemm_desc* d, int dtype, int prefer_dma, int force);
+/* kernel-selection switches of the plain 3x3 convolutions (padding 1) behind the diffusion UNet, the secondary model, the VGG
+ * perceptors and the up-scalers, for parity tests (no reference counterpart).  One convolution, described as those networks describe
+ * theirs; every tensor NHWC in `dtype` (MAUA_F32_SPLIT: float32 tensors), strides in elements, 0 = dense:
+ *   v = clamp(act(sum_{tap, ci < Ci} w[co][ci][tap] x[b][p + tap][ci] + bias[co]) * gain)     (clamp < 0: none)
+ *   y[b][p][y_coff + co] = v                                              without res
+ *                        = T(v) + res[b][p][co]                           with res: the value as it would have been stored, plus res
+ *                        = res_gain * T(T(v) + res) + res2[b][p][co]      with res2 as well (res2 needs res)
+ * T = rounding to the 16-bit storage type (the identity for the float32 types); the result is rounded once more when it is stored.
+ * x: x_pstride elements per pixel (>= Ci, 0 = Ci), x_bstride per sample; with x_up2 the tensor is [B][H / 2][W / 2] and the layer
+ * sees it up-sampled x2 by pixel repetition.  w: DEVICE float32 [Co][Ci][3][3], bias DEVICE float32 [Co] or NULL; both are prepared
+ * into the context's scratch arena on every call.  Ci_read (0 = Ci): input channels that are fetched at all - the weights of the
+ * others must be zero (LDS-direct kernel: rounded up to whole 32-channel chunks, at least two).  psum (optional, LDS-direct wide tiles):
+ * float [B][(H / 8) * (W / 32)][Co / 8][16] - per 8 x 32-pixel tile and 8-channel piece the 8 sums, then the 8 sums of squares, of
+ * the values stored.  variant: 128 = the LDS-direct kernel's 128-channel tile although 256 would divide.  Ci, Co multiples of 32.
+ * Kernels: 1 = generic (any such shape, every dtype; no x_up2 / psum / Ci_read); 2 = LDS-direct (MAUA_BF16: Ci % 64 == 0, Co % 128
+ * == 0, H % 8 == 0, W % 32 == 0 - the wide tiles - or Co of 32 / 64, H >= 8, W >= 32, Ci % 64 == 0 or Co == 32 and Ci % 32 == 0, Ci >= 96 -
+ * the narrow tiles, no psum; MAUA_F16: wide tiles only, no psum, no x_up2); 3 = split-K gather GEMM (MAUA_BF16 / MAUA_F32, H W <= 1024,
+ * Ci a multiple of 128 bytes, Co % 128 == 0, dense x, one residual, none of x_up2 / psum / Ci_read). */
+typedef struct {
+  const void* x; int x_pstride; long x_bstride;
+  const float* w; const float* bias;
+  void* y; int y_pstride, y_coff; long y_bstride;
+  const void* res; int res_pstride; long res_bstride;
+  const void* res2; int res2_pstride; long res2_bstride; float res_gain;
+  int B, H, W, Ci, Co;
+  int act; float alpha, gain, clamp;
+  int Ci_read, x_up2, variant;
+  float* psum;
+} maua_conv_desc;
+/* host only, no device needed: the kernel (1 .. 3) the diffusion UNet runs this convolution on under its option "route" =
+ * unet_route_option (0 per-shape routing, 1 always the generic kernel, 2 never the gather GEMM) - or, with unet_route_option = 100 +
+ * k, kernel k as maua_conv3x3_ex forces it.  *variant (may be NULL): kernel 1 - which of its tile rules fires, 1 .. 9 in the order of
+ * launch_modconv3x3's source (1 and 9: 256 pixels x 32 channels; 2 and 4: 256 x 128, 128-byte K chunks; 3: 256 x 128, 64-byte chunks;
+ * 5 / 6: 128 x 128 with 128 / 64-byte chunks; 7: 256 x 64, 3-tap stages; 8: 256 x 64, 9-tap stages); kernel 2 - output channels per
+ * workgroup, 256 / 128 / 64 / 32, + 1 for the 32-channel tile's odd-chunk form, + 2 for the piece-sum instantiations; kernel 3 - 0.
+ * *ksplit (may be NULL): kernel 3's K slices, else 0.  MAUA_ERR + maua_last_error() (the launcher's own message) if the kernel refuses
+ * the shape or the arguments.  Pointers are only checked, never dereferenced. */
+int maua_conv3x3_route(const maua_conv_desc* d, int dtype, int unet_route_option, int* variant, int* ksplit);
+/* launch on the context's stream: kernel 0 = the UNet's production routing (piece sums only where it takes the wide LDS-direct
+ * tiles, its own choice of `variant`), 1 .. 3 = that kernel, refused (no launch, no fall-back) when it cannot take the shape or the
+ * arguments */
+int maua_conv3x3_ex(maua_ctx* ctx, const maua_conv_desc* d, int dtype, int kernel);
 /* GroupNorm32(32, C)(x) [* (1 + scale) + shift with scale_shift [B][2C] (ResBlock use_scale_shift_norm)] [-> SiLU];
  * statistics in float64, eps 1e-5.  x, y [B][H][W][C] */
 int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift,

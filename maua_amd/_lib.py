@@ -147,3 +147,16 @@ class GemmDesc(C.Structure):
                 ("c", C.c_void_p), ("ldc", C.c_long), ("M", C.c_long), ("N", C.c_int),
                 ("epi", C.c_int), ("c2", C.c_void_p), ("ldc2", C.c_long), ("aux", C.c_void_p), ("ldaux", C.c_long),
                 ("batch", C.c_int), ("a_bstride", C.c_long), ("w_bstride", C.c_long), ("c_bstride", C.c_long)]
+
+
+class ConvDesc(C.Structure):
+    """maua_conv_desc (include/maua_hip.h): one plain 3x3 convolution for maua_conv3x3_route / maua_conv3x3_ex; pointers as integers."""
+    _fields_ = [("x", C.c_void_p), ("x_pstride", C.c_int), ("x_bstride", C.c_long),
+                ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("y", C.c_void_p), ("y_pstride", C.c_int), ("y_coff", C.c_int), ("y_bstride", C.c_long),
+                ("res", C.c_void_p), ("res_pstride", C.c_int), ("res_bstride", C.c_long),
+                ("res2", C.c_void_p), ("res2_pstride", C.c_int), ("res2_bstride", C.c_long), ("res_gain", C.c_float),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Ci", C.c_int), ("Co", C.c_int),
+                ("act", C.c_int), ("alpha", C.c_float), ("gain", C.c_float), ("clamp", C.c_float),
+                ("Ci_read", C.c_int), ("x_up2", C.c_int), ("variant", C.c_int),
+                ("psum", C.c_void_p)]

@@ -44,7 +44,8 @@ struct ConvArgs {
   const float* out_scale; // modconv_dma: [B][Co] or NULL - the stored features are multiplied by the NEXT layer's styles
   void* y_scaled;         // modconv_dma, with out_scale: y keeps the plain features (a separate toRGB pass reads them) and the
                           // scaled copy goes here, dense [B][H][W][Co] - instead of a premod pass over y afterwards
-  const void* res;        // optional residual added after activation / gain / clamp: NHWC, res_pstride elements per pixel
+  const void* res;        // optional residual added after activation / gain / clamp, to the value rounded to the network dtype (every
+                          // kernel: y = T(T(v) + res)): NHWC, res_pstride elements per pixel
   int res_pstride;
   long res_bstride;
   // optional second residual applied to the value as it would have been stored (rounded to the network dtype):
@@ -74,6 +75,7 @@ struct ConvArgs {
   float* psum;
 };
 int launch_modconv3x3(hipStream_t stream, int dtype, const ConvArgs& a);
+int modconv_tile(int esize, const ConvArgs& a);   // host only: which of launch_modconv3x3's tile rules fires (1 .. 9, see there)
 bool modconv_rgb_fusable(int dtype, int Ci, int Co, int up, int H, int W);
 
 // modconv_dma.hip: up = 1, bf16, input already multiplied by the styles (x * s); both operands by LDS-direct loads
@@ -81,6 +83,10 @@ bool dma_conv_supported(int dtype, int Ci, int Co, int up, int H, int W);
 bool dma_rgb_fusable(int Co);
 bool dma_conv_narrow_supported(int dtype, int Ci, int Co, int H, int W);  // 32 / 64 output channels (plain convs: x_pstride / y_pstride / y_coff / res honoured)
 int launch_modconv_dma(hipStream_t stream, const ConvArgs& a, int dtype = MAUA_BF16);
+// its two steps before the launch (host only): every refusal (MAUA_ERR + last error), and the tile - 256 / 128 / 64 / 32 output channels,
+// + 1 for the 32-channel tile's odd-chunk form, + 2 for the wide tiles' piece-sum instantiations
+int dma_conv_check(int dtype, const ConvArgs& a);
+int dma_conv_tile(int dtype, const ConvArgs& a);
 int dma_psum_rows(const ConvArgs& a);   // rows per sample of ConvArgs.psum for such a launch
 int launch_premod_nhwc(hipStream_t stream, const void* x, long x_bstride, const float* s, void* y, int B, long HW, int Ci,
                        int dtype = MAUA_BF16);
@@ -96,6 +102,15 @@ int launch_modconv_lowres(hipStream_t stream, int dtype, const ConvArgs& a, void
 bool gather_conv_supported(int dtype, int Ci, int Co, int H, int W);
 size_t gather_conv_workspace(int dtype, int B, int H, int W, int Ci, int Co);
 int launch_conv_gather(hipStream_t stream, int dtype, const ConvArgs& a, float* ws);
+int gather_conv_check(int dtype, const ConvArgs& a);   // host only: launch_conv_gather's refusals
+int gather_conv_ksplit(int dtype, int B, int H, int W, int Ci, int Co);   // host only: the K slices such a launch takes
+
+// unet.hip: the kernel the diffusion UNet runs a plain 3x3 convolution of [B][H][W][Ci] -> Co on (host only; Runner::conv and
+// maua_conv3x3_route / maua_conv3x3_ex share it).  kernel: 1 launch_modconv3x3, 2 launch_modconv_dma, 3 launch_conv_gather;
+// wide: the LDS-direct kernel's 256 / 128-channel tiles (the ones that can leave piece sums); variant: ConvArgs.variant for kernel 2.
+// route: the network's option "route" (0 per-shape, 1 always the generic kernel, 2 never the gather GEMM)
+struct UnetConvRoute { int kernel; bool wide; int variant; };
+UnetConvRoute unet_conv_route(int dtype, int route, int B, int H, int W, int Ci, int Co);
 
 // high-resolution specialisation (modconv_hires.hip): weights stationary in registers, persistent tile walk,
 // optional fused toRGB + skip on conv1 layers

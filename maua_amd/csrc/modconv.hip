@@ -460,11 +460,16 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void modconv3x3_kernel(ConvA
             }
           }
           if (a.out_scale) { v[0] *= sq[q].x; v[1] *= sq[q].y; v[2] *= sq[q].z; v[3] *= sq[q].w; }
-          if (a.res && inside) {  // residual connection (RRDB blocks): added after activation, gain and clamp
+          if (a.res && inside) {  // residual connection (RRDB blocks): added after activation, gain and clamp - to the value as it would
+            // have been stored (rounded to T), like the add in the network dtype this replaces and like modconv_dma.hip / lowres_epilogue_kernel
             const T* rp = reinterpret_cast<const T*>(a.res) + (long)b * a.res_bstride +
                           ((long)gy * a.W + gx) * a.res_pstride + co;
 #pragma unroll
-            for (int k = 0; k < 4; k++) v[k] += Elem<T>::load(rp + k);
+            for (int k = 0; k < 4; k++) {
+              float t = v[k];
+              if constexpr (sizeof(T) == 2) t = Fmt16<T>::round(t);
+              v[k] = t + Elem<T>::load(rp + k);
+            }
             if (a.res2) {  // second residual on the value as stored (rounded to T): y = res_gain * y + res2
               const T* rp2 = reinterpret_cast<const T*>(a.res2) + (long)b * a.res2_bstride +
                              ((long)gy * a.W + gx) * a.res2_pstride + co;
@@ -631,33 +636,49 @@ static int launch_variant(hipStream_t stream, const ConvArgs& a) {
   return MAUA_OK;
 }
 
+// The tile launch_modconv_t takes, as the number of the rule below that fires (1 .. 9; host only).  Rules 1 and 9 share one
+// instantiation (256 pixels x 32 channels, 9-tap stages), 2 and 4 another (256 x 128, 128-byte K chunks).  esize: bytes per element.
+int modconv_tile(int esize, const ConvArgs& a) {
+  const int cov = a.Co * a.up * a.up;  // virtual output channels: up-layers carry their 4 parities in N
+  // 8 / 16 waves per workgroup: measured 1.15x over 4 waves at the same tile (more waves hide the two barriers
+  // per stage); the 256-pixel tile pays off once a sample has >= 16 of them
+  // K chunk: 128 bytes (fewer, longer stages) measured 1.1-1.2x over 64 except on the 32^2 layers
+  const bool k128 = a.Ci % (128 / esize) == 0;
+  // tiny up=1 layers (4^2..16^2) are bound by the latency of streaming the weights through few workgroups: 32-channel
+  // N tiles give 4x the workgroups and 9-tap stages a third of the dependent stages (measured 0.058 -> 0.047 ms at 4^2,
+  // 0.065 -> 0.049 at 16^2; up=2 layers would re-stage the halo for 64 virtual-channel tiles and lose)
+  if (a.up == 1 && a.H * a.W <= 256 && cov % 128 == 0) return 1;
+  if (cov % 128 == 0 && a.H * a.W >= 4096 && k128) return 2;
+  if (cov % 128 == 0 && a.H * a.W >= 4096) return 3;
+  // 16 x 16 inputs (the 16^2 -> 32^2 up-layer of the synthesis network): the whole image as one 256-pixel tile of 16 waves with
+  // 128-byte K chunks - 0.70 -> 0.59 ms at B = 128 against the 128-pixel / 64-byte tile (round 5; 128 px x 128 B: 0.86, 256 x 64 B: 0.69)
+  if (cov % 128 == 0 && a.H * a.W == 256 && k128) return 4;
+  if (cov % 128 == 0 && a.H * a.W < 256 && k128) return 5;
+  if (cov % 128 == 0) return 6;
+  // 64 virtual channels on large maps (the secondary diffusion model's and the VGG perceptors' 64-channel layers at 256^2 / 128^2): the
+  // same 256 x 64 tile on 8 waves with 3-tap stages - secondary forward + VJP 8.12 -> 7.16 ms (split f32), 4.41 -> 3.77 (bf16) at batch 16
+  static const bool w4 = getenv("MAUA_CONV64_4W") != nullptr;
+  if (!w4 && cov % 64 == 0 && a.H * a.W >= 4096) return 7;
+  if (cov % 64 == 0) return 8;
+  return 9;
+}
+
 template <typename T>
 static int launch_modconv_t(hipStream_t stream, const ConvArgs& a) {
   MAUA_REQUIRE(a.Ci % 32 == 0, "modconv3x3: Ci must be a multiple of 32 (pad channels)");
   MAUA_REQUIRE(a.Co % 32 == 0, "modconv3x3: Co must be a multiple of 32 (pad channels)");
   MAUA_REQUIRE(a.up == 1 || a.up == 2, "modconv3x3: up must be 1 or 2");
   if (a.B == 0) return MAUA_OK;
-  const int cov = a.Co * a.up * a.up;  // virtual output channels: up-layers carry their 4 parities in N
-  // 8 / 16 waves per workgroup: measured 1.15x over 4 waves at the same tile (more waves hide the two barriers
-  // per stage); the 256-pixel tile pays off once a sample has >= 16 of them
-  // K chunk: 128 bytes (fewer, longer stages) measured 1.1-1.2x over 64 except on the 32^2 layers
-  const bool k128 = a.Ci % (128 / (int)sizeof(T)) == 0;
-  // tiny up=1 layers (4^2..16^2) are bound by the latency of streaming the weights through few workgroups: 32-channel
-  // N tiles give 4x the workgroups and 9-tap stages a third of the dependent stages (measured 0.058 -> 0.047 ms at 4^2,
-  // 0.065 -> 0.049 at 16^2; up=2 layers would re-stage the halo for 64 virtual-channel tiles and lose)
-  if (a.up == 1 && a.H * a.W <= 256 && cov % 128 == 0) return launch_variant<T, 4, 1, 2, 1, 9, 64>(stream, a);
-  if (cov % 128 == 0 && a.H * a.W >= 4096 && k128) return launch_variant<T, 4, 4, 2, 1, 3, 128>(stream, a);
-  if (cov % 128 == 0 && a.H * a.W >= 4096) return launch_variant<T, 4, 4, 2, 1, 3, 64>(stream, a);
-  // 16 x 16 inputs (the 16^2 -> 32^2 up-layer of the synthesis network): the whole image as one 256-pixel tile of 16 waves with
-  // 128-byte K chunks - 0.70 -> 0.59 ms at B = 128 against the 128-pixel / 64-byte tile (round 5; 128 px x 128 B: 0.86, 256 x 64 B: 0.69)
-  if (cov % 128 == 0 && a.H * a.W == 256 && k128) return launch_variant<T, 4, 4, 2, 1, 3, 128>(stream, a);
-  if (cov % 128 == 0 && a.H * a.W < 256 && k128) return launch_variant<T, 2, 4, 2, 1, 3, 128>(stream, a);
-  if (cov % 128 == 0) return launch_variant<T, 2, 4, 2, 1, 3, 64>(stream, a);
-  // 64 virtual channels on large maps (the secondary diffusion model's and the VGG perceptors' 64-channel layers at 256^2 / 128^2): the
-  // same 256 x 64 tile on 8 waves with 3-tap stages - secondary forward + VJP 8.12 -> 7.16 ms (split f32), 4.41 -> 3.77 (bf16) at batch 16
-  static const bool w4 = getenv("MAUA_CONV64_4W") != nullptr;
-  if (!w4 && cov % 64 == 0 && a.H * a.W >= 4096) return launch_variant<T, 4, 2, 2, 1, 3, 64>(stream, a);
-  if (cov % 64 == 0) return launch_variant<T, 4, 1, 2, 2, 9, 64>(stream, a);
+  switch (modconv_tile((int)sizeof(T), a)) {
+    case 1: return launch_variant<T, 4, 1, 2, 1, 9, 64>(stream, a);
+    case 2: return launch_variant<T, 4, 4, 2, 1, 3, 128>(stream, a);
+    case 3: return launch_variant<T, 4, 4, 2, 1, 3, 64>(stream, a);
+    case 4: return launch_variant<T, 4, 4, 2, 1, 3, 128>(stream, a);
+    case 5: return launch_variant<T, 2, 4, 2, 1, 3, 128>(stream, a);
+    case 6: return launch_variant<T, 2, 4, 2, 1, 3, 64>(stream, a);
+    case 7: return launch_variant<T, 4, 2, 2, 1, 3, 64>(stream, a);
+    case 8: return launch_variant<T, 4, 1, 2, 2, 9, 64>(stream, a);
+  }
   return launch_variant<T, 4, 1, 2, 1, 9, 64>(stream, a);
 }
 

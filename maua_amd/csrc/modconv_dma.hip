@@ -625,17 +625,16 @@ static int launch_dma_variant(hipStream_t stream, const ConvArgs& a) {
   return MAUA_OK;
 }
 
-// a.x must already carry the styles (x * s[b, ci]); a.s is not read.  dtype: MAUA_BF16, or MAUA_F16 on the two wide tiles (round 6: the
-// reference's own render dtype, render/ffmpeg.py:45 - same kernel, v_mfma_f32_32x32x16_f16, half conversions)
-int launch_modconv_dma(hipStream_t stream, const ConvArgs& a, int dtype) {
+// What launch_modconv_dma checks before it launches, and the tile it then takes (host only): 256 / 128 (wide), 64 / 32 (narrow) output
+// channels per workgroup, + 1 for the odd-chunk form of the 32-channel tile, + 2 for the instantiations that also write piece sums.
+int dma_conv_check(int dtype, const ConvArgs& a) {
   if (dtype == MAUA_F16) {
     MAUA_REQUIRE(dma_conv_supported(MAUA_F16, a.Ci, a.Co, a.up, a.H, a.W) && !a.psum && !a.x_up2 && a.B <= 65535 &&
                      (long)a.H * a.W * (a.x_pstride ? a.x_pstride : a.Ci) * 2 < (1L << 32) && (!a.y_scaled || (a.out_scale && !a.res)),
                  "modconv_dma (f16): unsupported shape / arguments");
-    if (a.B == 0) return MAUA_OK;
-    if (a.Co % 256 == 0 && a.variant != 128) return launch_dma_variant<2, 4, 4, 2, 1, 128, false, false, f16_t>(stream, a);
-    return launch_dma_variant<4, 2, 2, 2, 2, 64, false, false, f16_t>(stream, a);
+    return MAUA_OK;
   }
+  MAUA_REQUIRE(dtype == MAUA_BF16, "modconv_dma: unsupported dtype");
   const bool narrow = dma_conv_narrow_supported(MAUA_BF16, a.Ci, a.Co, a.H, a.W) && a.up == 1;
   MAUA_REQUIRE(narrow || dma_conv_supported(MAUA_BF16, a.Ci, a.Co, a.up, a.H, a.W), "modconv_dma: unsupported shape");
   MAUA_REQUIRE(a.B <= 65535, "modconv_dma: grid too large");
@@ -644,14 +643,17 @@ int launch_modconv_dma(hipStream_t stream, const ConvArgs& a, int dtype) {
   MAUA_REQUIRE(!a.y_scaled || (a.out_scale && !a.res), "modconv_dma: y_scaled goes with out_scale (and no residual)");
   MAUA_REQUIRE((long)a.H * a.W * (a.x_pstride ? a.x_pstride : a.Ci) * 2 < (1L << 32),
                "modconv_dma: a sample must stay below 4 GiB (32-bit offsets)");
-  // narrow N tiles (4 waves, 64-byte K rows, two taps per stage): 64 channels = 2 x 2 blocks per wave, 32 = 2 x 1
   if (narrow) {
     MAUA_REQUIRE(!a.rgb_out && !a.out_scale && !a.psum, "modconv_dma: the narrow tiles carry no toRGB / style scaling / piece sums");
     MAUA_REQUIRE(!(a.img_f32 || a.img_u8) || (a.Co == 32 && !a.res), "modconv_dma: image output is the 32-channel tile's, without a residual");
     MAUA_REQUIRE((a.H % TH == 0 && a.W % TW == 0) || !a.noise, "modconv_dma: overhanging tiles take no noise operand");
-    if (a.Co == 64) return launch_dma_variant<4, 1, 2, 2, 2, 64>(stream, a);
-    return (a.Ci / 32) % 2 ? launch_dma_variant<4, 1, 2, 1, 2, 64, false, true>(stream, a) : launch_dma_variant<4, 1, 2, 1, 2, 64>(stream, a);
   }
+  return MAUA_OK;
+}
+int dma_conv_tile(int dtype, const ConvArgs& a) {
+  // narrow N tiles (4 waves, 64-byte K rows, two taps per stage): 64 channels = 2 x 2 blocks per wave, 32 = 2 x 1
+  if (dtype == MAUA_BF16 && a.up == 1 && dma_conv_narrow_supported(MAUA_BF16, a.Ci, a.Co, a.H, a.W))
+    return a.Co == 64 ? 64 : 32 + ((a.Ci / 32) % 2 ? 1 : 0);
   // (channel-sliced operands and the residual are honoured by every tile shape: the kernel's address arithmetic is shared)
   // 256-channel N tile: 128-byte K rows, one tap per stage, 149 KB of LDS, one workgroup per CU.
   // 128-channel N tile: 64-byte K rows, two taps per stage, 75 KB -> two workgroups per CU (measured on the 256^2 layer,
@@ -659,11 +661,27 @@ int launch_modconv_dma(hipStream_t stream, const ConvArgs& a, int dtype) {
   // layers the two-workgroup shape measured the same as the big tile, which also keeps their toRGB fused)
   // (a.variant == 128: the caller asks for the 128-channel tile although 256 would divide - twice the workgroups for
   //  launches that would otherwise leave CUs idle, e.g. the diffusion UNet's 64^2 level at small batch)
-  if (a.psum) {
-    if (a.Co % 256 == 0 && a.variant != 128) return launch_dma_variant<2, 4, 4, 2, 1, 128, true>(stream, a);
-    return launch_dma_variant<4, 2, 2, 2, 2, 64, true>(stream, a);
+  return (a.Co % 256 == 0 && a.variant != 128 ? 256 : 128) + (a.psum ? 2 : 0);
+}
+
+// a.x must already carry the styles (x * s[b, ci]); a.s is not read.  dtype: MAUA_BF16, or MAUA_F16 on the two wide tiles (round 6: the
+// reference's own render dtype, render/ffmpeg.py:45 - same kernel, v_mfma_f32_32x32x16_f16, half conversions)
+int launch_modconv_dma(hipStream_t stream, const ConvArgs& a, int dtype) {
+  if (int rc = dma_conv_check(dtype, a)) return rc;
+  if (a.B == 0) return MAUA_OK;
+  const int tile = dma_conv_tile(dtype, a);
+  if (dtype == MAUA_F16) {
+    if (tile == 256) return launch_dma_variant<2, 4, 4, 2, 1, 128, false, false, f16_t>(stream, a);
+    return launch_dma_variant<4, 2, 2, 2, 2, 64, false, false, f16_t>(stream, a);
   }
-  if (a.Co % 256 == 0 && a.variant != 128) return launch_dma_variant<2, 4, 4, 2, 1, 128>(stream, a);
+  switch (tile) {
+    case 64: return launch_dma_variant<4, 1, 2, 2, 2, 64>(stream, a);
+    case 33: return launch_dma_variant<4, 1, 2, 1, 2, 64, false, true>(stream, a);
+    case 32: return launch_dma_variant<4, 1, 2, 1, 2, 64>(stream, a);
+    case 258: return launch_dma_variant<2, 4, 4, 2, 1, 128, true>(stream, a);
+    case 130: return launch_dma_variant<4, 2, 2, 2, 2, 64, true>(stream, a);
+    case 256: return launch_dma_variant<2, 4, 4, 2, 1, 128>(stream, a);
+  }
   return launch_dma_variant<4, 2, 2, 2, 2, 64>(stream, a);
 }
 

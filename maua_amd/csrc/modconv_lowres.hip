@@ -203,10 +203,15 @@ __global__ __launch_bounds__(256) void lowres_epilogue_kernel(ConvArgs a, const 
       v[k] = t;
     }
   }
-  if (a.res) {  // residual added after activation / gain / clamp (plain convolutions of the diffusion UNet, unet.hip)
+  if (a.res) {  // residual added after activation / gain / clamp (plain convolutions of the diffusion UNet, unet.hip) - to the value as it
+    // would have been stored (rounded to T): the add in the network dtype this replaces, and what modconv.hip / modconv_dma.hip compute
     const T* rp = reinterpret_cast<const T*>(a.res) + (long)b * a.res_bstride + opix * a.res_pstride + co;
 #pragma unroll
-    for (int k = 0; k < 4; k++) v[k] += Elem<T>::load(rp + k);
+    for (int k = 0; k < 4; k++) {
+      float t = v[k];
+      if constexpr (sizeof(T) == 2) t = Fmt16<T>::round(t);
+      v[k] = t + Elem<T>::load(rp + k);
+    }
   }
   const int yps = a.y_pstride ? a.y_pstride : a.Co;
   T* dst = reinterpret_cast<T*>(a.y) + (long)b * (a.y_bstride ? a.y_bstride : (long)Ho * Wo * yps) + opix * yps + a.y_coff + co;
@@ -290,12 +295,23 @@ size_t gather_conv_workspace(int dtype, int B, int H, int W, int Ci, int Co) {
   const LowresGeom g = lowres_geom(dtype == MAUA_BF16 ? 2 : 4, B, H, W, Ci, Co, 1, GATHER_TILES);
   return (size_t)g.ksplit * g.M * g.CoV * sizeof(float);
 }
-int launch_conv_gather(hipStream_t stream, int dtype, const ConvArgs& a, float* ws) {
-  MAUA_REQUIRE(gather_conv_supported(dtype, a.Ci, a.Co, a.H, a.W) && a.up == 1 && !a.s && !a.d && !a.x_pstride,
+// what launch_conv_gather checks before it launches (host only), and the K slices it then takes
+int gather_conv_check(int dtype, const ConvArgs& a) {
+  // (the epilogue knows one residual and nothing of the LDS-direct kernel's extras: refused rather than ignored)
+  MAUA_REQUIRE(gather_conv_supported(dtype, a.Ci, a.Co, a.H, a.W) && a.up == 1 && !a.s && !a.d && !a.x_pstride && !a.res2 && !a.x_up2 &&
+                   !a.psum && (!a.Ci_read || a.Ci_read == a.Ci),
                "conv_gather: unsupported shape / arguments");
   MAUA_REQUIRE(a.x_bstride == (long)a.H * a.W * a.Ci, "conv_gather: the input must be dense batch-major NHWC");
   if (a.B == 0) return MAUA_OK;
   MAUA_REQUIRE((long)a.B * a.H * a.W * std::max(a.Ci, a.Co) < (1L << 31), "conv_gather: 32-bit pixel indices");
+  return MAUA_OK;
+}
+int gather_conv_ksplit(int dtype, int B, int H, int W, int Ci, int Co) {
+  return lowres_geom(dtype == MAUA_BF16 ? 2 : 4, B, H, W, Ci, Co, 1, GATHER_TILES).ksplit;
+}
+int launch_conv_gather(hipStream_t stream, int dtype, const ConvArgs& a, float* ws) {
+  if (int rc = gather_conv_check(dtype, a)) return rc;
+  if (a.B == 0) return MAUA_OK;
   if (dtype == MAUA_BF16) return launch_lowres_t<bf16_t>(stream, a, nullptr, ws, GATHER_TILES);
   return launch_lowres_t<float>(stream, a, nullptr, ws, GATHER_TILES);
 }

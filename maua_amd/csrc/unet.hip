@@ -963,6 +963,33 @@ int build_structure(maua_unet* n) {
   return MAUA_OK;
 }
 
+}  // namespace
+
+// Which kernel a plain 3x3 convolution of the network runs on (see internal.h); a function of the shape and the batch only.
+UnetConvRoute maua::unet_conv_route(int dtype, int route, int B, int H, int W, int Ci, int Co) {
+  UnetConvRoute r{1, false, 0};
+  if (route == 1) return r;
+  const bool bf = dtype == MAUA_BF16;
+  const bool dma_wide = bf && dma_conv_supported(dtype, Ci, Co, 1, H, W);
+  const bool dma_narrow = bf && dma_conv_narrow_supported(dtype, Ci, Co, H, W);
+  const bool gather = gather_conv_supported(dtype, Ci, Co, H, W) && gather_conv_workspace(dtype, B, H, W, Ci, Co) > 0;
+  // enough workgroups for the chip on the LDS-direct kernel (8 x 32 pixel tiles x N tiles of 256 / 128 / Co channels)?
+  const long tiles = (long)B * (H / 8) * (W / 32);
+  long dma_wgs = dma_wide ? tiles * (Co % 256 == 0 ? Co / 256 : Co / 128) : tiles;
+  if (dma_wide && Co % 256 == 0 && dma_wgs < 512) {  // fewer than two rounds of big tiles: 128-channel tiles, 2 per CU
+    r.variant = 128;
+    dma_wgs *= 2;
+  }
+  r.wide = dma_wide;
+  if ((dma_wide || dma_narrow) && (dma_wgs >= 128 || !gather || route == 2)) r.kernel = 2;
+  else if (gather && route != 2) r.kernel = 3;
+  else if (dma_wide || dma_narrow) r.kernel = 2;
+  if (r.kernel != 2) { r.wide = false; r.variant = 0; }
+  return r;
+}
+
+namespace {
+
 // ------------------------------------------------------------------------------------------------------ forward
 template <typename T>
 struct Runner {
@@ -1005,29 +1032,16 @@ struct Runner {
     a.y = y; a.B = B; a.H = H; a.W = W; a.Ci = c.Cip; a.Co = c.Cop; a.up = 1;
     a.act = MAUA_ACT_LINEAR; a.alpha = 1.f; a.gain = 1.f; a.clamp = -1.f;
     a.res = res; a.res_pstride = c.Cop; a.res_bstride = (long)H * W * c.Cop;
-    const bool bf = n->dtype == MAUA_BF16;
-    if (n->route != 1) {
-      const bool dma_wide = bf && dma_conv_supported(n->dtype, c.Cip, c.Cop, 1, H, W);
-      const bool dma_narrow = bf && dma_conv_narrow_supported(n->dtype, c.Cip, c.Cop, H, W);
-      const bool gather = ws_need > 0;
-      // enough workgroups for the chip on the LDS-direct kernel (8 x 32 pixel tiles x N tiles of 256 / 128 / Co channels)?
-      const long tiles = (long)B * (H / 8) * (W / 32);
-      long dma_wgs = dma_wide ? tiles * (c.Cop % 256 == 0 ? c.Cop / 256 : c.Cop / 128) : tiles;
-      if (dma_wide && c.Cop % 256 == 0 && dma_wgs < 512) {  // fewer than two rounds of big tiles: 128-channel tiles, 2 per CU
-        a.variant = 128;
-        dma_wgs *= 2;
+    const UnetConvRoute r = unet_conv_route(n->dtype, n->route, B, H, W, c.Cip, c.Cop);
+    if (r.kernel == 2) {
+      a.variant = r.variant;
+      if (r.wide && psum) {   // the wide tiles can leave the statistics of what they store
+        a.psum = psum;
+        psums[y] = {psum, dma_psum_rows(a)};
       }
-      auto dma = [&]() -> int {
-        if (dma_wide && psum) {   // the wide tiles can leave the statistics of what they store
-          a.psum = psum;
-          psums[y] = {psum, dma_psum_rows(a)};
-        }
-        return launch_modconv_dma(st, a);
-      };
-      if ((dma_wide || dma_narrow) && (dma_wgs >= 128 || !gather || n->route == 2)) return dma();
-      if (gather && n->route != 2) return launch_conv_gather(st, n->dtype, a, gather_ws);
-      if (dma_wide || dma_narrow) return dma();
+      return launch_modconv_dma(st, a);
     }
+    if (r.kernel == 3) return launch_conv_gather(st, n->dtype, a, gather_ws);
     a.s = n->ones;
     return launch_modconv3x3(st, n->dtype, a);
   }
