@@ -586,6 +586,53 @@ int maua_conv3x3_route(const maua_conv_desc* d, int dtype, int unet_route_option
  * tiles, its own choice of `variant`), 1 .. 3 = that kernel, refused (no launch, no fall-back) when it cannot take the shape or the
  * arguments */
 int maua_conv3x3_ex(maua_ctx* ctx, const maua_conv_desc* d, int dtype, int kernel);
+/* kernel-selection switches of the MODULATED 3x3 convolutions of the StyleGAN2 synthesis network, for parity tests (no reference
+ * counterpart).  One layer as the network's forward describes it, on the route of the caller's choice:
+ *   v = clamp(act(d[b][co] * conv(x[b] * s[b], w)[co] + noise[b][p] * noise_strength * noise_scale[b] + bias[co]) * gain)
+ * conv: up == 1 a 3x3 correlation with padding 1; up == 2 conv_transpose2d(stride 2) + the [1, 3, 3, 1] FIR with gain 4 (flip: the
+ * weights are flipped first, the upstream behaviour).  y = T(v), or what the route makes of out_scale (the next layer's styles,
+ * [B][Co]) and y_scaled (the dual store: y plain, y_scaled scaled).  x NHWC [B][H][W][Ci] in `dtype`, x_bstride elements between
+ * samples (0: one sample for all); w DEVICE float32 [Co][Ci][3][3]; s [B][Ci], d [B][Co] or NULL: DEVICE float32, chosen by the caller;
+ * noise float32 [B | 1][H up][W up] or NULL; y NHWC [B][H up][W up][Co].  Optional fused toRGB + skip (rgb_out != NULL):
+ * rgb_out[b][c][p] = clamp(sum_co T(v)[co] rgb_wmod[b][c][co] + rgb_bias[c], rgb_clamp) + upsample2d(rgb_prev)[b][c][p], planar
+ * float32; rgb8_out: the same image as u8 HWC; rgb_skip_f32: only the u8 frame; y == NULL: the features are not stored.
+ * t (optional): where the transposed-convolution routes leave their intermediate [B][2H + 1][2W + 1][Co] (else scratch).
+ * Routes (synth.hip's Route enum): 0 Lowres, 1 Generic, 2 DmaConv1, 3 Hires, 4 Upwalk, 5 FusedWalk (d1 = the block's conv1 with
+ * its toRGB), 7 TconvFir, 8 TconvDma (edges + main + FIR / epilogue pass), 9 Tconv2 (+ FIR / epilogue pass), 10 the FIR / epilogue
+ * pass alone (x = t).  Weights are prepared, and the input pre-multiplied where the route reads it so, exactly as the network does,
+ * in the context's scratch arena on every call. */
+typedef struct {
+  const void* x; long x_bstride;
+  const float* w; int flip;
+  const float* s; const float* d;
+  const float* noise; long noise_bstride; float noise_strength; const float* noise_scale;
+  const float* bias;
+  void* y;
+  int B, H, W, Ci, Co, up;
+  int act; float alpha, gain, clamp;
+  const float* out_scale; void* y_scaled;
+  const float* rgb_wmod; const float* rgb_bias; const float* rgb_prev; float* rgb_out; float rgb_clamp;
+  unsigned char* rgb8_out; int rgb_skip_f32;
+  void* t;
+} maua_modconv_desc;
+/* host only, no device needed: MAUA_OK if `route` can compute the layer - its *_supported predicate and every refusal of its
+ * launchers, with the launcher's own message in maua_last_error() otherwise.  *tile (may be NULL): Generic - the tile rule, 1 .. 9;
+ * DmaConv1 - output channels per workgroup; Lowres - its K slices; else 0.  Pointers are only checked, never dereferenced.
+ * Not predicted here: the halo-register and LDS budgets that launch_modconv3x3 and launch_tconv2 check once their tile is laid out
+ * (no shape with Ci, Co multiples of 32 exceeds them today); maua_modconv_ex meets those after the weights were prepared. */
+int maua_modconv_route(const maua_modconv_desc* d, const maua_modconv_desc* d1, int dtype, int route, int* tile);
+/* launch on the context's stream; refused (no launch, no fall-back) when the route cannot take the layer.  force_segs / narrow_ok:
+ * the fused walk's row segments and narrow last strip (launch_upwalk_fused), ignored elsewhere */
+int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const maua_modconv_desc* d1, int dtype, int route, int force_segs,
+                    int narrow_ok);
+/* the separate toRGB launch: out[b][c][p] = clamp(sum_ch x[b][p][ch] wmod[b][c][ch] + bias[c], clamp) + upsample2d(prev)[b][c][p];
+ * x NHWC [B][H][W][C] in dtype, wmod [B][3][C], bias [3], prev [B][3][H / 2][W / 2] or NULL, out [B][3][H][W] float32 */
+int maua_torgb_ex(maua_ctx* ctx, const void* x, const float* wmod, const float* bias, const float* prev, float* out, int B, int H,
+                  int W, int C, float clamp, int dtype);
+/* the plan of the next forward (host only, no launch): per conv layer 7 ints {route, src (0 Kernel, 1 Producer, 2 Xm, 3 PremodPass),
+ * scale_next, dual, rgb, rgb8, skip_store} into conv_out [capacity][7], per block its toRGB route (0 Separate, 1 Fused, 2 Hook) into
+ * rgb_out [blocks]; *pack: the u8 frame is packed by its own launch.  Returns the number of conv layers through *n_layers. */
+int maua_synth_get_plan(maua_synth* net, int want_u8, int* conv_out, int capacity, int* rgb_out, int* pack, int* n_layers);
 /* GroupNorm32(32, C)(x) [* (1 + scale) + shift with scale_shift [B][2C] (ResBlock use_scale_shift_norm)] [-> SiLU];
  * statistics in float64, eps 1e-5.  x, y [B][H][W][C] */
 int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift,

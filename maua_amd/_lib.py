@@ -160,3 +160,25 @@ class ConvDesc(C.Structure):
                 ("act", C.c_int), ("alpha", C.c_float), ("gain", C.c_float), ("clamp", C.c_float),
                 ("Ci_read", C.c_int), ("x_up2", C.c_int), ("variant", C.c_int),
                 ("psum", C.c_void_p)]
+
+
+class ModconvDesc(C.Structure):
+    """maua_modconv_desc (include/maua_hip.h): one modulated 3x3 layer for maua_modconv_route / maua_modconv_ex; pointers as integers."""
+    _fields_ = [("x", C.c_void_p), ("x_bstride", C.c_long),
+                ("w", C.c_void_p), ("flip", C.c_int),
+                ("s", C.c_void_p), ("d", C.c_void_p),
+                ("noise", C.c_void_p), ("noise_bstride", C.c_long), ("noise_strength", C.c_float), ("noise_scale", C.c_void_p),
+                ("bias", C.c_void_p),
+                ("y", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Ci", C.c_int), ("Co", C.c_int), ("up", C.c_int),
+                ("act", C.c_int), ("alpha", C.c_float), ("gain", C.c_float), ("clamp", C.c_float),
+                ("out_scale", C.c_void_p), ("y_scaled", C.c_void_p),
+                ("rgb_wmod", C.c_void_p), ("rgb_bias", C.c_void_p), ("rgb_prev", C.c_void_p), ("rgb_out", C.c_void_p),
+                ("rgb_clamp", C.c_float),
+                ("rgb8_out", C.c_void_p), ("rgb_skip_f32", C.c_int),
+                ("t", C.c_void_p)]
+
+
+# routes of maua_modconv_route / maua_modconv_ex and of maua_synth_get_plan (csrc/synth.hip's Route enum; UPFIR: the FIR / epilogue pass alone)
+ROUTES = {"lowres": 0, "generic": 1, "dma_conv1": 2, "hires": 3, "upwalk": 4, "fused_walk": 5, "walk_done": 6, "tconv_fir": 7,
+          "tconv_dma": 8, "tconv2": 9, "upfir": 10}

@@ -193,6 +193,71 @@ bool tconv_fir_supported(int dtype, int Ci, int Co, int H, int W);
 int launch_tconv_fir(hipStream_t stream, const ConvArgs& a, const UpfirArgs& u, int dtype = MAUA_BF16);
 size_t prepped_weight_elems(int k, int up, int Cop, int Cip);
 
+// ---- how the launch arguments of one modulated layer are filled: synth.hip's forward and maua_modconv_ex (modconv_api.hip) both go
+// through these, so that the per-layer tests pin what the network passes to the launchers
+struct LayerOperands { const void* x; const void* w; const float* s; const float* d; const float* bias; void* y; int B, H, W, Ci, Co, up; };
+struct NoiseOperands { const float* noise; long bstride; float strength; const float* scale; };
+struct Epilogue { int act; float alpha, gain, clamp; };
+template <typename A>  // ConvArgs / HiresArgs / UpfirArgs
+inline void set_noise_args(A& a, const NoiseOperands& n) {
+  a.noise = n.noise; a.noise_bstride = n.bstride; a.noise_strength = n.strength; a.noise_scale = n.scale;
+}
+template <typename A>  // ConvArgs / HiresArgs / UpfirArgs
+inline void set_epilogue_args(A& a, const Epilogue& e) {
+  a.act = e.act; a.alpha = e.alpha; a.gain = e.gain; a.clamp = e.clamp;
+}
+template <typename A>  // what every modulated 3x3 launch shares (ConvArgs / HiresArgs)
+inline A layer_args(A a, const LayerOperands& l, const NoiseOperands& n, const Epilogue& e) {
+  a.x = l.x; a.w = l.w; a.s = l.s; a.d = l.d; a.bias = l.bias; a.y = l.y;
+  a.B = l.B; a.H = l.H; a.W = l.W; a.Ci = l.Ci; a.Co = l.Co; a.up = l.up;
+  set_noise_args(a, n);
+  set_epilogue_args(a, e);
+  return a;
+}
+template <typename A>  // the block's toRGB + skip in the epilogue (ConvArgs / HiresArgs); fir16: the 4x4 filter incl. gain 4
+inline void fuse_torgb_args(A& a, const float* wmod, const float* bias, const float* prev, float* out, float clamp, const float* fir16) {
+  a.rgb_wmod = wmod; a.rgb_bias = bias; a.rgb_prev = prev; a.rgb_out = out; a.rgb_clamp = clamp;
+  for (int i = 0; i < 16; i++) a.fir[i] = fir16[i];
+}
+inline void pack_u8_args(HiresArgs& a, uint8_t* rgb8_out, bool skip_f32) {  // the final frame packed to u8 in the same epilogue
+  a.rgb8_out = rgb8_out;
+  a.rgb_skip_f32 = skip_f32;  // (nobody reads the f32 image)
+}
+// the two halves of a transposed-convolution up-layer: t = conv_transpose(x s, w) into `t`, then FIR + epilogue from t into y
+inline ConvArgs tconv_args(const void* x, long x_bstride, const void* w, const float* s, void* t, int B, int H, int W, int Ci, int Co) {
+  ConvArgs a{};
+  a.x = x; a.x_bstride = x_bstride; a.w = w; a.s = s; a.y = t;
+  a.B = B; a.H = H; a.W = W; a.Ci = Ci; a.Co = Co; a.up = 2;
+  return a;
+}
+inline UpfirArgs upfir_args(void* y, const float* d, const float* bias, const float* out_scale, int B, int H, int W, int Co,
+                            const NoiseOperands& n, const Epilogue& e) {
+  UpfirArgs u{};
+  u.y = y; u.d = d; u.bias = bias; u.out_scale = out_scale; u.B = B; u.H = H; u.W = W; u.Co = Co;
+  set_noise_args(u, n);
+  set_epilogue_args(u, e);
+  return u;
+}
+inline void upsample_fir16(float* fir) {  // upsample2d: f * gain(4) = outer(g4, g4)
+  const float g4[4] = {0.25f, 0.75f, 0.75f, 0.25f};
+  for (int u = 0; u < 4; u++)
+    for (int v = 0; v < 4; v++) fir[u * 4 + v] = g4[u] * g4[v];
+}
+
+// What each launcher of a modulated layer checks before it launches, callable on its own (host only, no HIP call; MAUA_ERR + last
+// error when refused): the launchers call these first, maua_modconv_route (modconv_api.hip) calls nothing else.
+int modconv3x3_check(int dtype, const ConvArgs& a);
+int lowres_check(int dtype, const ConvArgs& a);
+int lowres_ksplit(int dtype, int B, int H, int W, int Ci, int Co, int up);   // the K slices launch_modconv_lowres takes
+int hires_check(const HiresArgs& a, int dtype);
+int upwalk_check(const HiresArgs& a, int dtype);
+int upwalk_fused_check(const HiresArgs& up, const HiresArgs& c1, int dtype);
+int tconv2_check(int dtype, const ConvArgs& a);
+int tconv_edges_check(const ConvArgs& a, int dtype);
+int tconv_dma_check(const ConvArgs& a, int dtype);
+int tconv_fir_check(const ConvArgs& a, const UpfirArgs& u, int dtype);
+int upfir_check(int dtype, const UpfirArgs& a);
+
 // resize.hip: bicubic / pad / crop of NHWC features (network dtype) or planar images; optional per-channel noise
 struct ResizeArgs {
   const void* x;

@@ -687,7 +687,26 @@ bool modconv_rgb_fusable(int dtype, int Ci, int Co, int up, int H, int W) {
   return (dtype == MAUA_BF16 || dtype == MAUA_F16) && up == 1 && Co == 128 && Ci % 32 == 0 && H * W >= 4096 && (H % 2) == 0 && (W % 2) == 0;
 }
 
+// what launch_modconv3x3 checks from the arguments alone (host only; the tile's halo / LDS budgets are checked where it is laid out)
+int modconv3x3_check(int dtype, const ConvArgs& a) {
+  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F16 || dtype == MAUA_F32 || dtype == MAUA_F32_SPLIT, "modconv3x3: unsupported dtype");
+  MAUA_REQUIRE(a.Ci % 32 == 0, "modconv3x3: Ci must be a multiple of 32 (pad channels)");
+  MAUA_REQUIRE(a.Co % 32 == 0, "modconv3x3: Co must be a multiple of 32 (pad channels)");
+  MAUA_REQUIRE(a.up == 1 || a.up == 2, "modconv3x3: up must be 1 or 2");
+  // the epilogue has no second store, and its fused toRGB reads the tile AFTER out_scale went into it: refused rather than ignored / wrong
+  MAUA_REQUIRE(!a.y_scaled, "modconv3x3: no y_scaled (the dual store is the LDS-direct kernel's)");
+  MAUA_REQUIRE(!a.rgb_out || !a.out_scale, "modconv3x3: fused toRGB and out_scale exclude each other");
+  if (a.B == 0) return MAUA_OK;
+  const int tile = modconv_tile(dtype == MAUA_BF16 || dtype == MAUA_F16 ? 2 : 4, a);
+  MAUA_REQUIRE(!a.rgb_out || ((dtype == MAUA_BF16 || dtype == MAUA_F16) && a.up == 1 && a.Co == 128 && tile >= 2 && tile <= 6 &&
+                              a.rgb_wmod && a.rgb_bias),
+               "modconv3x3: fused toRGB needs bf16, up == 1 and all output channels in one N tile");
+  MAUA_REQUIRE(a.B <= 65535, "modconv3x3: grid too large");
+  return MAUA_OK;
+}
+
 int launch_modconv3x3(hipStream_t stream, int dtype, const ConvArgs& a) {
+  if (int rc = modconv3x3_check(dtype, a)) return rc;
   if (dtype == MAUA_BF16) return launch_modconv_t<bf16_t>(stream, a);
   if (dtype == MAUA_F16) return launch_modconv_t<f16_t>(stream, a);
   if (dtype == MAUA_F32) return launch_modconv_t<float>(stream, a);

@@ -375,25 +375,36 @@ bool hires_supported(int dtype, int Ci, int Co, int up, int H, int W) {
   return W % 32 == 0 && H % th == 0;
 }
 
-int launch_modconv_hires(hipStream_t stream, const HiresArgs& a, int dtype) {
+// what launch_modconv_hires checks before it launches (host only)
+int hires_check(const HiresArgs& a, int dtype) {
   if (a.B == 0) return MAUA_OK;
   MAUA_REQUIRE(hires_supported(dtype, a.Ci, a.Co, a.up, a.H, a.W), "modconv_hires: unsupported shape");
   MAUA_REQUIRE((long)a.H * a.up * a.W * a.up * std::max(a.Ci, a.Co) * 2 < (1L << 31),
                "modconv_hires: a sample must stay below 2 GiB (32-bit in-sample offsets)");
   MAUA_REQUIRE(a.act == MAUA_ACT_LRELU || a.act == MAUA_ACT_LINEAR, "modconv_hires: lrelu / linear only");
   MAUA_REQUIRE(a.y || a.rgb_out, "modconv_hires: no output (y is optional only with the fused toRGB)");
+  const float alpha = a.act == MAUA_ACT_LINEAR ? 1.f : a.alpha;
+  MAUA_REQUIRE(alpha >= 0.f && alpha <= 1.f && a.gain > 0.f, "modconv_hires: needs 0 <= alpha <= 1 and gain > 0");
+  MAUA_REQUIRE(!a.rgb_out || a.up == 1, "modconv_hires: toRGB fusion is for conv1 layers");
+  // (fields the kernel would read through NULL or drop without a word)
+  MAUA_REQUIRE(!a.rgb_out || (a.rgb_wmod && a.rgb_bias), "modconv_hires: fused toRGB needs its weights and bias");
+  MAUA_REQUIRE(!a.rgb8_out || a.rgb_out, "modconv_hires: the u8 frame rides on the fused toRGB");
+  MAUA_REQUIRE(!a.rgb_skip_f32 || a.rgb8_out, "modconv_hires: fused toRGB without an output");
+  return MAUA_OK;
+}
+
+int launch_modconv_hires(hipStream_t stream, const HiresArgs& a, int dtype) {
+  if (int rc = hires_check(a, dtype)) return rc;
+  if (a.B == 0) return MAUA_OK;
   HiresArgs b = a;
   if (a.act == MAUA_ACT_LINEAR) b.alpha = 1.f;
-  MAUA_REQUIRE(b.alpha >= 0.f && b.alpha <= 1.f && b.gain > 0.f, "modconv_hires: needs 0 <= alpha <= 1 and gain > 0");
   if (dtype == MAUA_F16) {   // (round 6: the reference's own render dtype on the same kernels - v_mfma_f32_32x32x16_f16, half conversions)
     if (a.Ci == 32) return launch_hires_variant<32, 32, 1, f16_t>(stream, b);
     if (a.up == 1) return launch_hires_variant<64, 64, 1, f16_t>(stream, b);
-    MAUA_REQUIRE(!a.rgb_out, "modconv_hires: toRGB fusion is for conv1 layers");
     return launch_hires_variant<64, 32, 2, f16_t>(stream, b);
   }
   if (a.Ci == 32) return launch_hires_variant<32, 32, 1, bf16_t>(stream, b);
   if (a.up == 1) return launch_hires_variant<64, 64, 1, bf16_t>(stream, b);
-  MAUA_REQUIRE(!a.rgb_out, "modconv_hires: toRGB fusion is for conv1 layers");
   return launch_hires_variant<64, 32, 2, bf16_t>(stream, b);
 }
 

@@ -316,11 +316,26 @@ int launch_conv_gather(hipStream_t stream, int dtype, const ConvArgs& a, float* 
   return launch_lowres_t<float>(stream, a, nullptr, ws, GATHER_TILES);
 }
 
-int launch_modconv_lowres(hipStream_t stream, int dtype, const ConvArgs& a, void* xm, float* ws) {
+// what launch_modconv_lowres checks before it launches (host only), and the K slices it then takes
+int lowres_check(int dtype, const ConvArgs& a) {
   MAUA_REQUIRE(lowres_supported(dtype, a.Ci, a.Co, a.up, a.H, a.W), "modconv_lowres: unsupported shape");
+  // (the epilogue knows nothing of these: refused rather than ignored)
+  MAUA_REQUIRE(!a.out_scale && !a.y_scaled && !a.rgb_out && !a.res2 && !a.x_pstride && !a.x_up2 && !a.psum && !a.prelu &&
+                   !a.img_f32 && !a.img_u8 && (!a.Ci_read || a.Ci_read == a.Ci),
+               "modconv_lowres: no out_scale / y_scaled / fused toRGB / sliced input");
   if (a.B == 0) return MAUA_OK;
-  MAUA_REQUIRE(xm && ws && a.s, "modconv_lowres: NULL workspace / styles");
+  MAUA_REQUIRE(a.s, "modconv_lowres: NULL workspace / styles");
   MAUA_REQUIRE((long)a.B * a.H * a.W * std::max(a.Ci, a.Co * a.up * a.up) < (1L << 31), "modconv_lowres: 32-bit pixel indices");
+  return MAUA_OK;
+}
+int lowres_ksplit(int dtype, int B, int H, int W, int Ci, int Co, int up) {
+  return lowres_geom(dtype == MAUA_BF16 ? 2 : 4, B, H, W, Ci, Co, up).ksplit;
+}
+
+int launch_modconv_lowres(hipStream_t stream, int dtype, const ConvArgs& a, void* xm, float* ws) {
+  if (int rc = lowres_check(dtype, a)) return rc;
+  if (a.B == 0) return MAUA_OK;
+  MAUA_REQUIRE(xm && ws, "modconv_lowres: NULL workspace / styles");
   if (dtype == MAUA_BF16) return launch_lowres_t<bf16_t>(stream, a, xm, ws);
   return launch_lowres_t<float>(stream, a, xm, ws);
 }

@@ -277,7 +277,17 @@ static int launch_tconv_t(hipStream_t stream, const ConvArgs& a) {
   return MAUA_OK;
 }
 
+// what launch_tconv2 checks from the shape alone (host only; the halo budget is checked where the regions are laid out)
+int tconv2_check(int dtype, const ConvArgs& a) {
+  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F16 || dtype == MAUA_F32, "tconv2: unsupported dtype");
+  MAUA_REQUIRE(a.Ci % (TKCB / (dtype == MAUA_F32 ? 4 : 2)) == 0 && a.Co % 32 == 0, "tconv2: channel counts must be multiples of 32");
+  MAUA_REQUIRE((long)a.H * a.W * a.Ci < (1L << 31) && 16L * a.Co * a.Ci < (1L << 31), "tconv2: 32-bit offsets");
+  MAUA_REQUIRE(a.B <= 65535 && a.Co / 32 <= 65535, "tconv2: grid too large");
+  return MAUA_OK;
+}
+
 int launch_tconv2(hipStream_t stream, int dtype, const ConvArgs& a) {
+  if (int rc = tconv2_check(dtype, a)) return rc;
   if (dtype == MAUA_BF16) return launch_tconv_t<bf16_t>(stream, a);
   if (dtype == MAUA_F16) return launch_tconv_t<f16_t>(stream, a);
   if (dtype == MAUA_F32) return launch_tconv_t<float>(stream, a);

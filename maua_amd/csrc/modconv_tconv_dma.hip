@@ -282,12 +282,27 @@ __global__ __launch_bounds__(64) void tconv_edges_kernel(ConvArgs a, int row_til
   }
 }
 
+// what launch_tconv_edges / launch_tconv_dma check before they launch (host only)
+int tconv_edges_check(const ConvArgs& a, int dtype) {
+  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F16, "tconv_edges: unsupported dtype");
+  MAUA_REQUIRE(a.Ci % 16 == 0 && a.Co % 32 == 0, "tconv_edges: Ci % 16, Co % 32");
+  MAUA_REQUIRE(a.B <= 65535 && a.Co / 32 <= 65535, "tconv_edges: grid too large");
+  return MAUA_OK;
+}
+int tconv_dma_check(const ConvArgs& a, int dtype) {
+  MAUA_REQUIRE(tconv_dma_supported(dtype, a.Ci, a.Co, a.H, a.W), "tconv_dma: unsupported shape");
+  const int tiles = (a.H / PTH) * (a.W / PTW), CB = a.Co / 32, cbg = CB < 8 ? CB : 8;
+  MAUA_REQUIRE(CB % cbg == 0, "tconv_dma: channel blocks must split into groups of 8");
+  const long n_ts = (long)tiles * a.B, grid = ((n_ts + 7) / 8) * 8 * cbg * (CB / cbg);
+  MAUA_REQUIRE(grid < (1L << 31), "tconv_dma: grid too large");
+  return MAUA_OK;
+}
+
 // last row / column of positions; a.x must already carry the styles (as for launch_tconv_dma)
 int launch_tconv_edges(hipStream_t stream, const ConvArgs& a, int dtype) {
-  MAUA_REQUIRE(a.Ci % 16 == 0 && a.Co % 32 == 0, "tconv_edges: Ci % 16, Co % 32");
+  if (int rc = tconv_edges_check(a, dtype)) return rc;
   if (a.B == 0) return MAUA_OK;
   const int row_tiles = (a.W + 1 + 31) / 32, col_tiles = (a.H + 31) / 32;
-  MAUA_REQUIRE(a.B <= 65535 && a.Co / 32 <= 65535, "tconv_edges: grid too large");
   if (dtype == MAUA_F16)
     hipLaunchKernelGGL(tconv_edges_kernel<f16_t>, dim3(row_tiles + col_tiles, a.B, a.Co / 32), dim3(64), 0, stream, a, row_tiles);
   else
@@ -304,12 +319,10 @@ bool tconv_dma_supported(int dtype, int Ci, int Co, int H, int W) {
 // main H x W block of the position grid; a.x must already carry the styles.  The caller adds the last row / column with
 // launch_tconv_edges.
 int launch_tconv_dma(hipStream_t stream, const ConvArgs& a, int dtype) {
-  MAUA_REQUIRE(tconv_dma_supported(dtype, a.Ci, a.Co, a.H, a.W), "tconv_dma: unsupported shape");
+  if (int rc = tconv_dma_check(a, dtype)) return rc;
   if (a.B == 0) return MAUA_OK;
   const int tiles = (a.H / PTH) * (a.W / PTW), CB = a.Co / 32, cbg = CB < 8 ? CB : 8;
-  MAUA_REQUIRE(CB % cbg == 0, "tconv_dma: channel blocks must split into groups of 8");
   const long n_ts = (long)tiles * a.B, grid = ((n_ts + 7) / 8) * 8 * cbg * (CB / cbg);
-  MAUA_REQUIRE(grid < (1L << 31), "tconv_dma: grid too large");
   const size_t smem = std::max<size_t>((size_t)2 * WBUF + 2 * HBUF, (size_t)PTH * PTW * (128 * 2 + 16));
   if (dtype == MAUA_F16) {
     MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)tconv_dma_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));

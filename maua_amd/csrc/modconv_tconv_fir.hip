@@ -327,18 +327,27 @@ bool tconv_fir_supported(int dtype, int Ci, int Co, int H, int W) {
          16L * Co * Ci * 2 < (1L << 32);
 }
 
-// the whole up-layer: a = the transposed convolution's arguments (x already multiplied by the styles, w from
-// launch_prep_tconv_weights; y unused), u = the FIR / epilogue arguments (t unused; lrelu with 0 <= alpha <= 1, gain > 0)
-int launch_tconv_fir(hipStream_t stream, const ConvArgs& a, const UpfirArgs& u, int dtype) {
+// what launch_tconv_fir checks before it launches (host only)
+int tconv_fir_check(const ConvArgs& a, const UpfirArgs& u, int dtype) {
   MAUA_REQUIRE(tconv_fir_supported(dtype, a.Ci, a.Co, a.H, a.W), "tconv_fir: unsupported shape");
   MAUA_REQUIRE(u.act == MAUA_ACT_LRELU && u.alpha >= 0.f && u.alpha <= 1.f && u.gain > 0.f, "tconv_fir: lrelu epilogue only");
   MAUA_REQUIRE(!u.noise || (((uintptr_t)u.noise % 8) == 0 && u.noise_bstride % 2 == 0), "tconv_fir: noise must be 8-byte aligned");
-  if (a.B == 0) return MAUA_OK;
   const int pth = 8, upr = pth - 2;
   const int tiles = ((a.H + upr - 1) / upr) * ((a.W + 29) / 30), CB = a.Co / 32, cbg = CB < 8 ? CB : 8;
   MAUA_REQUIRE(CB % cbg == 0, "tconv_fir: channel blocks must split into groups of 8");
   const long n_ts = (long)tiles * a.B, grid = ((n_ts + 7) / 8) * 8 * cbg * (CB / cbg);
   MAUA_REQUIRE(grid < (1L << 31), "tconv_fir: grid too large");
+  return MAUA_OK;
+}
+
+// the whole up-layer: a = the transposed convolution's arguments (x already multiplied by the styles, w from
+// launch_prep_tconv_weights; y unused), u = the FIR / epilogue arguments (t unused; lrelu with 0 <= alpha <= 1, gain > 0)
+int launch_tconv_fir(hipStream_t stream, const ConvArgs& a, const UpfirArgs& u, int dtype) {
+  if (int rc = tconv_fir_check(a, u, dtype)) return rc;
+  if (a.B == 0) return MAUA_OK;
+  const int pth = 8, upr = pth - 2;
+  const int tiles = ((a.H + upr - 1) / upr) * ((a.W + 29) / 30), CB = a.Co / 32, cbg = CB < 8 ? CB : 8;
+  const long n_ts = (long)tiles * a.B, grid = ((n_ts + 7) / 8) * 8 * cbg * (CB / cbg);
   const size_t smem = std::max<size_t>((size_t)2 * WBUF + 2 * (pth + 1) * HW1 * KB, (size_t)pth * PTW * ES);
   if (dtype == MAUA_F16) {
     MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)tconv_fir_kernel<8, f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));

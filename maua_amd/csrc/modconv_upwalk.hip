@@ -744,7 +744,8 @@ bool upwalk_fused_supported(int dtype, int Ci, int Cm, int H, int W) {
   return (dtype == MAUA_BF16 || dtype == MAUA_F16) && Ci == 64 && Cm == 32 && H >= 2 && W >= 2 && (long)H * W * 4 * 3 < (1L << 31);
 }
 
-int launch_upwalk_fused(hipStream_t stream, const HiresArgs& up, const HiresArgs& c1, int force_segs, int narrow_ok, int dtype) {
+// what launch_upwalk_fused checks before it launches (host only)
+int upwalk_fused_check(const HiresArgs& up, const HiresArgs& c1, int dtype) {
   if (up.B == 0) return MAUA_OK;
   MAUA_REQUIRE(upwalk_fused_supported(dtype, up.Ci, up.Co, up.H, up.W) && c1.Ci == up.Co && c1.Co == up.Co &&
                    c1.H == 2 * up.H && c1.W == 2 * up.W && up.up == 2 && c1.up == 1,
@@ -752,14 +753,22 @@ int launch_upwalk_fused(hipStream_t stream, const HiresArgs& up, const HiresArgs
   MAUA_REQUIRE((long)up.H * up.W * up.Ci * 2 < (1L << 31), "upwalk_fused: a sample must stay below 2 GiB");
   MAUA_REQUIRE(c1.rgb_out && c1.rgb_wmod && c1.rgb_bias, "upwalk_fused: needs the block's toRGB (the features are not stored)");
   MAUA_REQUIRE(!c1.rgb_skip_f32 || c1.rgb8_out, "upwalk_fused: no output");
+  for (const HiresArgs* q : {&up, &c1}) {
+    MAUA_REQUIRE(q->act == MAUA_ACT_LRELU || q->act == MAUA_ACT_LINEAR, "upwalk_fused: lrelu / linear only");
+    const float alpha = q->act == MAUA_ACT_LINEAR ? 1.f : q->alpha;
+    MAUA_REQUIRE(alpha >= 0.f && alpha <= 1.f && q->gain > 0.f, "upwalk_fused: needs 0 <= alpha <= 1 and gain > 0");
+  }
+  return MAUA_OK;
+}
+
+int launch_upwalk_fused(hipStream_t stream, const HiresArgs& up, const HiresArgs& c1, int force_segs, int narrow_ok, int dtype) {
+  if (int rc = upwalk_fused_check(up, c1, dtype)) return rc;
+  if (up.B == 0) return MAUA_OK;
   WalkFusedArgs A;
   A.up = up;
   A.c1 = c1;
-  for (HiresArgs* q : {&A.up, &A.c1}) {
-    MAUA_REQUIRE(q->act == MAUA_ACT_LRELU || q->act == MAUA_ACT_LINEAR, "upwalk_fused: lrelu / linear only");
+  for (HiresArgs* q : {&A.up, &A.c1})
     if (q->act == MAUA_ACT_LINEAR) q->alpha = 1.f;
-    MAUA_REQUIRE(q->alpha >= 0.f && q->alpha <= 1.f && q->gain > 0.f, "upwalk_fused: needs 0 <= alpha <= 1 and gain > 0");
-  }
   constexpr int CI = 64, CM = 32;
   const size_t smem = 2 * 9 * 1024 + 6 * 132 * (CM * 2) + 2 * 3 * 3 * (CI / 16) * 64 * 16 + 3 * 256 * 4 + 2 * CM * 4;
   static const bool want_dbg = getenv("MAUA_UW_DBG") != nullptr;
@@ -820,16 +829,25 @@ bool upwalk_supported(int dtype, int Ci, int Co, int up, int H, int W) {
 
 size_t upwalk_weight_elems(int Co, int Ci) { return (size_t)18 * Co * Ci; }
 
-int launch_upwalk(hipStream_t stream, const HiresArgs& a, int dtype) {
+// what launch_upwalk checks before it launches, its grid included (host only)
+int upwalk_check(const HiresArgs& a, int dtype) {
   if (a.B == 0) return MAUA_OK;
   MAUA_REQUIRE(upwalk_supported(dtype, a.Ci, a.Co, a.up, a.H, a.W), "upwalk: unsupported shape");
   MAUA_REQUIRE((long)a.H * 2 * a.W * 2 * std::max(a.Ci, a.Co) * 2 < (1L << 31),
                "upwalk: a sample must stay below 2 GiB (32-bit in-sample offsets)");
   MAUA_REQUIRE(a.act == MAUA_ACT_LRELU || a.act == MAUA_ACT_LINEAR, "upwalk: lrelu / linear only");
   MAUA_REQUIRE(a.y && !a.rgb_out, "upwalk: features out, no toRGB fusion");
+  const float alpha = a.act == MAUA_ACT_LINEAR ? 1.f : a.alpha;
+  MAUA_REQUIRE(alpha >= 0.f && alpha <= 1.f && a.gain > 0.f, "upwalk: needs 0 <= alpha <= 1 and gain > 0");
+  MAUA_REQUIRE(a.B <= 65535 && std::max(1, a.H / 16) <= 65535, "upwalk: grid too large");
+  return MAUA_OK;
+}
+
+int launch_upwalk(hipStream_t stream, const HiresArgs& a, int dtype) {
+  if (int rc = upwalk_check(a, dtype)) return rc;
+  if (a.B == 0) return MAUA_OK;
   HiresArgs b = a;
   if (a.act == MAUA_ACT_LINEAR) b.alpha = 1.f;
-  MAUA_REQUIRE(b.alpha >= 0.f && b.alpha <= 1.f && b.gain > 0.f, "upwalk: needs 0 <= alpha <= 1 and gain > 0");
   constexpr int CI = 64, CO = 32;
   const size_t smem = 2 * (UW_TW + 2) * (CI * 2 + 16) + 4 * (2 * UW_TW) * (CO * 2) + 2 * 3 * (CI / 16) * 64 * 16 + CO * 4;
   auto kern = dtype == MAUA_F16 ? upwalk_kernel<CI, CO, f16_t> : upwalk_kernel<CI, CO, bf16_t>;

@@ -314,7 +314,8 @@ static bool reads_premod(Route r) { return r == Route::TconvFir || r == Route::T
 
 // Every launch of the next forward, decided from the net's state alone (shapes, dtype, options, hooks, feature capture, the
 // premod buffer) and from whether the caller wants u8 frames.  No HIP calls.
-static Plan plan_forward(const maua_synth* n, bool want_u8) {
+// have_xm: the premod buffer exists (ensure_workspace allocates it when some up-layer fits the LDS-direct transposed convolution)
+static Plan plan_forward(const maua_synth* n, bool want_u8, bool have_xm) {
   const size_t L = n->convs.size();
   Plan p;
   p.conv.resize(L);
@@ -346,7 +347,7 @@ static Plan plan_forward(const maua_synth* n, bool want_u8) {
           if (s.rgb) {
             s.scale_next = true;
             p.conv[li + 1].src = Src::Producer;
-          } else if (n->dual_store && n->xm && !next_replaced) {
+          } else if (n->dual_store && have_xm && !next_replaced) {
             s.scale_next = s.dual = true;
             p.conv[li + 1].src = Src::Xm;
           }
@@ -394,13 +395,8 @@ static Plan plan_forward(const maua_synth* n, bool want_u8) {
   return p;
 }
 
-template <typename A>  // ConvArgs / HiresArgs / UpfirArgs
-static void lrelu_epilogue(A& a) {
-  a.act = MAUA_ACT_LRELU;
-  a.alpha = 0.2f;
-  a.gain = std::sqrt(2.0f);
-  a.clamp = 256.f;
-}
+// every synthesis layer's epilogue: lrelu 0.2, gain sqrt 2, clamp 256
+static Epilogue lrelu_epilogue() { return Epilogue{MAUA_ACT_LRELU, 0.2f, std::sqrt(2.0f), 256.f}; }
 
 extern "C" {
 
@@ -470,9 +466,7 @@ int maua_synth_create(maua_ctx* ctx, int img_resolution, int w_dim, int channel_
     maua_synth_destroy(n);
     return fail(std::string("maua_synth_create: hipMalloc: ") + hipGetErrorString(e));
   }
-  const float g4[4] = {0.25f, 0.75f, 0.75f, 0.25f};  // upsample2d: f*gain(4) = outer(g4,g4)
-  for (int u = 0; u < 4; u++)
-    for (int v = 0; v < 4; v++) n->fir[u * 4 + v] = g4[u] * g4[v];
+  upsample_fir16(n->fir);
   *out = n;
   return MAUA_OK;
 }
@@ -714,7 +708,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
   MAUA_REQUIRE(img_out || rgb8_out, "maua_synth_forward: no output buffer");
   if (B == 0) return MAUA_OK;
   if (int rc = ensure_workspace(n, B)) return rc;
-  const Plan plan = plan_forward(n, rgb8_out != nullptr);
+  const Plan plan = plan_forward(n, rgb8_out != nullptr, n->xm != nullptr);
   hipStream_t st = n->ctx->stream;
   const int ntab = (int)(n->convs.size() + n->rgbs.size());
   int max_c = 0;
@@ -740,27 +734,23 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
     if (int rc = resize_feat(n->const_x, 0, 1, 4, 4, n->convs[0].Ci, n->const_rs)) return rc;
     x = n->const_rs;
   }
-  auto set_noise = [&](auto& a, size_t li) {  // (ConvArgs / HiresArgs / UpfirArgs)
+  auto layer_noise = [&](size_t li) {
     const ConvLayer& c = n->convs[li];
     const bool given = noise && noise[li];
-    a.noise = given ? noise[li] : c.noise_const;
-    a.noise_bstride = given ? (noise_bstride ? noise_bstride[li] : (long)c.oh * c.ow) : 0;
-    a.noise_strength = (n->nv_compat & 2) ? c.noise_strength : 1.f;
+    NoiseOperands z;
+    z.noise = given ? noise[li] : c.noise_const;
+    z.bstride = given ? (noise_bstride ? noise_bstride[li] : (long)c.oh * c.ow) : 0;
+    z.strength = (n->nv_compat & 2) ? c.noise_strength : 1.f;
     // (un-normalised Loop maps: the factor 1 / (rms + eps) of each sample rides on the noise strength; only with caller-supplied maps)
-    a.noise_scale = (n->nz_scales && given) ? n->nz_scales + (long)li * n->nz_scale_stride : nullptr;
+    z.scale = (n->nz_scales && given) ? n->nz_scales + (long)li * n->nz_scale_stride : nullptr;
+    return z;
   };
   auto layer_args = [&](auto a, size_t li, const void* in, void* out) {  // what every modulated 3x3 launch shares (ConvArgs / HiresArgs)
     const ConvLayer& c = n->convs[li];
-    a.x = in; a.w = c.wt; a.s = c.s; a.d = c.d; a.bias = c.bias; a.y = out;
-    a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = c.up;
-    set_noise(a, li);
-    lrelu_epilogue(a);
-    return a;
+    return maua::layer_args(a, LayerOperands{in, c.wt, c.s, c.d, c.bias, out, B, c.ih, c.iw, c.Ci, c.Co, c.up}, layer_noise(li),
+                            lrelu_epilogue());
   };
-  auto pack_u8 = [&](HiresArgs& a) {  // the final frame packed to u8 in the same epilogue
-    a.rgb8_out = rgb8_out;
-    a.rgb_skip_f32 = img_out == nullptr;  // (nobody reads the f32 image)
-  };
+  auto pack_u8 = [&](HiresArgs& a) { pack_u8_args(a, rgb8_out, img_out == nullptr); };
   const float* prev_img = nullptr;
   int img_cur = 0;
   size_t li = 0;
@@ -769,8 +759,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
     const RgbLayer& g = n->rgbs[blk];
     float* rgb_out = (blk == n->nblocks - 1 && img_out) ? img_out : n->img[img_cur];
     auto fuse_torgb = [&](auto& a) {  // the block's toRGB + skip in the epilogue (ConvArgs / HiresArgs)
-      a.rgb_wmod = g.wmod; a.rgb_bias = g.bias; a.rgb_prev = prev_img; a.rgb_out = rgb_out; a.rgb_clamp = 256.f;
-      memcpy(a.fir, n->fir, sizeof(a.fir));
+      fuse_torgb_args(a, g.wmod, g.bias, prev_img, rgb_out, 256.f, n->fir);
     };
     for (int k = 0; k < nconv; k++, li++) {
       const ConvLayer& c = n->convs[li];
@@ -816,13 +805,8 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
         case Route::TconvFir:
         case Route::TconvDma:
         case Route::Tconv2: {
-          ConvArgs a{};
-          a.x = x; a.x_bstride = x_bstride; a.w = c.wt_t; a.s = c.s; a.y = n->tbuf;
-          a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = 2;
-          UpfirArgs u{};
-          u.y = y; u.d = c.d; u.bias = c.bias; u.out_scale = next_s; u.B = B; u.H = c.ih; u.W = c.iw; u.Co = c.Co;
-          set_noise(u, li);
-          lrelu_epilogue(u);
+          ConvArgs a = tconv_args(x, x_bstride, c.wt_t, c.s, n->tbuf, B, c.ih, c.iw, c.Ci, c.Co);
+          UpfirArgs u = upfir_args(y, c.d, c.bias, next_s, B, c.ih, c.iw, c.Co, layer_noise(li), lrelu_epilogue());
           if (s.src == Src::PremodPass)  // (the input is small: inputs up to 64^2 at 1024^2 networks)
             if (int rc = launch_premod_nhwc(st, x, x_bstride, c.s, n->xm, B, (long)c.ih * c.iw, c.Ci, n->dtype)) return rc;
           if (s.src == Src::PremodPass || s.src == Src::Xm) {
@@ -912,6 +896,28 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
       if (int rc = launch_pack_rgb8(st, prev_img, rgb8_out, B, n->out_h, n->out_w)) return rc;
     prof_mark(n);  // zero-length when the last block's epilogue packed the frame
   }
+  return MAUA_OK;
+}
+
+// the plan of the next forward as plain ints (host only, no launch): what a test pins so that a threshold edit shows up as a diff
+int maua_synth_get_plan(maua_synth* n, int want_u8, int* conv_out, int capacity, int* rgb_out, int* pack, int* n_layers) {
+  MAUA_REQUIRE(n && n_layers, "maua_synth_get_plan: NULL argument");
+  bool have_xm = n->xm != nullptr;
+  if (!n->bcap)   // no workspace yet: what ensure_workspace will decide
+    for (auto& c : n->convs) have_xm = have_xm || tconv_dma_fits(n, c);
+  const Plan p = plan_forward(n, want_u8 != 0, have_xm);
+  *n_layers = (int)p.conv.size();
+  if (conv_out) {
+    MAUA_REQUIRE(capacity >= (int)p.conv.size(), "maua_synth_get_plan: capacity too small");
+    for (size_t i = 0; i < p.conv.size(); i++) {
+      const Step& s = p.conv[i];
+      const int v[7] = {(int)s.route, (int)s.src, s.scale_next, s.dual, s.rgb, s.rgb8, s.skip_store};
+      memcpy(conv_out + 7 * i, v, sizeof(v));
+    }
+  }
+  if (rgb_out)
+    for (int b = 0; b < n->nblocks; b++) rgb_out[b] = (int)p.rgb[b];
+  if (pack) *pack = p.pack;
   return MAUA_OK;
 }
 

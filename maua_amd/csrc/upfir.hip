@@ -157,8 +157,10 @@ __global__ __launch_bounds__(256) void upfir_epilogue_kernel(UpfirArgs a) {
   }
 }
 
-int launch_upfir_epilogue(hipStream_t stream, int dtype, const UpfirArgs& a) {
+// what launch_upfir_epilogue checks before it launches (host only)
+int upfir_check(int dtype, const UpfirArgs& a) {
   if (a.B == 0) return MAUA_OK;
+  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F16 || dtype == MAUA_F32, "upfir_epilogue: unsupported dtype");
   const int epc = dtype == MAUA_F32 ? 4 : 8;
   MAUA_REQUIRE(a.Co % epc == 0, "upfir_epilogue: Co must be a multiple of the 16-byte piece");
   MAUA_REQUIRE(!a.out_scale || ((uintptr_t)a.out_scale % 16) == 0, "upfir_epilogue: out_scale must be 16-byte aligned");
@@ -168,6 +170,14 @@ int launch_upfir_epilogue(hipStream_t stream, int dtype, const UpfirArgs& a) {
                "upfir_epilogue: noise must be 8-byte aligned");
   MAUA_REQUIRE((long)(2 * a.H + 1) * (2 * a.W + 1) * a.Co * (dtype == MAUA_F32 ? 4 : 2) < (1L << 31),
                "upfir_epilogue: a sample of t must stay below 2 GiB (32-bit offsets)");
+  MAUA_REQUIRE(a.B <= 65535, "upfir_epilogue: grid too large");
+  return MAUA_OK;
+}
+
+int launch_upfir_epilogue(hipStream_t stream, int dtype, const UpfirArgs& a) {
+  if (int rc = upfir_check(dtype, a)) return rc;
+  if (a.B == 0) return MAUA_OK;
+  const int epc = dtype == MAUA_F32 ? 4 : 8;
   const long total = (long)((2 * a.H + UPFIR_ROWS - 1) / UPFIR_ROWS) * a.W * (a.Co / epc);
   const dim3 grid((unsigned)((total + 255) / 256), a.B);
   const bool lr = a.act == MAUA_ACT_LRELU && a.alpha >= 0.f && a.alpha <= 1.f && a.gain > 0.f;  // folded-gain fast path
