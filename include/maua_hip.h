@@ -514,6 +514,32 @@ int maua_attention_causal(maua_ctx* ctx, const void* qkv, void* out, int B, int 
 /* its input gradient (autograd through QKVAttentionLegacy.forward): d_out [B][T][heads * head_ch] -> d_qkv like qkv */
 int maua_attention_legacy_vjp(maua_ctx* ctx, const void* qkv, const void* d_out, void* d_qkv, int B, int T, int heads, int head_ch,
                               int dtype);
+/* the fused attention kernels behind the three entry points above, the diffusion UNet and both CLIP towers with every launch argument
+ * in the caller's hand, for parity tests (no reference counterpart).  Per (sample b, head h), rows t of qkv at (b T + t) ld_qkv + 3 h
+ * head_ch + {0 | head_ch | 2 head_ch}: out[(b T + t) ld_out + h head_ch + c] = sum_j softmax_j(scale q_t . k_j) v_j[c], with causal != 0
+ * over the keys j <= t only; lse (optional, float [B][heads][T]): log sum_j exp(scale q_t . k_j), what the gradient rebuilds the
+ * weights from.  Strides in elements of dtype (MAUA_F32 or MAUA_BF16).  Checked: head_ch 32 or 64, T > 0, B and heads <= 65535, qkv
+ * and out 16-byte aligned, ld_qkv >= 3 heads head_ch and ld_out >= heads head_ch, both whole 16-byte pieces.  B == 0: nothing is done. */
+typedef struct {
+  const void* qkv; void* out; float* lse;
+  int B, T, heads, head_ch; long ld_qkv, ld_out;
+  float scale; int causal; int dtype;
+} maua_attn_desc;
+/* the input gradient: d_out (laid out like out) -> d_qkv (like qkv).  out and lse are operands: the forward's result and log-sum-exp
+ * rows as the caller has them; delta: float workspace [B][heads][T], left holding the rows' d_out . out.  The same checks, on every
+ * pointer; causal != 0 is refused (there is no gradient of the causal forward). */
+typedef struct {
+  const void* qkv; const void* out; const void* d_out; const float* lse; void* d_qkv; float* delta;
+  int B, T, heads, head_ch; long ld_qkv, ld_out;
+  float scale; int causal; int dtype;
+} maua_attn_vjp_desc;
+/* host only, no device needed: MAUA_OK, or MAUA_ERR + maua_last_error() with the launcher's own message.  Pointers are only checked,
+ * never dereferenced. */
+int maua_attention_check(const maua_attn_desc* d);
+int maua_attention_vjp_check(const maua_attn_vjp_desc* d);
+/* launch on the context's stream (the gradient: its three kernels); refused, with no launch, as the check refuses */
+int maua_attention_ex(maua_ctx* ctx, const maua_attn_desc* d);
+int maua_attention_vjp_ex(maua_ctx* ctx, const maua_attn_vjp_desc* d);
 /* conv_nd(1, K, N, 1) / a linear layer over rows (AttentionBlock.qkv / proj_out + residual, ResBlock.skip_connection):
  * c[M][N] = a[M][K] x w[N][K]^T + bias[N] (+ res[M][N]); K % 32 (bf16) / 16 (f32) == 0, N % 32 == 0 */
 int maua_linear_nt(maua_ctx* ctx, const void* a, const void* w, const float* bias, const void* res, void* c, long M, int N,

@@ -179,6 +179,21 @@ class ModconvDesc(C.Structure):
                 ("t", C.c_void_p)]
 
 
+class AttnDesc(C.Structure):
+    """maua_attn_desc (include/maua_hip.h): one attention forward for maua_attention_check / maua_attention_ex; pointers as integers."""
+    _fields_ = [("qkv", C.c_void_p), ("out", C.c_void_p), ("lse", C.c_void_p),
+                ("B", C.c_int), ("T", C.c_int), ("heads", C.c_int), ("head_ch", C.c_int), ("ld_qkv", C.c_long), ("ld_out", C.c_long),
+                ("scale", C.c_float), ("causal", C.c_int), ("dtype", C.c_int)]
+
+
+class AttnVjpDesc(C.Structure):
+    """maua_attn_vjp_desc (include/maua_hip.h): its input gradient for maua_attention_vjp_check / maua_attention_vjp_ex."""
+    _fields_ = [("qkv", C.c_void_p), ("out", C.c_void_p), ("d_out", C.c_void_p), ("lse", C.c_void_p), ("d_qkv", C.c_void_p),
+                ("delta", C.c_void_p),
+                ("B", C.c_int), ("T", C.c_int), ("heads", C.c_int), ("head_ch", C.c_int), ("ld_qkv", C.c_long), ("ld_out", C.c_long),
+                ("scale", C.c_float), ("causal", C.c_int), ("dtype", C.c_int)]
+
+
 # routes of maua_modconv_route / maua_modconv_ex and of maua_synth_get_plan (csrc/synth.hip's Route enum; UPFIR: the FIR / epilogue pass alone)
 ROUTES = {"lowres": 0, "generic": 1, "dma_conv1": 2, "hires": 3, "upwalk": 4, "fused_walk": 5, "walk_done": 6, "tconv_fir": 7,
           "tconv_dma": 8, "tconv2": 9, "upfir": 10}

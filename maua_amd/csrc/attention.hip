@@ -207,10 +207,21 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
 
 bool attention_supported(int head_ch) { return head_ch == 32 || head_ch == 64; }
 
-int launch_attention(hipStream_t stream, int dtype, const AttnArgs& a) {
+int attention_check(int dtype, const AttnArgs& a) {
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "attention: unsupported dtype");
   MAUA_REQUIRE(attention_supported(a.D), "attention: head channels must be 32 or 64");
-  MAUA_REQUIRE(a.qkv && a.out && a.T > 0 && a.heads > 0 && a.B <= 65535 && a.heads <= 65535, "attention: bad arguments");
+  MAUA_REQUIRE(a.qkv && a.out, "attention: NULL qkv / out");
+  MAUA_REQUIRE(a.B >= 0 && a.T > 0 && a.heads > 0, "attention: bad shape");
+  MAUA_REQUIRE(a.B <= 65535 && a.heads <= 65535, "attention: grid too large");
+  const long es = dtype == MAUA_BF16 ? 2 : 4;
+  MAUA_REQUIRE(((uintptr_t)a.qkv | (uintptr_t)a.out) % 16 == 0 && (uintptr_t)a.lse % 4 == 0, "attention: qkv / out must be 16-byte aligned");
+  MAUA_REQUIRE(a.ld_qkv >= 3L * a.heads * a.D && a.ld_out >= (long)a.heads * a.D, "attention: row strides below the heads' channels");
+  MAUA_REQUIRE(a.ld_qkv * es % 16 == 0 && a.ld_out * es % 16 == 0, "attention: row strides must be whole 16-byte pieces");
+  return MAUA_OK;
+}
+
+int launch_attention(hipStream_t stream, int dtype, const AttnArgs& a) {
+  if (int rc = attention_check(dtype, a)) return rc;
   if (a.B == 0) return MAUA_OK;
   dim3 grid((unsigned)((a.T + 127) / 128), (unsigned)a.heads, (unsigned)a.B);
 #define MAUA_ATTN(TT, DD)                                                                             \

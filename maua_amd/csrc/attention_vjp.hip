@@ -277,11 +277,24 @@ __global__ __launch_bounds__(256) void attention_vjp_kernel(AttnVjpArgs a) {
 
 }  // namespace
 
-int launch_attention_vjp(hipStream_t stream, int dtype, const AttnVjpArgs& a) {
+int attention_vjp_check(int dtype, const AttnVjpArgs& a) {
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "attention_vjp: unsupported dtype");
   MAUA_REQUIRE(attention_supported(a.D), "attention_vjp: head channels must be 32 or 64");
-  MAUA_REQUIRE(a.qkv && a.out && a.d_out && a.lse && a.d_qkv && a.delta && a.T > 0 && a.heads > 0 && a.B <= 65535 && a.heads <= 65535,
-               "attention_vjp: bad arguments");
+  MAUA_REQUIRE(!a.causal, "attention_vjp: no gradient of the causal forward");
+  MAUA_REQUIRE(a.qkv && a.out && a.d_out && a.lse && a.d_qkv && a.delta, "attention_vjp: NULL argument");
+  MAUA_REQUIRE(a.B >= 0 && a.T > 0 && a.heads > 0, "attention_vjp: bad shape");
+  MAUA_REQUIRE(a.B <= 65535 && a.heads <= 65535, "attention_vjp: grid too large");
+  const long es = dtype == MAUA_BF16 ? 2 : 4;
+  MAUA_REQUIRE(((uintptr_t)a.qkv | (uintptr_t)a.out | (uintptr_t)a.d_out | (uintptr_t)a.d_qkv) % 16 == 0 &&
+                   ((uintptr_t)a.lse | (uintptr_t)a.delta) % 4 == 0,
+               "attention_vjp: qkv / out / d_out / d_qkv must be 16-byte aligned");
+  MAUA_REQUIRE(a.ld_qkv >= 3L * a.heads * a.D && a.ld_out >= (long)a.heads * a.D, "attention_vjp: row strides below the heads' channels");
+  MAUA_REQUIRE(a.ld_qkv * es % 16 == 0 && a.ld_out * es % 16 == 0, "attention_vjp: row strides must be whole 16-byte pieces");
+  return MAUA_OK;
+}
+
+int launch_attention_vjp(hipStream_t stream, int dtype, const AttnVjpArgs& a) {
+  if (int rc = attention_vjp_check(dtype, a)) return rc;
   if (a.B == 0) return MAUA_OK;
   const long rows = (long)a.B * a.T * a.heads * (a.D * (dtype == MAUA_BF16 ? 2 : 4) / 16);   // 16-byte pieces of out / d_out
   dim3 grid((unsigned)((a.T + 127) / 128), (unsigned)a.heads, (unsigned)a.B);

@@ -369,10 +369,13 @@ struct AttnArgs {
   long ld_qkv, ld_out;
   float scale;          // 1 / sqrt(D)
   float* lse;           // optional [B][heads][T]: each row's log-sum-exp of the scaled scores (what the input gradient needs)
-  int causal;           // != 0: query i sees keys 0 .. i only (CLIP's text tower); forward only - attention_vjp.hip ignores it
+  int causal;           // != 0: query i sees keys 0 .. i only (CLIP's text tower); forward only - attention_vjp.hip refuses it
 };
 bool attention_supported(int head_ch);
 int launch_attention(hipStream_t stream, int dtype, const AttnArgs& a);
+// what launch_attention checks before it launches (host only, no HIP call; MAUA_ERR + last error when refused): every access of the
+// kernel is a 16-byte vector, so qkv / out and both row strides are whole 16-byte pieces; the strides cover the heads' channels
+int attention_check(int dtype, const AttnArgs& a);
 
 // attention_vjp.hip: the input gradient of launch_attention.  d_out [B][T][ld_out] -> d_qkv [B][T][ld_qkv]; lse = what the
 // forward left in AttnArgs.lse, out = its result; workspace: B * heads * T floats (the rows' sum d_out . out)
@@ -386,8 +389,10 @@ struct AttnVjpArgs {
   int B, T, heads, D;
   long ld_qkv, ld_out;
   float scale;
+  int causal;           // must be 0: there is no gradient of the causal forward (attention_vjp_check refuses it)
 };
 int launch_attention_vjp(hipStream_t stream, int dtype, const AttnVjpArgs& a);
+int attention_vjp_check(int dtype, const AttnVjpArgs& a);   // host only: launch_attention_vjp's refusals
 
 // groupnorm_vjp.hip: the input gradient of the UNet's GroupNorm (+ scale-shift) (+ SiLU) (+ resample) pass over [x0 | x1]
 // ([B][H][W][C0 | C1], dense NHWC in the network dtype).  dy, dres: [B][Ho][Wo][C0 + C1] at the forward's output size (dres: the
