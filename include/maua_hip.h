@@ -711,6 +711,15 @@ int maua_clip_create(maua_ctx* ctx, int input_resolution, int patch_size, int wi
                      maua_clip** out);
 void maua_clip_destroy(maua_clip* net);
 int maua_clip_load(maua_clip* net, const char* name, const float* host_data, size_t count);
+/* Any patch size that divides the input: a patch row of 3 * patch_size^2 values is held at a stride rounded up to a multiple of 64
+ * (ViT-L/14: 588 -> 640; 16 / 32-pixel patches: unchanged), zero-padded, so the patch embedding and its transpose stay plain GEMMs.
+ * The cutouts of a guidance call go through the tower in groups: as many cutouts per pass as the kernels' index ranges and a byte
+ * budget allow - kept activations + workspace per image (10 x [tokens][width] per layer: ViT-L/14 ~137 MB, @336px ~307 MB in bf16)
+ * plus the cutouts' scratch.  bytes = 0 (default): the device's free memory when a guidance call (or the guided loop) first sees a
+ * batch shape, plus what the tower already holds, less a reserve of 1/8 (at least 2 GiB); bytes > 0: that budget.  The group size
+ * stays fixed for a batch shape / cutn until the limit changes; the gradient is the sum over groups in a fixed order.  One cutout
+ * (B images) is never split: a budget below it is refused, with the bytes it needs in the message. */
+int maua_clip_set_workspace_limit(maua_clip* net, size_t bytes);
 /* VisionTransformer.forward (clip/model.py): images device f32 [N][3][R][R], already normalised -> embeds device f32 [N][E];
  * keep != 0 keeps the activations for maua_clip_encode_image_vjp: d_embeds [N][E] -> d_images [N][3][R][R] */
 int maua_clip_encode_image(maua_clip* net, const float* images, int N, int keep, float* embeds);

@@ -25,14 +25,20 @@ from . import _lib as L
 from .clip_tokenizer import tokenize  # noqa: F401  (clip.tokenize)
 
 # name -> (input_resolution, patch_size, width, layers, heads, output_dim): clip/model.py build_model on the released checkpoints
+# (heads = width // 64).  CLIP is not installed here: the shapes of the published checkpoints are restated, not read from them.
 VISION_CONFIGS = {
     "ViT-B/32": (224, 32, 768, 12, 12, 512),
     "ViT-B/16": (224, 16, 768, 12, 12, 512),
+    "ViT-L/14": (224, 14, 1024, 24, 16, 768),
+    "ViT-L/14@336px": (336, 14, 1024, 24, 16, 768),
 }
 # name -> (context_length, vocab_size, width, layers, heads, embed_dim): the text half of build_model on the released checkpoints
+# (restated likewise; heads = width // 64)
 TEXT_CONFIGS = {
     "ViT-B/32": (77, 49408, 512, 12, 8, 512),
     "ViT-B/16": (77, 49408, 512, 12, 8, 512),
+    "ViT-L/14": (77, 49408, 768, 12, 12, 768),
+    "ViT-L/14@336px": (77, 49408, 768, 12, 12, 768),
 }
 # entries of a whole CLIP state dict (or a TorchScript archive's) that belong to neither tower's parameters
 _NON_TEXT_KEYS = ("logit_scale", "input_resolution", "context_length", "vocab_size")
@@ -157,6 +163,11 @@ class VisionTransformer(torch.nn.Module):
                 L.check(L.lib().maua_clip_load(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
             self._dirty = False
         return self._h
+
+    def set_workspace_limit(self, nbytes=0):
+        """Bytes one pass through the tower may take in a guidance call (kept activations, workspace, cutout scratch): the cutouts of
+        a call go through in groups that fit.  0 (default): from the device's free memory.  ``maua_clip_set_workspace_limit``."""
+        L.check(L.lib().maua_clip_set_workspace_limit(self._handle(), C.c_size_t(int(nbytes))))
 
     # ------------------------------------------------------------------ forward / input gradient
     def forward(self, x, keep=False):
@@ -380,7 +391,7 @@ def load(name, jit=False, dtype=torch.bfloat16, state_dict=None, allow_random_in
     only with ``allow_random_init``); False - never.  ``bpe_path``: the tokenizer's vocabulary for string prompts."""
     if name not in VISION_CONFIGS:
         raise NotImplementedError(f"perceptor {name!r}: this build has the ViT image towers {sorted(VISION_CONFIGS)} "
-                                  "(ResNet towers and ViT-L/14's 14-pixel patches are not built)")
+                                  "(the ResNet towers are not built)")
     vt = VisionTransformer(*VISION_CONFIGS[name], dtype=dtype, generator=generator)
     if state_dict is None:
         path = os.path.expanduser(f"~/.cache/clip/{name.replace('/', '-')}.pt")

@@ -7,7 +7,7 @@
 // The library has no autograd: the gradient is the network walked backwards by hand, activations only (the perceptor's weights are
 // frozen, `requires_grad_(False)`, :106).
 //
-//   forward   patch rows [N * G^2][3 p p]  --GEMM conv1-->  [N * G^2][w]  -> tokens [N][T = G^2 + 1][w] (class token, + positional
+//   forward   patch rows [N * G^2][kpp >= 3 p p]  --GEMM conv1-->  [N * G^2][w]  -> tokens [N][T = G^2 + 1][w] (class token, + positional
 //             embedding) -> ln_pre -> L x { x += out_proj(attention(in_proj(ln_1(x))));  x += c_proj(QuickGELU(c_fc(ln_2(x)))) }
 //             -> ln_post(class token) @ proj -> embedding [N][E]
 //   head      per image, one workgroup, float32: ln_post, projection, F.normalize, distance 2 asin(|e - y| / 2)^2 to each target,
@@ -221,25 +221,26 @@ __global__ __launch_bounds__(256) void tokens_kernel(const T* __restrict__ pe, c
   Pc<T>::store(tok + nt * C + (long)pc * E, v);
 }
 
-// planar f32 images [N][3][R][R] <-> patch rows [N * G * G][3 p p] (k = c p p + ky p + kx: conv1.weight flattened); the patch
-// convolution has stride = kernel, so this is a permutation and its transpose
+// planar f32 images [N][3][R][R] <-> patch rows [N * G * G][ld] (k = c p p + ky p + kx < 3 p p: conv1.weight flattened); the patch
+// convolution has stride = kernel, so this is a permutation and its transpose.  ld >= 3 p p: the row stride (maua_clip::kpp); the
+// columns past 3 p p are not touched here (zeroed when the buffer is allocated / zeros out of the backward GEMM)
 template <typename T>
-__global__ __launch_bounds__(256) void im2patch_kernel(const float* __restrict__ img, T* __restrict__ rows, long N, int R, int p) {
+__global__ __launch_bounds__(256) void im2patch_kernel(const float* __restrict__ img, T* __restrict__ rows, long N, int R, int p, int ld) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= N * 3 * R * R) return;
   const int x = (int)(idx % R), y = (int)((idx / R) % R), c = (int)((idx / ((long)R * R)) % 3);
   const long n = idx / ((long)3 * R * R);
   const int G = R / p;
-  Elem<T>::store(rows + (n * G * G + (long)(y / p) * G + x / p) * (3 * p * p) + c * p * p + (y % p) * p + x % p, img[idx]);
+  Elem<T>::store(rows + (n * G * G + (long)(y / p) * G + x / p) * ld + c * p * p + (y % p) * p + x % p, img[idx]);
 }
 template <typename T>
-__global__ __launch_bounds__(256) void patch2im_kernel(const T* __restrict__ rows, float* __restrict__ img, long N, int R, int p) {
+__global__ __launch_bounds__(256) void patch2im_kernel(const T* __restrict__ rows, float* __restrict__ img, long N, int R, int p, int ld) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= N * 3 * R * R) return;
   const int x = (int)(idx % R), y = (int)((idx / R) % R), c = (int)((idx / ((long)R * R)) % 3);
   const long n = idx / ((long)3 * R * R);
   const int G = R / p;
-  img[idx] = Elem<T>::load(rows + (n * G * G + (long)(y / p) * G + x / p) * (3 * p * p) + c * p * p + (y % p) * p + x % p);
+  img[idx] = Elem<T>::load(rows + (n * G * G + (long)(y / p) * G + x / p) * ld + c * p * p + (y % p) * p + x % p);
 }
 
 // ------------------------------------------------------------------------------------------------ the head (per image, float32)
@@ -416,7 +417,12 @@ struct maua_clip {
   int dtype;
   size_t esize;
   int res, patch, width, layers, heads, E, G, Tk, kp;   // G = res / patch, Tk = G * G + 1 tokens, kp = 3 * patch^2
-  void *w_conv = nullptr, *w_conv_t = nullptr;          // [w][kp], [kp][w]
+  // kpp: elements between patch rows = kp rounded up to a multiple of 64 (one rule for both dtypes: the GEMMs take K in 64-byte
+  // chunks, the LDS-direct kernel in 64 elements).  p = 16 / 32: kpp == kp (768 / 3072); p = 14: 588 -> 640.  The pad columns of
+  // `patches` are zeroed by a kernel when the buffer is (re)allocated and no writer touches them afterwards; conv1.weight's pad
+  // columns (and its transpose's pad rows) are zeros, so the backward GEMM writes zeros there and the readers stop at kp.
+  int kpp;
+  void *w_conv = nullptr, *w_conv_t = nullptr;          // [w][kpp], [kpp][w]
   float *cls = nullptr, *pos = nullptr, *lnpre_g = nullptr, *lnpre_b = nullptr, *lnpost_g = nullptr, *lnpost_b = nullptr, *proj = nullptr;
   std::vector<maua::Layer> L;
   // workspaces for `cap` images
@@ -426,6 +432,10 @@ struct maua_clip {
   void *dxa = nullptr, *dxb = nullptr, *dqkv = nullptr, *dwide = nullptr, *dtmp = nullptr;
   float *st_pre = nullptr, *delta = nullptr, *embed = nullptr, *loss = nullptr;
   long kept_N = 0;         // images of the last kept forward (0: none)
+  // cutouts per pass through the tower, fixed by clip_prepare_guide for (grp_B, grp_H, grp_W, grp_cutn, grp_aug) until one of them or
+  // the limit changes (0: not fixed yet).  ws_limit: bytes one pass may take (maua_clip_set_workspace_limit; 0 = from free memory)
+  int grp = 0, grp_B = 0, grp_H = 0, grp_W = 0, grp_cutn = 0, grp_aug = 0;
+  size_t ws_limit = 0;
   // targets
   float *tgt = nullptr, *twt = nullptr;
   int S = 0, P = 0;
@@ -489,7 +499,7 @@ int ensure_ws(maua_clip* n, long N, int keep) {
   keep = std::max(keep, n->keep);
   free_ws(n);
   const size_t es = n->esize, w = n->width, M = (size_t)N * n->Tk, Mp = (size_t)N * n->G * n->G;
-  int rc = dalloc(&n->patches, Mp * n->kp * es);
+  int rc = dalloc(&n->patches, Mp * n->kpp * es);
   if (!rc) rc = dalloc(&n->pe, Mp * w * es);
   if (!rc) rc = dalloc(&n->tok, M * w * es);
   if (!rc) rc = dalloc(&n->x_last, M * w * es);
@@ -502,7 +512,7 @@ int ensure_ws(maua_clip* n, long N, int keep) {
     rc = dalloc(&n->dxa, M * w * es);
     if (!rc) rc = dalloc(&n->dxb, M * w * es);
     if (!rc) rc = dalloc(&n->dqkv, M * 3 * w * es);
-    if (!rc) rc = dalloc(&n->dwide, M * 4 * w * es);
+    if (!rc) rc = dalloc(&n->dwide, std::max(M * 4 * w, Mp * n->kpp) * es);   // (d act [M][4 w], later d patches [Mp][kpp])
     if (!rc) rc = dalloc(&n->dtmp, M * w * es);
     if (!rc) rc = dalloc((void**)&n->delta, (size_t)N * n->heads * n->Tk * 4);
   }
@@ -519,8 +529,23 @@ int ensure_ws(maua_clip* n, long N, int keep) {
     if (!rc) rc = dalloc((void**)&l.lse, (size_t)N * n->heads * n->Tk * 4);
   }
   if (rc) { free_ws(n); return fail("maua_clip: out of device memory for the image tower's activations"); }
+  if (n->kpp != n->kp) {   // the pad columns of the patch rows: zero from here on (no writer touches them); a kernel, like zero_dx
+    const long pieces = (long)(Mp * n->kpp * es / 16);
+    hipLaunchKernelGGL(zero16_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, n->ctx->stream, (u32x4*)n->patches, pieces);
+    MAUA_HIP_CHECK(hipGetLastError());
+    MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
+  }
   n->cap = N; n->keep = keep;
   return MAUA_OK;
+}
+
+// bytes ensure_ws(N, keep = 1) allocates per image (every buffer there is a multiple of the image count)
+size_t ws_bytes_per_image(const maua_clip* n) {
+  const size_t es = n->esize, w = n->width, T = n->Tk, Gp = (size_t)n->G * n->G, hd = n->heads;
+  size_t b = Gp * n->kpp * es + Gp * w * es + 3 * T * w * es + T * 4 * w * es + T * 8 + (size_t)n->E * 4 + 4;       // forward
+  b += 3 * T * w * es + T * 3 * w * es + std::max(T * 4 * w, Gp * n->kpp) * es + hd * T * 4;                      // backward
+  b += (size_t)n->layers * (10 * T * w * es + T * 16 + hd * T * 4);                                              // kept, per layer
+  return b;
 }
 
 int gemm(maua_clip* n, const void* a, long M, int K, const void* w, int N, const float* bias, const void* res, void* c, int epi = 0,
@@ -549,7 +574,7 @@ int run_forward(maua_clip* n, long N, bool keep) {
   const long M = N * Tk, Mp = N * n->G * n->G;
   constexpr int E = 16 / (int)sizeof(T);
   // patch embedding (conv1, no bias) -> tokens -> ln_pre
-  if (int rc = gemm(n, n->patches, Mp, n->kp, n->w_conv, w, nullptr, nullptr, n->pe)) return rc;
+  if (int rc = gemm(n, n->patches, Mp, n->kpp, n->w_conv, w, nullptr, nullptr, n->pe)) return rc;
   {
     const long total = M * (w / E);
     hipLaunchKernelGGL(tokens_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const T*)n->pe, n->cls, n->pos, (T*)n->tok, N,
@@ -640,7 +665,7 @@ int run_backward(maua_clip* n, long N) {
   // ln_pre backwards (dropping the class token: its inputs are parameters), then the patch embedding's transpose
   hipLaunchKernelGGL(layer_norm_vjp_kernel<T>, lgrid, dim3(256), 0, st, (const T*)n->tok, n->st_pre, n->lnpre_g, (const T*)dx, (const T*)nullptr,
                      (T*)n->dtmp, M, w, Tk);
-  if (int rc = gemm(n, n->dtmp, Mp, w, n->w_conv_t, n->kp, nullptr, nullptr, n->dwide)) return rc;
+  if (int rc = gemm(n, n->dtmp, Mp, w, n->w_conv_t, n->kpp, nullptr, nullptr, n->dwide)) return rc;
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -911,7 +936,7 @@ int clip_grad_group(maua_clip* n, const float* img, int B, int H, int W, const i
   p.img = img; p.rects = rects_dev; p.B = B; p.H = H; p.W = W; p.n_cut = n_cut; p.cs = n->res; p.mul = 0.5f; p.add = 0.5f;
   const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, sd[3] = {0.26862954f, 0.26130258f, 0.27577711f};   // grad.py:110
   for (int c = 0; c < 3; c++) { p.mean[c] = mean[c]; p.std[c] = sd[c]; }
-  p.patch = n->patch;
+  p.patch = n->patch; p.patch_ld = n->kpp;
   if (int rc = launch_cutout_tables(st, p, n->cut_tables)) return rc;
   if (int rc = launch_cutouts_forward(st, n->dtype, p, n->cut_tables, n->patches)) return rc;
   if (int rc = forward_any(n, N, true)) return rc;
@@ -921,9 +946,50 @@ int clip_grad_group(maua_clip* n, const float* img, int B, int H, int W, const i
   return launch_cutouts_vjp(st, n->dtype, p, n->cut_tables, n->dwide, n->cut_th, grad, accumulate);
 }
 
-// workspaces of a guidance call (all allocations happen here, none inside clip_grad_group: a captured loop calls this first)
-int clip_prepare_guide(maua_clip* n, int B, int H, int W, int n_cut_group) {
+// Cutouts per pass through the tower.  Shape bounds: 32-bit byte offsets inside the GEMM operands, <= 65535 images.  Byte budget:
+// one pass keeps ws_bytes_per_image() of activations and workspace per image, plus the cutouts' own scratch (tables, the horizontal
+// adjoint's rows, the augmented cutouts' two f32 buffers); the group is capped so that one pass fits in
+//   * ws_limit, when maua_clip_set_workspace_limit set one, else
+//   * the device's free memory now + what this tower's workspaces already hold, less a reserve of 1/8 of that and at least 2 GiB
+//     (the networks beside the tower plan their own workspaces after this call; fragmentation).
+// A cutout is B images and cannot be split: below that the call is refused with the bytes one cutout needs.
+size_t cutout_bytes(const maua_clip* n, int B, int H, int W, int aug_side) {   // of ONE cutout of the batch
+  const size_t per_image = ws_bytes_per_image(n) + (size_t)3 * n->res * std::min(H, W) * 4 + (size_t)2 * 3 * aug_side * aug_side * 4;
+  return per_image * (size_t)B + (size_t)n->res * (4 + 4 * 16) + 4;
+}
+int group_size(maua_clip* n, int B, int H, int W, int cutn, int aug_side, int* out) {
+  const long max_images = std::min<long>(65535, ((1L << 32) - 1) / ((long)n->Tk * 4 * n->width * (long)n->esize));
+  long grp = std::max<long>(1, std::min<long>(cutn, max_images / std::max(B, 1)));
+  const size_t one = cutout_bytes(n, B, H, W, aug_side);
+  size_t budget = n->ws_limit;
+  if (!budget) {
+    size_t free_b = 0, total_b = 0;
+    MAUA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    const size_t avail = free_b + (size_t)n->cap * ws_bytes_per_image(n) * (n->keep ? 1 : 0);
+    const size_t reserve = std::max<size_t>(avail / 8, (size_t)2 << 30);
+    budget = avail > reserve ? avail - reserve : 0;
+  }
+  if (budget / one < (size_t)grp) grp = (long)(budget / one);
+  if (grp < 1)
+    return fail("maua_clip: one cutout of this batch (" + std::to_string(B) + " images) needs " + std::to_string(one) +
+                " bytes of tower workspace, the budget is " + std::to_string(budget) +
+                (n->ws_limit ? " (maua_clip_set_workspace_limit)" : " (free device memory less the reserve)"));
+  *out = (int)grp;
+  return MAUA_OK;
+}
+
+// workspaces of a guidance call (all allocations happen here, none inside clip_grad_group: a captured loop calls this first), and
+// the group size its passes run with: fixed here, and kept while the batch shape, cutn and the limit stay the same - a captured loop
+// replays it, and a call's float32 sum over groups keeps its order from call to call
+int clip_prepare_guide(maua_clip* n, int B, int H, int W, int cutn, int aug_side) {
   MAUA_REQUIRE(n->tgt && n->P > 0, "maua_clip: no targets (maua_clip_set_targets)");
+  if (!(n->grp > 0 && n->grp_B == B && n->grp_H == H && n->grp_W == W && n->grp_cutn == cutn && n->grp_aug == aug_side)) {
+    int grp = 0;
+    if (int rc = group_size(n, B, H, W, cutn, aug_side, &grp)) return rc;
+    if (grp != n->grp) n->epoch++;   // (a captured loop holds the old split)
+    n->grp = grp; n->grp_B = B; n->grp_H = H; n->grp_W = W; n->grp_cutn = cutn; n->grp_aug = aug_side;
+  }
+  const int n_cut_group = n->grp;
   if (int rc = ensure_ws(n, (long)n_cut_group * B, 1)) return rc;
   const size_t tb = cutouts_table_bytes(n_cut_group, n->res), thb = cutouts_th_bytes(n_cut_group, B, n->res, std::min(H, W));
   if (tb > n->cut_tables_bytes || thb > n->cut_th_bytes || !n->parts) {
@@ -940,18 +1006,13 @@ int clip_prepare_guide(maua_clip* n, int B, int H, int W, int n_cut_group) {
   return MAUA_OK;
 }
 
-// cutouts per pass through the tower: all of a cutout batch when they fit (32-bit byte offsets inside the GEMM operands, <= 65535 images)
-int clip_group_size(maua_clip* n, int B, int cutn) {
-  const long max_images = std::min<long>(65535, ((1L << 32) - 1) / ((long)n->Tk * 4 * n->width * (long)n->esize));
-  return (int)std::max<long>(1, std::min<long>(cutn, max_images / std::max(B, 1)));
-}
-
 // the whole of CLIPGrads.forward (:145-159) on device rectangles [batches][cutn][3].  mult_dev: NULL, or [batches][cutn] multiplicities -
 // cutout n stands for mult identical cutouts of the reference's list (on a square image its first cutn // 4 cutouts are the same
 // rectangle, cutouts.py:16-27: one pass through the tower carries their weight) and cutn_total = what the multiplicities of a batch sum to
 int clip_guide_grad(maua_clip* n, const float* img, int B, int H, int W, const int* rects_dev, const float* mult_dev, int cutn, int cutn_total,
                     int batches, float scale, float clamp_gradient, float* grad) {
-  const int grp = clip_group_size(n, B, cutn);
+  MAUA_REQUIRE(n->grp > 0 && n->grp_B == B && n->grp_cutn == cutn, "maua_clip: clip_prepare_guide was not called for this batch / cutn");
+  const int grp = n->grp;   // fixed by clip_prepare_guide; the gradient is the sum over groups in this fixed order
   const float coef = 1.f / ((float)cutn_total * (float)batches);
   bool first = true;
   for (int k = 0; k < batches; k++)
@@ -990,7 +1051,7 @@ int clip_grad_group_aug(maua_clip* n, const float* img, int B, int H, int W, con
     if (int rc = aug_forward_out(st, MAUA_F32, recs, n_cut, B, S, 0, n->aug_x1, n->aug_x2, 0, zero3, one3)) return rc;
     p.img = n->aug_x2; p.rects = slot_rects_dev; p.H = S; p.W = S; p.mul = 1.f; p.add = 0.f; p.img_stride = (long)B * 3 * S * S;
     for (int c = 0; c < 3; c++) { p.mean[c] = mean[c]; p.std[c] = sd[c]; }
-    p.patch = n->patch;
+    p.patch = n->patch; p.patch_ld = n->kpp;
     if (int rc = launch_cutout_tables(st, p, n->cut_tables)) return rc;
     if (int rc = launch_cutouts_forward(st, n->dtype, p, n->cut_tables, n->patches)) return rc;
     if (int rc = forward_any(n, N, true)) return rc;
@@ -1007,12 +1068,12 @@ int clip_grad_group_aug(maua_clip* n, const float* img, int B, int H, int W, con
   if (int rc = launch_cutout_tables(st, p, n->cut_tables)) return rc;
   if (int rc = launch_cutouts_forward(st, MAUA_F32, p, n->cut_tables, n->aug_x2)) return rc;
   if (int rc = aug_forward_src(st, recs, 1, (int)N, cs, noise_i0, n->aug_x2, cs, cs, 1.f, 0.f, n->aug_x1)) return rc;
-  if (int rc = aug_forward_out(st, n->dtype, recs, 1, (int)N, cs, noise_i0, n->aug_x1, n->patches, n->patch, mean, sd)) return rc;
+  if (int rc = aug_forward_out(st, n->dtype, recs, 1, (int)N, cs, noise_i0, n->aug_x1, n->patches, n->patch, mean, sd, n->kpp)) return rc;
   if (int rc = forward_any(n, N, true)) return rc;
   if (int rc = zero_dx(n, N)) return rc;
   if (int rc = run_head(n, N, true, nullptr, B, coef, true, nullptr)) return rc;
   if (int rc = backward_any(n, N)) return rc;
-  if (int rc = aug_adjoint_out(st, n->dtype, recs, 1, (int)N, cs, n->dwide, n->patch, sd, n->aug_x2)) return rc;
+  if (int rc = aug_adjoint_out(st, n->dtype, recs, 1, (int)N, cs, n->dwide, n->patch, sd, n->aug_x2, n->kpp)) return rc;
   if (int rc = aug_adjoint_src(st, recs, 1, (int)N, cs, n->aug_x2, cs, cs, 1.f, n->aug_x1, 0)) return rc;
   return launch_cutouts_vjp(st, MAUA_F32, p, n->cut_tables, n->aug_x1, n->cut_th, grad, accumulate);
 }
@@ -1029,15 +1090,14 @@ int maua_clip_create(maua_ctx* ctx, int input_resolution, int patch_size, int wi
   MAUA_REQUIRE(width > 0 && heads > 0 && width % heads == 0 && attention_supported(width / heads), "maua_clip_create: head width must be 32 or 64");
   const int epc = dtype == MAUA_BF16 ? 8 : 4, kc = dtype == MAUA_BF16 ? 32 : 16;
   MAUA_REQUIRE(width % 32 == 0 && width % kc == 0 && width / epc <= 64 * LN_MAXP, "maua_clip_create: width must be a multiple of 32 (at most 4096 / 2048)");
-  MAUA_REQUIRE((3 * patch_size * patch_size) % 32 == 0, "maua_clip_create: 3 * patch_size^2 must be a multiple of 32");
   MAUA_REQUIRE(layers > 0 && output_dim > 0, "maua_clip_create: bad layer count / embedding size");
-  MAUA_REQUIRE(3 * patch_size * patch_size <= 4 * width, "maua_clip_create: a patch row must not be wider than the MLP (shared workspace)");
   maua_clip* n = new maua_clip();
   static std::atomic<unsigned long long> next_uid{1};
   n->uid = next_uid.fetch_add(1);
   n->ctx = ctx; n->dtype = dtype; n->esize = dtype == MAUA_BF16 ? 2 : 4;
   n->res = input_resolution; n->patch = patch_size; n->width = width; n->layers = layers; n->heads = heads; n->E = output_dim;
   n->G = input_resolution / patch_size; n->Tk = n->G * n->G + 1; n->kp = 3 * patch_size * patch_size;
+  n->kpp = (n->kp + 63) / 64 * 64;
   n->L.resize(layers);
   *out = n;
   return MAUA_OK;
@@ -1058,6 +1118,13 @@ void maua_clip_destroy(maua_clip* n) {
   delete n;
 }
 
+// bytes one pass through the tower may take in a guidance call (kept activations, workspace, cutout scratch); 0: automatic
+int maua_clip_set_workspace_limit(maua_clip* n, size_t bytes) {
+  MAUA_REQUIRE(n, "maua_clip_set_workspace_limit: NULL argument");
+  if (bytes != n->ws_limit) { n->ws_limit = bytes; n->grp = 0; }   // the next guidance call fixes the group size anew
+  return MAUA_OK;
+}
+
 // name: a key of CLIP's state dict below "visual." ("conv1.weight", "class_embedding", "positional_embedding", "ln_pre.weight", ...,
 // "transformer.resblocks.<i>.attn.in_proj_weight", ..., "ln_post.bias", "proj"); host float32 data in the checkpoint's layout
 int maua_clip_load(maua_clip* n, const char* name, const float* host, size_t count) {
@@ -1069,7 +1136,13 @@ int maua_clip_load(maua_clip* n, const char* name, const float* host, size_t cou
     if (count != c) return fail("maua_clip_load: " + s + ": wrong size");
     return MAUA_OK;
   };
-  if (s == "conv1.weight") { if (int rc = need((size_t)w * n->kp)) return rc; return upload_matrix(n, host, w, n->kp, nullptr, &n->w_conv, &n->w_conv_t); }
+  if (s == "conv1.weight") {   // rows padded with zeros to kpp: [w][kpp] and its transpose [kpp][w]
+    if (int rc = need((size_t)w * n->kp)) return rc;
+    if (n->kpp == n->kp) return upload_matrix(n, host, w, n->kp, nullptr, &n->w_conv, &n->w_conv_t);
+    std::vector<float> padded((size_t)w * n->kpp, 0.f);
+    for (int r = 0; r < w; r++) memcpy(&padded[(size_t)r * n->kpp], host + (size_t)r * n->kp, (size_t)n->kp * 4);
+    return upload_matrix(n, padded.data(), w, n->kpp, nullptr, &n->w_conv, &n->w_conv_t);
+  }
   if (s == "class_embedding") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &n->cls); }
   if (s == "positional_embedding") { if (int rc = need((size_t)n->Tk * w)) return rc; return upload_vec(host, (size_t)n->Tk * w, nullptr, &n->pos); }
   if (s == "ln_pre.weight") { if (int rc = need(w)) return rc; return upload_vec(host, w, nullptr, &n->lnpre_g); }
@@ -1100,9 +1173,9 @@ int maua_clip_encode_image(maua_clip* n, const float* images, int N, int keep, f
   hipStream_t st = n->ctx->stream;
   const long total = (long)N * 3 * n->res * n->res;
   if (n->dtype == MAUA_BF16)
-    hipLaunchKernelGGL(im2patch_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, images, (bf16_t*)n->patches, (long)N, n->res, n->patch);
+    hipLaunchKernelGGL(im2patch_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, images, (bf16_t*)n->patches, (long)N, n->res, n->patch, n->kpp);
   else
-    hipLaunchKernelGGL(im2patch_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, images, (float*)n->patches, (long)N, n->res, n->patch);
+    hipLaunchKernelGGL(im2patch_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, images, (float*)n->patches, (long)N, n->res, n->patch, n->kpp);
   if (int rc = forward_any(n, N, keep != 0)) return rc;
   if (int rc = run_head(n, N, false, nullptr, 1, 0.f, false)) return rc;
   MAUA_HIP_CHECK(hipMemcpyAsync(embeds, n->embed, (size_t)N * n->E * 4, hipMemcpyDeviceToDevice, st));
@@ -1119,9 +1192,9 @@ int maua_clip_encode_image_vjp(maua_clip* n, const float* d_embeds, int N, float
   if (int rc = backward_any(n, N)) return rc;
   const long total = (long)N * 3 * n->res * n->res;
   if (n->dtype == MAUA_BF16)
-    hipLaunchKernelGGL(patch2im_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)n->dwide, d_images, (long)N, n->res, n->patch);
+    hipLaunchKernelGGL(patch2im_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)n->dwide, d_images, (long)N, n->res, n->patch, n->kpp);
   else
-    hipLaunchKernelGGL(patch2im_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)n->dwide, d_images, (long)N, n->res, n->patch);
+    hipLaunchKernelGGL(patch2im_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)n->dwide, d_images, (long)N, n->res, n->patch, n->kpp);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -1206,7 +1279,7 @@ int maua_clip_guide_grad(maua_clip* n, const float* img, int B, int H, int W, co
   MAUA_HIP_CHECK(hipMemcpyAsync(n->rects_dev, rects, (size_t)batches * cutn * 12, hipMemcpyHostToDevice, n->ctx->stream));
   if (mult) MAUA_HIP_CHECK(hipMemcpyAsync(mult_dev, mult, (size_t)batches * cutn * 4, hipMemcpyHostToDevice, n->ctx->stream));
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));   // (the caller's arrays may be temporaries)
-  if (int rc = clip_prepare_guide(n, B, H, W, clip_group_size(n, B, cutn))) return rc;
+  if (int rc = clip_prepare_guide(n, B, H, W, cutn)) return rc;
   return clip_guide_grad(n, img, B, H, W, n->rects_dev, mult_dev, cutn, cutn_total, batches, scale, clamp_gradient, grad);
 }
 
@@ -1231,8 +1304,9 @@ int maua_clip_guide_grad_aug(maua_clip* n, const float* img, int B, int H, int W
   std::vector<char> recs((size_t)n_rec * aug_record_bytes());
   if (int rc = aug_records(augs, n_rec, per_call ? nullptr : rects, n->res, keys, per_call ? 1 : cutn, recs.data())) return rc;
   hipStream_t st = n->ctx->stream;
-  const int grp = clip_group_size(n, B, cutn);
   const int S = per_call ? n->res : std::min(H, W);
+  if (int rc = clip_prepare_guide(n, B, H, W, cutn, S)) return rc;
+  const int grp = n->grp;
   const size_t xb = (size_t)grp * B * 3 * S * S * 4;
   if ((size_t)total * 24 > n->aug_rects_cap || recs.size() > n->aug_recs_cap || xb > n->aug_x_bytes) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
@@ -1260,7 +1334,6 @@ int maua_clip_guide_grad_aug(maua_clip* n, const float* img, int B, int H, int W
   MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_rects + 3 * total, slot.data(), (size_t)total * 12, hipMemcpyHostToDevice, st));
   MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_recs, recs.data(), recs.size(), hipMemcpyHostToDevice, st));
   MAUA_HIP_CHECK(hipStreamSynchronize(st));   // (the host vectors die with this call)
-  if (int rc = clip_prepare_guide(n, B, H, W, grp)) return rc;
   const float coef = 1.f / ((float)cutn * (float)batches);
   const size_t rb = aug_record_bytes();
   bool first = true;

@@ -162,7 +162,7 @@ struct AugArgs {
   float* a_out;
   void* out;             // forward (2): planar f32 [n_rec * nimg][3][S][S] or patch rows (T) of S x S images
   const void* d_out;     // adjoint (1): the same layouts
-  int patch;
+  int patch, patch_ld;   // patch_ld: elements between patch rows (>= 3 p p; the columns past 3 p p are neither written nor read)
   float mean[3], inv_std[3];
   float* dst;            // adjoint (2): [nimg][3][H][W]
   int accumulate;
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void aug_fwd_src_kernel(AugArgs a) {
 template <typename T>
 __device__ __forceinline__ long patch_index(const AugArgs& a, long img, int c, int y, int x) {
   const int p = a.patch, g = a.S / p;
-  return (img * g * g + (long)(y / p) * g + x / p) * (3 * p * p) + c * p * p + (y % p) * p + x % p;
+  return (img * g * g + (long)(y / p) * g + x / p) * a.patch_ld + c * p * p + (y % p) * p + x % p;
 }
 
 template <typename T>
@@ -427,11 +427,12 @@ int aug_forward_src(hipStream_t st, const void* recs, int n_rec, int nimg, int S
 }
 
 int aug_forward_out(hipStream_t st, int dtype, const void* recs, int n_rec, int nimg, int S, int noise_i0, const float* x1, void* out,
-                    int patch, const float* mean3, const float* std3) {
+                    int patch, const float* mean3, const float* std3, int patch_ld) {
   if (int rc = check_grid(n_rec, nimg, S)) return rc;
   MAUA_REQUIRE(patch == 0 || S % patch == 0, "cutout augmentations: the side must be a whole number of patches");
+  MAUA_REQUIRE(patch_ld == 0 || (patch > 0 && patch_ld >= 3 * patch * patch), "cutout augmentations: the patch-row stride is below 3 * patch^2");
   AugArgs a = args(recs, n_rec, nimg, S, noise_i0);
-  a.a = x1; a.out = out; a.patch = patch;
+  a.a = x1; a.out = out; a.patch = patch; a.patch_ld = patch_ld ? patch_ld : 3 * patch * patch;
   for (int c = 0; c < 3; c++) { a.mean[c] = mean3[c]; a.inv_std[c] = 1.f / std3[c]; }
   const dim3 grid((unsigned)cdiv(S, AUG_TX), (unsigned)cdiv(S, AUG_TY), (unsigned)(n_rec * nimg)), block(AUG_TX, AUG_TY);
   if (dtype == MAUA_BF16) hipLaunchKernelGGL(aug_fwd_out_kernel<bf16_t>, grid, block, 0, st, a);
@@ -441,11 +442,12 @@ int aug_forward_out(hipStream_t st, int dtype, const void* recs, int n_rec, int 
 }
 
 int aug_adjoint_out(hipStream_t st, int dtype, const void* recs, int n_rec, int nimg, int S, const void* d_out, int patch,
-                    const float* std3, float* d_a) {
+                    const float* std3, float* d_a, int patch_ld) {
   if (int rc = check_grid(n_rec, nimg, S)) return rc;
   MAUA_REQUIRE(patch == 0 || S % patch == 0, "cutout augmentations: the side must be a whole number of patches");
+  MAUA_REQUIRE(patch_ld == 0 || (patch > 0 && patch_ld >= 3 * patch * patch), "cutout augmentations: the patch-row stride is below 3 * patch^2");
   AugArgs a = args(recs, n_rec, nimg, S, 0);
-  a.d_out = d_out; a.patch = patch; a.a_out = d_a;
+  a.d_out = d_out; a.patch = patch; a.patch_ld = patch_ld ? patch_ld : 3 * patch * patch; a.a_out = d_a;
   for (int c = 0; c < 3; c++) a.inv_std[c] = 1.f / std3[c];
   const dim3 grid((unsigned)cdiv(S, AUG_TX), (unsigned)cdiv(S, AUG_TY), (unsigned)(n_rec * nimg)), block(AUG_TX, AUG_TY);
   if (dtype == MAUA_BF16) hipLaunchKernelGGL(aug_adj_out_kernel<bf16_t>, grid, block, 0, st, a);

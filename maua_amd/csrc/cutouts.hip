@@ -86,8 +86,9 @@ struct CutArgs {
   int B, H, W, n_cut, cs;
   float mul, add;        // the affine applied to the image before the cutouts ((img + 1) / 2: 0.5, 0.5)
   float mean[3], inv_std[3];
-  void* out;             // planar f32 [n_cut * B][3][cs][cs] or patch rows (T) [n_cut * B * (cs / p)^2][3 p p]
+  void* out;             // planar f32 [n_cut * B][3][cs][cs] or patch rows (T) [n_cut * B * (cs / p)^2][patch_ld]
   int patch;             // 0: planar f32; p: patch rows
+  int patch_ld;          // elements between patch rows (>= 3 p p; the columns past 3 p p are never written and never read here)
   int smax;              // row stride of the horizontal-adjoint buffer = the largest cutout size
   long img_stride;       // CutoutPlan::img_stride
 };
@@ -99,7 +100,7 @@ __device__ __forceinline__ void store_px(const CutArgs& a, long image, int c, in
   } else {
     const int p = a.patch, g = a.cs / p;
     const long row = image * g * g + (long)(y / p) * g + x / p;
-    Elem<T>::store(reinterpret_cast<T*>(a.out) + row * (3 * p * p) + c * p * p + (y % p) * p + x % p, v);
+    Elem<T>::store(reinterpret_cast<T*>(a.out) + row * a.patch_ld + c * p * p + (y % p) * p + x % p, v);
   }
 }
 template <typename T>
@@ -107,7 +108,7 @@ __device__ __forceinline__ float load_px(const CutArgs& a, const void* d, long i
   if (a.patch == 0) return reinterpret_cast<const float*>(d)[((image * 3 + c) * a.cs + y) * a.cs + x];
   const int p = a.patch, g = a.cs / p;
   const long row = image * g * g + (long)(y / p) * g + x / p;
-  return Elem<T>::load(reinterpret_cast<const T*>(d) + row * (3 * p * p) + c * p * p + (y % p) * p + x % p);
+  return Elem<T>::load(reinterpret_cast<const T*>(d) + row * a.patch_ld + c * p * p + (y % p) * p + x % p);
 }
 
 // grid (bands, 3, n_cut * B); LDS: [CT_BAND][size] floats
@@ -245,7 +246,8 @@ static int fill(CutArgs& a, const CutoutPlan& p, void* tables) {
   MAUA_REQUIRE(std::min(p.H, p.W) <= 4 * p.cs - 1, "cutouts: images of more than 4 x the cut size need more than 16 filter taps");
   a.img = p.img; a.rects = p.rects; a.B = p.B; a.H = p.H; a.W = p.W; a.n_cut = p.n_cut; a.cs = p.cs; a.mul = p.mul; a.add = p.add;
   for (int c = 0; c < 3; c++) { a.mean[c] = p.mean[c]; a.inv_std[c] = 1.f / p.std[c]; }
-  a.patch = p.patch; a.smax = std::min(p.H, p.W); a.img_stride = p.img_stride;
+  MAUA_REQUIRE(p.patch_ld == 0 || (p.patch > 0 && p.patch_ld >= 3 * p.patch * p.patch), "cutouts: the patch-row stride is below 3 * patch^2");
+  a.patch = p.patch; a.patch_ld = p.patch_ld ? p.patch_ld : 3 * p.patch * p.patch; a.smax = std::min(p.H, p.W); a.img_stride = p.img_stride;
   char* t = (char*)tables;
   a.left = (const int*)t;
   a.wts = (const float*)(t + (size_t)p.n_cut * p.cs * 4);

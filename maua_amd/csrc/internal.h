@@ -420,7 +420,8 @@ int launch_group_norm_vjp(hipStream_t stream, int dtype, const GnVjpArgs& a, voi
 
 // cutouts.hip: random cutouts resized to the perceptor's input (maua/ops/cutouts.py:8-50 as CLIPGrads calls it) and their gradient.
 // rects: DEVICE [n_cut][3] (size, top, left); tables: cutouts_table_bytes() of device scratch filled by launch_cutout_tables;
-// out / d_out: planar f32 [n_cut * B][3][cs][cs] (patch == 0) or patch rows in dtype [n_cut * B * (cs / patch)^2][3 * patch^2];
+// out / d_out: planar f32 [n_cut * B][3][cs][cs] (patch == 0) or patch rows in dtype [n_cut * B * (cs / patch)^2][patch_ld]
+// (patch_ld >= 3 * patch^2 elements between rows, 0 = dense; the columns past 3 * patch^2 belong to the caller: never written, never read);
 // th: cutouts_th_bytes() of scratch; grad: [B][3][H][W] f32
 // a rectangle's size entry carries two flags in its high bits (DangoCutouts, cutouts.py:171-199): the cutout is converted to
 // 3-channel luma (torchvision Grayscale(3): 0.2989 r + 0.587 g + 0.114 b) / mirrored horizontally (TF.hflip)
@@ -432,6 +433,7 @@ struct CutoutPlan {
   float mul, add;          // affine applied to the image first ((img + 1) / 2: 0.5, 0.5)
   float mean[3], std[3];   // Normalize applied to the cutouts
   int patch;
+  int patch_ld;            // patch rows: elements between rows (0 = 3 * patch^2)
   long img_stride;         // 0: every cutout reads the same image batch; else cutout n reads its own batch at img + n * img_stride
 };                         // (and the gradient goes to its own slot grad + n * img_stride: the augmented crops of cutout_augs.hip)
 size_t cutouts_table_bytes(int n_cut, int cs);
@@ -450,9 +452,9 @@ int aug_records(const float* augs, int n_rec, const int* rects, int side, const 
 int aug_forward_src(hipStream_t st, const void* recs, int n_rec, int nimg, int S, int noise_i0, const float* src, int H, int W, float mul,
                     float add, float* x1);
 int aug_forward_out(hipStream_t st, int dtype, const void* recs, int n_rec, int nimg, int S, int noise_i0, const float* x1, void* out,
-                    int patch, const float* mean3, const float* std3);
+                    int patch, const float* mean3, const float* std3, int patch_ld = 0);   // patch_ld: as CutoutPlan's
 int aug_adjoint_out(hipStream_t st, int dtype, const void* recs, int n_rec, int nimg, int S, const void* d_out, int patch,
-                    const float* std3, float* d_a);
+                    const float* std3, float* d_a, int patch_ld = 0);
 int aug_adjoint_src(hipStream_t st, const void* recs, int n_rec, int nimg, int S, const float* d_a, int H, int W, float mul, float* dst,
                     int accumulate);
 
@@ -481,8 +483,9 @@ void secondary_stamp(maua_secondary* n, unsigned long long* uid, unsigned long l
 // clip_guide_grad = CLIPGrads.forward on DEVICE rectangles [batches][cutn][3]
 maua_ctx* clip_ctx(maua_clip* n);
 void clip_stamp(maua_clip* n, unsigned long long* uid, unsigned long long* epoch);
-int clip_group_size(maua_clip* n, int B, int cutn);
-int clip_prepare_guide(maua_clip* n, int B, int H, int W, int n_cut_group);
+// clip_prepare_guide also fixes the cutouts per pass through the tower (shape bounds and the workspace budget, see clip.hip) for
+// the clip_guide_grad calls that follow; aug_side: side of the augmented cutouts' f32 buffers per image (0: plain cutouts)
+int clip_prepare_guide(maua_clip* n, int B, int H, int W, int cutn, int aug_side = 0);
 int clip_guide_grad(maua_clip* n, const float* img, int B, int H, int W, const int* rects_dev, const float* mult_dev, int cutn, int cutn_total,
                     int batches, float scale, float clamp_gradient, float* grad);
 

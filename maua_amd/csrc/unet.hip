@@ -2029,7 +2029,7 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
                        n->gd_rects_host[i + 1] + (n->gd_rects_host[i] & CUT_SIZE_MASK) <= H &&
                        n->gd_rects_host[i + 2] + (n->gd_rects_host[i] & CUT_SIZE_MASK) <= W,
                    "maua_ddim_guided_loop: a cutout leaves the image");
-    if (int rc = clip_prepare_guide(clip, B, H, W, clip_group_size(clip, B, n->gd_cutn))) return rc;
+    if (int rc = clip_prepare_guide(clip, B, H, W, n->gd_cutn)) return rc;
   } else if (n->gd_guides.empty()) {
     MAUA_REQUIRE(target, "maua_ddim_guided_loop: target is NULL");
   }
