@@ -859,6 +859,48 @@ int maua_guide_grad(maua_guide* guide, const float* img, int B, int H, int W, fl
  * ignored).  n_guides == 0: back to the default.  The whole step stays inside the one captured hipGraph. */
 int maua_unet_set_guides(maua_unet* net, maua_guide* const* guides, int n_guides);
 
+/* ---- image operators of the multi-resolution pipeline (maua/diffusion/image.py:132-214: what runs between two scales; csrc/image_ops.hip).
+ * Planar device f32 images [B][3][H][W]; every operator is a gather with a fixed summation order (bit-identical from run to run).
+ *
+ * maua_image_resize: resize_right.resize(img, out_shape=(Ho, Wo), interp_method=...) (diffusion/image.py:66-71 cubic, :180 lanczos3) on
+ * `planes` = B * C planes.  The per-axis tap tables come from the caller (maua_amd/image.py resize_tables: the published float32
+ * arithmetic - kernel stretched by 1 / scale when shrinking, weights normalised per output sample): left_* DEVICE int [out], w_* DEVICE
+ * f32 [out][taps]; source indices outside the image contribute zero (zero padding).  left_y == NULL keeps the rows (H == Ho), left_x
+ * == NULL the columns.  Rows first, then columns.  dst = resized + add, or (dst + resized) + add when accumulate != 0 (the perlin init's
+ * `resize(a) + resize(b) - 1`, :65-69). */
+int maua_image_resize(maua_ctx* ctx, const float* src, int planes, int H, int W, float* dst, int Ho, int Wo, const int* left_y,
+                      const float* w_y, int taps_y, const int* left_x, const float* w_x, int taps_x, int accumulate, float add);
+/* destitch (maua/ops/image.py:15-23): out [(n_rows * n_cols) * B][3][T][T], tile (r, c) of image b at index (r * n_cols + c) * B + b;
+ * ys / xs HOST int arrays: the tile origins (the reference's linspace(0, H - T, n).round(), evaluated by the caller). */
+int maua_image_destitch(maua_ctx* ctx, const float* img, int B, int H, int W, int tile_size, const int* ys, int n_rows, const int* xs,
+                        int n_cols, float* out);
+/* restitch (maua/ops/image.py:26-62): tiles [n_rows * n_cols][3][T][T] -> out [1][3][H][W] = sum tile * wy * wx / sum wy * wx, in the
+ * reference's tile order; wy DEVICE f32 [n_rows][T], wx DEVICE f32 [n_cols][T]: blend_weight1d per tile row / column (smoothstep fades,
+ * none at the image's edges), built by the caller. */
+int maua_image_restitch(maua_ctx* ctx, const float* tiles, int tile_size, const int* ys, int n_rows, const int* xs, int n_cols,
+                        const float* wy, const float* wx, float* out, int H, int W);
+/* sharpen (maua/ops/image.py:70-71: torchvision adjust_sharpness of (img + 1) / 2, back to [-1, 1]): 3x3 blur [[1,1,1],[1,5,1],[1,1,1]] / 13
+ * on interior pixels, border pixels kept, strength * img + (1 - strength) * blurred, clamp to [0, 1]. */
+int maua_image_sharpen(maua_ctx* ctx, const float* img, int B, int H, int W, float strength, float* out);
+/* match_histogram mode "avg" (maua/ops/image.py:105-173) in two steps around a float64 host step (the symmetric square roots of the two
+ * 3x3 covariances and the inverse: maua_amd/image.py).  maua_image_moments: per frame f the 11 partial sums (3 sums, products 00 01 02 11
+ * 12 22, min, max) of every slice of 4096 pixels of value = mean of images f * navg .. + navg - 1 (source.mean(0), :134) + noise_scale *
+ * noise[f] (:141-144; noise optional DEVICE f32 [frames][3][HW]); min / max are of the images alone (:171-173).  partial DEVICE f32
+ * [frames][maua_image_moments_slices(HW)][11].  maua_image_match_apply, one frame [3][HW]: out = scale * (m (img + noise_scale * noise -
+ * mu_t) + mu_s) (+ out when accumulate: a list of sources, :130, :166), clamped to [lo, hi] when clamp; m / mu_t / mu_s HOST f32. */
+int maua_image_moments_slices(long HW);
+int maua_image_moments(maua_ctx* ctx, const float* img, int frames, int navg, long HW, const float* noise, float noise_scale,
+                       float* partial);
+int maua_image_match_apply(maua_ctx* ctx, const float* img, const float* noise, float noise_scale, long HW, const float* m,
+                           const float* mu_t, const float* mu_s, float scale, int accumulate, int clamp, float lo, float hi, float* out);
+/* create_perlin_noise (maua/ops/noise.py:90-132) from given gradient vectors: grads DEVICE f32, per (channel, octave) gx [(w + 1)][(h + 1)]
+ * then gy (torch.randn(2, w + 1, h + 1, 1, 1), :96, with w / h doubling per octave) at element offsets[channel * n_octaves + octave]
+ * (HOST long); octaves HOST f32 [n_octaves]; 1 channel when grayscale, else 3.  The octave sum, clamp(0, 1), to_pil_image's bytes,
+ * ImageOps.autocontrast and to_tensor -> out [3][width << n_octaves][height << n_octaves]; raw (optional): perlin_ms's sum before the
+ * clamp, [channels][..][..].  Uses the context's scratch arena. */
+int maua_image_perlin(maua_ctx* ctx, const float* grads, const long* offsets, const float* octaves, int n_octaves, int width, int height,
+                      int grayscale, float* raw, float* out);
+
 /* ---- build-owned counter RNG: Philox4x32-10, identical on every device / rank and in the oracle twin (oracle/rng.py,
  * pinned to the published known-answer vectors).  No reference counterpart: the reference's random-init generator and noise planes
  * come from torch's host generator (inference/stylegan2.py:216-227, selfsupervised/noise.py:42-53); the benchmark's synthetic

@@ -1039,13 +1039,15 @@ class GuidedDiffusion(torch.nn.Module):
 # ------------------------------------------------------------------- audio-onset-switched prompts (configs[3])
 def get_diffusion_model(diffusion="guided", timesteps: int = 50, sampler: str = "plms", guidance_speed: str = "fast", clip_scale: float = 0.0,
                         lpips_scale: float = 0.0, style_scale: float = 0.0, color_match_scale: float = 0.0, cfg_scale: float = 5.0, image=None,
-                        guided_kwargs=None):
+                        guided_kwargs=None, text_encoder=None, clip_models=None, text=None):
     """maua/diffusion/image.py:76-125 for the guided-diffusion processor: the grad-module list (CLIPGrads, LPIPSGrads, VGGGrads,
     ColorMatchGrads - each only when its scale is positive, in that order) around ``GuidedDiffusion``.  ``guided_kwargs`` (a dict) reach its
     constructor (``allow_random_init`` / ready ``model`` + ``diffusion`` objects: there are no checkpoints in the image; the perceptors
     follow ``allow_random_init``), except ``guided_kwargs["clip_kwargs"]``: a dict for ``CLIPGrads`` (``clip_models``, ``perceptors``,
-    ``text_tower``, ``bpe_path``, ``text_encoder``, ...).  The latent / stable / glide processors are other networks and not part of
-    this build."""
+    ``text_tower``, ``bpe_path``, ``text_encoder``, ...); ``text_encoder`` / ``clip_models`` given directly are passed to ``CLIPGrads``
+    as well.  ``text``: the text prompt the caller is going to use (maua/diffusion/image.py:194-195) - with CLIP guidance on and a
+    perceptor that cannot embed text, this raises here and not inside the first sampler call.  The latent / stable / glide processors
+    are other networks and not part of this build."""
     if isinstance(diffusion, GuidedDiffusion):
         return diffusion
     if diffusion != "guided":
@@ -1053,6 +1055,10 @@ def get_diffusion_model(diffusion="guided", timesteps: int = 50, sampler: str = 
     from .grad import CLIPGrads, ColorMatchGrads, LPIPSGrads, VGGGrads
     guided_kwargs = dict(guided_kwargs or {})
     clip_kwargs = dict(guided_kwargs.pop("clip_kwargs", None) or {})
+    if text_encoder is not None:
+        clip_kwargs["text_encoder"] = text_encoder
+    if clip_models is not None:
+        clip_kwargs["clip_models"] = clip_models
     rnd = dict(allow_random_init=True) if guided_kwargs.get("allow_random_init") else {}
     grad_modules = (
         ([CLIPGrads(scale=clip_scale, **{**rnd, **clip_kwargs})] if clip_scale > 0 else [])
@@ -1060,6 +1066,11 @@ def get_diffusion_model(diffusion="guided", timesteps: int = 50, sampler: str = 
         + ([VGGGrads(scale=style_scale, **rnd)] if style_scale > 0 else [])
         + ([ColorMatchGrads(scale=color_match_scale)] if color_match_scale > 0 else [])
     )
+    if text is not None and clip_scale > 0:
+        for m in grad_modules[0].clip_models:
+            if getattr(m, "text_encoder", None) is None and getattr(m, "text", None) is None and not hasattr(m, "transformer"):
+                raise ValueError("get_diffusion_model: a text prompt needs a text encoder - pass text_encoder= (text -> [1, E] embedding), "
+                                 "clip_models= with a text tower, or guided_kwargs['clip_kwargs'] with text_tower / bpe_path")
     return GuidedDiffusion(grad_modules=grad_modules, sampler=sampler, timesteps=timesteps, speed=guidance_speed, **guided_kwargs)
 
 
