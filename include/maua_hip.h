@@ -901,6 +901,50 @@ int maua_image_match_apply(maua_ctx* ctx, const float* img, const float* noise, 
 int maua_image_perlin(maua_ctx* ctx, const float* grads, const long* offsets, const float* octaves, int n_octaves, int width, int height,
                       int grayscale, float* raw, float* out);
 
+/* ---- optical-flow operators of the video pipeline (maua/diffusion/video.py:125-301 and what it uses of maua/flow/; csrc/flow.hip).
+ * Planar device f32 images [B][3][H][W]; flows [B][H][W][2] in (x, y) order, as the reference holds them.  Gathers only, fixed summation
+ * order, no atomics: a rerun is bit-identical.  No entry point allocates (maua_farneback_create plans the estimator's workspace).
+ *
+ * maua_flow_warp: warp(x, flow_warp_map(flow * exaggeration)) (flow/lib.py:51-63 with diffusion/video.py:161-162) in one launch, the grid
+ * not materialised: pixel (x, y) samples at linspace(-1, 1, W)[x] + exaggeration flow_x / W, linspace(-1, 1, H)[y] + exaggeration flow_y / H
+ * (the reference's normalisation as written: by W and H) with grid_sample(bilinear, padding_mode="reflection", align_corners=False).
+ * img / out [B][C][H][W]. */
+int maua_flow_warp(maua_ctx* ctx, const float* img, const float* flow, float exaggeration, int B, int C, int H, int W, float* out);
+/* check_consistency (flow/consistency.py:78-127; get_consistency_map's "full" mode, flow/lib.py:66-80) per sample: central differences of
+ * the backward flow (zero "same" padding, both channels summed), the forward flow sampled at p + backward (bilinear, align_corners=True,
+ * zero padding), motion_boundary -> 0, missed -> -0.75, overshoot -> 0 in that order, then torchvision's gaussian_blur(kernel_size=3)
+ * (sigma 0.8, reflect padding) and clip(0, 1).  Two launches: classes [B][H][W] (scratch of the caller's) then out [B][H][W].  Flow values
+ * are clamped to +-clamp as they are read (diffusion/video.py:148-149; INFINITY: none). */
+int maua_flow_consistency(maua_ctx* ctx, const float* forward, const float* backward, int B, int H, int W, float clamp, float* classes,
+                          float* out);
+/* F.interpolate(mode="bilinear", align_corners=False) of a channels-last tensor [B][H][W][C] -> [B][out_h][out_w][C] (diffusion/video.py:153-157:
+ * flows, C = 2, and consistency maps, C = 1): dst = interpolate(clamp(src, +-clamp)) * multiplier (:149, :156). */
+int maua_flow_resize_bilinear(maua_ctx* ctx, const float* src, int B, int H, int W, int C, float* dst, int out_h, int out_w, float multiplier,
+                              float clamp);
+/* The frame composition of diffusion/video.py:248-277 in one launch: mask = (consistency trust + 1 - trust) blend (consistency NULL: blend),
+ * init = (frame + mask warp(prev)) / (1 + mask) (prev NULL: frame); cached != NULL: fade init + (1 - fade) cached (:268-269); noise_scale != 0:
+ * + noise_scale z, z = element i of maua_philox_normal(seed, stream 0) for element i of [B][3][H][W] (:277; torch's randn_like values are
+ * not reproduced).  With prev and cached NULL this is the noise step alone (after pre_hook / hist_persist). */
+int maua_flow_compose(maua_ctx* ctx, const float* frame, const float* prev, const float* flow, const float* consistency, const float* cached,
+                      int B, int H, int W, float exaggeration, float trust, float blend, float fade, float noise_scale, unsigned long long seed,
+                      float* out);
+/* One turbo in-between frame (diffusion/video.py:221-238): prev_out = warp(prev) (prev may be NULL), next_out = warp(next) when warp_next
+ * (the t != 0 and f_n < N + wrap_around rule is the caller's), img = prev_out (1 - blend_t) + next' blend_t with next' the warped or the
+ * given next; without prev, img = next'.  One launch. */
+int maua_flow_turbo(maua_ctx* ctx, const float* prev, const float* next, const float* flow, int B, int H, int W, float exaggeration, int warp_next,
+                    float blend_t, float* prev_out, float* next_out, float* img);
+/* Farneback's dense flow (flow/__init__.py:35-55: cv2.calcOpticalFlowFarneback(pyr_scale=0.8, levels=15, winsize=15, iterations=15, poly_n=7,
+ * poly_sigma=1.5, flags=10) of luminance(im).mul(255).byte(), on the host there) restated from the published algorithm: box window, zero
+ * initial flow.  The handle owns a workspace planned for max_h x max_w.  maua_farneback_pair: im_a / im_b [3][H][W] in [0, 1] ->
+ * flow_ab = flow(prev = a, next = b) and flow_ba = flow(b, a), [H][W][2] each, both directions in one batched launch per stage.
+ * maua_farneback_levels: the number of pyramid levels an H x W pair is processed at (host only). */
+typedef struct maua_farneback maua_farneback;
+int maua_farneback_levels(int H, int W);
+int maua_farneback_create(maua_ctx* ctx, int max_h, int max_w, maua_farneback** out);
+int maua_farneback_destroy(maua_farneback* handle);
+int maua_farneback_pair(maua_farneback* handle, maua_ctx* ctx, const float* im_a, const float* im_b, int H, int W, float* flow_ab,
+                        float* flow_ba);
+
 /* ---- build-owned counter RNG: Philox4x32-10, identical on every device / rank and in the oracle twin (oracle/rng.py,
  * pinned to the published known-answer vectors).  No reference counterpart: the reference's random-init generator and noise planes
  * come from torch's host generator (inference/stylegan2.py:216-227, selfsupervised/noise.py:42-53); the benchmark's synthetic

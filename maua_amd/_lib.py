@@ -49,8 +49,23 @@ def lib():
                 l = C.CDLL(str(LIB_PATH))
                 l.maua_last_error.restype = C.c_char_p
                 l.maua_version.restype = C.c_char_p
+                _declare_flow(l)
                 _lib = l
     return _lib
+
+
+def _declare_flow(l):
+    """csrc/flow.hip's entry points (include/maua_hip.h: optical-flow operators of the video pipeline)."""
+    p, i, f = C.c_void_p, C.c_int, C.c_float
+    l.maua_flow_warp.argtypes = [p, p, p, f, i, i, i, i, p]
+    l.maua_flow_consistency.argtypes = [p, p, p, i, i, i, f, p, p]
+    l.maua_flow_resize_bilinear.argtypes = [p, p, i, i, i, i, p, i, i, f, f]
+    l.maua_flow_compose.argtypes = [p, p, p, p, p, p, i, i, i, f, f, f, f, f, C.c_ulonglong, p]
+    l.maua_flow_turbo.argtypes = [p, p, p, p, i, i, i, f, i, f, p, p, p]
+    l.maua_farneback_levels.argtypes = [i, i]
+    l.maua_farneback_create.argtypes = [p, i, i, C.POINTER(p)]
+    l.maua_farneback_destroy.argtypes = [p]
+    l.maua_farneback_pair.argtypes = [p, p, p, p, i, i, p, p]
 
 
 class host_threads:

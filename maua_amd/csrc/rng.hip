@@ -8,33 +8,11 @@
 //   normal:  words (x0, x1) and (x2, x3) of a counter -> Box-Muller pairs; u = ((x >> 9) + 0.5) 2^-23 (exact in f32, never 0 or 1)
 #include "common.h"
 #include "internal.h"
+#include "philox.h"   // philox4x32_10, unit23, box_muller
 
 namespace maua {
 
 namespace {
-
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return U4{c0, c1, c2, c3};
-}
-
-__device__ __forceinline__ float unit23(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
-
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-  const float r = sqrtf(-2.0f * logf(unit23(a)));
-  const float th = 6.283185307179586f * unit23(b);
-  z0 = r * cosf(th);
-  z1 = r * sinf(th);
-}
 
 // one thread per counter (4 outputs); offset: first element of the stream this call produces (any alignment)
 __global__ __launch_bounds__(256) void philox_kernel(uint32_t s0, uint32_t s1, uint32_t t0, uint32_t t1, unsigned long long offset,
