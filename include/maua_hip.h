@@ -668,6 +668,51 @@ int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const
  * gradient of x_upd(x), the same resampling of the raw input, added */
 int maua_group_norm_nhwc_vjp(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift, int silu,
                              int resample, const void* dy, const void* dres, int B, int H, int W, int C, int dtype, void* dx);
+/* the fused GroupNorm pass behind the two entry points above and every norm of the diffusion UNet, and its input gradient, with
+ * every launch argument in the caller's hand, for parity tests (no reference counterpart).  Tensors NHWC in dtype (MAUA_F32 or
+ * MAUA_BF16), 16 bytes = EPC elements (4 / 8) a piece.  The input is the virtual concatenation [x0 | x1] of [B][H][W][C0] and
+ * [B][H][W][C1] (x1 NULL, C1 0: one source; the boundary may fall inside a group), C = C0 + C1:
+ *   u = (x - mean) * rstd * gamma + beta;  ss != NULL: u = u * (1 + ss[b ss_ld + c]) + ss[b ss_ld + C + c];  silu: u = u sigmoid(u)
+ *   y [B][Ho][Wo][C] = R(u): mode 0 the identity, 1 the 2x2 average (Ho = H / 2, Wo = W / 2, floored like avg_pool2d), 2 nearest x2;
+ *   xr (optional, like y) = R(x), the ResBlock's x_upd.  Statistics per (sample, group of C / 32 channels) in float64, eps 1e-5.
+ * ss_ld: floats between the samples' scale-shift rows - 0 (one row for all) or >= 2 C.  ps0 / ps1 (optional, bf16 only): the piece
+ * sums maua_conv_desc.psum describes, float [B][rows][C_i / 8][16], left by the convolution that produced that source; the statistics
+ * are taken from them when the group kernels run and every source has them, else from a pass over the tensor.  stats_out
+ * (optional): float [B][32][2], left holding (mean, rstd).  force_route: 0 = as the network routes, 1 = the per-channel kernels.
+ * Routes: 0 = group kernels (C / 32 a multiple of EPC and B * Ho <= 65535), 1 = per-channel kernels; both read the tensor in
+ * chunks of ppc pixels, nchunk <= 128 per sample, RY = max(1, 512 / (C / EPC)) pixel rows per workgroup.
+ * Checked: dtype; x0, gamma, beta, y non-NULL; B >= 0, H, W, C0 > 0; C % 32 == 0, C / EPC <= 1024, C0 % EPC == 0; x1 non-NULL when
+ * C1 > 0; mode 0 .. 2, mode 1 needs H, W >= 2; ss_ld; every pointer and ss_ld whole 16-byte pieces; B <= 65535 and fewer than 2^31
+ * pixels per sample; piece sums: bf16, H % 8 == 0, W % 32 == 0, C_i % 128 == 0, rows_i == (H / 8) * (W / 32).  B == 0: nothing is done. */
+typedef struct {
+  const void* x0; int C0; const void* x1; int C1; int B, H, W;
+  const float* gamma; const float* beta; const float* ss; long ss_ld;
+  int silu, mode; void* y; void* xr;
+  const float* ps0; int rows0; const float* ps1; int rows1;
+  float* stats_out; int force_route; int dtype;
+} maua_gn_desc;
+/* the input gradient: dy, dres (optional; the gradient of xr or of an identity skip) [B][Ho][Wo][C] -> dx0 [B][H][W][C0], dx1
+ * [B][H][W][C1]; add0 / add1 (optional, may alias dx0 / dx1): gradients already known for x0 / x1, added.  stats: the forward's
+ * [B][32][2] (mean, rstd), an operand.  The same checks, on every pointer, plus: dx1 non-NULL when C1 > 0; mode 1 needs even H and
+ * W; H <= 65535.  The partial sums run RY = max(1, 256 / (C / EPC)) pixel rows per workgroup; the last kernel runs once per range of
+ * 65535 / H samples. */
+typedef struct {
+  const void* x0; int C0; const void* x1; int C1;
+  const float* stats; const float* gamma; const float* beta; const float* ss; long ss_ld;
+  int silu, mode; const void* dy; const void* dres; const void* add0; const void* add1; void* dx0; void* dx1;
+  int B, H, W; int dtype;
+} maua_gn_vjp_desc;
+/* host only, no device needed: MAUA_OK, or MAUA_ERR + maua_last_error() with the launcher's own message.  Pointers are only checked,
+ * never dereferenced. */
+int maua_group_norm_check(const maua_gn_desc* d);
+int maua_group_norm_vjp_check(const maua_gn_vjp_desc* d);
+/* host only: what the launch would run (any output pointer may be NULL); refused as the check refuses.  stats_source: 0 = a pass
+ * over the tensor, 1 = the piece sums.  ranges: launches of the gradient's last kernel. */
+int maua_group_norm_plan(const maua_gn_desc* d, int* route, int* RY, int* ppc, int* nchunk, int* stats_source);
+int maua_group_norm_vjp_plan(const maua_gn_vjp_desc* d, int* RY, int* ppc, int* nchunk, int* ranges);
+/* launch on the context's stream (workspaces from its scratch arena); refused, with no launch, as the check refuses */
+int maua_group_norm_ex(maua_ctx* ctx, const maua_gn_desc* d);
+int maua_group_norm_vjp_ex(maua_ctx* ctx, const maua_gn_vjp_desc* d);
 /* the unconditioned sampling loop of guided.py:333-337 inside the library: n_steps x (forward + DDIM update) on x in place;
  * model_t host f32 [n_steps], coef host f32 [n_steps][8]; use_graph: capture the loop in one hipGraph and replay it. */
 int maua_ddim_sample_loop(maua_unet* net, float* x, int B, int H, int W, const float* model_t, const float* coef, int n_steps,

@@ -209,6 +209,24 @@ class AttnVjpDesc(C.Structure):
                 ("scale", C.c_float), ("causal", C.c_int), ("dtype", C.c_int)]
 
 
+class GnDesc(C.Structure):
+    """maua_gn_desc (include/maua_hip.h): one fused GroupNorm pass for maua_group_norm_check / _plan / _ex; pointers as integers."""
+    _fields_ = [("x0", C.c_void_p), ("C0", C.c_int), ("x1", C.c_void_p), ("C1", C.c_int), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("ss", C.c_void_p), ("ss_ld", C.c_long),
+                ("silu", C.c_int), ("mode", C.c_int), ("y", C.c_void_p), ("xr", C.c_void_p),
+                ("ps0", C.c_void_p), ("rows0", C.c_int), ("ps1", C.c_void_p), ("rows1", C.c_int),
+                ("stats_out", C.c_void_p), ("force_route", C.c_int), ("dtype", C.c_int)]
+
+
+class GnVjpDesc(C.Structure):
+    """maua_gn_vjp_desc (include/maua_hip.h): its input gradient for maua_group_norm_vjp_check / _plan / _ex."""
+    _fields_ = [("x0", C.c_void_p), ("C0", C.c_int), ("x1", C.c_void_p), ("C1", C.c_int),
+                ("stats", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("ss", C.c_void_p), ("ss_ld", C.c_long),
+                ("silu", C.c_int), ("mode", C.c_int), ("dy", C.c_void_p), ("dres", C.c_void_p), ("add0", C.c_void_p),
+                ("add1", C.c_void_p), ("dx0", C.c_void_p), ("dx1", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
+
+
 # routes of maua_modconv_route / maua_modconv_ex and of maua_synth_get_plan (csrc/synth.hip's Route enum; UPFIR: the FIR / epilogue pass alone)
 ROUTES = {"lowres": 0, "generic": 1, "dma_conv1": 2, "hires": 3, "upwalk": 4, "fused_walk": 5, "walk_done": 6, "tconv_fir": 7,
           "tconv_dma": 8, "tconv2": 9, "upfir": 10}

@@ -316,14 +316,33 @@ size_t group_norm_vjp_workspace(int B, int C, long HW, int esize) {
   return (size_t)B * p.nchunk * C * 16 + (size_t)B * 32 * 2 * 4 + 256;
 }
 
-int launch_group_norm_vjp(hipStream_t stream, int dtype, const GnVjpArgs& a, void* workspace) {
+int group_norm_vjp_check(int dtype, const GnVjpArgs& a) {
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "group_norm_vjp: unsupported dtype");
-  const int esize = dtype == MAUA_BF16 ? 2 : 4, EPC = 16 / esize, C = a.C0 + a.C1;
-  MAUA_REQUIRE(a.x0 && a.stats && a.gamma && a.beta && a.dy && a.dx0 && workspace, "group_norm_vjp: NULL argument");
+  const int esize = dtype == MAUA_BF16 ? 2 : 4, EPC = 16 / esize;
+  MAUA_REQUIRE(a.x0 && a.stats && a.gamma && a.beta && a.dy && a.dx0, "group_norm_vjp: NULL argument");
+  MAUA_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.C0 > 0 && a.C1 >= 0, "group_norm_vjp: bad shape");
+  const long C = (long)a.C0 + a.C1;
   MAUA_REQUIRE(C % 32 == 0 && C / EPC <= 1024 && a.C0 % EPC == 0 && a.C1 % EPC == 0 && (a.C1 == 0 || (a.x1 && a.dx1)),
                "group_norm_vjp: C % 32 == 0, at most 1024 16-byte pieces per pixel");
   MAUA_REQUIRE(a.mode >= 0 && a.mode <= 2 && (a.mode != 1 || (a.H % 2 == 0 && a.W % 2 == 0)), "group_norm_vjp: bad resample mode");
-  MAUA_REQUIRE(a.H <= 65535 && a.B <= 65535, "group_norm_vjp: grid too large");
+  MAUA_REQUIRE(!a.ss || a.ss_ld == 0 || a.ss_ld >= 2 * C, "group_norm_vjp: ss_ld is 0 (one row for all samples) or at least 2 C");
+  const void* ptrs[] = {a.x0, a.x1, a.stats, a.gamma, a.beta, a.ss, a.dy, a.dres, a.add0, a.add1, a.dx0, a.dx1};
+  bool aligned = a.ss_ld % 4 == 0;
+  for (const void* q : ptrs) aligned = aligned && ((size_t)q & 15) == 0;
+  MAUA_REQUIRE(aligned, "group_norm_vjp: pointers and ss_ld must be whole 16-byte pieces");
+  MAUA_REQUIRE(a.H <= 65535 && a.B <= 65535 && (long)a.H * a.W <= 0x7fffffffL, "group_norm_vjp: grid too large");
+  return MAUA_OK;
+}
+
+GnVjpPlanInfo group_norm_vjp_plan(int dtype, const GnVjpArgs& a) {
+  const VjpPlan p = vjp_plan(a.C0 + a.C1, (long)a.H * a.W, dtype == MAUA_BF16 ? 2 : 4);
+  const int bmax = std::max(1, 65535 / a.H);
+  return GnVjpPlanInfo{p.RY, p.ppc, (int)p.nchunk, (a.B + bmax - 1) / bmax};
+}
+
+int launch_group_norm_vjp(hipStream_t stream, int dtype, const GnVjpArgs& a, void* workspace) {
+  if (int rc = group_norm_vjp_check(dtype, a)) return rc;
+  MAUA_REQUIRE(workspace, "group_norm_vjp: NULL argument");
   if (a.B == 0) return MAUA_OK;
   return dtype == MAUA_BF16 ? run<bf16_t>(stream, a, workspace) : run<float>(stream, a, workspace);
 }

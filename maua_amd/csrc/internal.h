@@ -417,6 +417,41 @@ struct GnVjpArgs {
 };
 size_t group_norm_vjp_workspace(int B, int C, long HW, int esize);
 int launch_group_norm_vjp(hipStream_t stream, int dtype, const GnVjpArgs& a, void* workspace);
+// host only: launch_group_norm_vjp's refusals (everything but the workspace), and the plan it launches with - RY rows of C / EPC
+// pieces per workgroup, ppc pixels per chunk, nchunk chunks per sample, `ranges` launches of the apply kernel (its grid's y extent
+// holds 65535 / H samples)
+int group_norm_vjp_check(int dtype, const GnVjpArgs& a);
+struct GnVjpPlanInfo { int RY, ppc, nchunk, ranges; };
+GnVjpPlanInfo group_norm_vjp_plan(int dtype, const GnVjpArgs& a);
+
+// unet.hip: GroupNorm32 (+ scale-shift) (+ SiLU) (+ resample: 0 none, 1 2x2 average, 2 nearest x2) of the virtually concatenated
+// [x0 | x1] ([B][H][W][C0 | C1], dense NHWC in the network dtype) -> y [B][Ho][Wo][C0 + C1]; xr (optional): the same resampling of
+// the raw input.  ps0 / ps1 (optional, bf16): the piece sums the producing LDS-direct convolution left (ConvArgs.psum,
+// [B][rows][C / 8][16]); the statistics come from them when the group kernels run and every source has them, else from a pass
+// over the tensor.  force_route 1: the per-channel kernels whatever the shape.
+struct GnArgs {
+  const void* x0; int C0;
+  const void* x1; int C1;
+  int B, H, W;
+  const float* gamma;
+  const float* beta;
+  const float* ss;      // [B][ss_ld]: scale at [c], shift at [C + c]; or NULL.  ss_ld 0: one row for every sample
+  long ss_ld;
+  int silu, mode;
+  void* y;
+  void* xr;
+  const float* ps0; int rows0;
+  const float* ps1; int rows1;
+  int force_route;
+};
+// route 0: the group kernels (gn_partial_group / gn_finalize_group | gn_finalize_psum / gn_apply_group), 1: the per-channel kernels
+// (gn_partial / gn_finalize / gn_apply); stats_source 0: a pass over the tensor, 1: the piece sums
+struct GnPlanInfo { int route, RY, ppc, nchunk, stats_source; };
+int group_norm_check(int dtype, const GnArgs& a);          // host only: launch_group_norm's refusals
+GnPlanInfo group_norm_plan(int dtype, const GnArgs& a);    // host only: what a legal `a` launches
+size_t group_norm_workspace(int B, int C, long HW, int esize);   // bytes of `part`
+// part: group_norm_workspace() bytes; stats: [B][32][2] floats, left holding (mean, rstd)
+int launch_group_norm(hipStream_t stream, int dtype, const GnArgs& a, double* part, float* stats);
 
 // cutouts.hip: random cutouts resized to the perceptor's input (maua/ops/cutouts.py:8-50 as CLIPGrads calls it) and their gradient.
 // rects: DEVICE [n_cut][3] (size, top, left); tables: cutouts_table_bytes() of device scratch filled by launch_cutout_tables;

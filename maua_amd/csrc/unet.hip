@@ -475,40 +475,41 @@ static GnPlan gn_plan(int B, int C, long HW, int esize) {
   p.part_bytes = p.fast ? (size_t)B * p.nchunk * 32 * 16 : (size_t)B * p.nchunk * p.RY * C * 16;
   return p;
 }
+static void gn_out_size(const GnArgs& a, int* Ho, int* Wo) {
+  *Ho = a.mode == 1 ? a.H / 2 : (a.mode == 2 ? a.H * 2 : a.H);
+  *Wo = a.mode == 1 ? a.W / 2 : (a.mode == 2 ? a.W * 2 : a.W);
+}
 
-// GroupNorm32 (+ scale-shift) (+ SiLU) (+ resample) of the virtually concatenated [x0 | x1]; part / stats: workspaces
+// the launches of maua::launch_group_norm (which has checked `a`) as maua::group_norm_plan describes them
 template <typename T>
-static int launch_group_norm(hipStream_t st, const T* x0, int C0, const T* x1, int C1, int B, int H, int W,
-                             const float* gamma, const float* beta, const float* ss, long ss_ld, int silu, int mode, T* y, T* xr,
-                             double* part, float* stats, const float* ps0 = nullptr, int rows0 = 0, const float* ps1 = nullptr,
-                             int rows1 = 0) {
+static int gn_launch(hipStream_t st, const GnArgs& a, const GnPlanInfo& pl, double* part, float* stats) {
   constexpr int EPC = 16 / (int)sizeof(T);
-  const int C = C0 + C1, PPP = C / EPC;
+  const T *x0 = (const T*)a.x0, *x1 = (const T*)a.x1;
+  T *y = (T*)a.y, *xr = (T*)a.xr;
+  const int C0 = a.C0, C1 = a.C1, C = C0 + C1, PPP = C / EPC, B = a.B, H = a.H, W = a.W;
   const long HW = (long)H * W;
-  MAUA_REQUIRE(C % 32 == 0 && PPP <= 1024 && C0 % EPC == 0, "group_norm: C % 32 == 0, at most 1024 16-byte pieces per pixel");
-  const GnPlan p = gn_plan(B, C, HW, (int)sizeof(T));
-  const int Ho = mode == 1 ? H / 2 : (mode == 2 ? H * 2 : H), Wo = mode == 1 ? W / 2 : (mode == 2 ? W * 2 : W);
-  if (p.fast && (long)B * Ho <= 65535) {
-    if (ps0 && (!x1 || ps1) && sizeof(T) == 2) {
+  int Ho, Wo;
+  gn_out_size(a, &Ho, &Wo);
+  if (pl.route == 0) {
+    if (pl.stats_source == 1) {
       // every source's producer left its piece sums: no statistics pass over the tensor
-      hipLaunchKernelGGL(gn_finalize_psum_kernel, dim3(B), dim3(256), 0, st, ps0, rows0, C0, ps1, rows1, C1,
+      hipLaunchKernelGGL(gn_finalize_psum_kernel, dim3(B), dim3(256), 0, st, a.ps0, a.rows0, C0, a.ps1, a.rows1, C1,
                          (double)HW * (C / 32), 1e-5f, stats);
     } else {
-      hipLaunchKernelGGL(gn_partial_group_kernel<T>, dim3((unsigned)p.nchunk, B), dim3(PPP * p.RY), 0, st, x0, C0, x1, C1, HW,
-                         p.ppc, part);
-      hipLaunchKernelGGL(gn_finalize_group_kernel, dim3(B), dim3(256), 0, st, part, (int)p.nchunk, (double)HW * (C / 32), 1e-5f,
+      hipLaunchKernelGGL(gn_partial_group_kernel<T>, dim3((unsigned)pl.nchunk, B), dim3(PPP * pl.RY), 0, st, x0, C0, x1, C1, HW,
+                         pl.ppc, part);
+      hipLaunchKernelGGL(gn_finalize_group_kernel, dim3(B), dim3(256), 0, st, part, pl.nchunk, (double)HW * (C / 32), 1e-5f,
                          stats);
     }
     hipLaunchKernelGGL(gn_apply_group_kernel<T>, dim3((unsigned)(((long)((Wo + GN_PX - 1) / GN_PX) * PPP + 255) / 256), (unsigned)(B * Ho)),
-                       dim3(256), 0, st, x0, C0, x1, C1, stats, gamma, beta, ss, ss_ld, silu, mode, y, xr, H, W, Ho, Wo);
+                       dim3(256), 0, st, x0, C0, x1, C1, stats, a.gamma, a.beta, a.ss, a.ss_ld, a.silu, a.mode, y, xr, H, W, Ho, Wo);
   } else {
-    const GnPlan q = p.fast ? GnPlan{0, p.RY, p.ppc, p.nchunk, 0} : p;
-    hipLaunchKernelGGL(gn_partial_kernel<T>, dim3((unsigned)q.nchunk, B), dim3(PPP * q.RY), 0, st, x0, C0, x1, C1, HW, q.ppc,
+    hipLaunchKernelGGL(gn_partial_kernel<T>, dim3((unsigned)pl.nchunk, B), dim3(PPP * pl.RY), 0, st, x0, C0, x1, C1, HW, pl.ppc,
                        part);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(32, B), dim3(256), 0, st, part, (int)(q.nchunk * q.RY), C, HW, 1e-5f, stats);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(32, B), dim3(256), 0, st, part, pl.nchunk * pl.RY, C, HW, 1e-5f, stats);
     const long total = (long)B * Ho * Wo * PPP;
-    hipLaunchKernelGGL(gn_apply_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x0, C0, x1, C1, stats, gamma,
-                       beta, ss, ss_ld, silu, mode, y, xr, B, H, W);
+    hipLaunchKernelGGL(gn_apply_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x0, C0, x1, C1, stats, a.gamma,
+                       a.beta, a.ss, a.ss_ld, a.silu, a.mode, y, xr, B, H, W);
   }
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
@@ -531,6 +532,66 @@ static size_t gn_part_bytes(int B, int C, long HW, int esize) {
   const GnPlan p = gn_plan(B, C, HW, esize);
   return std::max(p.part_bytes, (size_t)B * p.nchunk * p.RY * C * 16);
 }
+
+}  // namespace
+
+// ---- the one GroupNorm launcher: the network (Runner::gn), maua_group_norm_nhwc and maua_group_norm_ex all come through here
+static inline bool gn_aligned16(const void* p) { return ((size_t)p & 15) == 0; }
+
+int maua::group_norm_check(int dtype, const GnArgs& a) {
+  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "group_norm: unsupported dtype");
+  const int EPC = dtype == MAUA_BF16 ? 8 : 4;
+  MAUA_REQUIRE(a.x0 && a.gamma && a.beta && a.y, "group_norm: NULL argument");
+  MAUA_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.C0 > 0 && a.C1 >= 0, "group_norm: bad shape");
+  const long C = (long)a.C0 + a.C1;
+  MAUA_REQUIRE(C % 32 == 0 && C / EPC <= 1024 && a.C0 % EPC == 0, "group_norm: C % 32 == 0, at most 1024 16-byte pieces per pixel");
+  MAUA_REQUIRE(a.C1 == 0 || a.x1, "group_norm: x1 is NULL with C1 > 0");
+  MAUA_REQUIRE(a.mode >= 0 && a.mode <= 2 && (a.mode != 1 || (a.H >= 2 && a.W >= 2)), "group_norm: bad resample mode");
+  MAUA_REQUIRE(!a.ss || a.ss_ld == 0 || a.ss_ld >= 2 * C, "group_norm: ss_ld is 0 (one row for all samples) or at least 2 C");
+  MAUA_REQUIRE(gn_aligned16(a.x0) && gn_aligned16(a.x1) && gn_aligned16(a.y) && gn_aligned16(a.xr) && gn_aligned16(a.gamma) &&
+                   gn_aligned16(a.beta) && gn_aligned16(a.ss) && gn_aligned16(a.ps0) && gn_aligned16(a.ps1) && a.ss_ld % 4 == 0,
+               "group_norm: pointers and ss_ld must be whole 16-byte pieces");
+  int Ho, Wo;
+  gn_out_size(a, &Ho, &Wo);
+  // (blockIdx.y carries the sample in the statistics kernels; the apply kernels index pixels of a sample in 32 bits)
+  MAUA_REQUIRE(a.B <= 65535 && (long)Ho * Wo <= 0x7fffffffL && (long)a.H * a.W <= 0x7fffffffL &&
+                   ((long)a.B * Ho * Wo * (C / EPC) + 255) / 256 <= 0x7fffffffL,
+               "group_norm: grid too large");
+  MAUA_REQUIRE(!a.ps1 || a.C1 > 0, "group_norm: ps1 without a second source");
+  MAUA_REQUIRE((!a.ps0 && !a.ps1) || dtype == MAUA_BF16, "group_norm: piece sums are bf16 only");
+  const bool tiles = a.H % 8 == 0 && a.W % 32 == 0;
+  const int rows = (a.H / 8) * (a.W / 32);
+  MAUA_REQUIRE((!a.ps0 || (tiles && a.C0 % 128 == 0 && a.rows0 == rows)) && (!a.ps1 || (tiles && a.C1 % 128 == 0 && a.rows1 == rows)),
+               "group_norm: piece sums need H % 8 == 0, W % 32 == 0, C % 128 == 0 of their source and rows == (H / 8) * (W / 32)");
+  return MAUA_OK;
+}
+
+GnPlanInfo maua::group_norm_plan(int dtype, const GnArgs& a) {
+  const int esize = dtype == MAUA_BF16 ? 2 : 4, C = a.C0 + a.C1;
+  const GnPlan p = gn_plan(a.B, C, (long)a.H * a.W, esize);
+  int Ho, Wo;
+  gn_out_size(a, &Ho, &Wo);
+  GnPlanInfo pl;
+  // (the group kernels carry (sample, output row) in blockIdx.y; a shape with more rows runs the per-channel kernels on the same chunks)
+  pl.route = p.fast && (long)a.B * Ho <= 65535 && a.force_route != 1 ? 0 : 1;
+  pl.RY = p.RY;
+  pl.ppc = p.ppc;
+  pl.nchunk = (int)p.nchunk;
+  pl.stats_source = pl.route == 0 && a.ps0 && (a.C1 == 0 || a.ps1) && dtype == MAUA_BF16 ? 1 : 0;
+  return pl;
+}
+
+size_t maua::group_norm_workspace(int B, int C, long HW, int esize) { return gn_part_bytes(B, C, HW, esize); }
+
+int maua::launch_group_norm(hipStream_t stream, int dtype, const GnArgs& a, double* part, float* stats) {
+  if (int rc = group_norm_check(dtype, a)) return rc;
+  MAUA_REQUIRE(part && stats, "group_norm: NULL workspace");
+  if (a.B == 0) return MAUA_OK;
+  const GnPlanInfo pl = group_norm_plan(dtype, a);
+  return dtype == MAUA_BF16 ? gn_launch<bf16_t>(stream, a, pl, part, stats) : gn_launch<float>(stream, a, pl, part, stats);
+}
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------------ DDIM step
 // gaussian_diffusion.py ddim_sample for an epsilon-predicting model (clip_denoised False), in the reference's float32
@@ -1062,8 +1123,11 @@ struct Runner {
         auto it1 = psums.find(x1);
         if (it1 != psums.end()) { ps1 = it1->second.first; rows1 = it1->second.second; }
       }
-      rc = launch_group_norm<T>(st, x0, C0, x1, C1, B, H, W, g.gamma, g.beta, ss, n->emb_row ? 0L : (long)n->emb_total, silu,
-                                mode, y, xr, part, stats, ps0, rows0, ps1, rows1);
+      GnArgs a{};
+      a.x0 = x0; a.C0 = C0; a.x1 = x1; a.C1 = C1; a.B = B; a.H = H; a.W = W; a.gamma = g.gamma; a.beta = g.beta; a.ss = ss;
+      a.ss_ld = n->emb_row ? 0L : (long)n->emb_total; a.silu = silu; a.mode = mode; a.y = y; a.xr = xr;
+      a.ps0 = ps0; a.rows0 = rows0; a.ps1 = ps1; a.rows1 = rows1;
+      rc = launch_group_norm(st, n->dtype, a, part, stats);
     }
     ar.top = mark;
     return rc;
@@ -1774,11 +1838,10 @@ int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const
   if (int rc = scratch_reserve(ctx, part_bytes + (size_t)B * 64 * 4 + 512)) return rc;
   double* part = (double*)ctx->scratch;
   float* stats = (float*)((char*)ctx->scratch + ((part_bytes + 255) & ~(size_t)255));
-  if (dtype == MAUA_BF16)
-    return launch_group_norm<bf16_t>(ctx->stream, (const bf16_t*)x, C, nullptr, 0, B, H, W, gamma, beta, scale_shift, 2L * C,
-                                     silu, 0, (bf16_t*)y, nullptr, part, stats);
-  return launch_group_norm<float>(ctx->stream, (const float*)x, C, nullptr, 0, B, H, W, gamma, beta, scale_shift, 2L * C, silu,
-                                  0, (float*)y, nullptr, part, stats);
+  GnArgs a{};
+  a.x0 = x; a.C0 = C; a.B = B; a.H = H; a.W = W; a.gamma = gamma; a.beta = beta; a.ss = scale_shift; a.ss_ld = 2L * C; a.silu = silu;
+  a.y = y;
+  return launch_group_norm(ctx->stream, dtype, a, part, stats);
 }
 
 // Input gradients of the two operator-level blocks above (what maua_unet_vjp walks a network with).  Attention: qkv as the
