@@ -989,6 +989,33 @@ int maua_farneback_create(maua_ctx* ctx, int max_h, int max_w, maua_farneback** 
 int maua_farneback_destroy(maua_farneback* handle);
 int maua_farneback_pair(maua_farneback* handle, maua_ctx* ctx, const float* im_a, const float* im_b, int H, int W, float* flow_ab,
                         float* flow_ba);
+/* the estimator with its stages in the caller's hand, for parity tests (no reference counterpart).  maua_farneback_pair is this launch
+ * with level_hi = level_lo = -1, iterations 0, no initial flow and no dumps.
+ *   level_hi, level_lo: the pyramid levels level_hi .. level_lo are processed, downwards (-1, -1: the top level, maua_farneback_levels - 1,
+ *     down to 0).  flow_ab / flow_ba have level_lo's size [h][w][2] (maua_farneback_level_size).
+ *   iterations: 1 .. 15 per level; 0 means 15.
+ *   init_ab / init_ba (both or neither): the flows entering level_hi, [h][w][2] at that level's size; NULL: zero.
+ *   dumps (each optional), device-to-device copies out of the workspace behind the stage that filled it, all of level_lo:
+ *     gray [2][H][W] the 8-bit luminance of (a, b); blur [2][H][W] the level's Gaussian blur of it; level [2][h][w] its resize;
+ *     coef [2][5][h][w] the polynomial expansion's coefficients of x, y, x^2, y^2, xy; flow_in [2][h][w][2] the flow entering the level
+ *     (direction a -> b, then b -> a); mat [2][5][h][w] the update matrices before the first iteration.
+ * Refused, in front of the first launch: NULL or aliased arguments, an image below 15 x 15, above 2^26 pixels or above the handle's pixel
+ * count, a handle of another device, a level range out of order or above the top level, iterations outside 0 .. 15, one initial flow
+ * without the other, a pyramid blur wider than the image. */
+typedef struct {
+  const float* im_a; const float* im_b; int H, W;
+  float* flow_ab; float* flow_ba;
+  int level_hi, level_lo, iterations;
+  const float* init_ab; const float* init_ba;
+  float* gray; float* blur; float* level; float* coef; float* flow_in; float* mat;
+} maua_farneback_desc;
+/* host only: the size of pyramid level `level` (0 .. maua_farneback_levels - 1) of an H x W pair: round(W 0.8^level) by round(H 0.8^level),
+ * half to even, as the launcher computes it */
+int maua_farneback_level_size(int H, int W, int level, int* h, int* w);
+/* host only, no device needed: MAUA_OK, or MAUA_ERR + maua_last_error() with the launcher's own message.  Pointers are only checked, never
+ * dereferenced.  handle may be NULL (there is none without a device): the descriptor alone is checked. */
+int maua_farneback_check(const maua_farneback* handle, const maua_farneback_desc* d);
+int maua_farneback_pair_ex(maua_farneback* handle, maua_ctx* ctx, const maua_farneback_desc* d);
 
 /* ---- build-owned counter RNG: Philox4x32-10, identical on every device / rank and in the oracle twin (oracle/rng.py,
  * pinned to the published known-answer vectors).  No reference counterpart: the reference's random-init generator and noise planes

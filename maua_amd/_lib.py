@@ -66,6 +66,9 @@ def _declare_flow(l):
     l.maua_farneback_create.argtypes = [p, i, i, C.POINTER(p)]
     l.maua_farneback_destroy.argtypes = [p]
     l.maua_farneback_pair.argtypes = [p, p, p, p, i, i, p, p]
+    l.maua_farneback_level_size.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
+    l.maua_farneback_check.argtypes = [p, p]
+    l.maua_farneback_pair_ex.argtypes = [p, p, p]
 
 
 class host_threads:
@@ -225,6 +228,16 @@ class GnVjpDesc(C.Structure):
                 ("silu", C.c_int), ("mode", C.c_int), ("dy", C.c_void_p), ("dres", C.c_void_p), ("add0", C.c_void_p),
                 ("add1", C.c_void_p), ("dx0", C.c_void_p), ("dx1", C.c_void_p),
                 ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
+
+
+class FbDesc(C.Structure):
+    """maua_farneback_desc (include/maua_hip.h): one estimator run for maua_farneback_check / _pair_ex; pointers as integers."""
+    _fields_ = [("im_a", C.c_void_p), ("im_b", C.c_void_p), ("H", C.c_int), ("W", C.c_int),
+                ("flow_ab", C.c_void_p), ("flow_ba", C.c_void_p),
+                ("level_hi", C.c_int), ("level_lo", C.c_int), ("iterations", C.c_int),
+                ("init_ab", C.c_void_p), ("init_ba", C.c_void_p),
+                ("gray", C.c_void_p), ("blur", C.c_void_p), ("level", C.c_void_p), ("coef", C.c_void_p), ("flow_in", C.c_void_p),
+                ("mat", C.c_void_p)]
 
 
 # routes of maua_modconv_route / maua_modconv_ex and of maua_synth_get_plan (csrc/synth.hip's Route enum; UPFIR: the FIR / epilogue pass alone)

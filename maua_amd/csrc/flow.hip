@@ -274,13 +274,17 @@ struct PolyTaps {
   float ig11, ig03, ig33, ig55;
 };
 
-// luminance(im).mul(255).byte() (flow/__init__.py:41-42 with ops/image.py:176-177) as float32; z = image of the pair
+// luminance(im).mul(255).byte() (flow/__init__.py:41-42 with ops/image.py:176-177) as float32; z = image of the pair.  The byte is a
+// truncation, so the float32 value has to be torch's to the last bit: every product and sum is rounded on its own.  __fmul_rn / __fadd_rn
+// are plain operators inside a header to this compiler and were contracted into an fma (0.7152 g + 0.2126 r in one rounding), which
+// moved a luminance one ulp below an integer and the pixel one grey level down; the pragma governs the operators written in this body.
 __global__ __launch_bounds__(256) void fb_gray_kernel(const float* __restrict__ im_a, const float* __restrict__ im_b, float* __restrict__ gray, long hw) {
+#pragma clang fp contract(off)
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= hw) return;
   const float* im = blockIdx.z == 0 ? im_a : im_b;
-  const float lum = __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, im[idx]), __fmul_rn(0.7152f, im[hw + idx])), __fmul_rn(0.0722f, im[2 * hw + idx]));
-  const float v = fminf(fmaxf(__fmul_rn(lum, 255.f), 0.f), 255.f);
+  const float lum = (0.2126f * im[idx] + 0.7152f * im[hw + idx]) + 0.0722f * im[2 * hw + idx];
+  const float v = fminf(fmaxf(lum * 255.f, 0.f), 255.f);
   gray[(long)blockIdx.z * hw + idx] = (float)(int)v;
 }
 
@@ -673,12 +677,70 @@ int maua_farneback_destroy(maua_farneback* h) {
   return MAUA_OK;
 }
 
-int maua_farneback_pair(maua_farneback* fb, maua_ctx* ctx, const float* im_a, const float* im_b, int H, int W, float* flow_ab, float* flow_ba) {
-  MAUA_REQUIRE(fb && ctx, "maua_farneback_pair: NULL handle or ctx");
-  MAUA_REQUIRE(ctx->device == fb->device, "maua_farneback_pair: the handle belongs to another device");
-  MAUA_REQUIRE(im_a && im_b && flow_ab && flow_ba && flow_ab != flow_ba, "maua_farneback_pair: NULL or aliased argument");
-  MAUA_REQUIRE(H >= 2 * FB_POLY_N + 1 && W >= 2 * FB_POLY_N + 1, "maua_farneback_pair: the image must be at least 15 x 15");
-  MAUA_REQUIRE((long)H * W <= (long)fb->max_h * fb->max_w, "maua_farneback_pair: the image exceeds the size the handle was created for");
+namespace {
+
+// the size of pyramid level k and the standard deviation of its blur, as the launcher computes them
+void level_geometry(int H, int W, int k, int& h, int& w, double& sigma) {
+  double scale = 1;
+  for (int i = 0; i < k; i++) scale *= FB_PYR_SCALE;
+  sigma = (1. / scale - 1) * 0.5;
+  w = (int)round_half_even(W * scale);
+  h = (int)round_half_even(H * scale);
+}
+
+// every refusal of the estimator, in front of the first launch; fb NULL: the descriptor alone (no handle exists without a device).
+// The levels of the range and the iteration count go out through hi / lo / iters.
+int farneback_check(const maua_farneback* fb, const maua_farneback_desc* d, int& hi, int& lo, int& iters) {
+  MAUA_REQUIRE(d, "maua_farneback: the descriptor is NULL");
+  MAUA_REQUIRE(d->im_a && d->im_b && d->flow_ab && d->flow_ba && d->flow_ab != d->flow_ba && d->flow_ab != d->im_a && d->flow_ab != d->im_b &&
+                   d->flow_ba != d->im_a && d->flow_ba != d->im_b,
+               "maua_farneback: NULL or aliased argument");
+  MAUA_REQUIRE(d->H >= 2 * FB_POLY_N + 1 && d->W >= 2 * FB_POLY_N + 1, "maua_farneback: the image must be at least 15 x 15");
+  MAUA_REQUIRE((long)d->H * d->W <= (1L << 26), "maua_farneback: the image exceeds 2^26 pixels");
+  MAUA_REQUIRE(!fb || (long)d->H * d->W <= (long)fb->max_h * fb->max_w, "maua_farneback: the image exceeds the size the handle was created for");
+  const int top = pyramid_levels(d->H, d->W);
+  hi = d->level_hi, lo = d->level_lo;
+  if (hi == -1 && lo == -1) { hi = top; lo = 0; }
+  MAUA_REQUIRE(lo >= 0 && hi >= lo, "maua_farneback: level_hi .. level_lo must run downwards to a level >= 0 (-1, -1: every level)");
+  MAUA_REQUIRE(hi <= top, "maua_farneback: level_hi is above the top level of this size (maua_farneback_levels - 1)");
+  MAUA_REQUIRE(d->iterations >= 0 && d->iterations <= FB_ITERS, "maua_farneback: iterations must be 1 .. 15 (0: 15)");
+  iters = d->iterations ? d->iterations : FB_ITERS;
+  MAUA_REQUIRE((d->init_ab != nullptr) == (d->init_ba != nullptr), "maua_farneback: init_ab and init_ba go together");
+  MAUA_REQUIRE(!d->init_ab || (d->init_ab != d->init_ba && d->init_ab != d->flow_ab && d->init_ab != d->flow_ba && d->init_ba != d->flow_ab &&
+                               d->init_ba != d->flow_ba),
+               "maua_farneback: the initial flows must not alias each other or the outputs");
+  for (int k = hi; k >= lo; k--) {
+    int h, w;
+    double sigma;
+    level_geometry(d->H, d->W, k, h, w, sigma);
+    int ksize = (int)(round_half_even(sigma * 5) | 1);
+    if (ksize < 3) ksize = 3;
+    MAUA_REQUIRE(ksize <= FB_MAX_TAPS && ksize / 2 < d->H && ksize / 2 < d->W, "maua_farneback: pyramid blur wider than the image");
+  }
+  return MAUA_OK;
+}
+
+}  // namespace
+
+int maua_farneback_level_size(int H, int W, int level, int* h, int* w) {
+  MAUA_REQUIRE(h && w, "maua_farneback_level_size: NULL argument");
+  MAUA_REQUIRE(H > 0 && W > 0 && level >= 0 && level <= pyramid_levels(H, W), "maua_farneback_level_size: no such level at this size");
+  double sigma;
+  level_geometry(H, W, level, *h, *w, sigma);
+  return MAUA_OK;
+}
+
+int maua_farneback_check(const maua_farneback* fb, const maua_farneback_desc* d) {
+  int hi, lo, iters;
+  return farneback_check(fb, d, hi, lo, iters);
+}
+
+int maua_farneback_pair_ex(maua_farneback* fb, maua_ctx* ctx, const maua_farneback_desc* d) {
+  MAUA_REQUIRE(fb && ctx, "maua_farneback: NULL handle or ctx");
+  MAUA_REQUIRE(ctx->device == fb->device, "maua_farneback: the handle belongs to another device");
+  int hi, lo, iters;
+  if (farneback_check(fb, d, hi, lo, iters) != MAUA_OK) return MAUA_ERR;
+  const int H = d->H, W = d->W;
   hipStream_t st = ctx->stream;
   const long n = (long)H * W;
   float* p = fb->ws;
@@ -694,21 +756,29 @@ int maua_farneback_pair(maua_farneback* fb, maua_ctx* ctx, const float* im_a, co
   float* M[2];
   M[0] = p;         p += 10 * n;
   M[1] = p;
-  hipLaunchKernelGGL(fb_gray_kernel, dim3(blocks(n), 1, 2), dim3(256), 0, st, im_a, im_b, gray, n);
-  const int levels = pyramid_levels(H, W);
+  // a dump: a device-to-device copy out of the workspace behind the stage that filled it (stream order)
+  auto dump = [&](float* dst, const float* src, long floats) -> hipError_t {
+    return dst ? hipMemcpyAsync(dst, src, (size_t)floats * sizeof(float), hipMemcpyDeviceToDevice, st) : hipSuccess;
+  };
+  hipLaunchKernelGGL(fb_gray_kernel, dim3(blocks(n), 1, 2), dim3(256), 0, st, d->im_a, d->im_b, gray, n);
+  MAUA_HIP_CHECK(dump(d->gray, gray, 2 * n));
   int cur = 0, ph = 0, pw = 0;
-  for (int k = levels; k >= 0; k--) {
-    double scale = 1;
-    for (int i = 0; i < k; i++) scale *= FB_PYR_SCALE;
-    const double sigma = (1. / scale - 1) * 0.5;
-    const int w = (int)round_half_even(W * scale), h = (int)round_half_even(H * scale);
-    const long hw = (long)h * w;
+  long hw = 0;
+  for (int k = hi; k >= lo; k--) {
+    int h, w;
+    double sigma;
+    level_geometry(H, W, k, h, w, sigma);
+    hw = (long)h * w;
     Taps taps;
     blur_taps(sigma, taps);
-    MAUA_REQUIRE(2 * taps.radius + 1 <= FB_MAX_TAPS && taps.radius < H && taps.radius < W, "maua_farneback_pair: pyramid blur wider than the image");
     float* flow = fl[cur];
-    if (k == levels) {
-      MAUA_HIP_CHECK(hipMemsetAsync(flow, 0, (size_t)4 * hw * sizeof(float), st));
+    if (k == hi) {
+      if (d->init_ab) {
+        MAUA_HIP_CHECK(hipMemcpyAsync(flow, d->init_ab, (size_t)2 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
+        MAUA_HIP_CHECK(hipMemcpyAsync(flow + 2 * hw, d->init_ba, (size_t)2 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
+      } else {
+        MAUA_HIP_CHECK(hipMemsetAsync(flow, 0, (size_t)4 * hw * sizeof(float), st));
+      }
     } else {
       hipLaunchKernelGGL(fb_resize_kernel, dim3(blocks(hw * 2), 1, 2), dim3(256), 0, st, (const float*)fl[cur ^ 1], flow, ph, pw, h, w, 2,
                          (float)(1. / FB_PYR_SCALE));
@@ -719,18 +789,33 @@ int maua_farneback_pair(maua_farneback* fb, maua_ctx* ctx, const float* im_a, co
     hipLaunchKernelGGL(fb_poly_v_kernel, dim3(blocks(hw), 1, 2), dim3(256), 0, st, (const float*)lvl, pt, h, w, fb->poly);
     hipLaunchKernelGGL(fb_poly_h_kernel, dim3(blocks(hw), 1, 2), dim3(256), 0, st, (const float*)pt, R, h, w, fb->poly);
     hipLaunchKernelGGL(fb_matrices_kernel, dim3(blocks(hw), 1, 2), dim3(256), 0, st, (const float*)R, (const float*)flow, M[0], h, w);
+    if (k == lo) {
+      MAUA_HIP_CHECK(dump(d->blur, blur, 2 * n));
+      MAUA_HIP_CHECK(dump(d->level, lvl, 2 * hw));
+      MAUA_HIP_CHECK(dump(d->coef, R, 10 * hw));
+      MAUA_HIP_CHECK(dump(d->flow_in, flow, 4 * hw));
+      MAUA_HIP_CHECK(dump(d->mat, M[0], 10 * hw));
+    }
     const dim3 grid((w + FB_TW - 1) / FB_TW, (h + FB_TH - 1) / FB_TH, 2);
-    for (int i = 0; i < FB_ITERS; i++)
+    for (int i = 0; i < iters; i++)
       hipLaunchKernelGGL(fb_iterate_kernel, grid, dim3(FB_TW, FB_TH), 0, st, (const float*)M[i & 1], M[(i + 1) & 1], (const float*)R, flow, h, w,
-                         (int)(i < FB_ITERS - 1));
+                         (int)(i < iters - 1));
     ph = h; pw = w;
     cur ^= 1;
   }
   const float* last = fl[cur ^ 1];
-  MAUA_HIP_CHECK(hipMemcpyAsync(flow_ab, last, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToDevice, st));
-  MAUA_HIP_CHECK(hipMemcpyAsync(flow_ba, last + 2 * n, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(d->flow_ab, last, (size_t)2 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(d->flow_ba, last + 2 * hw, (size_t)2 * hw * sizeof(float), hipMemcpyDeviceToDevice, st));
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
+}
+
+// the default descriptor: every level of the size, 15 iterations, zero initial flow, no dumps
+int maua_farneback_pair(maua_farneback* fb, maua_ctx* ctx, const float* im_a, const float* im_b, int H, int W, float* flow_ab, float* flow_ba) {
+  maua_farneback_desc d = {};
+  d.im_a = im_a; d.im_b = im_b; d.H = H; d.W = W; d.flow_ab = flow_ab; d.flow_ba = flow_ba;
+  d.level_hi = d.level_lo = -1;
+  return maua_farneback_pair_ex(fb, ctx, &d);
 }
 
 }  // extern "C"

@@ -182,14 +182,16 @@ def compose(frame, prev=None, flow=None, consistency=None, cached=None, flow_exa
     return out
 
 
-def turbo_step(prev, nxt, flow, flow_exaggeration, warp_next, blend_t):
-    """One skipped frame of diffusion/video.py:224-237 in one launch -> (warped prev or None, next - warped when ``warp_next`` -, img)."""
+def turbo_step(prev, nxt, flow, flow_exaggeration, warp_next, blend_t, out=None):
+    """One skipped frame of diffusion/video.py:224-237 in one launch -> (warped prev or None, next - warped when ``warp_next`` -, img).
+    ``out``: (prev_out, next_out, img) tensors of the caller's to write (the first two as far as they are produced)."""
     nxt, f = _planar(nxt, "turbo_step", 3), _flow(flow, "turbo_step")
     B, _, H, W = nxt.shape
     prev = None if prev is None else _planar(prev, "turbo_step", 3)
-    prev_out = torch.empty_like(nxt) if prev is not None else None
-    next_out = torch.empty_like(nxt) if warp_next else None
-    img = torch.empty_like(nxt)
+    new = lambda i: torch.empty_like(nxt) if out is None else out[i]
+    prev_out = new(0) if prev is not None else None
+    next_out = new(1) if warp_next else None
+    img = new(2)
     L.check(L.lib().maua_flow_turbo(L.ctx(nxt.device), L.ptr(prev), L.ptr(nxt), L.ptr(f), B, H, W, C.c_float(flow_exaggeration), int(bool(warp_next)),
                                     C.c_float(blend_t), L.ptr(prev_out), L.ptr(next_out), L.ptr(img)))
     return prev_out, (next_out if warp_next else nxt), img
@@ -216,6 +218,13 @@ class Farneback:
         L.check(L.lib().maua_farneback_pair(self._h, L.ctx(a.device), L.ptr(a), L.ptr(b), H, W, L.ptr(out[0]), L.ptr(out[1])))
         return out[0], out[1]
 
+    def pair_ex(self, im_a, im_b, height, width, flow_ab, flow_ba, level_hi=-1, level_lo=-1, iterations=0, init_ab=None, init_ba=None,
+                **dumps):
+        """maua_farneback_pair_ex for the parity tests: every argument a device address (an integer; 0 or None: absent) of a buffer
+        of the caller's, ``dumps`` any of gray / blur / level / coef / flow_in / mat (include/maua_hip.h: maua_farneback_desc)."""
+        d = farneback_desc(im_a, im_b, height, width, flow_ab, flow_ba, level_hi, level_lo, iterations, init_ab, init_ba, **dumps)
+        L.check(L.lib().maua_farneback_pair_ex(self._h, L.ctx(self.device), C.byref(d)))
+
     def __call__(self, im1, im2):
         return self.pair(im1, im2)[0]
 
@@ -229,6 +238,31 @@ class Farneback:
             self.close()
         except Exception:
             pass
+
+
+def farneback_desc(im_a, im_b, height, width, flow_ab, flow_ba, level_hi=-1, level_lo=-1, iterations=0, init_ab=None, init_ba=None, **dumps):
+    """A maua_farneback_desc from device addresses (integers; 0 or None: absent)."""
+    d = L.FbDesc(im_a=im_a or None, im_b=im_b or None, H=int(height), W=int(width), flow_ab=flow_ab or None, flow_ba=flow_ba or None,
+                 level_hi=int(level_hi), level_lo=int(level_lo), iterations=int(iterations), init_ab=init_ab or None, init_ba=init_ba or None)
+    for k, v in dumps.items():
+        if k not in ("gray", "blur", "level", "coef", "flow_in", "mat"):
+            raise ValueError(f"farneback_desc: no dump named {k}")
+        setattr(d, k, v or None)
+    return d
+
+
+def farneback_check(desc, handle=None):
+    """maua_farneback_check (host only): None, or the launcher's own refusal.  Without a handle the descriptor alone is checked."""
+    if L.lib().maua_farneback_check(None if handle is None else handle._h, C.byref(desc)) != 0:
+        return L.lib().maua_last_error().decode()
+    return None
+
+
+def farneback_level_size(height, width, level):
+    """(rows, cols) of pyramid level ``level`` of a height x width pair (host arithmetic of the library)."""
+    h, w = C.c_int(), C.c_int()
+    L.check(L.lib().maua_farneback_level_size(int(height), int(width), int(level), C.byref(h), C.byref(w)))
+    return h.value, w.value
 
 
 def farneback_levels(height, width):

@@ -144,6 +144,7 @@ def turbo(prev, nxt, flow, exaggeration, warp_next, bt):
 # ------------------------------------------------------------------------------------------------------------------ Farneback
 PYR_SCALE, LEVELS, WINSIZE, ITERATIONS, POLY_N, POLY_SIGMA, MIN_SIZE = 0.8, 15, 15, 15, 7, 1.5, 32
 BORDER = (0.14, 0.14, 0.4472, 0.4472, 0.4472)
+V = 2.0 ** -24          # one float32 rounding, relative
 
 
 def to_gray_u8(im):
@@ -245,30 +246,7 @@ def poly_exp(img):
     return torch.stack([b2 * ig11, b3 * ig11, b1 * ig03 + b4 * ig33, b1 * ig03 + b5 * ig33, b6 * ig55])
 
 
-def update_matrices(R0, R1, flow):
-    """R0 / R1 [5, H, W], flow [H, W, 2] -> M [5, H, W]."""
-    _, h, w = R0.shape
-    dt = R0.dtype
-    y, x = torch.meshgrid([torch.arange(h), torch.arange(w)], indexing="ij")
-    dx, dy = flow[..., 0], flow[..., 1]
-    fx, fy = x.to(dt) + dx, y.to(dt) + dy
-    flx, fly = torch.floor(fx), torch.floor(fy)
-    inside = (flx >= 0) & (flx < w - 1) & (fly >= 0) & (fly < h - 1)
-    x1, y1 = flx.clamp(0, w - 2).long(), fly.clamp(0, h - 2).long()
-    tx, ty = fx - flx, fy - fly
-    a00, a01, a10, a11 = (1 - tx) * (1 - ty), tx * (1 - ty), (1 - tx) * ty, tx * ty
-    s = a00 * R1[:, y1, x1] + a01 * R1[:, y1, x1 + 1] + a10 * R1[:, y1 + 1, x1] + a11 * R1[:, y1 + 1, x1 + 1]
-    zero = torch.zeros_like(dx)
-    r2 = torch.where(inside, s[0], zero)
-    r3 = torch.where(inside, s[1], zero)
-    r4 = torch.where(inside, (R0[2] + s[2]) * 0.5, R0[2])
-    r5 = torch.where(inside, (R0[3] + s[3]) * 0.5, R0[3])
-    r6 = torch.where(inside, (R0[4] + s[4]) * 0.25, R0[4] * 0.5)
-    r2 = (R0[0] - r2) * 0.5
-    r3 = (R0[1] - r3) * 0.5
-    r2 = r2 + r4 * dx + r6 * dy
-    r3 = r3 + r6 * dx + r5 * dy
-
+def _border_scale(h, w, dt):
     def side(n):
         v = torch.ones(n, dtype=dt)
         b = torch.tensor(BORDER, dtype=torch.float32).to(dt)
@@ -276,21 +254,101 @@ def update_matrices(R0, R1, flow):
             v[i] = v[i] * b[i]
             v[n - 1 - i] = v[n - 1 - i] * b[i]
         return v
-    sc = side(h)[:, None] * side(w)[None, :]
+    return side(h)[:, None] * side(w)[None, :]
+
+
+def update_matrices(R0, R1, flow, with_bound=False):
+    """R0 / R1 [5, H, W], flow [H, W, 2] -> M [5, H, W].  The sampling positions x + dx, their floors and fractions are taken in the
+    flow's dtype (a float32 flow with float64 coefficients: the device's own positions, exact float32 operations, so the branch taken
+    is the device's at every pixel) and the rest in the coefficients'.  ``with_bound``: -> (M, bound [5, H, W], inside [H, W]), the
+    float32 rounding bound of the kernel's expression tree, element-wise, from the absolute values of the intermediate terms
+    (V = 2^-24 per rounding, contracted or not):
+        weights a = (1 - tx)(1 - ty) ...: two subtractions and a product, 3 V;  s = sum of 4 products: 4 V more -> Es = 7 V sum a |p|
+        r4 = (R0 + s) / 2: Es / 2 + V |R0 + s| / 2 (r5 alike, r6 with 1 / 4; r2' = (R0 - s) / 2);  outside the frame: exact
+        r2 = r2' + r4 dx + r6 dy: E2' + |dx| E4 + |dy| E6 + 3 V (|r2'| + |r4 dx| + |r6 dy|)
+        border scale (up to three products of table entries, one more on r): sc E + 4 V |r sc|, where sc != 1
+        m0 = r4^2 + r6^2: 2 |r4| E4 + 2 |r6| E6 + 2 V (r4^2 + r6^2);  m1 = (r4 + r5) r6: (E4 + E5) |r6| + |r4 + r5| E6 + 2 V |m1|
+        m3 = r4 r2 + r6 r3: |r4| E2 + |r2| E4 + |r6| E3 + |r3| E6 + 2 V (|r4 r2| + |r6 r3|)   (m2 like m0, m4 like m3)"""
+    _, h, w = R0.shape
+    dt, pt = R0.dtype, flow.dtype
+    y, x = torch.meshgrid([torch.arange(h), torch.arange(w)], indexing="ij")
+    fx, fy = x.to(pt) + flow[..., 0], y.to(pt) + flow[..., 1]
+    flx, fly = torch.floor(fx), torch.floor(fy)
+    inside = (flx >= 0) & (flx < w - 1) & (fly >= 0) & (fly < h - 1)
+    x1, y1 = flx.clamp(0, w - 2).long(), fly.clamp(0, h - 2).long()
+    tx, ty = (fx - flx).to(dt), (fy - fly).to(dt)
+    dx, dy = flow[..., 0].to(dt), flow[..., 1].to(dt)
+    a00, a01, a10, a11 = (1 - tx) * (1 - ty), tx * (1 - ty), (1 - tx) * ty, tx * ty
+    p00, p01, p10, p11 = R1[:, y1, x1], R1[:, y1, x1 + 1], R1[:, y1 + 1, x1], R1[:, y1 + 1, x1 + 1]
+    s = a00 * p00 + a01 * p01 + a10 * p10 + a11 * p11
+    zero = torch.zeros_like(dx)
+    r2 = torch.where(inside, s[0], zero)
+    r3 = torch.where(inside, s[1], zero)
+    r4 = torch.where(inside, (R0[2] + s[2]) * 0.5, R0[2])
+    r5 = torch.where(inside, (R0[3] + s[3]) * 0.5, R0[3])
+    r6 = torch.where(inside, (R0[4] + s[4]) * 0.25, R0[4] * 0.5)
+    r2p = (R0[0] - r2) * 0.5
+    r3p = (R0[1] - r3) * 0.5
+    r2 = r2p + r4 * dx + r6 * dy
+    r3 = r3p + r6 * dx + r5 * dy
+    sc = _border_scale(h, w, dt)
+    if with_bound:
+        Es = 7 * V * (a00 * p00.abs() + a01 * p01.abs() + a10 * p10.abs() + a11 * p11.abs())
+        E2p = torch.where(inside, 0.5 * (Es[0] + V * (R0[0] - s[0]).abs()), zero)
+        E3p = torch.where(inside, 0.5 * (Es[1] + V * (R0[1] - s[1]).abs()), zero)
+        E4 = torch.where(inside, 0.5 * (Es[2] + V * (R0[2] + s[2]).abs()), zero)
+        E5 = torch.where(inside, 0.5 * (Es[3] + V * (R0[3] + s[3]).abs()), zero)
+        E6 = torch.where(inside, 0.25 * (Es[4] + V * (R0[4] + s[4]).abs()), zero)
+        E2 = E2p + dx.abs() * E4 + dy.abs() * E6 + 3 * V * (r2p.abs() + (r4 * dx).abs() + (r6 * dy).abs())
+        E3 = E3p + dx.abs() * E6 + dy.abs() * E5 + 3 * V * (r3p.abs() + (r6 * dx).abs() + (r5 * dy).abs())
+        scaled = lambda r, E: sc * E + torch.where(sc != 1, 4 * V * (r * sc).abs(), zero)
+        E2, E3, E4, E5, E6 = scaled(r2, E2), scaled(r3, E3), scaled(r4, E4), scaled(r5, E5), scaled(r6, E6)
     r2, r3, r4, r5, r6 = r2 * sc, r3 * sc, r4 * sc, r5 * sc, r6 * sc
-    return torch.stack([r4 * r4 + r6 * r6, (r4 + r5) * r6, r5 * r5 + r6 * r6, r4 * r2 + r6 * r3, r6 * r2 + r5 * r3])
+    M = torch.stack([r4 * r4 + r6 * r6, (r4 + r5) * r6, r5 * r5 + r6 * r6, r4 * r2 + r6 * r3, r6 * r2 + r5 * r3])
+    if not with_bound:
+        return M
+    a = torch.abs
+    bound = torch.stack([2 * a(r4) * E4 + 2 * a(r6) * E6 + 2 * V * (r4 * r4 + r6 * r6),
+                         (E4 + E5) * a(r6) + a(r4 + r5) * E6 + 2 * V * a(M[1]),
+                         2 * a(r5) * E5 + 2 * a(r6) * E6 + 2 * V * (r5 * r5 + r6 * r6),
+                         a(r4) * E2 + a(r2) * E4 + a(r6) * E3 + a(r3) * E6 + 2 * V * (a(r4 * r2) + a(r6 * r3)),
+                         a(r6) * E2 + a(r2) * E6 + a(r5) * E3 + a(r3) * E5 + 2 * V * (a(r6 * r2) + a(r5 * r3))])
+    return M, bound, inside
 
 
-def blur_solve(M):
-    """15 x 15 box mean of M (replicated border) and the 2 x 2 solve -> flow [H, W, 2]."""
+def _box_mean(M):
     r = WINSIZE // 2
     ones = torch.ones(WINSIZE, dtype=M.dtype)
     x = F.pad(M[:, None], [r, r, r, r], mode="replicate")
     x = F.conv2d(x, ones.reshape(1, 1, 1, -1))
     x = F.conv2d(x, ones.reshape(1, 1, -1, 1))[:, 0]
-    g11, g12, g22, h1, h2 = x * torch.tensor(1.0 / (WINSIZE * WINSIZE), dtype=torch.float32).to(M.dtype)
-    idet = 1.0 / (g11 * g22 - g12 * g12 + torch.tensor(1e-3, dtype=torch.float32).to(M.dtype))
-    return torch.stack([(g22 * h1 - g12 * h2) * idet, (g11 * h2 - g12 * h1) * idet], dim=-1)
+    return x * torch.tensor(1.0 / (WINSIZE * WINSIZE), dtype=torch.float32).to(M.dtype)
+
+
+def blur_solve(M, E_M=None, with_bound=False):
+    """15 x 15 box mean of M (replicated border) and the 2 x 2 solve -> flow [H, W, 2].  ``with_bound``: -> (flow, bound [H, W, 2],
+    valid [H, W]) with the float32 rounding bound of the kernel, element-wise (V = 2^-24; E_M: a bound on M's own error, or None):
+        box mean: 225 terms through 30 additions and one product, e_c = mean(E_M) + 31 V mean(|M_c| + E_M)
+        det = g0 g2 - g1^2 + 1e-3: E_det = |g2| e0 + |g0| e2 + 2 |g1| e1 + 3 V (|g0 g2| + g1^2 + 1e-3)
+        num_x = g2 g3 - g1 g4: E_num = |g3| e2 + |g2| e3 + |g4| e1 + |g1| e4 + 2 V (|g2 g3| + |g1 g4|)    (num_y alike)
+        f = num (1 / det): E = (E_num + |f| E_det) / det + 3 V |f|;  valid where E_det < det / 2 (det >= 1e-3 by Cauchy-Schwarz)"""
+    g = _box_mean(M)
+    g11, g12, g22, h1, h2 = g
+    eps = torch.tensor(1e-3, dtype=torch.float32).to(M.dtype)
+    det = g11 * g22 - g12 * g12 + eps
+    idet = 1.0 / det
+    flow = torch.stack([(g22 * h1 - g12 * h2) * idet, (g11 * h2 - g12 * h1) * idet], dim=-1)
+    if not with_bound:
+        return flow
+    E_M = torch.zeros_like(M) if E_M is None else E_M
+    e = _box_mean(E_M) + 31 * V * _box_mean(M.abs() + E_M)
+    a = torch.abs
+    E_det = a(g22) * e[0] + a(g11) * e[2] + 2 * a(g12) * e[1] + 3 * V * (a(g11 * g22) + g12 * g12 + eps)
+    E_nx = a(h1) * e[2] + a(g22) * e[3] + a(h2) * e[1] + a(g12) * e[4] + 2 * V * (a(g22 * h1) + a(g12 * h2))
+    E_ny = a(h2) * e[0] + a(g11) * e[4] + a(h1) * e[1] + a(g12) * e[3] + 2 * V * (a(g11 * h2) + a(g12 * h1))
+    E_num = torch.stack([E_nx, E_ny], dim=-1)
+    bound = (E_num + a(flow) * E_det[..., None]) / det[..., None] + 3 * V * a(flow)
+    return flow, bound, E_det < det / 2
 
 
 def farneback_gray(prev_u8, next_u8, dtype=torch.float32):
@@ -325,6 +383,255 @@ def farneback_gray(prev_u8, next_u8, dtype=torch.float32):
 def farneback(im1, im2, dtype=torch.float32):
     """flow/__init__.py:38-55 for images [3, H, W] in [0, 1] -> [H, W, 2]."""
     return farneback_gray(to_gray_u8(im1), to_gray_u8(im2), dtype)
+
+
+# ------------------------------------------------------------------------------------------------------------------ stage by stage
+# What tests/test_gpu_farneback.py holds each kernel to and tests/test_farneback_host.py proves of the float32 restatement: the float64
+# result of one stage on the input that stage was given, and the float32 rounding bound of the kernel's own sequence of operations
+# (V = 2^-24 per rounding; a float32 sum of n products, in any order and contracted or not, lies within n V sum|terms| of exact).
+def level_size(rows, cols, k):
+    """(h, w) of pyramid level k, as farneback_gray computes it."""
+    scale = 1.0
+    for _ in range(k):
+        scale *= PYR_SCALE
+    return _round(rows * scale), _round(cols * scale)
+
+
+def level_taps(k):
+    """The pyramid blur's taps of level k, rounded to float32, as a float64 tensor."""
+    scale = 1.0
+    for _ in range(k):
+        scale *= PYR_SCALE
+    return blur_taps((1.0 / scale - 1) * 0.5).float().double()
+
+
+def pyr_blur(gray, taps, with_bound=False):
+    """[H, W] -> the rows' pass then the columns' pass, reflect-101.  Bound: the first pass leaves n V sum|terms|, the second carries that
+    through its taps and adds n V sum|terms| of its own input (the exact first pass and its error)."""
+    first = _conv_axis(gray, taps, 1, "reflect")
+    out = _conv_axis(first, taps, 0, "reflect")
+    if not with_bound:
+        return out
+    n = taps.shape[0]
+    e1 = n * V * _conv_axis(gray.abs(), taps, 1, "reflect")
+    return out, _conv_axis(e1, taps, 0, "reflect") + n * V * _conv_axis(first.abs() + e1, taps, 0, "reflect")
+
+
+def fb_resize_bound(x, h, w, mul=None):
+    """-> (fb_resize(x, h, w) [* mul], bound): each way is two products and a sum of a weight 1 - t that is itself rounded, 3 V
+    sum|terms|; the second way carries the first's error through its weights; the multiplier, when there is one, one rounding more."""
+    x0, x1, tx = _resize_coords(x.shape[-1], w)
+    y0, y1, ty = _resize_coords(x.shape[-2], h)
+    tx, ty = tx.to(x.dtype), ty.to(x.dtype)[:, None]
+    rows = x[..., x0] * (1 - tx) + x[..., x1] * tx
+    e_rows = 3 * V * (x[..., x0].abs() * (1 - tx) + x[..., x1].abs() * tx)
+    out = rows[..., y0, :] * (1 - ty) + rows[..., y1, :] * ty
+    e = e_rows[..., y0, :] * (1 - ty) + e_rows[..., y1, :] * ty
+    e = e + 3 * V * ((rows.abs() + e_rows)[..., y0, :] * (1 - ty) + (rows.abs() + e_rows)[..., y1, :] * ty)
+    if mul is not None:
+        out = out * mul
+        e = e * abs(mul) + V * out.abs()
+    return out, e
+
+
+def poly_exp_bound(img):
+    """-> (poly_exp(img), bound [5, H, W]).  Each pass is a sum of 8 terms tap * (left +- right): the pair's sum, the product and up to 7
+    accumulations, 9 V sum |tap| (|left| + |right|); the horizontal pass carries the vertical one's error through its taps and adds its
+    own on that pass's input; the final combinations: a product (V), or two products and their sum (2 V sum|terms|)."""
+    g, xg, xxg, (ig11, ig03, ig33, ig55) = poly_setup()
+    sym = lambda t: torch.cat([t[1:].flip(0), t])
+    anti = lambda t: torch.cat([-t[1:].flip(0), t])
+    cv = lambda x, t, ax: _conv_axis(x, t, ax, "replicate")
+    a = torch.abs
+    T, ET = [], []
+    for taps in (sym(g), anti(xg), sym(xxg)):
+        T.append(cv(img, taps, 0))
+        ET.append(9 * V * cv(a(img), a(taps), 0))
+
+    def second(i, taps):
+        return cv(T[i], taps, 1), cv(ET[i], a(taps), 1) + 9 * V * cv(a(T[i]) + ET[i], a(taps), 1)
+    (b1, e1), (b2, e2), (b4, e4) = second(0, sym(g)), second(0, anti(xg)), second(0, sym(xxg))
+    (b3, e3), (b6, e6) = second(1, sym(g)), second(1, anti(xg))
+    b5, e5 = second(2, sym(g))
+    out = torch.stack([b2 * ig11, b3 * ig11, b1 * ig03 + b4 * ig33, b1 * ig03 + b5 * ig33, b6 * ig55])
+    two = lambda p, ep, q, eq: abs(ig03) * ep + abs(ig33) * eq + 2 * V * (a(p * ig03) + a(q * ig33))
+    bound = torch.stack([abs(ig11) * e2 + V * a(out[0]), abs(ig11) * e3 + V * a(out[1]), two(b1, e1, b4, e4), two(b1, e1, b5, e5),
+                         abs(ig55) * e6 + V * a(out[4])])
+    return out, bound
+
+
+def worst_ratio(got, ref, bound, valid=None):
+    """max |got - ref| / bound over the valid elements (an error where the bound is zero: inf)."""
+    err = (got.double() - ref).abs()
+    assert bool(torch.isfinite(err).all()), "a value that is not finite"
+    r = torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err))
+    if valid is not None:
+        r = r[valid]
+    return float(r.max()) if r.numel() else 0.0
+
+
+def restate_level(a, b, k, init=None, iterations=1):
+    """One pyramid level of the estimator in float32, stage by stage, for images a / b [3, H, W] -> the dict of tensors the device's
+    dumps give (maua_farneback_desc): gray, blur [2, H, W], level [2, h, w], coef [2, 5, h, w], flow_in [2, h, w, 2] (init or zero),
+    mat [2, 5, h, w], and flow [2, h, w, 2] after ``iterations``."""
+    gray = torch.stack([to_gray_u8(a), to_gray_u8(b)])
+    h, w = level_size(gray.shape[1], gray.shape[2], k)
+    blur = torch.stack([pyr_blur(g, level_taps(k)) for g in gray])
+    level = fb_resize(blur, h, w)
+    coef = torch.stack([poly_exp(im) for im in level])
+    flow_in = torch.zeros(2, h, w, 2) if init is None else init.clone()
+    mat = torch.stack([update_matrices(coef[d], coef[1 - d], flow_in[d]) for d in range(2)])
+    flow, M = None, mat
+    for i in range(iterations):
+        flow = torch.stack([blur_solve(M[d]) for d in range(2)])
+        if i < iterations - 1:
+            M = torch.stack([update_matrices(coef[d], coef[1 - d], flow[d]) for d in range(2)])
+    return dict(gray=gray, blur=blur, level=level, coef=coef, flow_in=flow_in, mat=mat, flow=flow)
+
+
+# Each check takes such a dict - the device's or the float32 restatement's - and judges one stage on the input that stage was given:
+# the float64 result of the dict's own previous stage, inside the bound -> the worst error / bound.
+def check_blur(d, k):
+    return max(worst_ratio(d["blur"][i], *pyr_blur(d["gray"][i].double(), level_taps(k), True)) for i in range(2))
+
+
+def check_resize(d):
+    h, w = d["level"].shape[1:]
+    return worst_ratio(d["level"], *fb_resize_bound(d["blur"].double(), h, w))
+
+
+def check_poly(d):
+    return max(worst_ratio(d["coef"][i], *poly_exp_bound(d["level"][i].double())) for i in range(2))
+
+
+def check_matrices(d):
+    """-> (worst ratio over every pixel of both directions, the in-frame masks [2, h, w])"""
+    R = d["coef"].double()
+    res = [update_matrices(R[i], R[1 - i], d["flow_in"][i], True) for i in range(2)]
+    return max(worst_ratio(d["mat"][i], res[i][0], res[i][1]) for i in range(2)), torch.stack([r[2] for r in res])
+
+
+def check_iteration(d):
+    """The flow after one iteration against the box mean and solve of the dict's matrices -> (worst ratio, share of pixels left out)"""
+    res = [blur_solve(d["mat"][i].double(), None, True) for i in range(2)]
+    out = 1 - float(torch.stack([r[2] for r in res]).float().mean())
+    return max(worst_ratio(d["flow"][i], res[i][0], res[i][1], res[i][2]) for i in range(2)), out
+
+
+def check_second_iteration(d1, d2):
+    """d1: the run with one iteration, d2: the same run with two.  The matrices of d1's flow and their bound, carried through the box
+    mean and the solve -> (worst ratio, share of pixels left out)"""
+    R = d2["coef"].double()
+    worst, valid = 0.0, []
+    for i in range(2):
+        M, EM, _ = update_matrices(R[i], R[1 - i], d1["flow"][i], True)
+        f, bound, ok = blur_solve(M, EM, True)
+        worst = max(worst, worst_ratio(d2["flow"][i], f, bound, ok))
+        valid.append(ok)
+    return worst, 1 - float(torch.stack(valid).float().mean())
+
+
+def check_upsample(flow_k, flow_in, h, w):
+    """flow_k [2, hk, wk, 2] of level k, flow_in [2, h, w, 2] entering level k - 1"""
+    ref, bound = fb_resize_bound(flow_k.double().permute(0, 3, 1, 2), h, w, float(torch.tensor(1.0 / PYR_SCALE).float()))
+    return worst_ratio(flow_in.permute(0, 3, 1, 2), ref, bound)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the tests' inputs
+def textured_pair(h, w, shift=(1.5, -0.75), seed=0, sigma=1.6):
+    """A blurred noise field and the same field displaced by ``shift`` pixels (bilinear samples of the one field, so first(p) ~
+    second(p + shift)) -> (first, second) [3, h, w] in [0, 1]: texture at every scale the window sees, unlike sinusoid_pair."""
+    m = 8
+    g = torch.Generator().manual_seed(seed)
+    field = torch.rand(3, h + 2 * m, w + 2 * m, generator=g, dtype=torch.float64)
+    r = int(3 * sigma)
+    k = torch.exp(-(torch.arange(-r, r + 1, dtype=torch.float64) ** 2) / (2 * sigma * sigma))
+    k = k / k.sum()
+    for ax in (1, 0):
+        field = torch.stack([_conv_axis(c, k, ax, "reflect") for c in field])
+    field = (field - field.min()) / (field.max() - field.min())
+
+    def crop(dx, dy):
+        x0, y0 = math.floor(dx), math.floor(dy)
+        tx, ty = dx - x0, dy - y0
+        c = lambda yy, xx: field[:, m + yy:m + yy + h, m + xx:m + xx + w]
+        return (c(y0, x0) * (1 - tx) + c(y0, x0 + 1) * tx) * (1 - ty) + (c(y0 + 1, x0) * (1 - tx) + c(y0 + 1, x0 + 1) * tx) * ty
+    return crop(0.0, 0.0).float(), crop(-shift[0], -shift[1]).float()
+
+
+def gray_images(h, w, seed=3):
+    """Two images [3, h, w] in [-0.2, 1.2] (both clamps of the luminance are reached) with planted grey pixels (r = g = b) in the first
+    rows of the first image whose float32 luminance times 255 is: an integer exactly, that integer less one ulp, 0, and 255 exactly,
+    and one whose value depends on the products and sums not being contracted
+    -> (a, b, planted) with planted a list of (x, kind, the 8-bit value expected)."""
+    g = torch.Generator().manual_seed(seed)
+    a, b = (torch.rand(3, h, w, generator=g) * 1.4 - 0.2 for _ in range(2))
+    lum255 = lambda v: np.float32(np.float32(np.float32(np.float32(0.2126) * v + np.float32(0.7152) * v) + np.float32(0.0722) * v) * np.float32(255))
+    planted, col = [], 0
+    for target, kinds in ((100, ("integer", "below")), (37, ("integer", "below")), (255, ("integer",))):
+        want = {"integer": np.float32(target), "below": np.nextafter(np.float32(target), np.float32(0))}
+        v = np.float32(target / 255)
+        for _ in range(16):
+            v = np.nextafter(v, np.float32(0))
+        found = {}
+        for _ in range(64):
+            for kind in kinds:
+                if lum255(v) == want[kind]:
+                    found.setdefault(kind, v)
+            v = np.nextafter(v, np.float32(2))
+        for kind in kinds:
+            a[:, 0, col] = float(found[kind])            # KeyError: no float32 grey level gives this value (none seen)
+            planted.append((col, kind, target if kind == "integer" else target - 1))
+            col += 1
+    a[:, 0, col] = 0.0
+    planted.append((col, "zero", 0))
+    # a pixel of sinusoid_pair(130, 33): 106 with every product and sum rounded on its own, 105 as soon as 0.7152 g + 0.2126 r is one
+    # fused multiply-add (the luminance lands one ulp lower, below the integer)
+    a[:, 0, col + 1] = torch.tensor(CONTRACTION_PIXEL)
+    planted.append((col + 1, "contraction", 106))
+    return a, b, planted
+
+
+CONTRACTION_PIXEL = (float.fromhex("0x1.014ec4p-1"), float.fromhex("0x1.8af25ap-2"), float.fromhex("0x1.d40032p-2"))
+
+
+def gray_contracted(rgb):
+    """The 8-bit luminance of one pixel with 0.2126 r + 0.7152 g evaluated as a fused multiply-add (one rounding): what a compiler that
+    contracts the expression computes.  The product is exact in float64 and the sum's double rounding cannot matter at 29 spare bits."""
+    f = np.float32
+    r, g, b = (float(f(v)) for v in rgb)
+    first = float(f(float(f(0.7152)) * g + float(f(float(f(0.2126)) * r))))
+    lum = f(f(first) + f(f(0.0722) * f(b)))
+    return int(np.clip(f(lum * f(255)), 0, 255))
+
+
+def matrices_flows(h, w, seed=5, reach=0.35):
+    """Constructed flows entering a level, [2, h, w, 2] float32 (direction a -> b, b -> a): uniform in +- reach (w, h), so that about a
+    tenth of the pixels sample beyond each side of the frame; a few of +- 10 w; and planted pixels at the edges of the in-frame
+    predicate (positions exact in float32): x + dx = w - 1 exactly and one ulp below it, 0 exactly, and two tiny negatives (-1e-30 in
+    column 0; x = 5 with dx = -5 less one ulp), the same along y -> (flows, planted) with planted a list of (direction, y, x, inside)."""
+    g = torch.Generator().manual_seed(seed)
+    f = (torch.rand(2, h, w, 2, generator=g) - 0.5) * 2 * reach * torch.tensor([w, h], dtype=torch.float32)
+    big = torch.randint(0, h * w, (2, 6), generator=g)
+    for d in range(2):
+        for j, i in enumerate(big[d].tolist()):
+            f[d, i // w, i % w] = torch.tensor([10.0 * w, -10.0 * w] if j % 2 else [-10.0 * w, 10.0 * w])[: 2] * (1 if j < 3 else -1)
+    below = lambda v: float(np.nextafter(np.float32(v), np.float32(-1e30)))
+    planted = []
+    for d in range(2):
+        # one row each, its y position inside (dy = 0.25); then one column each, its x position inside (dx = 0.5)
+        for j, (x, dx, inside) in enumerate(((2, float(w - 1 - 2), False), (0, below(w - 1), True), (3, -3.0, True), (0, -1e-30, False),
+                                             (5, below(-5.0), False), (7, float(w - 2 - 7), True))):
+            y = 1 + 2 * j + d
+            f[d, y, x] = torch.tensor([dx, 0.25])
+            planted.append((d, y, x, inside))
+        for j, (y, dy, inside) in enumerate(((2, float(h - 1 - 2), False), (0, below(h - 1), True), (3, -3.0, True), (0, -1e-30, False),
+                                             (5, below(-5.0), False), (8, float(h - 2 - 8), True))):
+            x = 2 + 2 * j + d
+            f[d, y, x] = torch.tensor([0.5, dy])
+            planted.append((d, y, x, inside))
+    assert len({p[:3] for p in planted}) == len(planted)
+    return f, planted
 
 
 def sinusoid_pair(h=80, w=96, shift=(1.5, -0.75), n_waves=20, seed=38):

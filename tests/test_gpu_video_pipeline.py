@@ -239,3 +239,124 @@ def test_end_to_end_clip():
     assert torch.equal(a, b)
     c = VD.video_sample(gd, clip, blend=0, **kw)
     assert not torch.equal(a, c)
+
+
+# ------------------------------------------------------------------------------------------------------------------ batches, tails, guards
+# Two samples with different content against the per-sample reference (the per-batch offsets of the kernels), the composition's ragged
+# last counter, the warp at other channel counts, and every operator's outputs between guard regions (tests/test_gpu_farneback.py's Buf).
+def pair_batch():
+    """pair_17x13 and its vertical mirror (the y flow negated): two different samples, neither with a comparison near its threshold"""
+    fwd, bwd = pair_17x13()
+    m = torch.tensor([1.0, -1.0])
+    return torch.cat([fwd, fwd.flip(1) * m]), torch.cat([bwd, bwd.flip(1) * m])
+
+
+def test_consistency_of_a_batch():
+    import maua_amd.flow as F
+    fwd, bwd = pair_batch()
+    got = F.check_consistency(fwd, bwd).cpu()
+    assert tuple(got.shape) == (2, 13, 17)
+    for i in range(2):
+        exclude, frac = FR.near_threshold(fwd[i:i + 1], bwd[i:i + 1])
+        assert frac == 0 and not bool(exclude.any())
+        err = float((got[i] - FR.check_consistency(fwd[i:i + 1], bwd[i:i + 1])[0]).abs().max())
+        print(f"consistency, sample {i} of 2: max abs {err:.3e}")
+        assert err <= TOL
+    assert not torch.equal(got[0], got[1].flip(0))
+
+
+def test_bilinear_resize_of_a_batch():
+    import maua_amd.flow as F
+    g = torch.Generator().manual_seed(8)
+    flow = (torch.rand(2, 9, 7, 2, generator=g) - 0.5) * 14
+    got = F.resize_bilinear(flow, (20, 13), multiplier=1.7, clamp=5.0).cpu()
+    for i in range(2):
+        err = float((got[i:i + 1] - FR.resize_bilinear(flow[i:i + 1], (20, 13), 1.7, 5.0)).abs().max())
+        print(f"bilinear resize, sample {i} of 2: max abs {err:.3e}")
+        assert err <= TOL
+    cons = torch.rand(2, 9, 7, generator=g)
+    got = F.resize_bilinear(cons, (5, 16)).cpu()
+    for i in range(2):
+        assert float((got[i] - FR.resize_bilinear(cons[i:i + 1, ..., None], (5, 16))[0, ..., 0]).abs().max()) <= TOL
+
+
+@pytest.mark.parametrize("B", [1, 2])
+def test_composition_with_a_ragged_last_counter(B):
+    """5 x 7: B 3 H W = 105 / 210, no multiple of the four elements a thread takes, with the noise on"""
+    import maua_amd.flow as F
+    from maua_amd.rng import philox_normal
+    H, W, sigma, seed = 5, 7, 0.02, 0x1234567890ab
+    assert (B * 3 * H * W) % 4
+    img = smooth_images(3 * B, H, W, 31)
+    frame, prev, cached = img[:B], img[B:2 * B], img[2 * B:]
+    flow = wide_flow(B, H, W, 32, reach=0.6)
+    cons = torch.rand(B, 1, H, W, generator=torch.Generator().manual_seed(33))
+    noise = philox_normal((B, 3, H, W), seed, 0).cpu()
+    got = F.compose(frame, prev, flow, cons, cached, flow_exaggeration=1.2, consistency_trust=0.75, blend=2.0, fade=0.3, noise_injection=sigma,
+                    seed=seed).cpu()
+    for i in range(B):
+        s = slice(i, i + 1)
+        want = FR.compose(frame[s], prev[s], flow[s], cons[s], cached[s], 1.2, 0.75, 2.0, 0.3, sigma, noise[s])
+        err = float((got[s] - want).abs().max())
+        print(f"composition 7x5, sample {i} of {B}: max abs {err:.3e}")
+        assert err <= TOL
+    alone = F.compose(frame, noise_injection=sigma, seed=seed).cpu()
+    want = frame + sigma * noise
+    tail = (B * 3 * H * W) % 4
+    print(f"composition 7x5 B {B}: noise step alone max abs {float((alone - want).abs().max()):.3e}")
+    assert torch.equal(alone.flatten()[-tail:], want.flatten()[-tail:]) and float((alone - want).abs().max()) <= 1e-6
+
+
+def test_turbo_step_of_a_batch():
+    import maua_amd.flow as F
+    img = smooth_images(4, 9, 11, 41)
+    prev, nxt, flow = img[:2], img[2:], wide_flow(2, 9, 11, 42, reach=0.3)
+    p, n, im = F.turbo_step(prev, nxt, flow, 1.4, True, 1 / 3)
+    for i in range(2):
+        s = slice(i, i + 1)
+        wp, wn, wi = FR.turbo(prev[s], nxt[s], flow[s], 1.4, True, torch.tensor(1 / 3))
+        assert float((p[s].cpu() - wp).abs().max()) <= TOL and float((n[s].cpu() - wn).abs().max()) <= TOL and float((im[s].cpu() - wi).abs().max()) <= TOL
+
+
+@pytest.mark.parametrize("C", [1, 4])
+def test_warp_at_other_channel_counts(C):
+    import maua_amd.flow as F
+    H, W = 9, 11
+    img = smooth_images(4, H, W, 51)[:, :1].reshape(1, 4, H, W).repeat(2, 1, 1, 1)[:, :C].contiguous()
+    img[1] = img[1].flip(-1)
+    flow = wide_flow(2, H, W, 52)
+    err = float((F.warp_flow(img, flow, 1.3).cpu() - FR.warp_flow(img, flow, 1.3)).abs().max())
+    print(f"warp C {C}: max abs {err:.3e}")
+    assert err <= TOL
+
+
+def test_outputs_between_guard_regions():
+    """each of the five operators writes its outputs whole and nothing else: B = 2 at 5 x 7, sizes that fill no workgroup"""
+    import maua_amd.flow as F
+    from test_gpu_farneback import Buf
+    B, H, W = 2, 5, 7
+    img = smooth_images(3 * B, H, W, 61)
+    frame, prev, cached = img[:B], img[B:2 * B], img[2 * B:]
+    flow = wide_flow(B, H, W, 62, reach=0.6)
+    cons = torch.rand(B, 1, H, W, generator=torch.Generator().manual_seed(63))
+    o = Buf((B, 3, H, W))
+    assert torch.equal(F.warp_flow(frame, flow, 1.3, out=o.t).cpu(), F.warp_flow(frame, flow, 1.3).cpu())
+    o.check("warp")
+    fwd, bwd = pair_batch()
+    cl, res = Buf((2, 13, 17)), Buf((2, 13, 17))
+    assert torch.equal(F.check_consistency(fwd, bwd, out=(cl.t, res.t)).cpu(), F.check_consistency(fwd, bwd).cpu())
+    cl.check("consistency classes")
+    res.check("consistency map")
+    o = Buf((B, 9, 4, 2))
+    assert torch.equal(F.resize_bilinear(flow, (9, 4), 1.5, 5.0, out=o.t).cpu(), F.resize_bilinear(flow, (9, 4), 1.5, 5.0).cpu())
+    o.check("bilinear resize")
+    o = Buf((B, 3, H, W))
+    kw = dict(flow_exaggeration=1.2, consistency_trust=0.75, blend=2.0, fade=0.3, noise_injection=0.02, seed=77)
+    assert torch.equal(F.compose(frame, prev, flow, cons, cached, out=o.t, **kw).cpu(), F.compose(frame, prev, flow, cons, cached, **kw).cpu())
+    o.check("composition")
+    outs = [Buf((B, 3, H, W)) for _ in range(3)]
+    p, n, im = F.turbo_step(prev, frame, flow, 1.4, True, 0.25, out=tuple(b.t for b in outs))
+    q = F.turbo_step(prev, frame, flow, 1.4, True, 0.25)
+    assert all(torch.equal(x.cpu(), y.cpu()) for x, y in zip((p, n, im), q))
+    for b, what in zip(outs, ("turbo prev", "turbo next", "turbo img")):
+        b.check(what)
