@@ -1,8 +1,10 @@
 // Descriptor entry points of the fused attention kernels (maua_attention_check / _ex, maua_attention_vjp_check / _ex): one launch of
 // attention.hip or attention_vjp.hip with every argument of the launcher in the caller's hand - row strides, the softmax scale, the
 // causal flag, the log-sum-exp rows, and for the gradient the forward's result and log-sum-exp as operands (so a test can hand it the
-// kernel's own or a reference's).  For parity tests; no reference counterpart.  The networks and the operator entry points of unet.hip
-// fill AttnArgs / AttnVjpArgs themselves.
+// kernel's own or a reference's).  For parity tests; no reference counterpart.  The networks and the operator entry points at the end
+// of this file fill AttnArgs / AttnVjpArgs themselves.
+#include <cmath>
+
 #include "common.h"
 #include "internal.h"
 
@@ -48,3 +50,47 @@ extern "C" int maua_attention_vjp_ex(maua_ctx* ctx, const maua_attn_vjp_desc* d)
   MAUA_REQUIRE(ctx && d, "maua_attention_vjp_ex: NULL argument");
   return launch_attention_vjp(ctx->stream, d->dtype, attn_vjp_args(d));
 }
+
+// ---- operator-level entry points (NHWC tensors in the network dtype) -----------------------------------------------------------
+extern "C" {
+
+// QKVAttentionLegacy.forward: qkv [B][T][3 * heads * head_ch] (channel = head * 3 ch + {q, k, v} * ch + c) -> out [B][T][heads * ch]
+int maua_attention_legacy(maua_ctx* ctx, const void* qkv, void* out, int B, int T, int heads, int head_ch, int dtype) {
+  MAUA_REQUIRE(ctx, "maua_attention_legacy: ctx is NULL");
+  AttnArgs a{};
+  a.qkv = qkv; a.out = out; a.B = B; a.T = T; a.heads = heads; a.D = head_ch; a.ld_qkv = 3L * heads * head_ch;
+  a.ld_out = (long)heads * head_ch; a.scale = 1.f / sqrtf((float)head_ch);
+  return launch_attention(ctx->stream, dtype, a);
+}
+
+// the same with CLIP's causal mask (text tower): query t attends to keys 0 .. t
+int maua_attention_causal(maua_ctx* ctx, const void* qkv, void* out, int B, int T, int heads, int head_ch, int dtype) {
+  MAUA_REQUIRE(ctx, "maua_attention_causal: ctx is NULL");
+  AttnArgs a{};
+  a.qkv = qkv; a.out = out; a.B = B; a.T = T; a.heads = heads; a.D = head_ch; a.ld_qkv = 3L * heads * head_ch;
+  a.ld_out = (long)heads * head_ch; a.scale = 1.f / sqrtf((float)head_ch); a.causal = 1;
+  return launch_attention(ctx->stream, dtype, a);
+}
+
+// Input gradient of maua_attention_legacy (what maua_unet_vjp walks a network with): qkv as the forward's, d_out [B][T][C] -> d_qkv
+// [B][T][3C] (the forward is re-run here for the rows' log-sum-exp and the result).
+int maua_attention_legacy_vjp(maua_ctx* ctx, const void* qkv, const void* d_out, void* d_qkv, int B, int T, int heads, int head_ch,
+                              int dtype) {
+  MAUA_REQUIRE(ctx && qkv && d_out && d_qkv, "maua_attention_legacy_vjp: NULL argument");
+  MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_attention_legacy_vjp: f32 / bf16");
+  if (B == 0) return MAUA_OK;
+  const size_t esize = dtype == MAUA_BF16 ? 2 : 4;
+  const size_t out_bytes = ((size_t)B * T * heads * head_ch * esize + 255) & ~(size_t)255, row_bytes = ((size_t)B * heads * T * 4 + 255) & ~(size_t)255;
+  if (int rc = scratch_reserve(ctx, out_bytes + 2 * row_bytes + 512)) return rc;
+  char* ws = (char*)ctx->scratch;
+  AttnArgs f{};
+  f.qkv = qkv; f.out = ws; f.B = B; f.T = T; f.heads = heads; f.D = head_ch; f.ld_qkv = 3L * heads * head_ch;
+  f.ld_out = (long)heads * head_ch; f.scale = 1.f / sqrtf((float)head_ch); f.lse = (float*)(ws + out_bytes);
+  if (int rc = launch_attention(ctx->stream, dtype, f)) return rc;
+  AttnVjpArgs a{};
+  a.qkv = qkv; a.out = ws; a.d_out = d_out; a.lse = f.lse; a.d_qkv = d_qkv; a.delta = (float*)(ws + out_bytes + row_bytes); a.B = B; a.T = T;
+  a.heads = heads; a.D = head_ch; a.ld_qkv = f.ld_qkv; a.ld_out = f.ld_out; a.scale = f.scale;
+  return launch_attention_vjp(ctx->stream, dtype, a);
+}
+
+}  // extern "C"

@@ -450,7 +450,7 @@ struct maua_clip {
   float *aug_x1 = nullptr, *aug_x2 = nullptr; size_t aug_x_bytes = 0;
   double* parts = nullptr;
   unsigned long long uid = 0, epoch = 0;   // identity of this tower / generation of its buffers (a captured graph holds pointers into
-};                                          // them: unet.hip compares both before a replay)
+};                                          // them: sampler.hip compares both before a replay)
 
 // CLIP's text tower (CLIP.encode_text): forward only - prompts are constants of the guided loop
 struct maua_clip_text {

@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void screened_add_kernel(const float* __restri
 }
 
 // (zeroing by kernel, not by a memset node: these calls are also captured into the guided loop's hipGraph, where replays of small
-//  memset nodes were seen misbehaving on ROCm 7.0.2 - unet.hip)
+//  memset nodes were seen misbehaving on ROCm 7.0.2 - sampler.hip)
 __global__ __launch_bounds__(256) void zero_u32_kernel(uint32_t* __restrict__ p, long n) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = 0u;

@@ -421,3 +421,13 @@ int maua_gemm_nt_ex(maua_ctx* ctx, const maua_gemm_desc* d, int dtype, int prefe
   if (int rc = gemm_plan(dtype, g, prefer_dma, force, &r)) return rc;
   return launch_gemm_routed(ctx->stream, dtype, g, r);
 }
+
+// conv_nd(1, K, N, 1) / nn.Linear on rows: c[M][N] = a[M][K] x w[N][K]^T + bias (+ res[M][N]); a, w, res, c in dtype
+int maua_linear_nt(maua_ctx* ctx, const void* a, const void* w, const float* bias, const void* res, void* c, long M, int N,
+                   int K, int dtype) {
+  MAUA_REQUIRE(ctx, "maua_linear_nt: ctx is NULL");
+  GemmArgs g{};
+  g.a0 = a; g.lda0 = K; g.K0 = K; g.w = w; g.bias = bias; g.res = res; g.ldr = N; g.c = c; g.ldc = N; g.M = M; g.N = N;
+  g.prefer_dma = ctx->linear_dma;   // (option "linear_dma": large shapes on gemm_dma.hip - what the CLIP tower's projections run on)
+  return launch_gemm_nt(ctx->stream, dtype, g);
+}

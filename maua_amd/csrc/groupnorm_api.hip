@@ -1,5 +1,5 @@
 // Descriptor entry points of the fused GroupNorm pass and its input gradient (maua_group_norm_check / _plan / _ex,
-// maua_group_norm_vjp_check / _plan / _ex): one call of unet.hip's launch_group_norm or groupnorm_vjp.hip's launch_group_norm_vjp
+// maua_group_norm_vjp_check / _plan / _ex): one call of groupnorm.hip's launch_group_norm or groupnorm_vjp.hip's launch_group_norm_vjp
 // - the launchers the diffusion UNet and the operator entry points go through - with every argument in the caller's hand: both
 // sources of the virtual concatenation, the resampling mode and the raw second output, the scale-shift row stride, the producing
 // convolution's piece sums, the kernel route, and for the gradient the forward's statistics as an operand.  For parity tests; no
@@ -92,3 +92,46 @@ extern "C" int maua_group_norm_vjp_ex(maua_ctx* ctx, const maua_gn_vjp_desc* d) 
   if (int rc = scratch_reserve(ctx, group_norm_vjp_workspace(d->B, d->C0 + d->C1, (long)d->H * d->W, d->dtype == MAUA_BF16 ? 2 : 4))) return rc;
   return launch_group_norm_vjp(ctx->stream, d->dtype, a, ctx->scratch);
 }
+
+// ---- operator-level entry points (NHWC tensors in the network dtype) -----------------------------------------------------------
+extern "C" {
+
+// GroupNorm32(32, C) (+ optional per-sample scale-shift [B][2C]: y * (1 + scale) + shift) (+ SiLU) on NHWC x -> y
+int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift,
+                         int silu, int B, int H, int W, int C, int dtype, void* y) {
+  MAUA_REQUIRE(ctx && x && gamma && beta && y, "maua_group_norm_nhwc: NULL argument");
+  MAUA_REQUIRE(C % 32 == 0 && (dtype == MAUA_F32 || dtype == MAUA_BF16), "maua_group_norm_nhwc: C % 32, f32 / bf16");
+  if (B == 0) return MAUA_OK;
+  const size_t part_bytes = group_norm_workspace(B, C, (long)H * W, dtype == MAUA_BF16 ? 2 : 4);
+  if (int rc = scratch_reserve(ctx, part_bytes + (size_t)B * 64 * 4 + 512)) return rc;
+  double* part = (double*)ctx->scratch;
+  float* stats = (float*)((char*)ctx->scratch + ((part_bytes + 255) & ~(size_t)255));
+  GnArgs a{};
+  a.x0 = x; a.C0 = C; a.B = B; a.H = H; a.W = W; a.gamma = gamma; a.beta = beta; a.ss = scale_shift; a.ss_ld = 2L * C; a.silu = silu;
+  a.y = y;
+  return launch_group_norm(ctx->stream, dtype, a, part, stats);
+}
+
+// GroupNorm32 (+ scale-shift) (+ SiLU) (+ resample: 0 none, 1 2x2 average, 2 nearest x2 - behind the activation, as the
+// ResBlocks' h_upd): dy [B][Ho][Wo][C] -> dx [B][H][W][C]; dres (optional, like dy): the gradient of the resampled raw x, added.
+int maua_group_norm_nhwc_vjp(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift, int silu,
+                             int resample, const void* dy, const void* dres, int B, int H, int W, int C, int dtype, void* dx) {
+  MAUA_REQUIRE(ctx && x && gamma && beta && dy && dx, "maua_group_norm_nhwc_vjp: NULL argument");
+  MAUA_REQUIRE(C % 32 == 0 && (dtype == MAUA_F32 || dtype == MAUA_BF16), "maua_group_norm_nhwc_vjp: C % 32, f32 / bf16");
+  if (B == 0) return MAUA_OK;
+  const int esize = dtype == MAUA_BF16 ? 2 : 4;
+  const size_t part_bytes = (group_norm_workspace(B, C, (long)H * W, esize) + 255) & ~(size_t)255;
+  const size_t vjp_bytes = group_norm_vjp_workspace(B, C, (long)H * W, esize);
+  if (int rc = scratch_reserve(ctx, part_bytes + (size_t)B * 64 * 4 + 512 + vjp_bytes)) return rc;
+  double* part = (double*)ctx->scratch;
+  float* stats = (float*)((char*)ctx->scratch + part_bytes);
+  void* ws = (char*)ctx->scratch + part_bytes + (size_t)B * 64 * 4 + 256;
+  // the forward's statistics (its output goes nowhere: the statistics passes only)
+  if (int rc = launch_group_norm_stats(ctx->stream, dtype, x, C, B, H, W, part, stats)) return rc;
+  GnVjpArgs a{};
+  a.x0 = x; a.C0 = C; a.stats = stats; a.gamma = gamma; a.beta = beta; a.ss = scale_shift; a.ss_ld = 2L * C; a.silu = silu; a.mode = resample;
+  a.dy = dy; a.dres = dres; a.dx0 = dx; a.B = B; a.H = H; a.W = W;
+  return launch_group_norm_vjp(ctx->stream, dtype, a, ws);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Input gradient of the UNet's fused GroupNorm pass (unet.hip: gn_apply_kernel) - one of the pieces of guidance speed "regular",
+// Input gradient of the UNet's fused GroupNorm pass (groupnorm.hip: gn_apply_kernel) - one of the pieces of guidance speed "regular",
 // which differentiates the loss through the diffusion UNet itself.
 //
 // Replaces (reference): the autograd of maua/diffusion/processors/guided.py:258-272 (`torch.autograd.grad(img, x, img_grad)` with

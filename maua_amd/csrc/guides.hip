@@ -1,5 +1,5 @@
 // Grad modules of the guided sampler as library objects, so that a LIST of them can be evaluated inside the captured guided loop
-// (maua_unet_set_guides, unet.hip) - the reference sums up to four modules per step (maua/diffusion/image.py:92-97,
+// (maua_unet_set_guides, sampler.hip) - the reference sums up to four modules per step (maua/diffusion/image.py:92-97,
 // guided.py:258-266: `for grad_mod in self.grad_modules: ... img_grad += sub_grad`).
 //
 // A guide holds what one module's forward needs besides the image: VGGGrads (maua/grad.py:90-93) = the perceptor handle, its style

@@ -69,7 +69,7 @@ struct ConvArgs {
   int img_h, img_w;       // the u8 frame's own size (0 = H x W): only the top-left img_h x img_w window is written, densely - an up-scaler
                           // whose input was reflect-padded (RealESRGANer.pre_pad) crops its output in the store instead of in a copy
   const float* prelu;     // optional per-channel negative slopes [Co] (PReLU: replaces act / alpha; SRVGGNetCompact, super.hip)
-  // modconv_dma (wide tiles) only: optional side output for a GroupNorm that follows (unet.hip) - per (sample, 8 x 32-pixel tile)
+  // modconv_dma (wide tiles) only: optional side output for a GroupNorm that follows (groupnorm.hip) - per (sample, 8 x 32-pixel tile)
   // row and 8-channel piece the sum and the sum of squares of the STORED values: psum[b][tile][Co / 8][16] floats
   // ([0..8) sums, [8..16) sums of squares of the piece's channels).  Saves the statistics pass its read of the tensor.
   float* psum;
@@ -424,7 +424,7 @@ int group_norm_vjp_check(int dtype, const GnVjpArgs& a);
 struct GnVjpPlanInfo { int RY, ppc, nchunk, ranges; };
 GnVjpPlanInfo group_norm_vjp_plan(int dtype, const GnVjpArgs& a);
 
-// unet.hip: GroupNorm32 (+ scale-shift) (+ SiLU) (+ resample: 0 none, 1 2x2 average, 2 nearest x2) of the virtually concatenated
+// groupnorm.hip: GroupNorm32 (+ scale-shift) (+ SiLU) (+ resample: 0 none, 1 2x2 average, 2 nearest x2) of the virtually concatenated
 // [x0 | x1] ([B][H][W][C0 | C1], dense NHWC in the network dtype) -> y [B][Ho][Wo][C0 + C1]; xr (optional): the same resampling of
 // the raw input.  ps0 / ps1 (optional, bf16): the piece sums the producing LDS-direct convolution left (ConvArgs.psum,
 // [B][rows][C / 8][16]); the statistics come from them when the group kernels run and every source has them, else from a pass
@@ -452,6 +452,8 @@ GnPlanInfo group_norm_plan(int dtype, const GnArgs& a);    // host only: what a 
 size_t group_norm_workspace(int B, int C, long HW, int esize);   // bytes of `part`
 // part: group_norm_workspace() bytes; stats: [B][32][2] floats, left holding (mean, rstd)
 int launch_group_norm(hipStream_t stream, int dtype, const GnArgs& a, double* part, float* stats);
+// the statistics passes alone, over one dense tensor x [B][H][W][C] (per-channel kernels: any C % 32 == 0); part, stats as above
+int launch_group_norm_stats(hipStream_t stream, int dtype, const void* x, int C, int B, int H, int W, double* part, float* stats);
 
 // cutouts.hip: random cutouts resized to the perceptor's input (maua/ops/cutouts.py:8-50 as CLIPGrads calls it) and their gradient.
 // rects: DEVICE [n_cut][3] (size, top, left); tables: cutouts_table_bytes() of device scratch filled by launch_cutout_tables;
@@ -514,7 +516,7 @@ maua_ctx* secondary_ctx(maua_secondary* n);
 // (uid, epoch) of a secondary model's device buffers: whoever caches pointers into them (a captured graph) compares both before reuse
 void secondary_stamp(maua_secondary* n, unsigned long long* uid, unsigned long long* epoch);
 
-// clip.hip: pieces the captured guided loop (unet.hip) drives.  clip_prepare_guide allocates (never inside a capture);
+// clip.hip: pieces the captured guided loop (sampler.hip) drives.  clip_prepare_guide allocates (never inside a capture);
 // clip_guide_grad = CLIPGrads.forward on DEVICE rectangles [batches][cutn][3]
 maua_ctx* clip_ctx(maua_clip* n);
 void clip_stamp(maua_clip* n, unsigned long long* uid, unsigned long long* epoch);

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void sec_grad_out_kernel(const T* __restrict__
 
 struct maua_secondary {
   maua_ctx* ctx;
-  // identity of this model and of its device buffers: a captured graph that holds pointers into them (unet.hip's guided loop) is valid
+  // identity of this model and of its device buffers: a captured graph that holds pointers into them (sampler.hip's guided loop) is valid
   // for one (uid, epoch) only.  uid is never reused (an allocator may hand a later model the freed one's address); epoch moves whenever
   // a workspace or table is freed or reallocated.
   unsigned long long uid = 0, epoch = 0;

@@ -20,7 +20,8 @@
 // block's up / down resampling are ONE pass that writes the convolution's input; the decoder's channel concatenation is
 // never materialised (GroupNorm and the 1x1 skip GEMM read both tensors); all ResBlocks' timestep projections are one
 // batched GEMV at the top of the forward.  A forward is a fixed sequence of launches on one stream over a
-// pre-planned arena (no allocation, no host sync), so maua_ddim_sample_loop can capture the whole sampler in a hipGraph.
+// pre-planned arena (no allocation, no host sync), so maua_ddim_sample_loop (sampler.hip) can capture the whole sampler in a hipGraph.
+// The fused GroupNorm pass is groupnorm.hip; the network's state and what the sampler loops use of it: unet_internal.h.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -30,6 +31,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "unet_internal.h"
 
 using namespace maua;
 
@@ -101,768 +103,7 @@ __global__ __launch_bounds__(256) void transpose_flip_kernel(const float* __rest
   dst[((long)i * Co + o) * kk + (kk - 1 - k)] = src[idx];
 }
 
-// ------------------------------------------------------------------------------------------------------ GroupNorm
-// Statistics in float64 (sum and sum of squares of exactly representable f32 products): no cancellation whatever the
-// mean / spread ratio; fixed summation order (bit-reproducible).  Pass 1: per (sample, pixel chunk, row slot) per-channel
-// partial sums; pass 2: per (sample, group) mean and 1 / sqrt(var + eps).
-template <typename T>
-__global__ void gn_partial_kernel(const T* __restrict__ x0, int C0, const T* __restrict__ x1, int C1, long HW, int ppc,
-                                  double* __restrict__ part) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int C = C0 + C1, PPP = C / EPC;
-  const int pc = threadIdx.x % PPP, ry = threadIdx.x / PPP, RY = blockDim.x / PPP;
-  const int chunk = blockIdx.x, b = blockIdx.y;
-  if (ry >= RY) return;
-  const int c = pc * EPC;
-  const T* src;
-  long stride;
-  if (c < C0) { src = x0 + (long)b * HW * C0 + c; stride = C0; }
-  else { src = x1 + (long)b * HW * C1 + (c - C0); stride = C1; }
-  const long p0 = (long)chunk * ppc, p1 = p0 + ppc < HW ? p0 + ppc : HW;
-  double s[EPC], ss[EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; e++) s[e] = ss[e] = 0.0;
-  for (long p = p0 + ry; p < p1; p += RY) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(src + p * stride);
-#pragma unroll
-    for (int e = 0; e < EPC; e++) {
-      float f;
-      if constexpr (sizeof(T) == 2) f = bf2f((bf16_t)((v[e >> 1] >> ((e & 1) * 16)) & 0xffffu));
-      else f = __uint_as_float(v[e]);
-      const double d = (double)f;
-      s[e] += d;
-      ss[e] += d * d;
-    }
-  }
-  double* dst = part + ((((long)b * gridDim.x + chunk) * RY + ry) * C + c) * 2;
-#pragma unroll
-  for (int e = 0; e < EPC; e++) { dst[2 * e] = s[e]; dst[2 * e + 1] = ss[e]; }
-}
-
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part, int rows, int C, long HW, float eps,
-                                                          float* __restrict__ stats) {
-  __shared__ double red[2][256];
-  const int g = blockIdx.x, b = blockIdx.y;
-  const int cpg = C / 32;
-  const long n = (long)rows * cpg;
-  double s = 0.0, ss = 0.0;
-  for (long i = threadIdx.x; i < n; i += 256) {
-    const long row = i / cpg;
-    const int c = g * cpg + (int)(i - row * cpg);
-    const double* p = part + (((long)b * rows + row) * C + c) * 2;
-    s += p[0];
-    ss += p[1];
-  }
-  red[0][threadIdx.x] = s;
-  red[1][threadIdx.x] = ss;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + o];
-      red[1][threadIdx.x] += red[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double cnt = (double)HW * cpg;
-    const double mean = red[0][0] / cnt;
-    double var = red[1][0] / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    stats[((long)b * 32 + g) * 2] = (float)mean;
-    stats[((long)b * 32 + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-}
-
-// y = [silu]( gn(x) [* (1 + scale) + shift] ), optionally resampled (mode 1: 2x2 average of the activated values - the
-// ResBlock's Downsample sits BEHIND norm + SiLU; mode 2: nearest x2), written dense NHWC as the next convolution's input.
-// xr (optional, modes 1 / 2): the same resampling of the raw input (the block's x_upd, its residual branch).
-template <typename T>
-__global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x0, int C0, const T* __restrict__ x1, int C1,
-                                                       const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, const float* __restrict__ ss, long ss_ld,
-                                                       int silu, int mode, T* __restrict__ y, T* __restrict__ xr, int B, int H,
-                                                       int W) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int C = C0 + C1, PPP = C / EPC, cpg = C / 32;
-  const int Ho = mode == 1 ? H / 2 : (mode == 2 ? H * 2 : H), Wo = mode == 1 ? W / 2 : (mode == 2 ? W * 2 : W);
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)B * Ho * Wo * PPP) return;
-  const int pc = (int)(idx % PPP);
-  long p = idx / PPP;
-  const int ox = (int)(p % Wo); p /= Wo;
-  const int oy = (int)(p % Ho);
-  const int b = (int)(p / Ho);
-  const int c = pc * EPC;
-  const T* src;
-  long stride;
-  if (c < C0) { src = x0 + (long)b * H * W * C0 + c; stride = C0; }
-  else { src = x1 + (long)b * H * W * C1 + (c - C0); stride = C1; }
-  float ca[EPC], cb[EPC], sc[EPC], sh[EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; e++) {
-    const int g = (c + e) / cpg;
-    const float mean = stats[((long)b * 32 + g) * 2], rstd = stats[((long)b * 32 + g) * 2 + 1];
-    ca[e] = rstd * gamma[c + e];
-    cb[e] = beta[c + e] - mean * ca[e];
-    sc[e] = ss ? 1.f + ss[(long)b * ss_ld + c + e] : 1.f;
-    sh[e] = ss ? ss[(long)b * ss_ld + C + c + e] : 0.f;
-  }
-  float acc[EPC], raw[EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; e++) acc[e] = raw[e] = 0.f;
-  const int taps = mode == 1 ? 4 : 1;
-  for (int t = 0; t < taps; t++) {
-    int iy, ix;
-    if (mode == 1) { iy = 2 * oy + (t >> 1); ix = 2 * ox + (t & 1); }
-    else if (mode == 2) { iy = oy >> 1; ix = ox >> 1; }
-    else { iy = oy; ix = ox; }
-    const u32x4 v = *reinterpret_cast<const u32x4*>(src + ((long)iy * W + ix) * stride);
-#pragma unroll
-    for (int e = 0; e < EPC; e++) {
-      float f;
-      if constexpr (sizeof(T) == 2) f = bf2f((bf16_t)((v[e >> 1] >> ((e & 1) * 16)) & 0xffffu));
-      else f = __uint_as_float(v[e]);
-      raw[e] += f;
-      float u = fmaf(f, ca[e], cb[e]);
-      if (ss) u = fmaf(u, sc[e], sh[e]);
-      if (silu) u = u / (1.f + expf(-u));
-      acc[e] += u;
-    }
-  }
-  const float norm = mode == 1 ? 0.25f : 1.f;
-  u32x4 o, ro;
-  if constexpr (sizeof(T) == 2) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      o[k] = pack2bf(acc[2 * k] * norm, acc[2 * k + 1] * norm);
-      ro[k] = pack2bf(raw[2 * k] * norm, raw[2 * k + 1] * norm);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; k++) { o[k] = __float_as_uint(acc[k] * norm); ro[k] = __float_as_uint(raw[k] * norm); }
-  }
-  const long opix = ((long)b * Ho + oy) * Wo + ox;
-  *reinterpret_cast<u32x4*>(y + opix * C + c) = o;
-  if (xr) *reinterpret_cast<u32x4*>(xr + opix * C + c) = ro;
-}
-
-// ---- fast path (C / 32 channels per group a multiple of the 16-byte piece: every real layer of the network; the
-// per-channel kernels above serve narrow test networks).  Same arithmetic, organised for the memory system:
-//   * partial sums per GROUP, reduced inside the workgroup (LDS, fixed order) -> one row of 32 (sum, sumsq) pairs per
-//     pixel chunk; a finalize launch of B x 32 threads adds the <= 128 chunk rows;
-//   * the apply pass indexes (sample, row) by blockIdx.y and (pixel, piece) by 32-bit arithmetic, loads its piece's
-//     coefficients as float4s, and in bf16 mode uses the hardware exp / reciprocal for SiLU (exact in f32 mode).
-// (Folding the finalize into this kernel - the last workgroup of a sample, found by an atomic ticket, adds the chunk rows - was
-//  built and measured in round 3: 26.7 -> 35.3 ms per UNet step at B = 8.  A device-scope release fence per workgroup writes
-//  the XCD's L2 back (8 XCDs, one L2 each): far dearer than the ~5 us launch it saves.  The finalize stays its own launch.)
-template <typename T>
-__global__ void gn_partial_group_kernel(const T* __restrict__ x0, int C0, const T* __restrict__ x1, int C1, long HW, int ppc,
-                                        double* __restrict__ part) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  __shared__ double red[2][1024];
-  const int C = C0 + C1, PPP = C / EPC;
-  const int pc = threadIdx.x % PPP, ry = threadIdx.x / PPP, RY = blockDim.x / PPP;
-  const int chunk = blockIdx.x, b = blockIdx.y;
-  const int c = pc * EPC;
-  const T* src;
-  long stride;
-  if (c < C0) { src = x0 + (long)b * HW * C0 + c; stride = C0; }
-  else { src = x1 + (long)b * HW * C1 + (c - C0); stride = C1; }
-  const long p0 = (long)chunk * ppc, p1 = p0 + ppc < HW ? p0 + ppc : HW;
-  double s = 0.0, ss = 0.0;
-  for (long p = p0 + ry; p < p1; p += RY) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(src + p * stride);
-    float fs = 0.f, fq = 0.f;   // 8 (4) values: exact enough in f32 before they join the f64 sums
-#pragma unroll
-    for (int e = 0; e < EPC; e++) {
-      float f;
-      if constexpr (sizeof(T) == 2) f = bf2f((bf16_t)((v[e >> 1] >> ((e & 1) * 16)) & 0xffffu));
-      else f = __uint_as_float(v[e]);
-      if constexpr (sizeof(T) == 2) { fs += f; fq = fmaf(f, f, fq); }
-      else { s += (double)f; ss += (double)f * (double)f; }
-    }
-    if constexpr (sizeof(T) == 2) { s += (double)fs; ss += (double)fq; }
-  }
-  red[0][threadIdx.x] = s;
-  red[1][threadIdx.x] = ss;
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    const int g = threadIdx.x, ppg = PPP / 32;
-    double ts = 0.0, tq = 0.0;
-    for (int r = 0; r < RY; r++)
-      for (int j = 0; j < ppg; j++) {
-        ts += red[0][r * PPP + g * ppg + j];
-        tq += red[1][r * PPP + g * ppg + j];
-      }
-    double* dst = part + (((long)b * gridDim.x + chunk) * 32 + g) * 2;
-    dst[0] = ts;
-    dst[1] = tq;
-  }
-}
-
-__global__ __launch_bounds__(256) void gn_finalize_group_kernel(const double* __restrict__ part, int nchunk, double cnt,
-                                                                float eps, float* __restrict__ stats) {
-  // 32 groups x 8 lanes: lane j adds chunks j, j + 8, ... (independent loads in flight), then a fixed-order LDS tree
-  __shared__ double red[2][256];
-  const int g = threadIdx.x & 31, j = threadIdx.x >> 5, b = blockIdx.x;
-  double s = 0.0, ss = 0.0;
-  for (int k = j; k < nchunk; k += 8) {
-    const double* p = part + (((long)b * nchunk + k) * 32 + g) * 2;
-    s += p[0];
-    ss += p[1];
-  }
-  red[0][threadIdx.x] = s;
-  red[1][threadIdx.x] = ss;
-  __syncthreads();
-  if (j == 0) {
-#pragma unroll
-    for (int q = 1; q < 8; q++) { s += red[0][q * 32 + g]; ss += red[1][q * 32 + g]; }
-    const double mean = s / cnt;
-    double var = ss / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    stats[((long)b * 32 + g) * 2] = (float)mean;
-    stats[((long)b * 32 + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-}
-
-// Statistics from the piece sums a producing convolution left behind (ConvArgs.psum: per 8 x 32-pixel tile and 8-channel
-// piece, sums and sums of squares of the stored values) - the tensor itself is not read again.  Two sources like everywhere
-// (the decoder's virtual concatenation); 32 groups x 8 lanes, rows j, j + 8, ... per lane, fixed-order LDS tree.
-__global__ __launch_bounds__(256) void gn_finalize_psum_kernel(const float* __restrict__ ps0, int rows0, int C0,
-                                                               const float* __restrict__ ps1, int rows1, int C1, double cnt,
-                                                               float eps, float* __restrict__ stats) {
-  __shared__ double red[2][256];
-  const int g = threadIdx.x & 31, j = threadIdx.x >> 5, b = blockIdx.x;
-  const int np0 = C0 >> 3, np1 = C1 >> 3, ppg = (np0 + np1) >> 5;
-  double s = 0.0, ss = 0.0;
-  for (int pi = 0; pi < ppg; pi++) {
-    const int piece = g * ppg + pi;
-    const bool first = piece < np0;
-    const float* src = first ? ps0 : ps1;
-    const int rows = first ? rows0 : rows1, np = first ? np0 : np1, pc = first ? piece : piece - np0;
-    for (int r = j; r < rows; r += 8) {
-      const float4* p = reinterpret_cast<const float4*>(src + (((long)b * rows + r) * np + pc) * 16);
-      const float4 a0 = p[0], a1 = p[1], q0 = p[2], q1 = p[3];
-      s += (double)a0.x + (double)a0.y + (double)a0.z + (double)a0.w + (double)a1.x + (double)a1.y + (double)a1.z + (double)a1.w;
-      ss += (double)q0.x + (double)q0.y + (double)q0.z + (double)q0.w + (double)q1.x + (double)q1.y + (double)q1.z + (double)q1.w;
-    }
-  }
-  red[0][threadIdx.x] = s;
-  red[1][threadIdx.x] = ss;
-  __syncthreads();
-  if (j == 0) {
-#pragma unroll
-    for (int q = 1; q < 8; q++) { s += red[0][q * 32 + g]; ss += red[1][q * 32 + g]; }
-    const double mean = s / cnt;
-    double var = ss / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    stats[((long)b * 32 + g) * 2] = (float)mean;
-    stats[((long)b * 32 + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
-}
-
-// A thread owns one 16-byte channel piece and walks GN_PX output pixels of its row with it (round 5: one pixel per thread spent
-// 136 bytes of parameter loads - gamma, beta, scale, shift, statistics - on 16 bytes of data and ran at 1.7 TB/s).
-constexpr int GN_PX = 8;
-template <typename T>
-__global__ __launch_bounds__(256) void gn_apply_group_kernel(const T* __restrict__ x0, int C0, const T* __restrict__ x1, int C1,
-                                                             const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, const float* __restrict__ ss,
-                                                             long ss_ld, int silu, int mode, T* __restrict__ y,
-                                                             T* __restrict__ xr, int H, int W, int Ho, int Wo) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const unsigned C = C0 + C1, PPP = C / EPC, cpg = C / 32;
-  const unsigned li = blockIdx.x * 256u + threadIdx.x;
-  const unsigned nxg = ((unsigned)Wo + GN_PX - 1) / GN_PX;
-  if (li >= nxg * PPP) return;
-  const unsigned oxg = li / PPP, pc = li - oxg * PPP;
-  const unsigned b = blockIdx.y / (unsigned)Ho, oy = blockIdx.y - b * (unsigned)Ho;
-  const unsigned c = pc * EPC;
-  const T* src;
-  unsigned stride;
-  if (c < (unsigned)C0) { src = x0 + (long)b * H * W * C0 + c; stride = C0; }
-  else { src = x1 + (long)b * H * W * C1 + (c - C0); stride = C1; }
-  const unsigned g = c / cpg;
-  const float2 mr = *reinterpret_cast<const float2*>(stats + ((long)b * 32 + g) * 2);
-  float ca[EPC], cb[EPC], sc[EPC], sh[EPC];
-#pragma unroll
-  for (int q4 = 0; q4 < EPC / 4; q4++) {
-    const float4 gm = *reinterpret_cast<const float4*>(gamma + c + 4 * q4);
-    const float4 bt = *reinterpret_cast<const float4*>(beta + c + 4 * q4);
-    const float gv[4] = {gm.x, gm.y, gm.z, gm.w}, bv[4] = {bt.x, bt.y, bt.z, bt.w};
-    float sv[4] = {1.f, 1.f, 1.f, 1.f}, hv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (ss) {
-      const float4 s4 = *reinterpret_cast<const float4*>(ss + (long)b * ss_ld + c + 4 * q4);
-      const float4 h4 = *reinterpret_cast<const float4*>(ss + (long)b * ss_ld + C + c + 4 * q4);
-      sv[0] = 1.f + s4.x; sv[1] = 1.f + s4.y; sv[2] = 1.f + s4.z; sv[3] = 1.f + s4.w;
-      hv[0] = h4.x; hv[1] = h4.y; hv[2] = h4.z; hv[3] = h4.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int e = 4 * q4 + k;
-      ca[e] = mr.y * gv[k];
-      cb[e] = bv[k] - mr.x * ca[e];
-      sc[e] = sv[k];
-      sh[e] = hv[k];
-    }
-  }
-  const int taps = mode == 1 ? 4 : 1;
-  const float norm = mode == 1 ? 0.25f : 1.f;
-  // the pixel group's loads are requested together (mode 0 / 2: one per pixel; the 4-tap average pool walks pixel by pixel)
-  u32x4 vin[GN_PX];
-  if (taps == 1) {
-#pragma unroll
-    for (int k = 0; k < GN_PX; k++) {
-      const unsigned ox = min(oxg * GN_PX + k, (unsigned)Wo - 1);
-      const unsigned iy = mode == 2 ? oy >> 1 : oy, ix = mode == 2 ? ox >> 1 : ox;
-      vin[k] = *reinterpret_cast<const u32x4*>(src + (long)(iy * (unsigned)W + ix) * stride);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < GN_PX; k++) {
-    const unsigned ox = oxg * GN_PX + k;
-    if (ox >= (unsigned)Wo) break;
-    float acc[EPC], raw[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; e++) acc[e] = raw[e] = 0.f;
-    for (int t = 0; t < taps; t++) {
-      u32x4 v;
-      if (taps == 1) v = vin[k];
-      else v = *reinterpret_cast<const u32x4*>(src + (long)((2 * oy + (t >> 1)) * (unsigned)W + 2 * ox + (t & 1)) * stride);
-#pragma unroll
-      for (int e = 0; e < EPC; e++) {
-        float f;
-        if constexpr (sizeof(T) == 2) f = bf2f((bf16_t)((v[e >> 1] >> ((e & 1) * 16)) & 0xffffu));
-        else f = __uint_as_float(v[e]);
-        raw[e] += f;
-        float u = fmaf(f, ca[e], cb[e]);
-        if (ss) u = fmaf(u, sc[e], sh[e]);
-        if (silu) {
-          if constexpr (sizeof(T) == 2) u = __fdividef(u, 1.f + __expf(-u));
-          else u = u / (1.f + expf(-u));
-        }
-        acc[e] += u;
-      }
-    }
-    u32x4 o, ro;
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        o[q] = pack2bf(acc[2 * q] * norm, acc[2 * q + 1] * norm);
-        ro[q] = pack2bf(raw[2 * q] * norm, raw[2 * q + 1] * norm);
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++) { o[q] = __float_as_uint(acc[q] * norm); ro[q] = __float_as_uint(raw[q] * norm); }
-    }
-    const long opix = ((long)b * Ho + oy) * Wo + ox;
-    *reinterpret_cast<u32x4*>(y + opix * C + c) = o;
-    if (xr) *reinterpret_cast<u32x4*>(xr + opix * C + c) = ro;
-  }
-}
-
-// workspace (bytes) of one GroupNorm over [B][HW][C]: partial sums + the [B][32][2] statistics
-struct GnPlan { int fast, RY, ppc; long nchunk; size_t part_bytes; };
-static GnPlan gn_plan(int B, int C, long HW, int esize) {
-  GnPlan p;
-  const int EPC = 16 / esize, PPP = C / EPC, cpg = C / 32;
-  p.fast = cpg % EPC == 0 && PPP <= 1024;
-  p.RY = std::max(1, 512 / PPP);
-  long nchunk = HW / ((long)p.RY * 4);
-  nchunk = std::max(1L, std::min(128L, nchunk));
-  p.ppc = (int)((HW + nchunk - 1) / nchunk);
-  p.nchunk = (HW + p.ppc - 1) / p.ppc;
-  p.part_bytes = p.fast ? (size_t)B * p.nchunk * 32 * 16 : (size_t)B * p.nchunk * p.RY * C * 16;
-  return p;
-}
-static void gn_out_size(const GnArgs& a, int* Ho, int* Wo) {
-  *Ho = a.mode == 1 ? a.H / 2 : (a.mode == 2 ? a.H * 2 : a.H);
-  *Wo = a.mode == 1 ? a.W / 2 : (a.mode == 2 ? a.W * 2 : a.W);
-}
-
-// the launches of maua::launch_group_norm (which has checked `a`) as maua::group_norm_plan describes them
-template <typename T>
-static int gn_launch(hipStream_t st, const GnArgs& a, const GnPlanInfo& pl, double* part, float* stats) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const T *x0 = (const T*)a.x0, *x1 = (const T*)a.x1;
-  T *y = (T*)a.y, *xr = (T*)a.xr;
-  const int C0 = a.C0, C1 = a.C1, C = C0 + C1, PPP = C / EPC, B = a.B, H = a.H, W = a.W;
-  const long HW = (long)H * W;
-  int Ho, Wo;
-  gn_out_size(a, &Ho, &Wo);
-  if (pl.route == 0) {
-    if (pl.stats_source == 1) {
-      // every source's producer left its piece sums: no statistics pass over the tensor
-      hipLaunchKernelGGL(gn_finalize_psum_kernel, dim3(B), dim3(256), 0, st, a.ps0, a.rows0, C0, a.ps1, a.rows1, C1,
-                         (double)HW * (C / 32), 1e-5f, stats);
-    } else {
-      hipLaunchKernelGGL(gn_partial_group_kernel<T>, dim3((unsigned)pl.nchunk, B), dim3(PPP * pl.RY), 0, st, x0, C0, x1, C1, HW,
-                         pl.ppc, part);
-      hipLaunchKernelGGL(gn_finalize_group_kernel, dim3(B), dim3(256), 0, st, part, pl.nchunk, (double)HW * (C / 32), 1e-5f,
-                         stats);
-    }
-    hipLaunchKernelGGL(gn_apply_group_kernel<T>, dim3((unsigned)(((long)((Wo + GN_PX - 1) / GN_PX) * PPP + 255) / 256), (unsigned)(B * Ho)),
-                       dim3(256), 0, st, x0, C0, x1, C1, stats, a.gamma, a.beta, a.ss, a.ss_ld, a.silu, a.mode, y, xr, H, W, Ho, Wo);
-  } else {
-    hipLaunchKernelGGL(gn_partial_kernel<T>, dim3((unsigned)pl.nchunk, B), dim3(PPP * pl.RY), 0, st, x0, C0, x1, C1, HW, pl.ppc,
-                       part);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(32, B), dim3(256), 0, st, part, pl.nchunk * pl.RY, C, HW, 1e-5f, stats);
-    const long total = (long)B * Ho * Wo * PPP;
-    hipLaunchKernelGGL(gn_apply_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x0, C0, x1, C1, stats, a.gamma,
-                       a.beta, a.ss, a.ss_ld, a.silu, a.mode, y, xr, B, H, W);
-  }
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-// the statistics passes alone (per-channel kernels: any C % 32 == 0)
-template <typename T>
-static int launch_group_norm_stats(hipStream_t st, const T* x, int C, int B, int H, int W, double* part, float* stats) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  const int PPP = C / EPC;
-  const long HW = (long)H * W;
-  MAUA_REQUIRE(C % 32 == 0 && PPP <= 1024, "group_norm: C % 32 == 0, at most 1024 16-byte pieces per pixel");
-  const GnPlan p = gn_plan(B, C, HW, (int)sizeof(T));
-  hipLaunchKernelGGL(gn_partial_kernel<T>, dim3((unsigned)p.nchunk, B), dim3(PPP * p.RY), 0, st, x, C, (const T*)nullptr, 0, HW, p.ppc, part);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(32, B), dim3(256), 0, st, part, (int)(p.nchunk * p.RY), C, HW, 1e-5f, stats);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-static size_t gn_part_bytes(int B, int C, long HW, int esize) {
-  // (the per-channel layout is the larger one and also serves the fall-back of a fast-path shape with too many rows)
-  const GnPlan p = gn_plan(B, C, HW, esize);
-  return std::max(p.part_bytes, (size_t)B * p.nchunk * p.RY * C * 16);
-}
-
 }  // namespace
-
-// ---- the one GroupNorm launcher: the network (Runner::gn), maua_group_norm_nhwc and maua_group_norm_ex all come through here
-static inline bool gn_aligned16(const void* p) { return ((size_t)p & 15) == 0; }
-
-int maua::group_norm_check(int dtype, const GnArgs& a) {
-  MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "group_norm: unsupported dtype");
-  const int EPC = dtype == MAUA_BF16 ? 8 : 4;
-  MAUA_REQUIRE(a.x0 && a.gamma && a.beta && a.y, "group_norm: NULL argument");
-  MAUA_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.C0 > 0 && a.C1 >= 0, "group_norm: bad shape");
-  const long C = (long)a.C0 + a.C1;
-  MAUA_REQUIRE(C % 32 == 0 && C / EPC <= 1024 && a.C0 % EPC == 0, "group_norm: C % 32 == 0, at most 1024 16-byte pieces per pixel");
-  MAUA_REQUIRE(a.C1 == 0 || a.x1, "group_norm: x1 is NULL with C1 > 0");
-  MAUA_REQUIRE(a.mode >= 0 && a.mode <= 2 && (a.mode != 1 || (a.H >= 2 && a.W >= 2)), "group_norm: bad resample mode");
-  MAUA_REQUIRE(!a.ss || a.ss_ld == 0 || a.ss_ld >= 2 * C, "group_norm: ss_ld is 0 (one row for all samples) or at least 2 C");
-  MAUA_REQUIRE(gn_aligned16(a.x0) && gn_aligned16(a.x1) && gn_aligned16(a.y) && gn_aligned16(a.xr) && gn_aligned16(a.gamma) &&
-                   gn_aligned16(a.beta) && gn_aligned16(a.ss) && gn_aligned16(a.ps0) && gn_aligned16(a.ps1) && a.ss_ld % 4 == 0,
-               "group_norm: pointers and ss_ld must be whole 16-byte pieces");
-  int Ho, Wo;
-  gn_out_size(a, &Ho, &Wo);
-  // (blockIdx.y carries the sample in the statistics kernels; the apply kernels index pixels of a sample in 32 bits)
-  MAUA_REQUIRE(a.B <= 65535 && (long)Ho * Wo <= 0x7fffffffL && (long)a.H * a.W <= 0x7fffffffL &&
-                   ((long)a.B * Ho * Wo * (C / EPC) + 255) / 256 <= 0x7fffffffL,
-               "group_norm: grid too large");
-  MAUA_REQUIRE(!a.ps1 || a.C1 > 0, "group_norm: ps1 without a second source");
-  MAUA_REQUIRE((!a.ps0 && !a.ps1) || dtype == MAUA_BF16, "group_norm: piece sums are bf16 only");
-  const bool tiles = a.H % 8 == 0 && a.W % 32 == 0;
-  const int rows = (a.H / 8) * (a.W / 32);
-  MAUA_REQUIRE((!a.ps0 || (tiles && a.C0 % 128 == 0 && a.rows0 == rows)) && (!a.ps1 || (tiles && a.C1 % 128 == 0 && a.rows1 == rows)),
-               "group_norm: piece sums need H % 8 == 0, W % 32 == 0, C % 128 == 0 of their source and rows == (H / 8) * (W / 32)");
-  return MAUA_OK;
-}
-
-GnPlanInfo maua::group_norm_plan(int dtype, const GnArgs& a) {
-  const int esize = dtype == MAUA_BF16 ? 2 : 4, C = a.C0 + a.C1;
-  const GnPlan p = gn_plan(a.B, C, (long)a.H * a.W, esize);
-  int Ho, Wo;
-  gn_out_size(a, &Ho, &Wo);
-  GnPlanInfo pl;
-  // (the group kernels carry (sample, output row) in blockIdx.y; a shape with more rows runs the per-channel kernels on the same chunks)
-  pl.route = p.fast && (long)a.B * Ho <= 65535 && a.force_route != 1 ? 0 : 1;
-  pl.RY = p.RY;
-  pl.ppc = p.ppc;
-  pl.nchunk = (int)p.nchunk;
-  pl.stats_source = pl.route == 0 && a.ps0 && (a.C1 == 0 || a.ps1) && dtype == MAUA_BF16 ? 1 : 0;
-  return pl;
-}
-
-size_t maua::group_norm_workspace(int B, int C, long HW, int esize) { return gn_part_bytes(B, C, HW, esize); }
-
-int maua::launch_group_norm(hipStream_t stream, int dtype, const GnArgs& a, double* part, float* stats) {
-  if (int rc = group_norm_check(dtype, a)) return rc;
-  MAUA_REQUIRE(part && stats, "group_norm: NULL workspace");
-  if (a.B == 0) return MAUA_OK;
-  const GnPlanInfo pl = group_norm_plan(dtype, a);
-  return dtype == MAUA_BF16 ? gn_launch<bf16_t>(stream, a, pl, part, stats) : gn_launch<float>(stream, a, pl, part, stats);
-}
-
-namespace {
-
-// ------------------------------------------------------------------------------------------------------ DDIM step
-// gaussian_diffusion.py ddim_sample for an epsilon-predicting model (clip_denoised False), in the reference's float32
-// operation order; coefficients per sample: cf[b] = {sqrt_recip_ac, sqrt_recipm1_ac, sqrt(1 - ac), sqrt(ac_prev),
-// sqrt(1 - ac_prev - sigma^2), sigma * nonzero_mask, 0, 0}.  model_out [B][Cm][HW] (eps = first C channels), x [B][C][HW].
-__global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ model_out,
-                                                        const float* __restrict__ grad, const float* __restrict__ noise,
-                                                        const float* __restrict__ cf, int C, int Cm, long HW, long total,
-                                                        float* __restrict__ sample, float* __restrict__ pred_out) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const long chw = (long)C * HW;
-  const int b = (int)(idx / chw);
-  const long rem = idx - (long)b * chw;
-  const float* k = cf + b * 8;
-  const float xv = x[idx];
-  const float eps_m = model_out[(long)b * Cm * HW + rem];
-  float pred = k[0] * xv - k[1] * eps_m;           // _predict_xstart_from_eps
-  if (grad) {                                      // condition_score
-    float eps = (k[0] * xv - pred) / k[1];
-    eps = eps - k[2] * grad[idx];
-    pred = k[0] * xv - k[1] * eps;
-  }
-  const float eps = (k[0] * xv - pred) / k[1];     // _predict_eps_from_xstart
-  float s = pred * k[3] + k[4] * eps;
-  if (noise) s += k[5] * noise[idx];
-  sample[idx] = s;
-  if (pred_out) pred_out[idx] = pred;
-}
-
-// gaussian_diffusion.py p_sample (ancestral step) for an epsilon model with learned-range variance (learn_sigma: the second half
-// of the model's channels interpolates between the posterior and the beta log-variance), clip_denoised False, optional
-// condition_mean.  cf[b] = {sqrt_recip_ac, sqrt_recipm1_ac, posterior_mean_coef1, posterior_mean_coef2,
-// posterior_log_variance_clipped, log(beta), nonzero_mask, 0}.
-__global__ __launch_bounds__(256) void p_sample_step_kernel(const float* __restrict__ x, const float* __restrict__ model_out,
-                                                            const float* __restrict__ grad, const float* __restrict__ noise,
-                                                            const float* __restrict__ cf, int C, long HW, long total,
-                                                            float* __restrict__ sample, float* __restrict__ pred_out) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const long chw = (long)C * HW;
-  const int b = (int)(idx / chw);
-  const long rem = idx - (long)b * chw;
-  const float* k = cf + b * 8;
-  const float xv = x[idx];
-  const float* mo = model_out + (long)b * 2 * chw;
-  const float eps = mo[rem], vv = mo[chw + rem];
-  const float frac = (vv + 1.f) / 2.f;
-  const float logvar = frac * k[5] + (1.f - frac) * k[4];
-  const float pred = k[0] * xv - k[1] * eps;                 // _predict_xstart_from_eps
-  float mean = k[2] * pred + k[3] * xv;                      // q_posterior_mean_variance
-  if (grad) mean = mean + expf(logvar) * grad[idx];          // condition_mean: mean + variance * gradient
-  sample[idx] = mean + k[6] * expf(0.5f * logvar) * noise[idx];
-  if (pred_out) pred_out[idx] = pred;
-}
-
-// One model evaluation of plms_sample (the pseudo linear multistep sampler of the guided-diffusion fork the reference
-// vendors as a submodule): pred_orig = x0 from the network's epsilon; with a condition gradient the score is conditioned
-// (condition_score) -> pred; eps = _predict_eps_from_xstart(x, t, pred).  cf[b] = maua_ddim_step's coefficients.
-__global__ __launch_bounds__(256) void plms_eps_kernel(const float* __restrict__ x, const float* __restrict__ model_out,
-                                                       const float* __restrict__ grad, const float* __restrict__ cf, int C,
-                                                       int Cm, long HW, long total, float* __restrict__ eps_out,
-                                                       float* __restrict__ pred_out, float* __restrict__ pred_orig_out) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const long chw = (long)C * HW;
-  const int b = (int)(idx / chw);
-  const long rem = idx - (long)b * chw;
-  const float* k = cf + b * 8;
-  const float xv = x[idx];
-  const float eps_m = model_out[(long)b * Cm * HW + rem];
-  const float pred_orig = k[0] * xv - k[1] * eps_m;
-  float pred = pred_orig;
-  if (grad) {
-    float e = (k[0] * xv - pred) / k[1];
-    e = e - k[2] * grad[idx];
-    pred = k[0] * xv - k[1] * e;
-  }
-  eps_out[idx] = (k[0] * xv - pred) / k[1];
-  if (pred_out) pred_out[idx] = pred;
-  if (pred_orig_out) pred_orig_out[idx] = pred_orig;
-}
-
-// The multistep update: eps' = (sum_i w[i] * eps_i) / div (i < n: Adams-Bashforth weights, or (1, 1) / 2 for the improved-Euler start),
-// pred' = _predict_xstart_from_eps(x, t, eps'), mean = pred' sqrt(ac_prev) + sqrt(1 - ac_prev) eps',
-// sample = mean * nonzero + pred * (1 - nonzero).  cf[b] = {sqrt_recip_ac, sqrt_recipm1_ac, sqrt(ac_prev), sqrt(1 - ac_prev),
-// nonzero_mask, 0, 0, 0}
-struct PlmsEps { const float* e[4]; float w[4]; float div; int n; };
-__global__ __launch_bounds__(256) void plms_update_kernel(const float* __restrict__ x, PlmsEps pe, const float* __restrict__ pred,
-                                                          const float* __restrict__ cf, long chw, long total,
-                                                          float* __restrict__ sample) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int b = (int)(idx / chw);
-  const float* k = cf + b * 8;
-  // (separately rounded products and sums, left to right, then the division: the order of the reference's expression)
-  float ep = __fmul_rn(pe.w[0], pe.e[0][idx]);
-  for (int i = 1; i < pe.n; i++) ep = __fadd_rn(ep, __fmul_rn(pe.w[i], pe.e[i][idx]));
-  ep = ep / pe.div;
-  const float pp = k[0] * x[idx] - k[1] * ep;
-  const float mean = pp * k[2] + k[3] * ep;
-  sample[idx] = mean * k[4] + pred[idx] * (1.f - k[4]);
-}
-
-// out = a[b] * x + c[b] * y (q_sample: sqrt(ac) * x_start + sqrt(1 - ac) * noise), per-sample coefficients
-__global__ __launch_bounds__(256) void axpby_rows_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                         const float* __restrict__ ab, long row, long total,
-                                                         float* __restrict__ out) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int b = (int)(idx / row);
-  out[idx] = ab[2 * b] * x[idx] + ab[2 * b + 1] * y[idx];
-}
-
-// the image-MSE grad module of the guided sampler: g = (img - target) * k[b] (k = 2 scale / numel, one per sample; read from device
-// memory so that a captured loop serves every scale), one target per sample or one for all (tstride 0); any NaN raises *flag
-__global__ __launch_bounds__(256) void mse_guide_grad_kernel(const float* __restrict__ img, const float* __restrict__ target,
-                                                             long tstride, const float* __restrict__ kdev, long row, long total,
-                                                             float* __restrict__ out, int* __restrict__ flag) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;
-  if (idx < total) {
-    const long b = idx / row, i = idx - b * row;
-    const float v = (img[idx] - target[b * tstride + i]) * kdev[b];
-    out[idx] = v;
-    bad = v != v;
-  }
-  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-// GradientGuidedConditioning.forward (guided.py:262-265): a grad module whose output holds a NaN contributes zeros
-// eps = the first C channels of a model output [B][Cm][HW], made contiguous (speed "regular": pred_xstart is built from it with
-// axpby_rows_kernel, exactly as the step-by-step path does - same kernel, same bits)
-__global__ __launch_bounds__(256) void eps_rows_kernel(const float* __restrict__ model_out, long chw, long cmhw, long total,
-                                                       float* __restrict__ eps) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const long b = i / chw;
-  eps[i] = model_out[b * cmhw + (i - b * chw)];
-}
-
-__global__ __launch_bounds__(256) void zero_if_flag_kernel(float* __restrict__ g, long total, const int* __restrict__ flag) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  // (an agent-scope load: served by L2, where the previous launch's atomicOr landed - not by the scalar / vector L1)
-  if (idx < total && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) g[idx] = 0.f;
-}
-
-// ----------------------------------------------------------------------------------------------------- parameters
-struct UGN { int C = 0; float* gamma = nullptr; float* beta = nullptr; };
-struct UConv { int Ci = 0, Co = 0, Cip = 0, Cop = 0; void* wt = nullptr; float* bias = nullptr; void* wt_t = nullptr; };   // wt_t: the input-gradient convolution (option "vjp")
-struct ULin { int K = 0, N = 0; void* w = nullptr; float* bias = nullptr; void* w_t = nullptr; };   // w_t [K][N]: the input-gradient GEMM
-struct URes { int Cin, Cout, updown; UGN n1; UConv c1; int emb_off; UGN n2; UConv c2; bool skip; ULin sk; };
-struct UAttn { int C, heads; UGN n; ULin qkv, proj; };
-struct ULayer { int kind; int idx; };  // 0 conv_in, 1 res, 2 attn
-struct UBlock { std::vector<ULayer> layers; int out_ch = 0; };
-
-enum PKind { P_GN_G, P_GN_B, P_CONV_W, P_CONV_B, P_LIN_W, P_LIN_B, P_F32 };
-struct PRef { PKind kind; void* obj; float* f32 = nullptr; size_t count = 0; };
-
-// What a kept forward (maua_unet_forward_keep) leaves for maua_unet_vjp: per layer, the tensors its input gradient reads
-struct TapeOp {
-  int kind, idx;                  // 1 ResBlock, 2 AttentionBlock (index into res / attn)
-  const void* x0; int C0;         // the layer's input (virtually concatenated [x0 | x1])
-  const void* x1; int C1;
-  int H, W;                       // input size
-  void* out;                      // its output
-  void* h1;                       // ResBlock: conv1's output (the second GroupNorm's input); Attention: qkv
-  void* ao;                       // Attention: the attention result (proj_out's input)
-  float* st1;                     // statistics of the first / only GroupNorm
-  float* st2;                     // ... of the ResBlock's second
-  float* lse;                     // Attention: log-sum-exp rows
-};
-
-struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, top = 0, peak = 0;
-  bool plan = true;
-  void* get(size_t bytes) {
-    const size_t o = (top + 255) & ~(size_t)255;
-    top = o + bytes;
-    if (top > peak) peak = top;
-    return plan ? (void*)(uintptr_t)(o + 256) : (void*)(base + o);  // (planning: a non-NULL token, never dereferenced)
-  }
-};
-
-}  // namespace
-
-struct maua_unet {
-  maua_ctx* ctx;
-  int image_size, in_ch, mc, out_ch, nrb, head_ch, dtype;
-  size_t esize;
-  std::vector<float> mult;
-  std::vector<int> attn_ds;
-  int emb_dim;
-  UConv conv_in, conv_out;
-  UGN out_norm;
-  std::vector<URes> res;
-  std::vector<UAttn> attn;
-  std::vector<UBlock> input, output;
-  UBlock middle;
-  int final_ch = 0;
-  // f32 timestep path: time_embed.{0,2}, all emb_layers stacked [emb_total][emb_dim]
-  float *te0_w = nullptr, *te0_b = nullptr, *te2_w = nullptr, *te2_b = nullptr, *embw = nullptr, *embb = nullptr;
-  float* freqs = nullptr;  // [mc / 2] timestep-embedding frequencies (optional upload: "timestep_embedding.freqs")
-  int freqs_loaded = 0;
-  int emb_total = 0;
-  std::unordered_map<std::string, PRef> params;
-  std::vector<void*> owned;
-  float* ones = nullptr;
-  int ones_b = 0, max_ch = 0;
-  Arena arena;
-  size_t planned_key = 0;  // B, H, W the arena was planned for
-  size_t gather_bytes = 0; // split-K workspace of the gather GEMM at that shape
-  size_t out_cap = 0;      // bytes behind g_out + g_pred
-  int route = 0;           // debugging / ablation: 1 = every 3x3 convolution on the generic kernel
-  int psum_off = 0;        // 1: GroupNorm statistics always by their own pass (A/B of the convolution epilogues' piece sums)
-  // sampler graph (maua_ddim_sample_loop)
-  hipGraphExec_t graph_exec = nullptr;
-  size_t graph_key = 0;
-  float* emb_table = nullptr;        // [n_steps][emb_total]: every step's emb_layers outputs, computed once per sampler loop
-  size_t emb_table_rows = 0;
-  const float* emb_row = nullptr;    // non-NULL during a sampler-loop forward: this step's row (all samples share the timestep)
-  hipStream_t cap_stream = nullptr;  // capture happens on a private stream (the caller's may be the legacy NULL stream)
-  int graph_failed = 0;              // capture / instantiation failed once: the loop runs eagerly from then on
-  float *g_x = nullptr, *g_out = nullptr, *g_pred = nullptr, *g_t = nullptr, *g_cf = nullptr;
-  int g_steps = 0;
-  // guided sampler graph (maua_ddim_guided_loop): its own executable; the sample, the target and every per-step constant live in
-  // library buffers, so one capture serves every call of a shape
-  hipGraphExec_t gd_exec = nullptr;
-  size_t gd_key = 0;
-  unsigned long long gd_sec_uid = 0, gd_sec_epoch = 0;   // the secondary model (and its buffers' generation) gd_exec points into
-  // text-prompt guidance (maua_unet_set_clip_guide): CLIPGrads instead of the image-MSE module in the guided loop
-  std::vector<maua_guide*> gd_guides;   // maua_unet_set_guides: grad modules evaluated (after CLIPGrads, if set) and summed per step
-  std::vector<unsigned long long> gd_guide_uids, gd_guide_epochs;   // (epochs: as of the capture)
-  int* gd_gflag = nullptr;           // the NaN screen's flag of the guides' sum
-  maua_clip* gd_clip = nullptr;
-  int* gd_rects = nullptr;           // device [n_steps][batches][cutn][3] (+ [n_steps][batches][cutn] float multiplicities behind them)
-  float* gd_mult = nullptr;          // NULL: every cutout counts once
-  int gd_last_graph = 0;             // the LAST guided loop replayed a captured graph (maua_unet_guided_graph_active)
-  int gd_cutn_total = 0;
-  size_t gd_rects_cap = 0;
-  std::vector<int> gd_rects_host;
-  int gd_rect_steps = 0, gd_cutn = 0, gd_batches = 0;
-  float gd_clip_scale = 1.f, gd_clip_clamp = 0.f;
-  unsigned long long gd_clip_uid = 0, gd_clip_epoch = 0, gd_guide_gen = 0, gd_guide_gen_seen = 0;
-  int gd_failed = 0;
-  float* gd_buf = nullptr;           // x | v | pred | eps | img | g | jv | grad | target, B * C * H * W floats each
-  size_t gd_cap = 0;
-  float* gd_tab = nullptr;           // cos_t [S][B] | (sigma, 1 - sigma) [S][B][2] | grad coefficients [S][B][2] | k [B]
-  size_t gd_tab_cap = 0;
-  int* gd_flag = nullptr;            // [gd_flags] one NaN flag per step, zeroed before every loop (outside the graph)
-  int gd_flags = 0;
-  // the guidance branch of a step (secondary forward, grad module, secondary VJP) depends on x only: it runs BESIDE the UNet forward
-  // on a side stream (a parallel branch of the captured graph) and joins at the DDIM update; option "guided_fork" = 0: one stream
-  int gd_fork = 1;
-  hipStream_t side_stream = nullptr, cap_side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // input gradient (maua_unet_forward_keep + maua_unet_vjp; option "vjp" = 1 before the weights are loaded)
-  int vjp = 0;
-  float* zero_bias = nullptr;        // [max padded channels] zeros: the gradient convolutions have no bias
-  std::vector<TapeOp> tape;
-  bool tape_valid = false;           // the arena still holds the kept forward the tape describes
-  int tape_B = 0, tape_H = 0, tape_W = 0;
-  void* tape_h0 = nullptr;           // conv_in's output
-  void* tape_hf = nullptr;           // the last block's output (out_norm's input)
-  int tape_cf = 0;
-  float* tape_stf = nullptr;         // out_norm's statistics
-  float* tape_emb = nullptr;         // the emb_layers outputs of that forward
-  long tape_emb_ld = 0;
-  size_t tape_top = 0;               // arena top behind the kept forward
-  float* tape_gather_ws = nullptr;   // the split-K workspace of that forward (the gradient convolutions share it)
-};
 
 namespace {
 
@@ -1112,7 +353,7 @@ struct Runner {
          T* xr, float* stats_keep = nullptr) {
     const size_t mark = ar.top;
     float* stats = stats_keep ? stats_keep : (float*)ar.get((size_t)B * 32 * 2 * 4);
-    double* part = (double*)ar.get(gn_part_bytes(B, C0 + C1, (long)H * W, (int)sizeof(T)));
+    double* part = (double*)ar.get(group_norm_workspace(B, C0 + C1, (long)H * W, (int)sizeof(T)));
     int rc = MAUA_OK;
     if (!plan) {
       const float *ps0 = nullptr, *ps1 = nullptr;
@@ -1249,14 +490,7 @@ struct Runner {
     if (!plan && n->emb_row) {
       emb_all = const_cast<float*>(n->emb_row);   // (read-only; the samples' rows coincide: stride 0 below)
     } else if (!plan) {
-      const int half = mc / 2;
-      hipLaunchKernelGGL(timestep_embedding_kernel, dim3((B * half + 255) / 256), dim3(256), 0, st, t,
-                         n->freqs_loaded ? n->freqs : nullptr, e0, B, mc);
-      hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e0, n->te0_w, n->te0_b, e1, B, mc, E, 0, 1);
-      hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e1, n->te2_w, n->te2_b, e2, B, E, E, 0, 0);
-      hipLaunchKernelGGL(linear_rows_kernel, dim3((n->emb_total + 3) / 4), dim3(256), 0, st, e2, n->embw, n->embb, emb_all, B,
-                         E, n->emb_total, 1, 0);
-      MAUA_HIP_CHECK(hipGetLastError());
+      if ((rc = unet_emb_rows(n, st, t, B, e0, e1, e2, emb_all))) return rc;
     }
     // split-K workspace of the gather GEMM: sized in the planning pass, placed here in the real one
     gather_ws = (float*)ar.get(plan ? 0 : n_gather_bytes);
@@ -1431,17 +665,8 @@ struct Runner {
     return MAUA_OK;
   }
 };
-
-size_t shape_key(int B, int H, int W) { return ((size_t)B << 40) ^ ((size_t)H << 20) ^ (size_t)W; }
-
-// the captured sampler loops hold pointers into the arena / the per-step tables: whatever moves those drops both executables
-void drop_sampler_graphs(maua_unet* n) {
-  if (n->graph_exec) { hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; n->graph_key = 0; }
-  if (n->gd_exec) { hipGraphExecDestroy(n->gd_exec); n->gd_exec = nullptr; n->gd_key = 0; }
-}
-
 template <typename T>
-int run_forward(maua_unet* n, const float* x, const float* t, int B, int H, int W, float* out, bool keep = false) {
+int run_forward(maua_unet* n, const float* x, const float* t, int B, int H, int W, float* out, bool keep) {
   hipStream_t st = n->ctx->stream;
   const size_t key = shape_key(B, H, W) ^ (keep ? (size_t)1 << 62 : 0);
   n->tape_valid = false;
@@ -1491,7 +716,7 @@ int run_forward(maua_unet* n, const float* x, const float* t, int B, int H, int 
 // the gradient's walk continues on the arena where the kept forward stopped (its tensors stay where they are)
 // g_channels: channels of g_out actually handed in ([B][g_channels][H][W]; the remaining output channels' gradient is zero)
 template <typename T>
-int run_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels = 0) {
+int run_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels) {
   hipStream_t st = n->ctx->stream;
   n->arena.plan = false; n->arena.top = n->tape_top;
   Runner<T> r(n, st, n->tape_B, false, true);
@@ -1502,6 +727,29 @@ int run_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels = 0) {
 }
 
 }  // namespace
+
+// ---- what sampler.hip uses of the network (unet_internal.h)
+int maua::unet_forward(maua_unet* n, const float* x, const float* t, int B, int H, int W, float* out, bool keep) {
+  return n->dtype == MAUA_BF16 ? run_forward<bf16_t>(n, x, t, B, H, W, out, keep) : run_forward<float>(n, x, t, B, H, W, out, keep);
+}
+
+int maua::unet_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels) {
+  return n->dtype == MAUA_BF16 ? run_vjp<bf16_t>(n, g_out, g_x, g_channels) : run_vjp<float>(n, g_out, g_x, g_channels);
+}
+
+int maua::unet_emb_rows(maua_unet* n, hipStream_t st, const float* t, int rows, float* e0, float* e1, float* e2, float* emb) {
+  const int E = n->emb_dim, mc = n->mc, half = mc / 2;
+  hipLaunchKernelGGL(timestep_embedding_kernel, dim3((rows * half + 255) / 256), dim3(256), 0, st, t,
+                     n->freqs_loaded ? n->freqs : nullptr, e0, rows, mc);
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e0, n->te0_w, n->te0_b, e1, rows, mc, E, 0, 1);
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e1, n->te2_w, n->te2_b, e2, rows, E, E, 0, 0);
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((n->emb_total + 3) / 4), dim3(256), 0, st, e2, n->embw, n->embb, emb, rows, E,
+                     n->emb_total, 1, 0);
+  MAUA_HIP_CHECK(hipGetLastError());
+  return MAUA_OK;
+}
+
+bool maua::unet_planned(const maua_unet* n, int B, int H, int W) { return n->planned_key == shape_key(B, H, W) && B <= n->ones_b; }
 
 extern "C" {
 
@@ -1537,20 +785,10 @@ int maua_unet_create(maua_ctx* ctx, int image_size, int in_channels, int model_c
 void maua_unet_destroy(maua_unet* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  if (n->graph_exec) hipGraphExecDestroy(n->graph_exec);
-  if (n->gd_exec) hipGraphExecDestroy(n->gd_exec);
-  if (n->cap_stream) hipStreamDestroy(n->cap_stream);
-  if (n->side_stream) hipStreamDestroy(n->side_stream);
-  if (n->cap_side) hipStreamDestroy(n->cap_side);
-  if (n->ev_fork) hipEventDestroy(n->ev_fork);
-  if (n->ev_join) hipEventDestroy(n->ev_join);
-  for (void* p : {(void*)n->gd_buf, (void*)n->gd_tab, (void*)n->gd_flag, (void*)n->gd_rects, (void*)n->gd_gflag})
-    if (p) hipFree(p);
+  n->smp.release();
   for (void* p : n->owned) hipFree(p);
   if (n->arena.base) hipFree(n->arena.base);
   if (n->ones) hipFree(n->ones);
-  for (float* p : {n->g_out, n->g_pred, n->g_t, n->g_cf, n->emb_table})  // (g_x is the caller's tensor the graph was captured on)
-    if (p) hipFree(p);
   delete n;
 }
 
@@ -1570,7 +808,7 @@ int maua_unet_set_option(maua_unet* n, const char* key, int value) {
     return MAUA_OK;
   }
   if (!strcmp(key, "guided_fork")) {   // 1 (default): the guidance branch of maua_ddim_guided_loop beside the UNet forward; 0: behind it
-    n->gd_fork = value ? 1 : 0;
+    n->smp.gd_fork = value ? 1 : 0;
     drop_sampler_graphs(n);
     return MAUA_OK;
   }
@@ -1585,13 +823,6 @@ int maua_unet_set_option(maua_unet* n, const char* key, int value) {
     return MAUA_OK;
   }
   return fail(std::string("maua_unet_set_option: unknown option ") + key);
-}
-
-// 1 when the last maua_ddim_sample_loop(use_graph = 1) replayed a captured hipGraph, 0 when it ran eagerly
-int maua_unet_graph_active(maua_unet* n, int* active) {
-  MAUA_REQUIRE(n && active, "maua_unet_graph_active: NULL argument");
-  *active = n->graph_exec && !n->graph_failed ? 1 : 0;
-  return MAUA_OK;
 }
 
 int maua_unet_param_count(maua_unet* n, long* count) {
@@ -1694,7 +925,7 @@ int maua_unet_forward(maua_unet* n, const float* x, const float* timesteps, int 
   const int down = 1 << (n->mult.size() - 1);
   MAUA_REQUIRE(H % down == 0 && W % down == 0, "maua_unet_forward: H and W must be multiples of 2^(levels - 1)");
   if (B == 0) return MAUA_OK;
-  return n->dtype == MAUA_BF16 ? run_forward<bf16_t>(n, x, timesteps, B, H, W, out) : run_forward<float>(n, x, timesteps, B, H, W, out);
+  return unet_forward(n, x, timesteps, B, H, W, out, false);
 }
 
 // The forward again, keeping what its input gradient needs (GroupNorm inputs + statistics, qkv + the attention rows' log-sum-exp)
@@ -1709,651 +940,14 @@ int maua_unet_forward_keep(maua_unet* n, const float* x, const float* timesteps,
   MAUA_REQUIRE(B > 0 && H > 0 && W > 0, "maua_unet_forward_keep: bad shape");
   const int down = 1 << (n->mult.size() - 1);
   MAUA_REQUIRE(H % down == 0 && W % down == 0, "maua_unet_forward_keep: H and W must be multiples of 2^(levels - 1)");
-  return n->dtype == MAUA_BF16 ? run_forward<bf16_t>(n, x, timesteps, B, H, W, out, true) : run_forward<float>(n, x, timesteps, B, H, W, out, true);
+  return unet_forward(n, x, timesteps, B, H, W, out, true);
 }
 
 int maua_unet_vjp(maua_unet* n, const float* g_out, int B, int H, int W, float* g_x) {
   MAUA_REQUIRE(n && g_out && g_x, "maua_unet_vjp: NULL argument");
   MAUA_REQUIRE(n->tape_valid && n->tape_B == B && n->tape_H == H && n->tape_W == W,
                "maua_unet_vjp: no kept forward of this shape (call maua_unet_forward_keep first, nothing in between)");
-  return n->dtype == MAUA_BF16 ? run_vjp<bf16_t>(n, g_out, g_x) : run_vjp<float>(n, g_out, g_x);
-}
-
-// One DDIM update (gaussian_diffusion.py ddim_sample, epsilon model, clip_denoised False).  x [B][C][H][W], model_out
-// [B][Cm][H][W] (Cm >= C: the learned-variance channels are not used by DDIM), cond_grad = cond_fn(x, t) or NULL, noise or
-// NULL (eta = 0), coef: device f32 [B][8] = {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
-// sqrt(1 - alphas_cumprod), sqrt(alphas_cumprod_prev), sqrt(1 - alphas_cumprod_prev - sigma^2), sigma * (t != 0), 0, 0}.
-int maua_ddim_step(maua_ctx* ctx, const float* x, const float* model_out, const float* cond_grad, const float* noise,
-                   const float* coef, int B, int C, int Cm, long HW, float* sample, float* pred_xstart) {
-  MAUA_REQUIRE(ctx, "maua_ddim_step: ctx is NULL");
-  if (B == 0 || HW == 0) return MAUA_OK;
-  MAUA_REQUIRE(x && model_out && coef && sample && C > 0 && Cm >= C, "maua_ddim_step: NULL argument");
-  const long total = (long)B * C * HW;
-  hipLaunchKernelGGL(ddim_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, x, model_out,
-                     cond_grad, noise, coef, C, Cm, HW, total, sample, pred_xstart);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// One p_sample update (gaussian_diffusion.py p_sample + p_mean_variance with learned-range variance, epsilon model,
-// clip_denoised False; cond_grad = cond_fn(x, t) or NULL: condition_mean).  model_out [B][2 C][H][W]; noise [B][C][H][W];
-// coef: device f32 [B][8] = {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
-// posterior_log_variance_clipped, log(betas), t != 0, 0}.
-int maua_p_sample_step(maua_ctx* ctx, const float* x, const float* model_out, const float* cond_grad, const float* noise,
-                       const float* coef, int B, int C, long HW, float* sample, float* pred_xstart) {
-  MAUA_REQUIRE(ctx, "maua_p_sample_step: ctx is NULL");
-  if (B == 0 || HW == 0) return MAUA_OK;
-  MAUA_REQUIRE(x && model_out && noise && coef && sample && C > 0, "maua_p_sample_step: NULL argument");
-  const long total = (long)B * C * HW;
-  hipLaunchKernelGGL(p_sample_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, x, model_out,
-                     cond_grad, noise, coef, C, HW, total, sample, pred_xstart);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// plms_sample's get_model_output: eps (after the optional condition_score), its pred_xstart and the unconditioned one.
-// coef: maua_ddim_step's table.
-int maua_plms_eps(maua_ctx* ctx, const float* x, const float* model_out, const float* cond_grad, const float* coef, int B,
-                  int C, int Cm, long HW, float* eps, float* pred_xstart, float* pred_xstart_orig) {
-  MAUA_REQUIRE(ctx, "maua_plms_eps: ctx is NULL");
-  if (B == 0 || HW == 0) return MAUA_OK;
-  MAUA_REQUIRE(x && model_out && coef && eps && C > 0 && Cm >= C, "maua_plms_eps: NULL argument");
-  const long total = (long)B * C * HW;
-  hipLaunchKernelGGL(plms_eps_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, x, model_out,
-                     cond_grad, coef, C, Cm, HW, total, eps, pred_xstart, pred_xstart_orig);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// plms_sample's update from n_eps (1..4) epsilon tensors: eps' = (sum_i weights[i] eps_list[i]) / divisor, accumulated left to
-// right like the reference's expressions ((3 e1 - e2) / 2, (23 e1 - 16 e2 + 5 e3) / 12, ...); coef: device f32 [B][8] = {sqrt_recip_ac, sqrt_recipm1_ac, sqrt(ac_prev),
-// sqrt(1 - ac_prev), t != 0, 0, 0, 0}.
-int maua_plms_update(maua_ctx* ctx, const float* x, const float* const* eps_list, const float* weights, int n_eps,
-                     float divisor, const float* pred_xstart, const float* coef, int B, long chw, float* sample) {
-  MAUA_REQUIRE(ctx, "maua_plms_update: ctx is NULL");
-  if (B == 0 || chw == 0) return MAUA_OK;
-  MAUA_REQUIRE(x && eps_list && weights && pred_xstart && coef && sample && n_eps >= 1 && n_eps <= 4, "maua_plms_update: bad argument");
-  MAUA_REQUIRE(divisor != 0.f, "maua_plms_update: divisor is zero");
-  PlmsEps pe{};
-  pe.n = n_eps; pe.div = divisor;
-  for (int i = 0; i < n_eps; i++) {
-    MAUA_REQUIRE(eps_list[i], "maua_plms_update: NULL epsilon tensor");
-    pe.e[i] = eps_list[i]; pe.w[i] = weights[i];
-  }
-  const long total = (long)B * chw;
-  hipLaunchKernelGGL(plms_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, x, pe, pred_xstart,
-                     coef, chw, total, sample);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// out[b] = ab[b][0] * x[b] + ab[b][1] * y[b] over rows of `row` elements (q_sample, gaussian_diffusion.py)
-int maua_axpby_rows(maua_ctx* ctx, const float* x, const float* y, const float* ab, int B, long row, float* out) {
-  MAUA_REQUIRE(ctx, "maua_axpby_rows: ctx is NULL");
-  if (B == 0 || row == 0) return MAUA_OK;
-  MAUA_REQUIRE(x && y && ab && out, "maua_axpby_rows: NULL argument");
-  const long total = (long)B * row;
-  hipLaunchKernelGGL(axpby_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, x, y, ab, row,
-                     total, out);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// ---- operator-level entry points of the UNet's building blocks (NHWC tensors in the network dtype) --------------------
-// QKVAttentionLegacy.forward: qkv [B][T][3 * heads * head_ch] (channel = head * 3 ch + {q, k, v} * ch + c) -> out [B][T][heads * ch]
-int maua_attention_legacy(maua_ctx* ctx, const void* qkv, void* out, int B, int T, int heads, int head_ch, int dtype) {
-  MAUA_REQUIRE(ctx, "maua_attention_legacy: ctx is NULL");
-  AttnArgs a{};
-  a.qkv = qkv; a.out = out; a.B = B; a.T = T; a.heads = heads; a.D = head_ch; a.ld_qkv = 3L * heads * head_ch;
-  a.ld_out = (long)heads * head_ch; a.scale = 1.f / sqrtf((float)head_ch);
-  return launch_attention(ctx->stream, dtype, a);
-}
-
-// the same with CLIP's causal mask (text tower): query t attends to keys 0 .. t
-int maua_attention_causal(maua_ctx* ctx, const void* qkv, void* out, int B, int T, int heads, int head_ch, int dtype) {
-  MAUA_REQUIRE(ctx, "maua_attention_causal: ctx is NULL");
-  AttnArgs a{};
-  a.qkv = qkv; a.out = out; a.B = B; a.T = T; a.heads = heads; a.D = head_ch; a.ld_qkv = 3L * heads * head_ch;
-  a.ld_out = (long)heads * head_ch; a.scale = 1.f / sqrtf((float)head_ch); a.causal = 1;
-  return launch_attention(ctx->stream, dtype, a);
-}
-
-// conv_nd(1, K, N, 1) / nn.Linear on rows: c[M][N] = a[M][K] x w[N][K]^T + bias (+ res[M][N]); a, w, res, c in dtype
-int maua_linear_nt(maua_ctx* ctx, const void* a, const void* w, const float* bias, const void* res, void* c, long M, int N,
-                   int K, int dtype) {
-  MAUA_REQUIRE(ctx, "maua_linear_nt: ctx is NULL");
-  GemmArgs g{};
-  g.a0 = a; g.lda0 = K; g.K0 = K; g.w = w; g.bias = bias; g.res = res; g.ldr = N; g.c = c; g.ldc = N; g.M = M; g.N = N;
-  g.prefer_dma = ctx->linear_dma;   // (option "linear_dma": large shapes on gemm_dma.hip - what the CLIP tower's projections run on)
-  return launch_gemm_nt(ctx->stream, dtype, g);
-}
-
-// GroupNorm32(32, C) (+ optional per-sample scale-shift [B][2C]: y * (1 + scale) + shift) (+ SiLU) on NHWC x -> y
-int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift,
-                         int silu, int B, int H, int W, int C, int dtype, void* y) {
-  MAUA_REQUIRE(ctx && x && gamma && beta && y, "maua_group_norm_nhwc: NULL argument");
-  MAUA_REQUIRE(C % 32 == 0 && (dtype == MAUA_F32 || dtype == MAUA_BF16), "maua_group_norm_nhwc: C % 32, f32 / bf16");
-  if (B == 0) return MAUA_OK;
-  const size_t part_bytes = gn_part_bytes(B, C, (long)H * W, dtype == MAUA_BF16 ? 2 : 4);
-  if (int rc = scratch_reserve(ctx, part_bytes + (size_t)B * 64 * 4 + 512)) return rc;
-  double* part = (double*)ctx->scratch;
-  float* stats = (float*)((char*)ctx->scratch + ((part_bytes + 255) & ~(size_t)255));
-  GnArgs a{};
-  a.x0 = x; a.C0 = C; a.B = B; a.H = H; a.W = W; a.gamma = gamma; a.beta = beta; a.ss = scale_shift; a.ss_ld = 2L * C; a.silu = silu;
-  a.y = y;
-  return launch_group_norm(ctx->stream, dtype, a, part, stats);
-}
-
-// Input gradients of the two operator-level blocks above (what maua_unet_vjp walks a network with).  Attention: qkv as the
-// forward's, d_out [B][T][C] -> d_qkv [B][T][3C] (the forward is re-run here for the rows' log-sum-exp and the result).
-int maua_attention_legacy_vjp(maua_ctx* ctx, const void* qkv, const void* d_out, void* d_qkv, int B, int T, int heads, int head_ch,
-                              int dtype) {
-  MAUA_REQUIRE(ctx && qkv && d_out && d_qkv, "maua_attention_legacy_vjp: NULL argument");
-  MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_attention_legacy_vjp: f32 / bf16");
-  if (B == 0) return MAUA_OK;
-  const size_t esize = dtype == MAUA_BF16 ? 2 : 4;
-  const size_t out_bytes = ((size_t)B * T * heads * head_ch * esize + 255) & ~(size_t)255, row_bytes = ((size_t)B * heads * T * 4 + 255) & ~(size_t)255;
-  if (int rc = scratch_reserve(ctx, out_bytes + 2 * row_bytes + 512)) return rc;
-  char* ws = (char*)ctx->scratch;
-  AttnArgs f{};
-  f.qkv = qkv; f.out = ws; f.B = B; f.T = T; f.heads = heads; f.D = head_ch; f.ld_qkv = 3L * heads * head_ch;
-  f.ld_out = (long)heads * head_ch; f.scale = 1.f / sqrtf((float)head_ch); f.lse = (float*)(ws + out_bytes);
-  if (int rc = launch_attention(ctx->stream, dtype, f)) return rc;
-  AttnVjpArgs a{};
-  a.qkv = qkv; a.out = ws; a.d_out = d_out; a.lse = f.lse; a.d_qkv = d_qkv; a.delta = (float*)(ws + out_bytes + row_bytes); a.B = B; a.T = T;
-  a.heads = heads; a.D = head_ch; a.ld_qkv = f.ld_qkv; a.ld_out = f.ld_out; a.scale = f.scale;
-  return launch_attention_vjp(ctx->stream, dtype, a);
-}
-
-// GroupNorm32 (+ scale-shift) (+ SiLU) (+ resample: 0 none, 1 2x2 average, 2 nearest x2 - behind the activation, as the
-// ResBlocks' h_upd): dy [B][Ho][Wo][C] -> dx [B][H][W][C]; dres (optional, like dy): the gradient of the resampled raw x, added.
-int maua_group_norm_nhwc_vjp(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* scale_shift, int silu,
-                             int resample, const void* dy, const void* dres, int B, int H, int W, int C, int dtype, void* dx) {
-  MAUA_REQUIRE(ctx && x && gamma && beta && dy && dx, "maua_group_norm_nhwc_vjp: NULL argument");
-  MAUA_REQUIRE(C % 32 == 0 && (dtype == MAUA_F32 || dtype == MAUA_BF16), "maua_group_norm_nhwc_vjp: C % 32, f32 / bf16");
-  if (B == 0) return MAUA_OK;
-  const int esize = dtype == MAUA_BF16 ? 2 : 4;
-  const size_t part_bytes = (gn_part_bytes(B, C, (long)H * W, esize) + 255) & ~(size_t)255;
-  const size_t vjp_bytes = group_norm_vjp_workspace(B, C, (long)H * W, esize);
-  if (int rc = scratch_reserve(ctx, part_bytes + (size_t)B * 64 * 4 + 512 + vjp_bytes)) return rc;
-  double* part = (double*)ctx->scratch;
-  float* stats = (float*)((char*)ctx->scratch + part_bytes);
-  void* ws = (char*)ctx->scratch + part_bytes + (size_t)B * 64 * 4 + 256;
-  // the forward's statistics (its output goes nowhere: the statistics passes only)
-  if (int rc = dtype == MAUA_BF16 ? launch_group_norm_stats<bf16_t>(ctx->stream, (const bf16_t*)x, C, B, H, W, part, stats)
-                                  : launch_group_norm_stats<float>(ctx->stream, (const float*)x, C, B, H, W, part, stats))
-    return rc;
-  GnVjpArgs a{};
-  a.x0 = x; a.C0 = C; a.stats = stats; a.gamma = gamma; a.beta = beta; a.ss = scale_shift; a.ss_ld = 2L * C; a.silu = silu; a.mode = resample;
-  a.dy = dy; a.dres = dres; a.dx0 = dx; a.B = B; a.H = H; a.W = W;
-  return launch_group_norm_vjp(ctx->stream, dtype, a, ws);
-}
-
-// The unconditioned sampler loop inside the library: n_steps x (UNet forward + DDIM update), x updated in place.
-// model_t: host f32 [n_steps] (the timestep the network sees at each step, same for every sample); coef: host f32
-// [n_steps][8] (maua_ddim_step's coefficients).  use_graph: capture the whole loop in ONE hipGraph on first use for a
-// (B, H, W, n_steps) and replay it afterwards (a forward is ~400 short launches: the graph removes the launch gaps).
-// pred_xstart (optional) receives the last step's prediction.
-// what both sampler loops need on the device before their first step: the timesteps [n_steps][B], the DDIM coefficients
-// [n_steps][B][8], the model-output / pred_xstart buffers and every step's timestep projections (emb_table)
-static int prepare_sampler(maua_unet* n, int B, int H, int W, const float* model_t, const float* coef, int n_steps) {
-  hipStream_t st = n->ctx->stream;
-  const long chw = (long)n->in_ch * H * W;
-  // per-step constants on the device: timesteps [n_steps][B], coefficients [n_steps][B][8]
-  if (n->g_steps < n_steps * B || !n->g_t) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    for (float** p : {&n->g_t, &n->g_cf}) { if (*p) hipFree(*p); *p = nullptr; }
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->g_t, (size_t)n_steps * B * 4));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->g_cf, (size_t)n_steps * B * 8 * 4));
-    n->g_steps = n_steps * B;
-    drop_sampler_graphs(n);
-  }
-  {
-    std::vector<float> ht((size_t)n_steps * B), hc((size_t)n_steps * B * 8);
-    for (int s = 0; s < n_steps; s++)
-      for (int b = 0; b < B; b++) {
-        ht[(size_t)s * B + b] = model_t[s];
-        memcpy(&hc[((size_t)s * B + b) * 8], coef + (size_t)s * 8, 32);
-      }
-    MAUA_HIP_CHECK(hipMemcpyAsync(n->g_t, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
-    MAUA_HIP_CHECK(hipMemcpyAsync(n->g_cf, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, st));
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-  }
-  const size_t out_bytes = (size_t)B * n->out_ch * H * W * 4, pred_bytes = (size_t)B * chw * 4;
-  if (!n->g_out || n->out_cap < out_bytes + pred_bytes) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    for (float** p : {&n->g_out, &n->g_pred}) { if (*p) hipFree(*p); *p = nullptr; }
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->g_out, out_bytes));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->g_pred, pred_bytes));
-    n->out_cap = out_bytes + pred_bytes;
-    drop_sampler_graphs(n);
-  }
-  // every step's timestep projections at once: the timesteps are known up front and shared by the samples, so the stacked
-  // emb_layers GEMV (51 k x 1024 f32 weights at the 256^2 configuration) runs once per loop with n_steps rows instead of
-  // once per step with B rows
-  if (n->emb_table_rows < (size_t)n_steps) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->emb_table) hipFree(n->emb_table);
-    n->emb_table = nullptr; n->emb_table_rows = 0;
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->emb_table, (size_t)n_steps * n->emb_total * 4));
-    n->emb_table_rows = n_steps;
-    drop_sampler_graphs(n);
-  }
-  {
-    const int E = n->emb_dim, mc = n->mc, half = mc / 2;
-    float *tt, *e0, *e1, *e2;
-    MAUA_HIP_CHECK(hipMalloc((void**)&tt, (size_t)n_steps * (1 + mc + 2 * E) * 4));
-    e0 = tt + n_steps; e1 = e0 + (size_t)n_steps * mc; e2 = e1 + (size_t)n_steps * E;
-    MAUA_HIP_CHECK(hipMemcpyAsync(tt, model_t, (size_t)n_steps * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(timestep_embedding_kernel, dim3((n_steps * half + 255) / 256), dim3(256), 0, st, tt,
-                       n->freqs_loaded ? n->freqs : nullptr, e0, n_steps, mc);
-    hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e0, n->te0_w, n->te0_b, e1, n_steps, mc, E, 0, 1);
-    hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e1, n->te2_w, n->te2_b, e2, n_steps, E, E, 0, 0);
-    hipLaunchKernelGGL(linear_rows_kernel, dim3((n->emb_total + 3) / 4), dim3(256), 0, st, e2, n->embw, n->embb, n->emb_table,
-                       n_steps, E, n->emb_total, 1, 0);
-    MAUA_HIP_CHECK(hipGetLastError());
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    hipFree(tt);
-  }
-  return MAUA_OK;
-}
-
-int maua_ddim_sample_loop(maua_unet* n, float* x, int B, int H, int W, const float* model_t, const float* coef, int n_steps,
-                          int use_graph, float* pred_xstart) {
-  MAUA_REQUIRE(n && x && model_t && coef && n_steps > 0, "maua_ddim_sample_loop: NULL argument");
-  if (B == 0) return MAUA_OK;
-  hipStream_t st = n->ctx->stream;
-  const long chw = (long)n->in_ch * H * W;
-  const size_t key = shape_key(B, H, W) ^ ((size_t)n_steps << 52);
-  if (int rc = prepare_sampler(n, B, H, W, model_t, coef, n_steps)) return rc;
-  const size_t pred_bytes = (size_t)B * chw * 4;
-  auto body = [&](int s) -> int {
-    n->emb_row = n->emb_table + (size_t)s * n->emb_total;
-    int rc = maua_unet_forward(n, x, n->g_t + (size_t)s * B, B, H, W, n->g_out);
-    n->emb_row = nullptr;
-    if (rc) return rc;
-    return maua_ddim_step(n->ctx, x, n->g_out, nullptr, nullptr, n->g_cf + (size_t)s * B * 8, B, n->in_ch, n->out_ch,
-                          (long)H * W, x, n->g_pred);
-  };
-  if (use_graph && !n->graph_failed) {
-    if (!n->graph_exec || n->graph_key != key || n->g_x != x) {
-      // one eager forward first: plans the arena, sets the kernels' attributes (nothing of that is capturable)
-      // - on a scratch copy so that x is not advanced
-      if (n->planned_key != shape_key(B, H, W) || B > n->ones_b) {
-        float* tmp;
-        MAUA_HIP_CHECK(hipMalloc((void**)&tmp, pred_bytes));
-        MAUA_HIP_CHECK(hipMemcpyAsync(tmp, x, pred_bytes, hipMemcpyDeviceToDevice, st));
-        int rc = maua_unet_forward(n, tmp, n->g_t, B, H, W, n->g_out);
-        hipStreamSynchronize(st);
-        hipFree(tmp);
-        if (rc) return rc;
-      }
-      if (n->graph_exec) { hipGraphExecDestroy(n->graph_exec); n->graph_exec = nullptr; }
-      if (!n->cap_stream) MAUA_HIP_CHECK(hipStreamCreateWithFlags(&n->cap_stream, hipStreamNonBlocking));
-      MAUA_HIP_CHECK(hipStreamSynchronize(st));
-      hipGraph_t graph = nullptr;
-      hipError_t e = hipStreamBeginCapture(n->cap_stream, hipStreamCaptureModeThreadLocal);
-      int rc = MAUA_OK;
-      if (e == hipSuccess) {
-        n->ctx->stream = n->cap_stream;   // the launchers read the context's stream
-        for (int s = 0; s < n_steps && !rc; s++) rc = body(s);
-        n->ctx->stream = st;
-        e = hipStreamEndCapture(n->cap_stream, &graph);
-      }
-      if (!rc && e == hipSuccess) e = hipGraphInstantiate(&n->graph_exec, graph, nullptr, nullptr, 0);
-      if (graph) hipGraphDestroy(graph);
-      if (rc || e != hipSuccess) {
-        (void)hipGetLastError();  // clear the sticky error; run eagerly from now on
-        n->graph_exec = nullptr;
-        n->graph_failed = 1;
-        if (getenv("MAUA_VERBOSE"))
-          fprintf(stderr, "[maua] ddim_sample_loop: graph capture unavailable (%s), running eagerly\n",
-                  rc ? maua_last_error() : hipGetErrorString(e));
-      } else {
-        n->graph_key = key;
-        n->g_x = x;
-      }
-    }
-  }
-  if (use_graph && n->graph_exec && !n->graph_failed) {
-    MAUA_HIP_CHECK(hipGraphLaunch(n->graph_exec, st));
-  } else {
-    for (int s = 0; s < n_steps; s++)
-      if (int rc = body(s)) return rc;
-  }
-  if (pred_xstart) MAUA_HIP_CHECK(hipMemcpyAsync(pred_xstart, n->g_pred, pred_bytes, hipMemcpyDeviceToDevice, st));
-  return MAUA_OK;
-}
-
-// g = (img - target) * k over rows, zeros when any element is NaN (MSEGuide + the NaN rule of guided.py:262-265); k: device scalar
-// (reset_flag = false: *flag was zeroed by the caller - the captured sampler loop keeps memset nodes out of its graph: replays of a
-//  graph holding a 4-byte memset node were seen reading a non-zero flag after an eager run of the same calls, on ROCm 7.0.2)
-static int mse_guide_grad(maua_ctx* ctx, const float* img, const float* target, long tstride, const float* kdev, int B, long row,
-                          float* out, int* flag, bool reset_flag = true) {
-  const long total = (long)B * row;
-  if (reset_flag) MAUA_HIP_CHECK(hipMemsetAsync(flag, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(mse_guide_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, img, target, tstride,
-                     kdev, row, total, out, flag);
-  hipLaunchKernelGGL(zero_if_flag_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, out, total, flag);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// The image-MSE grad module as an operator: out = (img - target) * k, zeros if that holds a NaN.  img, out [B][row]; target [B][row]
-// (target_bstride = row) or one row for all samples (0).
-int maua_mse_guide_grad(maua_ctx* ctx, const float* img, const float* target, long target_bstride, float k, int B, long row, float* out) {
-  MAUA_REQUIRE(ctx, "maua_mse_guide_grad: ctx is NULL");
-  if (B == 0 || row == 0) return MAUA_OK;
-  MAUA_REQUIRE(img && target && out, "maua_mse_guide_grad: NULL argument");
-  if (int rc = scratch_reserve(ctx, 256 + (size_t)B * 4)) return rc;
-  int* flag = reinterpret_cast<int*>(ctx->scratch);
-  float* kd = reinterpret_cast<float*>(reinterpret_cast<char*>(ctx->scratch) + 256);
-  std::vector<float> hk((size_t)B, k);
-  MAUA_HIP_CHECK(hipMemcpyAsync(kd, hk.data(), (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
-  MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // (hk lives on this call's stack)
-  return mse_guide_grad(ctx, img, target, target_bstride, kd, B, row, out, flag);
-}
-
-// configs[3] as BASELINE states it: the GUIDED DDIM loop inside the library, one hipGraph per shape.  Per step s (guided.py:302-311,
-// 333-337 with cond_fn = GradientGuidedConditioning, speed "fast", :236-272, and the image-MSE grad module):
-//   out  = unet(x, t_s)                                      pred = secondary(x, cos_t_s).pred          (:252-253)
-//   img  = sigma_s pred + (1 - sigma_s) x                    g    = (img - target) k, zeros if NaN      (:254, :256-265)
-//   grad = c0_s g + c1_s (dv/dx)^T g                         x, pred_xstart = ddim_step(x, out, grad)   (:266-268, ddim_sample)
-// guide: host f32 [n_steps][5] = {cos_t, sigma, 1 - sigma, -(sigma a_c + 1 - sigma), sigma s_c} as GradientGuidedConditioning.forward
-// evaluates them.  target: device [B][C][H][W] (target_bstride = C H W) or one image for all samples (0).  x is updated in place.
-// sec == NULL: speed "regular" - out = forward_keep(x, t_s); eps = out[:, :C]; pred = ra x - rm eps; img, g as above;
-// grad = c0_s g + c1_s (d eps / d x)^T g from maua_unet_vjp's walk; guide[s] = {-, sigma, 1 - sigma, -(sigma ra + 1 - sigma), sigma rm}.
-int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, int H, int W, const float* model_t, const float* coef,
-                          const float* guide, int n_steps, const float* target, long target_bstride, float mse_k, int use_graph,
-                          float* pred_xstart) {
-  MAUA_REQUIRE(n && x && model_t && coef && guide && n_steps > 0, "maua_ddim_guided_loop: NULL argument");
-  // sec == NULL: speed "regular" (guided.py:214-218, 250-252) - the gradient goes through THIS network: a kept forward + its input
-  // gradient per step, no secondary model
-  const bool regular = sec == nullptr;
-  if (regular) {
-    MAUA_REQUIRE(n->vjp && n->conv_in.wt_t && n->conv_out.wt_t, "maua_ddim_guided_loop: speed \"regular\" needs option \"vjp\" = 1 before the weights are loaded");
-    MAUA_REQUIRE(n->out_ch >= n->in_ch, "maua_ddim_guided_loop: the model output must hold an epsilon per image channel");
-  } else {
-    MAUA_REQUIRE(n->in_ch == 3, "maua_ddim_guided_loop: the secondary model guides 3-channel images");
-    MAUA_REQUIRE(secondary_ctx(sec) == n->ctx, "maua_ddim_guided_loop: both networks must live on one context (one stream)");
-  }
-  const long chw = (long)n->in_ch * H * W;
-  MAUA_REQUIRE(target_bstride == 0 || target_bstride == chw, "maua_ddim_guided_loop: target_bstride is 0 or C * H * W");
-  if (B == 0) return MAUA_OK;
-  hipStream_t st = n->ctx->stream;
-  const size_t key = shape_key(B, H, W) ^ ((size_t)n_steps << 52) ^ ((size_t)(uintptr_t)sec << 1) ^ (target_bstride ? 1u : 0u) ^ (regular ? 2u : 0u);
-  maua_clip* const clip = n->gd_clip;
-  if (clip) {
-    MAUA_REQUIRE(clip_ctx(clip) == n->ctx, "maua_ddim_guided_loop: the image tower must live on the networks' context");
-    MAUA_REQUIRE(n->gd_rect_steps == n_steps, "maua_ddim_guided_loop: maua_unet_set_clip_guide was given another number of steps");
-    MAUA_REQUIRE(n->in_ch == 3, "maua_ddim_guided_loop: CLIP guides 3-channel images");
-    for (size_t i = 0; i < n->gd_rects_host.size(); i += 3)
-      MAUA_REQUIRE((n->gd_rects_host[i] & CUT_SIZE_MASK) > 0 && n->gd_rects_host[i + 1] >= 0 && n->gd_rects_host[i + 2] >= 0 &&
-                       n->gd_rects_host[i + 1] + (n->gd_rects_host[i] & CUT_SIZE_MASK) <= H &&
-                       n->gd_rects_host[i + 2] + (n->gd_rects_host[i] & CUT_SIZE_MASK) <= W,
-                   "maua_ddim_guided_loop: a cutout leaves the image");
-    if (int rc = clip_prepare_guide(clip, B, H, W, n->gd_cutn)) return rc;
-  } else if (n->gd_guides.empty()) {
-    MAUA_REQUIRE(target, "maua_ddim_guided_loop: target is NULL");
-  }
-  const bool guides = !n->gd_guides.empty();
-  if (guides) {
-    MAUA_REQUIRE(n->in_ch == 3, "maua_ddim_guided_loop: the grad modules guide 3-channel images");
-    for (maua_guide* g : n->gd_guides) {
-      MAUA_REQUIRE(guide_ctx(g) == n->ctx, "maua_ddim_guided_loop: a grad module lives on another context");
-      if (int rc = guide_prepare(g, B, H, W)) return rc;
-    }
-  }
-  if (int rc = prepare_sampler(n, B, H, W, model_t, coef, n_steps)) return rc;
-  const size_t tb = (size_t)B * chw, tab = (size_t)n_steps * B * 7 + B;
-  if (n->gd_cap < 10 * tb || n->gd_tab_cap < tab || !n->gd_flag || n->gd_flags < n_steps) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    for (void* p : {(void*)n->gd_buf, (void*)n->gd_tab, (void*)n->gd_flag})
-      if (p) hipFree(p);
-    n->gd_buf = nullptr; n->gd_tab = nullptr; n->gd_flag = nullptr; n->gd_cap = n->gd_tab_cap = 0;
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->gd_buf, 10 * tb * 4));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->gd_tab, tab * 4));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->gd_flag, (size_t)n_steps * 4));
-    n->gd_cap = 10 * tb; n->gd_tab_cap = tab; n->gd_flags = n_steps;
-    drop_sampler_graphs(n);
-  }
-  float *bx = n->gd_buf, *bv = bx + tb, *bp = bv + tb, *be = bp + tb, *bimg = be + tb, *bg = bimg + tb, *bjv = bg + tb,
-        *bgrad = bjv + tb, *btgt = bgrad + tb, *bsub = btgt + tb;
-  float *t_ct = n->gd_tab, *t_img = t_ct + (size_t)n_steps * B, *t_grad = t_img + (size_t)n_steps * B * 2,
-        *t_pred = t_grad + (size_t)n_steps * B * 2, *t_k = t_pred + (size_t)n_steps * B * 2;
-  {
-    std::vector<float> h(tab);
-    for (int s = 0; s < n_steps; s++)
-      for (int b = 0; b < B; b++) {
-        const float* gs = guide + (size_t)s * 5;
-        h[(size_t)s * B + b] = gs[0];
-        h[(size_t)n_steps * B + ((size_t)s * B + b) * 2] = gs[1];
-        h[(size_t)n_steps * B + ((size_t)s * B + b) * 2 + 1] = gs[2];
-        h[(size_t)n_steps * B * 3 + ((size_t)s * B + b) * 2] = gs[3];
-        h[(size_t)n_steps * B * 3 + ((size_t)s * B + b) * 2 + 1] = gs[4];
-        h[(size_t)n_steps * B * 5 + ((size_t)s * B + b) * 2] = coef[(size_t)s * 8];        // (ra, -rm): pred_xstart from eps (regular)
-        h[(size_t)n_steps * B * 5 + ((size_t)s * B + b) * 2 + 1] = -coef[(size_t)s * 8 + 1];
-      }
-    for (int b = 0; b < B; b++) h[(size_t)n_steps * B * 7 + b] = mse_k;
-    MAUA_HIP_CHECK(hipMemcpyAsync(n->gd_tab, h.data(), tab * 4, hipMemcpyHostToDevice, st));
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-  }
-  MAUA_HIP_CHECK(hipMemsetAsync(n->gd_flag, 0, (size_t)n_steps * 4, st));
-  MAUA_HIP_CHECK(hipMemcpyAsync(bx, x, tb * 4, hipMemcpyDeviceToDevice, st));
-  if (!clip && !guides) MAUA_HIP_CHECK(hipMemcpyAsync(btgt, target, (target_bstride ? tb : (size_t)chw) * 4, hipMemcpyDeviceToDevice, st));
-  // the grad module(s) of step s on the context's current stream: bimg -> bg
-  auto guide_grad = [&](int s) -> int {
-    int rc = MAUA_OK;
-    if (clip)
-      rc = clip_guide_grad(clip, bimg, B, H, W, n->gd_rects + (size_t)s * n->gd_batches * n->gd_cutn * 3,
-                           n->gd_mult ? n->gd_mult + (size_t)s * n->gd_batches * n->gd_cutn : nullptr, n->gd_cutn, n->gd_cutn_total,
-                           n->gd_batches, n->gd_clip_scale, n->gd_clip_clamp, bg);
-    else if (!guides)
-      return mse_guide_grad(n->ctx, bimg, btgt, target_bstride ? chw : 0, t_k, B, chw, bg, n->gd_flag + s, false);
-    // guided.py:258-266: img_grad += sub_grad per module, a module whose gradient holds a NaN skipped
-    for (size_t k = 0; k < n->gd_guides.size() && !rc; k++) {
-      rc = guide_eval(n->gd_guides[k], bimg, B, H, W, bsub);
-      if (!rc) rc = screened_accumulate(n->ctx->stream, bsub, bg, (long)tb, !clip && k == 0, n->gd_gflag);
-    }
-    return rc;
-  };
-  const long tstride = target_bstride ? chw : 0;
-  if (n->gd_fork && !n->ev_fork) {
-    MAUA_HIP_CHECK(hipEventCreateWithFlags(&n->ev_fork, hipEventDisableTiming));
-    MAUA_HIP_CHECK(hipEventCreateWithFlags(&n->ev_join, hipEventDisableTiming));
-    MAUA_HIP_CHECK(hipStreamCreateWithFlags(&n->side_stream, hipStreamNonBlocking));
-    MAUA_HIP_CHECK(hipStreamCreateWithFlags(&n->cap_side, hipStreamNonBlocking));
-  }
-  // one step on (main, side): the UNet forward on main; the guidance branch - it reads x and nothing the forward writes - on side
-  // (main itself when the fork is off); the DDIM update on main behind both.  Every launcher reads the context's stream.
-  // speed "regular": no parallel branch (the gradient needs the forward it differentiates); everything on `main`
-  auto step_regular = [&](int s, hipStream_t main) -> int {
-    n->ctx->stream = main;
-    n->emb_row = n->emb_table + (size_t)s * n->emb_total;
-    int rc = n->dtype == MAUA_BF16 ? run_forward<bf16_t>(n, bx, n->g_t + (size_t)s * B, B, H, W, n->g_out, true)
-                                   : run_forward<float>(n, bx, n->g_t + (size_t)s * B, B, H, W, n->g_out, true);
-    if (!rc) {
-      // pred_xstart = ra x - rm eps (gaussian_diffusion.py _predict_xstart_from_eps), img = sigma pred + (1 - sigma) x (:252)
-      const long total = (long)B * chw;
-      hipLaunchKernelGGL(eps_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, main, n->g_out, chw, (long)n->out_ch * H * W,
-                         total, be);
-      if (hipGetLastError() != hipSuccess) rc = fail("maua_ddim_guided_loop: launch failed");
-      if (!rc) rc = maua_axpby_rows(n->ctx, bx, be, t_pred + (size_t)s * B * 2, B, chw, bp);
-      if (!rc) rc = maua_axpby_rows(n->ctx, bp, bx, t_img + (size_t)s * B * 2, B, chw, bimg);
-    }
-    if (!rc) rc = guide_grad(s);
-    if (!rc) rc = n->dtype == MAUA_BF16 ? run_vjp<bf16_t>(n, bg, bjv, n->in_ch) : run_vjp<float>(n, bg, bjv, n->in_ch);
-    n->emb_row = nullptr;
-    if (!rc) rc = maua_axpby_rows(n->ctx, bg, bjv, t_grad + (size_t)s * B * 2, B, chw, bgrad);
-    if (rc) return rc;
-    return maua_ddim_step(n->ctx, bx, n->g_out, bgrad, nullptr, n->g_cf + (size_t)s * B * 8, B, n->in_ch, n->out_ch, (long)H * W, bx,
-                          n->g_pred);
-  };
-  auto step_on = [&](int s, hipStream_t main, hipStream_t side) -> int {
-    if (regular) return step_regular(s, main);
-    const bool fork = side != main;
-    if (fork) {
-      MAUA_HIP_CHECK(hipEventRecord(n->ev_fork, main));
-      MAUA_HIP_CHECK(hipStreamWaitEvent(side, n->ev_fork, 0));
-    }
-    n->ctx->stream = main;
-    n->emb_row = n->emb_table + (size_t)s * n->emb_total;
-    int rc = maua_unet_forward(n, bx, n->g_t + (size_t)s * B, B, H, W, n->g_out);
-    n->emb_row = nullptr;
-    if (!rc) {
-      n->ctx->stream = side;
-      rc = maua_secondary_forward(sec, bx, t_ct + (size_t)s * B, B, H, W, bv, bp, be);
-      if (!rc) rc = maua_axpby_rows(n->ctx, bp, bx, t_img + (size_t)s * B * 2, B, chw, bimg);
-      if (!rc) rc = guide_grad(s);
-      if (!rc) rc = maua_secondary_vjp(sec, bg, B, H, W, bjv);
-      if (!rc) rc = maua_axpby_rows(n->ctx, bg, bjv, t_grad + (size_t)s * B * 2, B, chw, bgrad);
-    }
-    n->ctx->stream = main;
-    if (fork) {   // (joined whatever happened: a capture must not end with an unjoined stream)
-      hipError_t e1 = hipEventRecord(n->ev_join, side), e2 = hipStreamWaitEvent(main, n->ev_join, 0);
-      if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) rc = fail("maua_ddim_guided_loop: joining the guidance branch failed");
-    }
-    if (rc) return rc;
-    return maua_ddim_step(n->ctx, bx, n->g_out, bgrad, nullptr, n->g_cf + (size_t)s * B * 8, B, n->in_ch, n->out_ch, (long)H * W, bx,
-                          n->g_pred);
-  };
-  auto body = [&](int s) -> int {   // eager: on the caller's stream (+ the side stream)
-    int rc = step_on(s, st, n->gd_fork ? n->side_stream : st);
-    n->ctx->stream = st;
-    return rc;
-  };
-  // the captured graph holds raw pointers into the secondary model's weights and workspaces: it is this model's, at this generation
-  // of its buffers, or it is recaptured (the address alone does not identify a model: a freed one's can be handed out again)
-  unsigned long long sec_uid = 0, sec_epoch = 0;
-  unsigned long long clip_uid = 0, clip_ep = 0;
-  auto sec_matches = [&]() {
-    secondary_stamp(sec, &sec_uid, &sec_epoch);
-    clip_stamp(clip, &clip_uid, &clip_ep);
-    bool guides_same = n->gd_guide_epochs.size() == n->gd_guides.size();
-    for (size_t k = 0; guides_same && k < n->gd_guides.size(); k++) guides_same = guide_epoch(n->gd_guides[k]) == n->gd_guide_epochs[k];
-    return sec_uid == n->gd_sec_uid && sec_epoch == n->gd_sec_epoch && clip_uid == n->gd_clip_uid && clip_ep == n->gd_clip_epoch &&
-           n->gd_guide_gen == n->gd_guide_gen_seen && guides_same;
-  };
-  if (use_graph && !n->gd_failed) {
-    if (!n->gd_exec || n->gd_key != key || !sec_matches()) {
-      // one eager step on scratch copies first: it plans both networks' workspaces and sets the kernels' attributes (none of that
-      // can be captured); bx is restored afterwards
-      {
-        int rc = body(0);
-        if (rc) return rc;
-        MAUA_HIP_CHECK(hipMemcpyAsync(bx, x, tb * 4, hipMemcpyDeviceToDevice, st));
-        MAUA_HIP_CHECK(hipMemsetAsync(n->gd_flag, 0, (size_t)n_steps * 4, st));
-      }
-      if (n->gd_exec) { hipGraphExecDestroy(n->gd_exec); n->gd_exec = nullptr; }
-      if (!n->cap_stream) MAUA_HIP_CHECK(hipStreamCreateWithFlags(&n->cap_stream, hipStreamNonBlocking));
-      MAUA_HIP_CHECK(hipStreamSynchronize(st));
-      hipGraph_t graph = nullptr;
-      hipError_t e = hipStreamBeginCapture(n->cap_stream, hipStreamCaptureModeThreadLocal);
-      int rc = MAUA_OK;
-      if (e == hipSuccess) {
-        for (int s = 0; s < n_steps && !rc; s++) rc = step_on(s, n->cap_stream, n->gd_fork ? n->cap_side : n->cap_stream);
-        n->ctx->stream = st;
-        e = hipStreamEndCapture(n->cap_stream, &graph);
-      }
-      if (!rc && e == hipSuccess) e = hipGraphInstantiate(&n->gd_exec, graph, nullptr, nullptr, 0);
-      if (graph) hipGraphDestroy(graph);
-      if (rc || e != hipSuccess) {
-        (void)hipGetLastError();
-        n->gd_exec = nullptr;
-        n->gd_failed = 1;
-        if (getenv("MAUA_VERBOSE"))
-          fprintf(stderr, "[maua] ddim_guided_loop: graph capture unavailable (%s), running launch by launch\n",
-                  rc ? maua_last_error() : hipGetErrorString(e));
-      } else {
-        n->gd_key = key;
-        secondary_stamp(sec, &n->gd_sec_uid, &n->gd_sec_epoch);   // (after the eager step: that is what sized the workspaces)
-        clip_stamp(clip, &n->gd_clip_uid, &n->gd_clip_epoch);
-        n->gd_guide_gen_seen = n->gd_guide_gen;
-        n->gd_guide_epochs.clear();
-        for (maua_guide* g : n->gd_guides) n->gd_guide_epochs.push_back(guide_epoch(g));
-      }
-    }
-  }
-  if (use_graph && n->gd_exec && !n->gd_failed) {
-    // (the copies / memset above are stream-ordered before the graph anyway; one host wait per 100-step loop costs nothing and keeps
-    //  the replay independent of how the runtime orders copy engines against graph launches)
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    MAUA_HIP_CHECK(hipGraphLaunch(n->gd_exec, st));
-    n->gd_last_graph = 1;
-  } else {
-    n->gd_last_graph = 0;
-    for (int s = 0; s < n_steps; s++)
-      if (int rc = body(s)) return rc;
-  }
-  MAUA_HIP_CHECK(hipMemcpyAsync(x, bx, tb * 4, hipMemcpyDeviceToDevice, st));
-  if (pred_xstart) MAUA_HIP_CHECK(hipMemcpyAsync(pred_xstart, n->g_pred, tb * 4, hipMemcpyDeviceToDevice, st));
-  return MAUA_OK;
-}
-
-// CLIPGrads as the guided loop's grad module (maua/grad.py:96-165 in place of the image-MSE module); rects: host [n_steps][batches][cutn][3]
-int maua_unet_set_clip_guide(maua_unet* n, maua_clip* clip, const int* rects, const float* mult, int n_steps, int cutn, int batches,
-                             float scale, float clamp_gradient) {
-  MAUA_REQUIRE(n, "maua_unet_set_clip_guide: net is NULL");
-  if (!clip) {
-    if (n->gd_clip) n->gd_guide_gen++;
-    n->gd_clip = nullptr;
-    return MAUA_OK;
-  }
-  MAUA_REQUIRE(rects && n_steps > 0 && cutn > 0 && batches > 0, "maua_unet_set_clip_guide: bad arguments");
-  hipStream_t st = n->ctx->stream;
-  const size_t per = (size_t)n_steps * batches * cutn, cnt = per * 4;   // 3 ints + 1 float per cutout
-  int cutn_total = cutn;
-  if (mult) {
-    for (size_t b = 0; b < (size_t)n_steps * batches; b++) {
-      double t = 0;
-      for (int i = 0; i < cutn; i++) t += mult[b * cutn + i];
-      if (b == 0) cutn_total = (int)(t + 0.5);
-      MAUA_REQUIRE((int)(t + 0.5) == cutn_total && cutn_total >= cutn,
-                   "maua_unet_set_clip_guide: every cutout batch must stand for the same number (>= cutn) of cutouts");
-    }
-  }
-  if (cnt > n->gd_rects_cap) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->gd_rects) hipFree(n->gd_rects);
-    n->gd_rects = nullptr; n->gd_rects_cap = 0;
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->gd_rects, cnt * 4));
-    n->gd_rects_cap = cnt;
-    n->gd_guide_gen++;
-  }
-  float* mult_dev = mult ? (float*)(n->gd_rects + per * 3) : nullptr;
-  // (everything a captured loop bakes into its launches moves the generation; the rectangles themselves are data it reads)
-  if (n->gd_clip != clip || n->gd_rect_steps != n_steps || n->gd_cutn != cutn || n->gd_batches != batches || n->gd_clip_scale != scale ||
-      n->gd_clip_clamp != clamp_gradient || n->gd_mult != mult_dev || n->gd_cutn_total != cutn_total)
-    n->gd_guide_gen++;
-  n->gd_rects_host.assign(rects, rects + per * 3);
-  MAUA_HIP_CHECK(hipMemcpyAsync(n->gd_rects, n->gd_rects_host.data(), per * 12, hipMemcpyHostToDevice, st));
-  if (mult) MAUA_HIP_CHECK(hipMemcpyAsync(mult_dev, mult, per * 4, hipMemcpyHostToDevice, st));
-  MAUA_HIP_CHECK(hipStreamSynchronize(st));
-  n->gd_clip = clip; n->gd_rect_steps = n_steps; n->gd_cutn = cutn; n->gd_batches = batches; n->gd_clip_scale = scale;
-  n->gd_clip_clamp = clamp_gradient; n->gd_mult = mult_dev; n->gd_cutn_total = cutn_total;
-  return MAUA_OK;
-}
-
-// a list of grad modules (guides.hip) as the guided loop's conditioning: evaluated after CLIPGrads (if set) and summed
-int maua_unet_set_guides(maua_unet* n, maua_guide* const* guides, int n_guides) {
-  MAUA_REQUIRE(n && n_guides >= 0 && (n_guides == 0 || guides), "maua_unet_set_guides: bad arguments");
-  std::vector<unsigned long long> uids;
-  for (int k = 0; k < n_guides; k++) {
-    MAUA_REQUIRE(guides[k], "maua_unet_set_guides: NULL guide");
-    uids.push_back(guide_uid(guides[k]));
-  }
-  if (uids != n->gd_guide_uids) n->gd_guide_gen++;   // (a captured loop bakes the list into its launches)
-  n->gd_guide_uids = uids;
-  n->gd_guides.assign(guides, guides + n_guides);
-  if (n_guides && !n->gd_gflag) MAUA_HIP_CHECK(hipMalloc((void**)&n->gd_gflag, 256));
-  return MAUA_OK;
-}
-
-// 1 when the last maua_ddim_guided_loop(use_graph = 1) replayed a captured hipGraph
-int maua_unet_guided_graph_active(maua_unet* n, int* active) {
-  MAUA_REQUIRE(n && active, "maua_unet_guided_graph_active: NULL argument");
-  *active = n->gd_exec && !n->gd_failed && n->gd_last_graph ? 1 : 0;
-  return MAUA_OK;
+  return unet_vjp(n, g_out, g_x, 0);
 }
 
 }  // extern "C"

@@ -583,6 +583,35 @@ def test_guided_loop_as_one_graph_equals_the_step_by_step_loop(sec_dt, sec_exact
         SecondaryDiffusionImageNet2(dtype=torch.float32).vjp(torch.zeros(1, 3, 64, 64))
 
 
+def test_both_sampler_graphs_on_one_network_are_dropped_and_recaptured_together():
+    """One network carries both captured loops (maua_ddim_sample_loop's and maua_ddim_guided_loop's executables, csrc/sampler.hip).  A
+    larger batch regrows the arena and the per-step tables they point into: both are dropped and captured again; back at the first
+    batch likewise.  At every stage each loop - unguided, guided speed "fast" (secondary model, image-MSE target) and speed "regular"
+    (through the network itself) - replays a graph and gives the bits of the same loop run launch by launch.  32 x 32 is the smallest
+    legal size (three levels, attention still at 8 x 8); equality only, so no tolerance."""
+    from maua_amd.diffusion import GradientGuidedConditioning, ImageTarget, MSEGuide, SpacedDiffusion, space_timesteps
+    cfg, p, net = _build(SMALL, torch.float32)
+    net.enable_vjp()                                   # (before the weights load: the library object is created on first use)
+    sd = SpacedDiffusion(space_timesteps(1000, "ddim20"), OD.linear_betas(1000), rescale_timesteps=True)
+    sec, _ = _secondary(torch.float32, 1)
+    g = torch.Generator().manual_seed(23)
+    target = torch.randn(3, 32, 32, generator=g).clamp(-1, 1)
+    fast = GradientGuidedConditioning(sd, sec, [MSEGuide(scale=800.0)], speed="fast")
+    regular = GradientGuidedConditioning(sd, net, [MSEGuide(scale=800.0)], speed="regular")
+    for cond in (fast, regular):
+        cond.set_targets([ImageTarget(target)], None)
+    loops = {"unguided": (lambda x, ug: sd.ddim_sample_loop(net, x, 6, 4, use_graph=ug), net.graph_active),
+             "fast": (lambda x, ug: sd.ddim_guided_loop(net, fast, x, 6, 4, use_graph=ug), net.guided_graph_active),
+             "regular": (lambda x, ug: sd.ddim_guided_loop(net, regular, x, 6, 4, use_graph=ug), net.guided_graph_active)}
+    xs = {B: torch.randn(B, 3, 32, 32, generator=g) for B in (1, 3)}
+    for stage, B in enumerate((1, 3, 1)):
+        for name, (loop, active) in loops.items():
+            sample, pred = loop(xs[B].clone(), True)
+            assert active(), (stage, B, name)
+            sample_e, pred_e = loop(xs[B].clone(), False)
+            assert torch.equal(sample, sample_e) and torch.equal(pred, pred_e), (stage, B, name)
+
+
 def L_dev(t):
     from maua_amd import _lib as L
     return L.dev_tensor(t, torch.float32)

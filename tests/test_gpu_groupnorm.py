@@ -1,4 +1,4 @@
-"""The fused GroupNorm kernels (csrc/unet.hip: gn_partial / gn_finalize / gn_apply, gn_partial_group / gn_finalize_group /
+"""The fused GroupNorm kernels (csrc/groupnorm.hip: gn_partial / gn_finalize / gn_apply, gn_partial_group / gn_finalize_group /
 gn_finalize_psum / gn_apply_group; csrc/groupnorm_vjp.hip: gn_vjp_partial / gn_vjp_finalize / gn_vjp_apply), launched through
 maua_group_norm_ex / maua_group_norm_vjp_ex (csrc/groupnorm_api.hip) - the launchers the diffusion UNet runs - with both sources of
 the virtual concatenation, the resampling modes and the raw second output, the scale-shift row stride, the convolution's piece sums,

@@ -1,6 +1,6 @@
 """CPU-only side of the GroupNorm parity tests.
 
-1. What the fused GroupNorm launchers (csrc/unet.hip launch_group_norm, csrc/groupnorm_vjp.hip launch_group_norm_vjp) refuse before
+1. What the fused GroupNorm launchers (csrc/groupnorm.hip launch_group_norm, csrc/groupnorm_vjp.hip launch_group_norm_vjp) refuse before
    they launch, through the host-only maua_group_norm_check / maua_group_norm_vjp_check: return code and the launcher's own text for
    every refusal; the shapes the 256 and 512 px networks pass on the accepting side; the plan queries' answers at the route and
    chunk edges.  Pointers are fake (the checks never dereference them).  The method of tests/test_attention_host.py.
