@@ -121,6 +121,7 @@ int maua_synth_num_layers(const maua_synth* net);  /* synthesis layers in execut
  * FIR/epilogue pass (0 = four 3x3 phase kernels everywhere, 4x the MACs; v > 1 = every up-layer with input size <= v);
  * "tconv_dma" (default 1) runs that transposed convolution on LDS-direct loads (0 = register-staged kernel);
  * "tconv_fir" (default 256) fuses it with the FIR/epilogue pass from this input size up (0 = never);
+ * "tconv_walk" (default 1) lets that fused kernel walk down its column strips (0 = overlapping tiles; same bits);
  * "dma_conv" (default 1) runs the conv1 behind such an up-layer on LDS-direct loads, on pre-modulated input;
  * "dual_store" (default 1) lets a conv1 with a separate toRGB pass also store its output pre-modulated for the next up-layer;
  * "use_hires" (default 1) / "fuse_torgb" (default 1) select the register-stationary high-resolution kernels and
@@ -648,7 +649,8 @@ typedef struct {
  * (no shape with Ci, Co multiples of 32 exceeds them today); maua_modconv_ex meets those after the weights were prepared. */
 int maua_modconv_route(const maua_modconv_desc* d, const maua_modconv_desc* d1, int dtype, int route, int* tile);
 /* launch on the context's stream; refused (no launch, no fall-back) when the route cannot take the layer.  force_segs / narrow_ok:
- * the fused walk's row segments and narrow last strip (launch_upwalk_fused), ignored elsewhere */
+ * the fused walk's row segments and narrow last strip (launch_upwalk_fused); on the tconv_fir route force_segs > 0 forces the row
+ * segments of its strip walk and force_segs < 0 selects its tile form (synth option "tconv_walk" = 0); ignored elsewhere */
 int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const maua_modconv_desc* d1, int dtype, int route, int force_segs,
                     int narrow_ok);
 /* the separate toRGB launch: out[b][c][p] = clamp(sum_ch x[b][p][ch] wmod[b][c][ch] + bias[c], clamp) + upsample2d(prev)[b][c][p];

@@ -188,9 +188,11 @@ struct UpfirArgs {
 };
 int launch_upfir_epilogue(hipStream_t stream, int dtype, const UpfirArgs& a);
 // modconv_tconv_fir.hip: both halves in one kernel, t stays in LDS (bf16; x already multiplied by the styles); the output is
-// bit-identical to launch_tconv_dma (+ edges) followed by launch_upfir_epilogue
+// bit-identical to launch_tconv_dma (+ edges) followed by launch_upfir_epilogue.  walk = 1: a workgroup walks down its 30-column strip
+// and carries the three t rows the next step needs (force_segs > 0: that many row segments instead of the cost model's choice);
+// walk = 0: the tile form, which recomputes them.  Same bits either way.
 bool tconv_fir_supported(int dtype, int Ci, int Co, int H, int W);
-int launch_tconv_fir(hipStream_t stream, const ConvArgs& a, const UpfirArgs& u, int dtype = MAUA_BF16);
+int launch_tconv_fir(hipStream_t stream, const ConvArgs& a, const UpfirArgs& u, int dtype = MAUA_BF16, int walk = 1, int force_segs = 0);
 size_t prepped_weight_elems(int k, int up, int Cop, int Cip);
 
 // ---- how the launch arguments of one modulated layer are filled: synth.hip's forward and maua_modconv_ex (modconv_api.hip) both go

@@ -226,7 +226,7 @@ extern "C" int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const 
       a.x = x; a.x_bstride = x_bstride; a.w = base + o_w; a.y = t;
       if (route != R_T2) a.s = (const float*)(base + o_ones);
       UpfirArgs u = upfir_args(d);
-      if (route == R_TFIR) return launch_tconv_fir(st, a, u, dtype);
+      if (route == R_TFIR) return launch_tconv_fir(st, a, u, dtype, force_segs >= 0, force_segs);   // (force_segs < 0: the tile form)
       if (route == R_TDMA) {
         if (int rc = launch_tconv_edges(st, a, dtype)) return rc;
         if (int rc = launch_tconv_dma(st, a, dtype)) return rc;

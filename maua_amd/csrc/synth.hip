@@ -74,6 +74,8 @@ struct maua_synth {
   int tconv_fir = 256; // up-layers with inputs of at least this size: transposed conv + FIR + epilogue in ONE kernel, t stays in
                        // LDS (modconv_tconv_fir.hip); 0 = never.  Measured at B = 128 (pair -> fused): 256^2 inputs 3.61 -> 3.48 ms,
                        // 128^2 2.33 -> 2.62, 64^2 1.89 -> 2.65: the 1.42x MACs pay only where the t round trip was HBM-bound.
+  int tconv_walk = 1;  // ... as a walk down 30-column strips that carries three t rows from step to step (0 = the tile form, which
+                       // recomputes a one-position frame: 1.27x the steps' K-loop work); same bits (option "tconv_walk")
   const float* nz_scales = nullptr;   // [num_layers][nz_scale_stride] per-sample noise factors (maua_synth_set_noise_scale) or NULL
   long nz_scale_stride = 0;
   int dma_conv = 1;    // conv1 layers behind such an up-layer: LDS-direct-load kernel on pre-modulated input (bf16 / f16)
@@ -583,6 +585,7 @@ int maua_synth_set_option(maua_synth* n, const char* key, int value) {
       {"lowres", &maua_synth::lowres},         {"use_hires", &maua_synth::use_hires}, {"upwalk", &maua_synth::upwalk},
       {"walk_segs", &maua_synth::walk_segs},   {"walk_narrow", &maua_synth::walk_narrow},
       {"fuse_torgb", &maua_synth::fuse_torgb}, {"tconv_up", &maua_synth::tconv_up},   {"tconv_fir", &maua_synth::tconv_fir},
+      {"tconv_walk", &maua_synth::tconv_walk},
       {"tconv_dma", &maua_synth::tconv_dma},   {"dma_conv", &maua_synth::dma_conv},   {"dual_store", &maua_synth::dual_store}};
   for (const auto& o : routing)
     if (!strcmp(key, o.first)) {
@@ -815,7 +818,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
           }
           if (reads_premod(s.route)) a.s = n->ones;
           if (s.route == Route::TconvFir) {  // the whole layer in one kernel: t never leaves LDS (bit-identical output)
-            if (int rc = launch_tconv_fir(st, a, u, n->dtype)) return rc;
+            if (int rc = launch_tconv_fir(st, a, u, n->dtype, n->tconv_walk, 0)) return rc;
             prof_mark(n);  // (two profile slots like the two-launch path: the second measures ~0)
             break;
           }
