@@ -1019,6 +1019,50 @@ int maua_farneback_level_size(int H, int W, int level, int* h, int* w);
 int maua_farneback_check(const maua_farneback* handle, const maua_farneback_desc* d);
 int maua_farneback_pair_ex(maua_farneback* handle, maua_ctx* ctx, const maua_farneback_desc* d);
 
+/* ---- audio-reactivity instruments: per-frame visual features and matrix correlations (csrc/video_features.hip) ---------------
+ * Per-frame features of maua/audiovisual/audioreactive/selfsupervised/features/video.py:12-75, taken while the frames are on the device:
+ *   the histograms of R, G, B (video.py:12-31) and of H, S, V (:35-57; kornia.color.rgb_to_hsv restated from its published form: v = max,
+ *     s = (max - min) / (max + 1e-8), the hue of the first maximal channel, h = 2 pi ((h_k / deltac / 6) % 1) with torch's remainder):
+ *     torch.histc(frame, bins) with the frame-channel's own minimum and maximum as the range ([v - 1, v + 1] when they coincide), bin
+ *     int((x - min) * bins / (max - min)) in float32 with the right edge folded into the last bin, each histogram divided by its largest bin;
+ *   visual_variance (:61-62): the unbiased variance over N = 3 H W;
+ *   absdiff (:66-75): sum |frame_b - frame_{b-1}|; the handle carries a device copy of the last frame of the previous push, so a stream
+ *     may be pushed in batches of any size (the reference's 64-frame chunking changes nothing in the result and is not reproduced).
+ * frames: `B` dense frames in one of three layouts; a uint8 value k means k / 255 by a correctly rounded division (decord ... .div(255),
+ * video.py:208).  Outputs (device): hist [B][6][bins] float32 in the order R, G, B, H, S, V; counts [B][6][bins] int32, optional (NULL), the
+ * raw bin counts; variance [B]; diff [B], against the carried frame for b = 0 and 0 for the very first frame of a stream.  The reference's
+ * absdiff is cat(diff[1:], diff[-1:]) over the stream.
+ * Counts and the uint8 sums are integers throughout and every float operation is correctly rounded and uncontracted: counts and hist agree
+ * with a float32 host restatement to the bit, a rerun is bit-identical.  float32 frames: the sums are accumulated in float64.
+ * No entry point allocates: maua_vfeat_create plans the workspace for max_batch frames of H x W.  Refused, in front of the first launch: a
+ * layout outside 0 .. 2, bins outside 1 .. 256, B above max_batch, a frame size other than the handle's (or above 2^24 pixels, where a float32
+ * bin count stops being exact), a handle of another device, NULL outputs, a layout that changes inside a stream.  maua_vfeat_reset forgets
+ * the carried frame: the next push starts a stream. */
+enum { MAUA_VFEAT_U8_HWC = 0, MAUA_VFEAT_U8_CHW = 1, MAUA_VFEAT_F32_CHW = 2 };
+typedef struct maua_vfeat maua_vfeat;
+int maua_vfeat_create(maua_ctx* ctx, int H, int W, int bins, int max_batch, maua_vfeat** out);
+int maua_vfeat_destroy(maua_vfeat* handle);
+int maua_vfeat_reset(maua_vfeat* handle);
+/* host only, no device needed: MAUA_OK, or MAUA_ERR + maua_last_error() with maua_vfeat_push's own message.  Pointers are only checked, never
+ * dereferenced.  handle may be NULL (there is none without a device): then H, W, bins and max_batch describe the plan; with a handle, bins
+ * and max_batch are the handle's. */
+int maua_vfeat_check(const maua_vfeat* handle, int H, int W, int bins, int max_batch, const void* frames, int layout, int B, const float* hist,
+                     const int* counts, const float* variance, const float* diff);
+int maua_vfeat_push(maua_vfeat* handle, maua_ctx* ctx, const void* frames, int layout, int B, int H, int W, float* hist, int* counts,
+                    float* variance, float* diff);
+/* Matrix correlations between x [T][Fx] and y [T][Fy] (device float32, rows = time), correlation.py:353-382 with :14-56, :72-121, :278-282:
+ * pearson and concordance (torch.median's lower median over the column pairs), autocorrcorr, rv, rv2 (the modified RV) and r1.  No T x T
+ * matrix is formed: trace(XX^T YY^T) = |X^T Y|_F^2, the modified RV subtracts sum_t |x_t|^2 |y_t|^2, and autocorrcorr's five sums over the
+ * pairs i < j follow from |sum_t x^_t|^2, |X^^T X^|_F^2, |X^^T Y^|_F^2 and the unit diagonals.  Column means, row norms and one
+ * [Fx + Fy] x T x [Fx + Fy] product in float64, summed over T in slabs of 64 rows in a fixed order, no atomics; a finishing kernel writes the
+ * metric to out [1] (device float32).  ws: maua_correlation_workspace() bytes of device memory, 256-byte aligned (nothing is allocated).
+ * Refused, in front of the first launch: an unknown metric, Fx != Fy for pearson / concordance / r1, Fx + Fy above 1024, T below 2 (3 for
+ * autocorrcorr), NULL arguments, a short workspace.  maua_correlation_check: host only, the same refusals. */
+enum { MAUA_CORR_PEARSON = 0, MAUA_CORR_CONCORDANCE = 1, MAUA_CORR_AUTOCORRCORR = 2, MAUA_CORR_RV = 3, MAUA_CORR_RV2 = 4, MAUA_CORR_R1 = 5 };
+long maua_correlation_workspace(int T, int Fx, int Fy);
+int maua_correlation_check(const float* x, const float* y, int T, int Fx, int Fy, int metric, const void* ws, long ws_bytes, const float* out);
+int maua_correlation(maua_ctx* ctx, const float* x, const float* y, int T, int Fx, int Fy, int metric, void* ws, long ws_bytes, float* out);
+
 /* ---- build-owned counter RNG: Philox4x32-10, identical on every device / rank and in the oracle twin (oracle/rng.py,
  * pinned to the published known-answer vectors).  No reference counterpart: the reference's random-init generator and noise planes
  * come from torch's host generator (inference/stylegan2.py:216-227, selfsupervised/noise.py:42-53); the benchmark's synthetic

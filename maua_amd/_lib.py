@@ -50,6 +50,7 @@ def lib():
                 l.maua_last_error.restype = C.c_char_p
                 l.maua_version.restype = C.c_char_p
                 _declare_flow(l)
+                _declare_video_features(l)
                 _lib = l
     return _lib
 
@@ -69,6 +70,24 @@ def _declare_flow(l):
     l.maua_farneback_level_size.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
     l.maua_farneback_check.argtypes = [p, p]
     l.maua_farneback_pair_ex.argtypes = [p, p, p]
+
+
+VFEAT_LAYOUTS = {"u8_hwc": 0, "u8_chw": 1, "f32_chw": 2}
+CORR_METRICS = {"pearson": 0, "concordance": 1, "autocorrcorr": 2, "rv": 3, "rv2": 4, "r1": 5}
+
+
+def _declare_video_features(l):
+    """csrc/video_features.hip's entry points (include/maua_hip.h: audio-reactivity instruments)."""
+    p, i, g = C.c_void_p, C.c_int, C.c_long
+    l.maua_vfeat_create.argtypes = [p, i, i, i, i, C.POINTER(p)]
+    l.maua_vfeat_destroy.argtypes = [p]
+    l.maua_vfeat_reset.argtypes = [p]
+    l.maua_vfeat_check.argtypes = [p, i, i, i, i, p, i, i, p, p, p, p]
+    l.maua_vfeat_push.argtypes = [p, p, p, i, i, i, i, p, p, p, p]
+    l.maua_correlation_workspace.argtypes = [i, i, i]
+    l.maua_correlation_workspace.restype = g
+    l.maua_correlation_check.argtypes = [p, p, i, i, i, i, p, g, p]
+    l.maua_correlation.argtypes = [p, p, p, i, i, i, i, p, g, p]
 
 
 class host_threads:

@@ -17,7 +17,12 @@ class FFMPEG(Renderer):
         self.audio_file, self.audio_offset, self.audio_duration = audio_file, audio_offset, audio_duration
         self.batch_size = batch_size
 
-    def __call__(self, synthesizer, inputs, postprocess=None, fp16=True, rank=0, world=1):
+    def __call__(self, synthesizer, inputs, postprocess=None, fp16=True, rank=0, world=1, analyzer=None):
+        """``analyzer``: a video_features.VideoAnalyzer (no reference counterpart): every batch of packed frames is pushed to it on the
+        device just before it goes to the writer, so the clip's visual features exist when the render ends; the frames are not touched."""
+        if analyzer is not None and world > 1:
+            raise NotImplementedError("FFMPEG(analyzer=...) with world > 1 is not built: absdiff's frame before a shard's first lies on "
+                                      "another rank")
         T = n_frames_of(inputs)
         lo, hi = frame_range(T, rank, world)
         W, H = synthesizer.output_size
@@ -45,5 +50,7 @@ class FFMPEG(Renderer):
                     if tuple(frames.shape[-2:]) != (H, W):
                         raise ValueError(f"postprocess returned {tuple(frames.shape[-2:])}, the writer expects {(H, W)}")
                     L.check(L.lib().maua_pack_rgb8(L.ctx(frames.device), L.ptr(frames), L.ptr(u8), b, H, W))
+                if analyzer is not None:
+                    analyzer.push(u8)
                 video.write(u8)
         return self.output_file

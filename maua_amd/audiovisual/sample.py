@@ -151,7 +151,7 @@ def generate(audio_file: str, stylegan2_checkpoint: Optional[str] = None, patch_
              audio_duration: Optional[float] = None, downscale_factor: float = 4, aspect_ratio: float = 1,
              batch_size: int = 32, device: str = "cuda", tempo: Optional[float] = None, out_dir: str = "output",
              reference_tail: bool = False, dtype=torch.bfloat16, upscale: Optional[str] = None, upscale_batch: int = 4,
-             upscale_random_init: bool = False):
+             upscale_random_init: bool = False, analyze: bool = False):
     """sample.py:36-101.  ``reference_tail=True`` reproduces the reference loop's dropped tail.
     ``tempo``: BPM for the "loop" sub-patches; None = estimated from the onset envelope like the reference (mir.py:27-30).
 
@@ -161,7 +161,16 @@ def generate(audio_file: str, stylegan2_checkpoint: Optional[str] = None, patch_
     through a video file (generate, then super/video/frame_by_frame.py:22-33).  A 4096^2 frame is 48 MiB (3600 frames: 169 GB),
     so there is NO gather in this mode: every rank encodes its own contiguous frame range into ``<stem>_partRRR.mp4`` and rank 0
     joins the parts in order (ffmpeg concat demuxer, stream copy; without ffmpeg the raw parts and the list stay) -
-    returns (joined file | list file, None)."""
+    returns (joined file | list file, None).
+
+    ``analyze=True`` (no reference counterpart) also scores the render's audio-reactivity: every batch of frames goes through a
+    video_features.VideoAnalyzer as it is rendered, and the function returns (file, frames, score table) with the table of
+    score.audiovisual_score between the clip's audio features and its video features.  Single rank, without ``upscale``."""
+    if analyze and world_info()[1] > 1:
+        raise NotImplementedError("generate(analyze=True) with world > 1 is not built: absdiff's frame before a shard's first lies on another "
+                                  "rank")
+    if analyze and upscale is not None:
+        raise NotImplementedError("generate(analyze=True) with upscale is not built: the analyser sees the rendered frames, not the up-scaled ones")
     if seed is None:
         seed = int(torch.randint(0, 2 ** 31, size=()).item())
     rank, world = world_info()
@@ -198,10 +207,16 @@ def generate(audio_file: str, stylegan2_checkpoint: Optional[str] = None, patch_
     # straight into the clip buffer)
     sg = StreamingGather(T, (rh, rw, 3), batch_size, dtype=torch.uint8, device="cuda", rank=rank, world=world)
     assert (sg.lo, sg.hi) == (lo, hi)
+    analyzer = None
+    if analyze:
+        from ..video_features import VideoAnalyzer
+        analyzer = VideoAnalyzer(rh, rw, max_batch=batch_size)
     for off, b in sg.chunks():
         i = lo + off
         nz = {f"noise{j}": m.forward(i, b)[:, None] for j, m in enumerate(noise)}
         G.synthesizer(latents=latents[i:i + b], rgb8_out=sg.local[off:off + b], **nz)
+        if analyzer is not None:
+            analyzer.push(sg.local[off:off + b])
         sg.chunk_done()
     frames = sg.finish()
     if rank == 0:
@@ -215,6 +230,11 @@ def generate(audio_file: str, stylegan2_checkpoint: Optional[str] = None, patch_
                     chunk = f.clamp(0, 255).round().byte().permute(0, 2, 3, 1).contiguous()
                 video.write(chunk)
         patch.save(out_file.replace(".mp4", ".json"))
+    if analyzer is not None:
+        from .score import audiovisual_score
+        table = audiovisual_score({k: v[:T] for k, v in features.items()}, analyzer.features())
+        analyzer.close()
+        return out_file, frames, table
     return out_file, frames
 
 
@@ -265,6 +285,7 @@ def main(argv=None):
     ap.add_argument("--upscale", default=None, help="RealESRGAN model name: render -> x4 per frame, one part file per rank (configs[4])")
     ap.add_argument("--upscale_batch", type=int, default=4)
     ap.add_argument("--upscale_random_init", action="store_true")
+    ap.add_argument("--analyze", action="store_true", help="also score the render's audio-reactivity (audiovisual/score.py)")
     a = ap.parse_args(argv)
     from ..distributed import maybe_init_process_group
     maybe_init_process_group()
