@@ -747,7 +747,7 @@ int maua_mse_guide_grad(maua_ctx* ctx, const float* img, const float* target, lo
  * Normalize, clip_model.encode_image (OpenAI CLIP VisionTransformer: un-vendored pip dependency, published architecture restated,
  * parity unpinned), spherical_dist_loss to the target embeddings (maua/loss.py:22-25), weights, mean over cutouts,
  * torch.autograd.grad(loss.sum() * scale, img) / cutout_batches }, clamp_gradient.  The gradient is evaluated on the transposed
- * network inside the library (csrc/clip.hip, cutouts.hip, gemm_dma.hip).  Target embeddings are handed in (set_targets :117-143,
+ * network inside the library (csrc/clip.hip, clip_guide.hip, transformer.hip, cutouts.hip, gemm_dma.hip).  Target embeddings are handed in (set_targets :117-143,
  * computed once, off the loop): text prompts through the text tower below (maua_clip_text_*), image (style) targets with
  * maua_clip_encode_image.  dtype: MAUA_BF16 (the reference runs the perceptor in fp16) or MAUA_F32 (exact products, parity mode).
  * Parameter names: CLIP's state-dict keys below "visual." (conv1.weight, class_embedding, positional_embedding, ln_pre.*,

@@ -5,11 +5,11 @@ Drop-in for what maua/grad.py:96-165 (``CLIPGrads``) needs of ``clip.load(name)[
 ``encode_image`` and ``encode_text``.  ``clip`` (setup.py:37, "clip @ git+https://github.com/OpenAI/CLIP") is a pip dependency that is absent from
 /root/reference and from this image: the published architecture (clip/model.py ``VisionTransformer`` / ``ResidualAttentionBlock`` /
 ``QuickGELU`` / fp32 ``LayerNorm``) is restated, **parity unpinned**; the keys are CLIP's, so the ``visual.*`` half of a released
-checkpoint loads unchanged.  The network runs behind the C ABI (``maua_clip_*``, csrc/clip.hip); ``vjp`` is the input gradient the
+checkpoint loads unchanged.  The network runs behind the C ABI (``maua_clip_*``, csrc/clip.hip on csrc/transformer.hip's residual block); ``vjp`` is the input gradient the
 library evaluates by walking the network backwards (what ``torch.autograd.grad`` gives the reference).
 
 The text tower (``CLIP.encode_text``: token embedding, causal pre-LN transformer, ``ln_final`` of the EOT row, ``text_projection``) runs
-behind ``maua_clip_text_*`` (csrc/clip.hip, causal attention in csrc/attention.hip).  Its parity is **unpinned**: neither CLIP's
+behind ``maua_clip_text_*`` (csrc/clip_text.hip, causal attention in csrc/attention.hip).  Its parity is **unpinned**: neither CLIP's
 vocabulary nor a checkpoint is available to the tests, so it is checked against a CPU restatement of CLIP's published
 ``encode_text`` (tests/), not against CLIP itself.  Text prompts may still enter as precomputed embeddings
 (``maua_amd.grad.EmbeddingPrompt``) or through a caller-supplied ``text_encoder``.

@@ -306,3 +306,41 @@ int launch_cutouts_vjp(hipStream_t stream, int dtype, const CutoutPlan& p, void*
 }
 
 }  // namespace maua
+
+using namespace maua;
+
+extern "C" {
+
+// operator-level pieces (tests, other perceptors): the cutouts and their gradient on HOST rectangles [n_cut][3]
+int maua_cutouts(maua_ctx* ctx, const float* img, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul, float add,
+                 const float* mean3, const float* std3, float* out) {
+  MAUA_REQUIRE(ctx && img && rects && out && mean3 && std3, "maua_cutouts: NULL argument");
+  const size_t tb = cutouts_table_bytes(n_cut, cut_size);
+  if (int rc = scratch_reserve(ctx, tb + (size_t)n_cut * 12 + 512)) return rc;
+  int* rd = (int*)((char*)ctx->scratch + ((tb + 255) & ~(size_t)255));
+  MAUA_HIP_CHECK(hipMemcpyAsync(rd, rects, (size_t)n_cut * 12, hipMemcpyHostToDevice, ctx->stream));
+  MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  CutoutPlan p{};
+  p.img = img; p.rects = rd; p.B = B; p.H = H; p.W = W; p.n_cut = n_cut; p.cs = cut_size; p.mul = mul; p.add = add;
+  for (int c = 0; c < 3; c++) { p.mean[c] = mean3[c]; p.std[c] = std3[c]; }
+  if (int rc = launch_cutout_tables(ctx->stream, p, ctx->scratch)) return rc;
+  return launch_cutouts_forward(ctx->stream, MAUA_F32, p, ctx->scratch, out);
+}
+
+int maua_cutouts_vjp(maua_ctx* ctx, const float* d_out, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul,
+                     const float* std3, float* d_img) {
+  MAUA_REQUIRE(ctx && d_out && rects && d_img && std3, "maua_cutouts_vjp: NULL argument");
+  const size_t tb = (cutouts_table_bytes(n_cut, cut_size) + 255) & ~(size_t)255;
+  const size_t thb = (cutouts_th_bytes(n_cut, B, cut_size, std::min(H, W)) + 255) & ~(size_t)255;
+  if (int rc = scratch_reserve(ctx, tb + thb + (size_t)n_cut * 12 + 512)) return rc;
+  int* rd = (int*)((char*)ctx->scratch + tb + thb);
+  MAUA_HIP_CHECK(hipMemcpyAsync(rd, rects, (size_t)n_cut * 12, hipMemcpyHostToDevice, ctx->stream));
+  MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  CutoutPlan p{};
+  p.img = nullptr; p.rects = rd; p.B = B; p.H = H; p.W = W; p.n_cut = n_cut; p.cs = cut_size; p.mul = mul; p.add = 0.f;
+  for (int c = 0; c < 3; c++) { p.mean[c] = 0.f; p.std[c] = std3[c]; }
+  if (int rc = launch_cutout_tables(ctx->stream, p, ctx->scratch)) return rc;
+  return launch_cutouts_vjp(ctx->stream, MAUA_F32, p, ctx->scratch, d_out, (float*)((char*)ctx->scratch + tb), d_img, 0);
+}
+
+}  // extern "C"

@@ -4,12 +4,12 @@
 // Replaces (reference): the nn.Linear / nn.MultiheadAttention projections of the CLIP image tower that maua/grad.py:96-165 (CLIPGrads)
 // evaluates and differentiates per cutout batch (clip/model.py ResidualAttentionBlock: in_proj, out_proj, mlp.c_fc, mlp.c_proj - and
 // the same four products against the transposed weights on the way back): 200 000 rows x 768 ... 3072 columns, K = 768 ... 3072,
-// 95 % of a text-guided step's FLOPs.  Callers opt in with GemmArgs.prefer_dma (clip.hip); everything else - the diffusion UNet's 1x1
+// 95 % of a text-guided step's FLOPs.  Callers opt in with GemmArgs.prefer_dma (transformer.hip's block_gemm for clip.hip); everything else - the diffusion UNet's 1x1
 // layers (K of 8-16 chunks: measured no faster here, scripts/experiments/README.md round 5 (v)), f32 parity mode, ragged shapes -
 // stays on gemm.hip's register-staged kernels.
 //
 // Epilogue forms (GemmArgs.epi), both applied to the value as stored (rounded to bf16), so that they equal the separate element-wise
-// kernels of clip.hip bit for bit (both sides evaluate quick_gelu.h's one definition):  1 = c2 <- QuickGELU(c) stored beside c (mlp.c_fc: the pre-activation is kept for the gradient,
+// kernels of transformer.hip bit for bit (both sides evaluate quick_gelu.h's one definition):  1 = c2 <- QuickGELU(c) stored beside c (mlp.c_fc: the pre-activation is kept for the gradient,
 // the activation feeds c_proj);  2 = c <- c * QuickGELU'(aux) (the gradient through the activation on the way back).
 //
 // Why a second kernel: gemm.hip stages a chunk through registers one stage ahead - 16 MFMAs per wave are shorter than an HBM round trip
@@ -58,7 +58,7 @@ __device__ __forceinline__ void mma(f32x16& acc, const u32x4& w, const u32x4& x)
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
 }
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-// QuickGELU and its derivative: quick_gelu.h's definitions at bf16's precision (__expf), as clip.hip's bf16 element-wise kernels use them
+// QuickGELU and its derivative: quick_gelu.h's definitions at bf16's precision (__expf), as transformer.hip's bf16 element-wise kernels use them
 __device__ __forceinline__ float qgelu(float x) { return quick_gelu_f(x, false); }
 __device__ __forceinline__ float qgelu_grad(float x) { return quick_gelu_grad_f(x, false); }
 

@@ -329,7 +329,7 @@ struct GemmArgs {
   long M;
   int N;
   int c_f32;
-  // gemm_dma.hip only (prefer_dma: large plain GEMMs of the CLIP image tower, clip.hip; bf16, N % 128 == 0, K % 64 == 0):
+  // gemm_dma.hip only (prefer_dma: large plain GEMMs of the CLIP image tower, clip.hip through transformer.hip; bf16, N % 128 == 0, K % 64 == 0):
   int prefer_dma;       // route to the LDS-direct kernel when the shape allows it
   int epi;              // 0; 1: c2 <- QuickGELU(c) as well; 2: c <- c * QuickGELU'(aux)
   void* c2; long ldc2;
@@ -518,11 +518,11 @@ maua_ctx* secondary_ctx(maua_secondary* n);
 // (uid, epoch) of a secondary model's device buffers: whoever caches pointers into them (a captured graph) compares both before reuse
 void secondary_stamp(maua_secondary* n, unsigned long long* uid, unsigned long long* epoch);
 
-// clip.hip: pieces the captured guided loop (sampler.hip) drives.  clip_prepare_guide allocates (never inside a capture);
+// clip_guide.hip: pieces the captured guided loop (sampler.hip) drives.  clip_prepare_guide allocates (never inside a capture);
 // clip_guide_grad = CLIPGrads.forward on DEVICE rectangles [batches][cutn][3]
 maua_ctx* clip_ctx(maua_clip* n);
 void clip_stamp(maua_clip* n, unsigned long long* uid, unsigned long long* epoch);
-// clip_prepare_guide also fixes the cutouts per pass through the tower (shape bounds and the workspace budget, see clip.hip) for
+// clip_prepare_guide also fixes the cutouts per pass through the tower (shape bounds and the workspace budget, see clip_guide.hip) for
 // the clip_guide_grad calls that follow; aug_side: side of the augmented cutouts' f32 buffers per image (0: plain cutouts)
 int clip_prepare_guide(maua_clip* n, int B, int H, int W, int cutn, int aug_side = 0);
 int clip_guide_grad(maua_clip* n, const float* img, int B, int H, int W, const int* rects_dev, const float* mult_dev, int cutn, int cutn_total,

@@ -1,5 +1,5 @@
 // QuickGELU (clip/model.py: x * sigmoid(1.702 x)) and its derivative s + 1.702 x s (1 - s), one definition for every kernel that
-// applies them: clip.hip's element-wise kernels and gemm_dma.hip's GEMM epilogues (GemmArgs.epi).  Both sides call the same inline
+// applies them: transformer.hip's element-wise kernels and gemm_dma.hip's GEMM epilogues (GemmArgs.epi).  Both sides call the same inline
 // expression, so a fused epilogue and the separate kernel give the same bits by construction.  exact: expf (f32 networks) or __expf
 // (bf16 networks).
 #pragma once

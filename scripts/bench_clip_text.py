@@ -1,4 +1,4 @@
-"""CLIP's text tower (CLIP.encode_text, csrc/clip.hip + the causal attention of csrc/attention.hip) on one GPU: device-event time of
+"""CLIP's text tower (CLIP.encode_text, csrc/clip_text.hip + the causal attention of csrc/attention.hip) on one GPU: device-event time of
 one ``TextTransformer`` forward at the ViT-B/16 text config (77 tokens, width 512, 12 layers, 8 heads), bf16, random init, for 1 / 16
 / 64 prompts after warm-up.  ``--profile``: the same run again in a child process under ``rocprofv3 --kernel-trace --stats``, and the
 causal attention kernel's share of the summed kernel time.  Not part of bench.py: the tower runs once per prompt set, off the loop.

@@ -174,7 +174,7 @@ def test_refuses_epilogues_off_the_dma_kernels():
 # ---- the callers' shape families, pinned to the kernel each takes today
 VIT_M, VIT_W = 1024 * 197, 768
 CALLERS = [
-    # CLIP ViT-B/16 image tower (clip.hip gemm(), ctx option gemm_dma = 1): forward, then the backward's transposed products
+    # CLIP ViT-B/16 image tower (transformer.hip block_gemm(), ctx option gemm_dma = 1): forward, then the backward's transposed products
     ("vit qkv", desc(VIT_M, 3 * VIT_W, VIT_W, bias=True), BF16, 1, (4, 0)),
     ("vit out_proj + residual", desc(VIT_M, VIT_W, VIT_W, bias=True, res=True), BF16, 1, (4, 0)),
     ("vit c_fc + QuickGELU", desc(VIT_M, 4 * VIT_W, VIT_W, bias=True, epi=1), BF16, 1, (4, 0)),
