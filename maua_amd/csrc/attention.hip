@@ -27,27 +27,11 @@
 // ends at min(T, its first query + 128): the blocks wholly above the diagonal are neither loaded nor multiplied.
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 namespace maua {
 
 namespace {
-
-template <typename T> struct AMma;
-template <> struct AMma<bf16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0,
-                                                  0, 0);
-  }
-};
-template <> struct AMma<float> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[2], bf[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[3], bf[3], acc, 0, 0, 0);
-  }
-};
 
 template <typename T, int D, bool CAUSAL>
 __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
@@ -127,7 +111,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
 #pragma unroll
     for (int ks = 0; ks < QS; ks++) {
       const u32x4 kf = *reinterpret_cast<const u32x4*>(k_s + r * KRS + ks * 32 + h * 16);
-      AMma<T>::step(s, kf, qf[ks]);
+      Mma<T>::step(s, kf, qf[ks]);
     }
     // lane (query r, half h): s[e] is the score of key kb + 8 (e / 4) + 4 h + e % 4
     float mx = -1.0e30f;
@@ -180,7 +164,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
           // element e of half h <-> key 8 j + 4 h + e
           vf = *reinterpret_cast<const u32x4*>(vrow + (8 * j + 4 * h) * 4);
         }
-        AMma<T>::step(o[i], vf, pf);
+        Mma<T>::step(o[i], vf, pf);
       }
     }
   }

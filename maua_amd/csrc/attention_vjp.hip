@@ -13,26 +13,11 @@
 // bf16: v_mfma_f32_32x32x16_bf16 with P / dS rounded to bf16 (as every mixed-precision attention backward does); f32: exact products.
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 namespace maua {
 
 namespace {
-
-template <typename T> struct VMma;
-template <> struct VMma<bf16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-  }
-};
-template <> struct VMma<float> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[2], bf[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[3], bf[3], acc, 0, 0, 0);
-  }
-};
 
 // delta[b][head][t] = d_out[b][t][head] . out[b][t][head].  One thread per 16-byte piece of a row (coalesced: a wave streams whole
 // rows of both tensors), the pieces of a head - D * sizeof(T) / 16 = 4 ... 16 neighbouring lanes - summed by a shuffle tree (round 6: the
@@ -198,8 +183,8 @@ __global__ __launch_bounds__(256) void attention_vjp_kernel(AttnVjpArgs a) {
     for (int ks = 0; ks < QS; ks++) {
       const u32x4 f1 = *reinterpret_cast<const u32x4*>(y1_s + r * RS + ks * 32 + h * 16);
       const u32x4 f2 = *reinterpret_cast<const u32x4*>(y2_s + r * RS + ks * 32 + h * 16);
-      VMma<T>::step(s, f1, x1f[ks]);
-      VMma<T>::step(dp, f2, x2f[ks]);
+      Mma<T>::step(s, f1, x1f[ks]);
+      Mma<T>::step(dp, f2, x2f[ks]);
     }
     // lane (own r, half h): element e belongs to walked row yb + 8 (e / 4) + 4 h + e % 4.  s becomes p, dp becomes ds.
 #pragma unroll
@@ -248,8 +233,8 @@ __global__ __launch_bounds__(256) void attention_vjp_kernel(AttnVjpArgs a) {
           t1 = *reinterpret_cast<const u32x4*>(row1 + (8 * j + 4 * h) * 4);
           if (MODE == 1) t2 = *reinterpret_cast<const u32x4*>(row2 + (8 * j + 4 * h) * 4);
         }
-        VMma<T>::step(g1[i], t1, df);                  // MODE 0: dQ^T += K^T ds^T;  MODE 1: dK^T += Q^T ds
-        if (MODE == 1) VMma<T>::step(g2[i], t2, pf);   //                            MODE 1: dV^T += dO^T p
+        Mma<T>::step(g1[i], t1, df);                  // MODE 0: dQ^T += K^T ds^T;  MODE 1: dK^T += Q^T ds
+        if (MODE == 1) Mma<T>::step(g2[i], t2, pf);   //                            MODE 1: dV^T += dO^T p
       }
     }
   }

@@ -59,19 +59,6 @@ template <> struct Fmt16<f16_t> {
   __device__ static __forceinline__ float round(float f) { return h2f((uint16_t)(pack2h(f, 0.f) & 0xffffu)); }
 };
 
-// the 32x32x16 matrix instruction of a 16-bit storage format (operands as raw 16-byte register quads)
-template <typename F> struct Mma16;
-template <> struct Mma16<bf16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-  }
-};
-template <> struct Mma16<f16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-  }
-};
-
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int kDtype = MAUA_F32;
@@ -116,24 +103,36 @@ __device__ __forceinline__ float activate(float x, int act, float alpha) {
   return x;
 }
 
-// LDS-direct load, 16 bytes per lane: lane l of the wave fetches 16 bytes from its own global address into bytes
-// [16 l, 16 l + 16) of the 1 KB LDS slot at `lds_wave_base` (wave-uniform) - no registers in flight, no ds_write.
+// LDS-direct loads: lane l of the wave fetches 16 (dma16_*, lds_dma_b128) or 4 (lds_dma_b32) bytes from its own global address
+// into bytes [16 l, 16 l + 16) of the 1 KB LDS slot (resp. [4 l, 4 l + 4) of the 256-byte slot) at the wave-uniform LDS byte
+// offset `lds_dst` - no registers in flight, no ds_write.  The source is a per-lane pointer (_v) or a wave-uniform base pointer
+// (SGPR pair) + a 32-bit per-lane byte offset (_s: one address VGPR instead of two).
 // Issued from inline assembly on purpose: with the builtin the compiler's waitcnt insertion treats later LDS reads as
 // aliasing and drains vmcnt(0) before the first of them, which also waits for every prefetch issued in between.  The
 // caller orders the data itself: the request is OLDER than register loads whose consumption (counted vmcnt retires in
-// order) precedes a barrier, and the LDS data are read only after that barrier.  M0 carries the LDS base; the kernels
-// that use this do not use M0 for anything else.
-__device__ __forceinline__ void lds_dma_b128(const void* g, void* lds_wave_base) {
-  const unsigned base =
-      __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_wave_base);
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(base) : "memory");
+// order) precedes a barrier - or is waited for with an explicit s_waitcnt vmcnt - and the LDS data are read only after
+// that barrier.  M0 carries the LDS offset and is written in the same statement that uses it; the kernels that use this
+// do not use M0 for anything else.
+__device__ __forceinline__ unsigned lds_off(const void* p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
 }
-
-// same with a wave-uniform base pointer (SGPR pair) + a 32-bit per-lane byte offset: one address VGPR instead of two
+__device__ __forceinline__ void dma16_v(const void* gptr, unsigned lds_dst) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gptr), "s"(lds_dst) : "memory");
+}
+__device__ __forceinline__ void dma16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
+               : "memory");
+}
+// the same with the slot given as a pointer into LDS (made wave-uniform here)
+__device__ __forceinline__ void lds_dma_b128(const void* g, void* lds_wave_base) {
+  dma16_v(g, __builtin_amdgcn_readfirstlane(lds_off(lds_wave_base)));
+}
 __device__ __forceinline__ void lds_dma_b128(const void* sbase, unsigned voff_bytes, void* lds_wave_base) {
-  const unsigned base =
-      __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_wave_base);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(base)
+  dma16_s(sbase, voff_bytes, __builtin_amdgcn_readfirstlane(lds_off(lds_wave_base)));
+}
+__device__ __forceinline__ void lds_dma_b32(const void* sbase, unsigned voff_bytes, void* lds_wave_base) {
+  const unsigned base = __builtin_amdgcn_readfirstlane(lds_off(lds_wave_base));
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(base)
                : "memory");
 }
 

@@ -19,27 +19,11 @@
 
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 namespace maua {
 
 namespace {
-
-template <typename T> struct GMma;
-template <> struct GMma<bf16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0,
-                                                  0, 0);
-  }
-};
-template <> struct GMma<float> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[2], bf[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[3], bf[3], acc, 0, 0, 0);
-  }
-};
 
 constexpr int GKCB = 64, GRS = GKCB + 16, GBM = 64, GBN = 128;
 
@@ -94,8 +78,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs g) {
       const u32x4 bf = *reinterpret_cast<const u32x4*>(b_s + (wave * 32 + r) * GRS + ks * 32 + h * 16);
       const u32x4 f0 = *reinterpret_cast<const u32x4*>(a_s + r * GRS + ks * 32 + h * 16);
       const u32x4 f1 = *reinterpret_cast<const u32x4*>(a_s + (32 + r) * GRS + ks * 32 + h * 16);
-      GMma<T>::step(acc[0], bf, f0);  // rows = output columns n, columns = rows m: a lane owns one m and 4-column runs
-      GMma<T>::step(acc[1], bf, f1);
+      Mma<T>::step(acc[0], bf, f0);  // rows = output columns n, columns = rows m: a lane owns one m and 4-column runs
+      Mma<T>::step(acc[1], bf, f1);
     }
   }
 #undef GEMM_LOAD
@@ -213,7 +197,7 @@ __global__ __launch_bounds__(256) void gemm_nt128_kernel(GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < 2; i++)
 #pragma unroll
-        for (int j = 0; j < 2; j++) GMma<T>::step(acc[i][j], bf[j], af[i]);   // rows = columns n, columns = rows m
+        for (int j = 0; j < 2; j++) Mma<T>::step(acc[i][j], bf[j], af[i]);   // rows = columns n, columns = rows m
     }
   }
 #undef GEMMW_LOAD

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 #include "quick_gelu.h"
 
 namespace maua {
@@ -37,14 +38,7 @@ constexpr int ABUF = DBM * DKB, BBUF = DBN * DKB, STAGE = ABUF + BBUF;   // 32 K
 constexpr int AJ = ABUF / 1024 / DNW, BJ = BBUF / 1024 / DNW;             // 4 + 2 LDS-direct instructions per wave per chunk
 constexpr int DES = DBN * 2 + 16, DPPP = DBN / 8;                          // epilogue tile row stride, 16-byte pieces per row
 
-__device__ __forceinline__ unsigned lds_off(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-__device__ __forceinline__ void dma16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory");
-}
-// the same under a wave-uniform predicate (mask = all ones or zero): with EXEC cleared the request is not issued - a branch-free
+// dma16_s (common.h) under a wave-uniform predicate (mask = all ones or zero): with EXEC cleared the request is not issued - a branch-free
 // "only if that chunk exists" inside a straight-line MFMA sequence
 __device__ __forceinline__ void dma16_s_if(const void* sbase, unsigned voff, unsigned lds_dst, int go) {
   unsigned long long saved;
@@ -53,9 +47,6 @@ __device__ __forceinline__ void dma16_s_if(const void* sbase, unsigned voff, uns
                : "=&s"(saved)
                : "v"(voff), "s"(sbase), "s"(lds_dst), "s"(go)
                : "memory", "scc");
-}
-__device__ __forceinline__ void mma(f32x16& acc, const u32x4& w, const u32x4& x) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
 }
 __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
 // QuickGELU and its derivative: quick_gelu.h's definitions at bf16's precision (__expf), as transformer.hip's bf16 element-wise kernels use them
@@ -146,8 +137,8 @@ __global__ __launch_bounds__(DNT) void gemm_dma_kernel(GemmArgs g) {
 #pragma unroll
     for (int ks = 0; ks < 3; ks++) {
       const u32x4 A0 = GD_A(0, ks, buf), A1 = GD_A(1, ks, buf), B0 = GD_B(0, ks, buf), B1 = GD_B(1, ks, buf);
-      mma(acc[0][0], B0, A0); mma(acc[0][1], B1, A0);
-      mma(acc[1][0], B0, A1); mma(acc[1][1], B1, A1);
+      Mma<bf16_t>::step(acc[0][0], B0, A0); Mma<bf16_t>::step(acc[0][1], B1, A0);
+      Mma<bf16_t>::step(acc[1][0], B0, A1); Mma<bf16_t>::step(acc[1][1], B1, A1);
     }
     {
       // the chunk's last fragments are read BEFORE the barrier that frees its buffer for chunk c + 2
@@ -156,8 +147,8 @@ __global__ __launch_bounds__(DNT) void gemm_dma_kernel(GemmArgs g) {
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();                                   // ... for everybody; everybody's reads of chunk c have returned
       if (c + 3 < n_chunks) GD_ISSUE(c + 3, buf)
-      mma(acc[0][0], B0, A0); mma(acc[0][1], B1, A0);
-      mma(acc[1][0], B0, A1); mma(acc[1][1], B1, A1);
+      Mma<bf16_t>::step(acc[0][0], B0, A0); Mma<bf16_t>::step(acc[0][1], B1, A0);
+      Mma<bf16_t>::step(acc[1][0], B0, A1); Mma<bf16_t>::step(acc[1][1], B1, A1);
     }
     buf = buf == 2 ? 0 : buf + 1;
   }
@@ -311,8 +302,8 @@ __global__ __launch_bounds__(QNT) void gemm256_kernel(GemmArgs g) {
   }
 #define GQ_MMA(F_)                                                              \
   _Pragma("unroll") for (int i = 0; i < 4; i++) {                              \
-    mma(acc[i][0], Bf[F_][0], Af[F_][i]);                                       \
-    mma(acc[i][1], Bf[F_][1], Af[F_][i]);                                       \
+    Mma<bf16_t>::step(acc[i][0], Bf[F_][0], Af[F_][i]);                         \
+    Mma<bf16_t>::step(acc[i][1], Bf[F_][1], Af[F_][i]);                         \
   }
   // the last k-step: MFMA pairs with one A piece and one W piece of chunk C2_ requested behind each (C2_ < 0: nothing to request)
 #define GQ_MMA_ISSUE(F_, C2_, BUF_)                                                                                  \
@@ -321,9 +312,9 @@ __global__ __launch_bounds__(QNT) void gemm256_kernel(GemmArgs g) {
     const char* as_ = a0 + (long)(C2_) * DKB;                                                                        \
     const char* ws_ = wp + (long)(C2_) * DKB;                                                                        \
     _Pragma("unroll") for (int i = 0; i < 4; i++) {                                                                 \
-      mma(acc[i][0], Bf[F_][0], Af[F_][i]);                                                                          \
+      Mma<bf16_t>::step(acc[i][0], Bf[F_][0], Af[F_][i]);                                                            \
       dma16_s_if(as_, aoff[i], lds0 + (BUF_) * QSTAGE + (wave + QNW * i) * 1024, go_);                               \
-      mma(acc[i][1], Bf[F_][1], Af[F_][i]);                                                                          \
+      Mma<bf16_t>::step(acc[i][1], Bf[F_][1], Af[F_][i]);                                                            \
       dma16_s_if(ws_, boff[i], lds0 + (BUF_) * QSTAGE + QABUF + (wave + QNW * i) * 1024, go_);                       \
     }                                                                                                                \
   }

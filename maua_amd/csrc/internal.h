@@ -154,11 +154,11 @@ bool upwalk_fused_supported(int dtype, int Ci, int Cm, int H, int W);
 int launch_upwalk_fused(hipStream_t stream, const HiresArgs& up, const HiresArgs& c1, int force_segs = 0, int narrow_ok = 1,
                         int dtype = MAUA_BF16);
 
-// weight preparation: f32 [Co][Ci][k][k] -> T [phases][k*k][Cop][Cip] (+ Wsq f32 [Co][Ci] = sum_k W^2)
+// modconv_prep.hip - weight preparation: f32 [Co][Ci][k][k] -> T [phases][k*k][Cop][Cip] (+ Wsq f32 [Co][Ci] = sum_k W^2)
 int launch_prep_weights(hipStream_t stream, int dtype, const float* w, void* wt, float* wsq, int Co, int Ci, int k,
                         int up, int flip, int Cop, int Cip);
 // MAUA_F32_SPLIT: a float32 weight buffer prepared by launch_prep_weights(MAUA_F32, ...) -> [hi x 8 | lo x 8] bf16 per 8 floats (one 32-byte
-// group per lane half of modconv.hip's k-step), in place; n_floats % 8 == 0
+// group per lane half of modconv.hip's k-step: mma.h), in place; n_floats % 8 == 0
 int launch_f32_split_inplace(hipStream_t stream, void* w, long n_floats);
 
 // modconv_tconv.hip: up-layer as the minimal stride-2 transposed convolution; writes the raw tensor
@@ -193,7 +193,7 @@ int launch_upfir_epilogue(hipStream_t stream, int dtype, const UpfirArgs& a);
 // walk = 0: the tile form, which recomputes them.  Same bits either way.
 bool tconv_fir_supported(int dtype, int Ci, int Co, int H, int W);
 int launch_tconv_fir(hipStream_t stream, const ConvArgs& a, const UpfirArgs& u, int dtype = MAUA_BF16, int walk = 1, int force_segs = 0);
-size_t prepped_weight_elems(int k, int up, int Cop, int Cip);
+size_t prepped_weight_elems(int k, int up, int Cop, int Cip);   // modconv_prep.hip
 
 // ---- how the launch arguments of one modulated layer are filled: synth.hip's forward and maua_modconv_ex (modconv_api.hip) both go
 // through these, so that the per-layer tests pin what the network passes to the launchers
@@ -280,7 +280,7 @@ int launch_skip_add(hipStream_t stream, const float* y, const float* prev, float
 int launch_warp_affine_nhwc(hipStream_t stream, int dtype, const void* x, void* y, const float* minv, int B, int H, int W,
                             int C);
 
-// styles / demod / toRGB pre-modulation for a list of layers in one launch
+// styles.hip: styles / demod / toRGB pre-modulation for a list of layers in one launch
 struct StyleLayer {
   const float* affine_w;  // [Cin][w_dim]
   const float* affine_b;  // [Cin]
@@ -297,11 +297,11 @@ struct StyleLayer {
 // are formed (ops.py:161-165; MAUA_F16 networks)
 int launch_styles(hipStream_t stream, const StyleLayer* layers_dev, int n_layers, const float* ws, int num_ws,
                   int w_dim, int B, int max_channels, int f16_prenorm = 0);
-// ops.py:161-165 on plain tensors: out[co] = w[co] / (max |w[co]| * sqrt(Ci kk)); s[b][0 .. Cin) /= max |s[b]|
+// ops.py:161-165 on plain tensors: out[co] = w[co] / (max |w[co]| * sqrt(Ci kk)) (modconv_prep.hip); s[b][0 .. Cin) /= max |s[b]| (styles.hip)
 int launch_f16_prenorm_weights(hipStream_t stream, const float* w, float* out, int Co, int Ci, int kk);
 int launch_f16_prenorm_styles(hipStream_t stream, float* s, int B, int Cs, int Cin);
 
-// toRGB (1x1 modconv, no demod, + bias, clamp) + FIR-upsampled skip + add -> f32 planar image
+// torgb.hip: toRGB (1x1 modconv, no demod, + bias, clamp) + FIR-upsampled skip + add -> f32 planar image
 struct RgbArgs {
   const void* x;      // NHWC [B][H][W][C] (T)
   const float* wmod;  // [B][3][C]

@@ -6,13 +6,13 @@
 //
 // Formulation (shared weights, no per-sample weight tensor):
 //   y[b,co,p] = act( d[b,co] * sum_{tap,ci} W[co,ci,tap] * (s[b,ci] * x[b,ci,p+tap]) + ns*noise[b,p] + bias[co] ) * gain
-//   d[b,co]   = rsqrt( sum_ci s[b,ci]^2 * sum_tap W[co,ci,tap]^2 + 1e-8 )          (launch_styles)
+//   d[b,co]   = rsqrt( sum_ci s[b,ci]^2 * sum_tap W[co,ci,tap]^2 + 1e-8 )          (launch_styles, styles.hip)
 // which equals the reference's per-sample-weight grouped convolution up to rounding order.
 //
 // up = 2: the reference's stride-2 transposed conv (pad 0) followed by the 4x4 FIR (pad 1, gain 4) is exactly
 // four 3x3 correlations on the input grid, one per output parity (a,b), with phase kernels
 //   Kp[a][b][ky][kx] = K[2ky+1-a][2kx+1-b],  K = full_conv2d(flip(W), 4f)   (6x6)
-// prepared once by prep_weights_kernel; the conv kernel then only differs in where it stores.
+// prepared once by prep_weights_kernel (modconv_prep.hip); the conv kernel then only differs in where it stores.
 //
 // GEMM mapping per workgroup: M = a TH x TW patch of output-grid pixels of one sample (halo tile staged once per
 // K-chunk in LDS and re-read for the 9 taps), N = BN output channels, K = 9 taps x Ci.
@@ -24,106 +24,11 @@
 
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 namespace maua {
 
 // KCB = bytes of K (input channels) per LDS row chunk (template parameter: 64 or 128); the LDS row stride is KCB + 16
-
-// An operand fragment is prepared once (Mma<T>::prep_w for the weight side, prep_x for the pixel side) and used in WM x WN steps:
-// the identity for every type but the split-f32 one.
-template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
-  using FW = u32x4;
-  using FX = u32x4;
-  __device__ static __forceinline__ FW prep_w(const u32x4& v) { return v; }
-  __device__ static __forceinline__ FX prep_x(const u32x4& v) { return v; }
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0,
-                                                  0, 0);
-  }
-  // scale 8 bf16 by 8 f32 styles, round to nearest even
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    u32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      o[k] = pack2bf(bf2f((bf16_t)(v[k] & 0xffff)) * sv[2 * k], bf2f((bf16_t)(v[k] >> 16)) * sv[2 * k + 1]);
-    return o;
-  }
-};
-template <> struct Mma<f16_t> {
-  using FW = u32x4;
-  using FX = u32x4;
-  __device__ static __forceinline__ FW prep_w(const u32x4& v) { return v; }
-  __device__ static __forceinline__ FX prep_x(const u32x4& v) { return v; }
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-  }
-  // scale 8 halves by 8 f32 styles, round to nearest even (the styles arrive pre-normalised, |s| <= 1: the product cannot overflow)
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    u32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; k++) o[k] = pack2h(Fmt16<f16_t>::lo(v[k]) * sv[2 * k], Fmt16<f16_t>::hi(v[k]) * sv[2 * k + 1]);
-    return o;
-  }
-};
-template <> struct Mma<float> {
-  using FW = u32x4;
-  using FX = u32x4;
-  __device__ static __forceinline__ FW prep_w(const u32x4& v) { return v; }
-  __device__ static __forceinline__ FX prep_x(const u32x4& v) { return v; }
-  // lane half h holds k = 8j+4h+e (e = 0..3): MFMA e consumes element e of both operands, so A and B see the
-  // same K permutation and the sum is over the same set of products.
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[2], bf[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[3], bf[3], acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    f32x4 f = __builtin_bit_cast(f32x4, v);
-    f[0] *= sv[0]; f[1] *= sv[1]; f[2] *= sv[2]; f[3] *= sv[3];
-    return __builtin_bit_cast(u32x4, f);
-  }
-};
-
-// MAUA_F32_SPLIT: float32 tensors, products on the bf16 matrix cores.  x = hi + lo, hi = bf16(x) (round to nearest even),
-// lo = bf16(x - hi) (x - hi is exact in f32).  Every aligned group of 8 floats (two 16-byte pieces: what the two lane halves of one
-// k-step hold) is kept in LDS - and, for the weights, in HBM: launch_f32_split_inplace after launch_prep_weights - as
-// [hi0 .. hi7 | lo0 .. lo7] bf16: piece 2 j = the eight hi parts, piece 2 j + 1 = the eight lo parts.  The pixel side is split ONCE
-// per element when the halo tile is staged (scale() + one exchange between the two lanes that hold a group); a k-step of the
-// convolution is then three full v_mfma_f32_32x32x16_bf16 over 16 real k:
-//     w_hi x_hi  +  w_hi x_lo  +  w_lo x_hi          (w_lo x_lo, <= 2^-16 of the product, is dropped)
-// 96 matrix-core cycles per 16 k where the exact path's eight v_mfma_f32_32x32x2_f32 take 512 (a first form with [hi x 4 | lo x 4] per
-// piece spent one of four operand slots on zeros: 128 cycles).
-__device__ __forceinline__ u32x4 f32_split4(const f32x4& f) {
-  const uint32_t h0 = pack2bf(f[0], f[1]), h1 = pack2bf(f[2], f[3]);
-  return u32x4{h0, h1, pack2bf(f[0] - __uint_as_float(h0 << 16), f[1] - __uint_as_float(h0 & 0xffff0000u)),
-               pack2bf(f[2] - __uint_as_float(h1 << 16), f[3] - __uint_as_float(h1 & 0xffff0000u))};
-}
-// {hi x 4 | lo x 4} of this lane's piece q and of lane ^ 1's piece q ^ 1 -> this lane's piece of the group format above
-__device__ __forceinline__ u32x4 f32_split_pair(const u32x4& v, int q) {
-  const bool odd = q & 1;
-  const uint32_t r0 = __shfl_xor(odd ? v[0] : v[2], 1), r1 = __shfl_xor(odd ? v[1] : v[3], 1);   // even lanes receive hi, odd lanes lo
-  return odd ? u32x4{r0, r1, v[2], v[3]} : u32x4{v[0], v[1], r0, r1};
-}
-template <> struct Mma<f32s_t> {
-  using FW = u32x4;
-  using FX = u32x4;
-  __device__ static __forceinline__ FW prep_w(const u32x4& v) { return v; }
-  __device__ static __forceinline__ FX prep_x(const u32x4& v) { return v; }
-  __device__ static __forceinline__ void step(f32x16& acc, const FW& w, const FX& x) {   // (one of the three products of a k-step)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
-  }
-  // the halo tile's 4 floats x 4 styles -> {hi x 4 | lo x 4} (the staging code then exchanges halves with the neighbouring lane)
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    f32x4 f = __builtin_bit_cast(f32x4, v);
-    f[0] *= sv[0]; f[1] *= sv[1]; f[2] *= sv[2]; f[3] *= sv[3];
-    return f32_split4(f);
-  }
-};
-template <typename T> struct IsSplit { static constexpr bool value = false; };
-template <> struct IsSplit<f32s_t> { static constexpr bool value = true; };
 
 struct ConvGeom {
   int tw_log2, th;      // tile = th x (1 << tw_log2) pixels
@@ -344,14 +249,13 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void modconv3x3_kernel(ConvA
         } else
 #pragma unroll
         for (int ks = 0; ks < KCB / 32; ks++) {
-          typename Mma<T>::FX af[WM];
-          typename Mma<T>::FW bf[WN];
+          u32x4 af[WM], bf[WN];
 #pragma unroll
-          for (int i = 0; i < WM; i++) af[i] = Mma<T>::prep_x(*reinterpret_cast<const u32x4*>(halo + offa[i] + tapoff + ks * 32));
+          for (int i = 0; i < WM; i++) af[i] = *reinterpret_cast<const u32x4*>(halo + offa[i] + tapoff + ks * 32);
 #pragma unroll
           for (int j = 0; j < WN; j++)
-            bf[j] = Mma<T>::prep_w(DMAW ? *reinterpret_cast<const u32x4*>(wtb + t * BN * KCB + offb[j] + (((h + 2 * ks) ^ swz) << 4))
-                                        : *reinterpret_cast<const u32x4*>(wtb + t * BN * RS + offb[j] + ks * 32));
+            bf[j] = DMAW ? *reinterpret_cast<const u32x4*>(wtb + t * BN * KCB + offb[j] + (((h + 2 * ks) ^ swz) << 4))
+                         : *reinterpret_cast<const u32x4*>(wtb + t * BN * RS + offb[j] + ks * 32);
 #pragma unroll
           for (int i = 0; i < WM; i++)
 #pragma unroll
@@ -712,445 +616,6 @@ int launch_modconv3x3(hipStream_t stream, int dtype, const ConvArgs& a) {
   if (dtype == MAUA_F32) return launch_modconv_t<float>(stream, a);
   if (dtype == MAUA_F32_SPLIT) return launch_modconv_t<f32s_t>(stream, a);
   return fail("modconv3x3: unsupported dtype");
-}
-
-// a prepared float32 weight buffer (launch_prep_weights, MAUA_F32) -> the split form above, in place: n floats, n % 8 == 0 (K, the
-// innermost dimension, is a multiple of 32 channels)
-__global__ __launch_bounds__(256) void f32_split_inplace_kernel(float* __restrict__ w, long n8) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n8) return;
-  const u32x4 a = f32_split4(*reinterpret_cast<const f32x4*>(w + 8 * i)), b = f32_split4(*reinterpret_cast<const f32x4*>(w + 8 * i + 4));
-  *reinterpret_cast<u32x4*>(w + 8 * i) = u32x4{a[0], a[1], b[0], b[1]};        // hi of floats 0 .. 7
-  *reinterpret_cast<u32x4*>(w + 8 * i + 4) = u32x4{a[2], a[3], b[2], b[3]};    // lo of floats 0 .. 7
-}
-int launch_f32_split_inplace(hipStream_t stream, void* w, long n) {
-  MAUA_REQUIRE(w && n >= 0 && n % 8 == 0, "f32_split_inplace: bad argument");
-  if (n == 0) return MAUA_OK;
-  hipLaunchKernelGGL(f32_split_inplace_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, stream, (float*)w, n / 8);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ weight prep
-// f32 [Co][Ci][k][k] -> T [k*k][phases][Cop][Cip] (zero padded; the phase is part of a 'virtual' output-channel
-// index n_v = phase*Cop + co, so one workgroup can produce several output parities from one input halo) and
-// Wsq[co][ci] = sum_taps W^2.
-// up == 2 (k == 3): phase kernels from K = full_conv2d(flip(W), 4f), f = outer([1,3,3,1])/64.
-template <typename T>
-__global__ __launch_bounds__(256) void prep_weights_kernel(const float* __restrict__ w, T* __restrict__ wt,
-                                                           float* __restrict__ wsq, int Co, int Ci, int k, int up,
-                                                           int flip, int Cop, int Cip) {
-  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)Cop * Cip) return;
-  int co = (int)(idx / Cip), ci = (int)(idx - (long)co * Cip);
-  const int kk = k * k;
-  float wv[9];
-  bool real = co < Co && ci < Ci;
-  float sq = 0.f;
-  for (int t = 0; t < kk; t++) {
-    wv[t] = real ? w[((long)co * Ci + ci) * kk + t] : 0.f;
-    sq += wv[t] * wv[t];
-  }
-  if (wsq && real) wsq[(long)co * Ci + ci] = sq;
-  const long plane = (long)Cop * Cip;
-  if (up == 1) {
-    for (int t = 0; t < kk; t++) Elem<T>::store(wt + (long)t * plane + idx, wv[t]);
-    return;
-  }
-  // up == 2, k == 3
-  const float g4[4] = {0.25f, 0.75f, 0.75f, 0.25f};  // 2 * [1,3,3,1]/8 per axis  (4f = outer(g4, g4))
-  float K[6][6];
-  for (int u = 0; u < 6; u++)
-    for (int v = 0; v < 6; v++) {
-      float s = 0.f;
-      for (int i = 0; i < 3; i++) {
-        int fu = u - i;
-        if (fu < 0 || fu > 3) continue;
-        for (int j = 0; j < 3; j++) {
-          int fv = v - j;
-          if (fv < 0 || fv > 3) continue;
-          // A = flip(W) in-tree (no flip before the transposed conv), A = W under nv_compat
-          float aij = flip ? wv[i * 3 + j] : wv[(2 - i) * 3 + (2 - j)];
-          s += aij * g4[fu] * g4[fv];
-        }
-      }
-      K[u][v] = s;
-    }
-  for (int pa = 0; pa < 2; pa++)
-    for (int pb = 0; pb < 2; pb++)
-      for (int ky = 0; ky < 3; ky++)
-        for (int kx = 0; kx < 3; kx++) {
-          int ph = pa * 2 + pb, t = ky * 3 + kx;
-          Elem<T>::store(wt + ((long)t * 4 + ph) * plane + idx, K[2 * ky + 1 - pa][2 * kx + 1 - pb]);
-        }
-}
-
-size_t prepped_weight_elems(int k, int up, int Cop, int Cip) { return (size_t)up * up * k * k * Cop * Cip; }
-
-int launch_prep_weights(hipStream_t stream, int dtype, const float* w, void* wt, float* wsq, int Co, int Ci, int k,
-                        int up, int flip, int Cop, int Cip) {
-  MAUA_REQUIRE(k == 1 || k == 3, "prep_weights: kernel size must be 1 or 3");
-  MAUA_REQUIRE(up == 1 || (up == 2 && k == 3), "prep_weights: up=2 needs a 3x3 kernel");
-  long n = (long)Cop * Cip;
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(prep_weights_kernel<bf16_t>, grid, dim3(256), 0, stream, w, (bf16_t*)wt, wsq, Co, Ci, k, up, flip,
-                       Cop, Cip);
-  else if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(prep_weights_kernel<f16_t>, grid, dim3(256), 0, stream, w, (f16_t*)wt, wsq, Co, Ci, k, up, flip,
-                       Cop, Cip);
-  else if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(prep_weights_kernel<float>, grid, dim3(256), 0, stream, w, (float*)wt, wsq, Co, Ci, k, up, flip,
-                       Cop, Cip);
-  else
-    return fail("prep_weights: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ styles / demod
-// Two launches per batch for ALL layers (17 conv + 9 toRGB at 1024^2): (1) s = affine(w) (stylegan2.py:48-58,:230,
-// :269), (2) demod coefficients (ops.py:168-171) / pre-modulated toRGB weights.  Both are small GEMMs
-// out[row][sample] = sum_k M[row][k] * vec[sample][k] (rows = channels, <= 32 samples per pass), done with the exact
-// f32 MFMA (v_mfma_f32_32x32x2_f32): a workgroup owns 32 matrix rows of one layer for all samples, its 4 waves split
-// K and reduce through LDS.  A sample is a column of the MFMA, so its arithmetic does not depend on where it sits in
-// the batch (frames stay bit-identical under any batching / sharding).
-//   lane (r = l & 31, h = l >> 5) feeds M[row0 + r][k8 + 4h + v] and vec[n = r][k8 + 4h + v] to MFMA number v of
-//   the 8-column block k8: one float4 load per operand per lane per block.
-template <typename VecLoad, typename Store>
-__device__ __forceinline__ void rows_times_samples(const float* __restrict__ M, int K, int row0, int rows_valid, int B,
-                                                   VecLoad vec_load, Store store, float* red /* LDS [4][16][64] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int kq = (K / 4 + 7) / 8 * 8;  // K columns per wave, a multiple of the 8-column block
-  const int k_lo = wave * kq, k_hi = min(K, k_lo + kq);
-  const bool row_ok = r < rows_valid;
-  const float* mrow = M + (long)(row0 + (row_ok ? r : 0)) * K;
-  for (int b0 = 0; b0 < B; b0 += 32) {
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; e++) acc[e] = 0.f;
-    const bool smp_ok = b0 + r < B;
-#pragma unroll 4
-    for (int k8 = k_lo; k8 < k_hi; k8 += 8) {
-      const int k = k8 + 4 * h;
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row_ok && k < K) a = *reinterpret_cast<const float4*>(mrow + k);
-      if (smp_ok && k < K) v = vec_load(b0 + r, k);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, v.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, v.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, v.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, v.w, acc, 0, 0, 0);
-    }
-    // K-split reduction, fixed order wave 0 + 1 + 2 + 3
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; e++) red[(wave * 16 + e) * 64 + lane] = acc[e];
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const float t = ((red[e * 64 + lane] + red[(16 + e) * 64 + lane]) + red[(32 + e) * 64 + lane]) + red[(48 + e) * 64 + lane];
-        const int row = (e & 3) + 8 * (e >> 2) + 4 * h;  // D layout: lane = column (sample), 16 rows per lane
-        if (row < rows_valid && smp_ok) store(b0 + r, row0 + row, t);
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void styles_affine_kernel(const StyleLayer* __restrict__ layers,
-                                                            const float* __restrict__ ws, int num_ws, int w_dim, int B) {
-  __shared__ float red[4 * 16 * 64];
-  const StyleLayer L = layers[blockIdx.x];
-  const int c0 = blockIdx.y * 32;
-  if (c0 >= L.Cs) return;
-  const float wgain = rsqrtf((float)w_dim);
-  const float* wbase = ws + (long)L.w_index * w_dim;
-  const long wstride = (long)num_ws * w_dim;
-  rows_times_samples(
-      L.affine_w, w_dim, c0, min(32, L.Cin - c0), B,
-      [&](int b, int k) { return *reinterpret_cast<const float4*>(wbase + b * wstride + k); },
-      [&](int b, int ci, float t) { L.s[(long)b * L.Cs + ci] = (t * wgain + L.affine_b[ci]) * L.scale; }, red);
-  // channel padding of the styles buffer
-  for (int i = threadIdx.x; i < B * 32; i += blockDim.x) {
-    const int b = i >> 5, ci = c0 + (i & 31);
-    if (ci >= L.Cin && ci < L.Cs) L.s[(long)b * L.Cs + ci] = 0.f;
-  }
-}
-
-__global__ __launch_bounds__(256) void styles_demod_kernel(const StyleLayer* __restrict__ layers, int B) {
-  __shared__ float red[4 * 16 * 64];
-  const StyleLayer L = layers[blockIdx.x];
-  if (L.d) {
-    const int c0 = blockIdx.y * 32;
-    if (c0 >= L.Cd) return;
-    rows_times_samples(
-        L.wsq, L.Cin, c0, min(32, L.Co - c0), B,
-        [&](int b, int k) {
-          const float4 v = *reinterpret_cast<const float4*>(L.s + (long)b * L.Cs + k);
-          return make_float4(v.x * v.x, v.y * v.y, v.z * v.z, v.w * v.w);
-        },
-        [&](int b, int co, float t) { L.d[(long)b * L.Cd + co] = rsqrtf(t + 1e-8f); }, red);
-    for (int i = threadIdx.x; i < B * 32; i += blockDim.x) {
-      const int b = i >> 5, co = c0 + (i & 31);
-      if (co >= L.Co && co < L.Cd) L.d[(long)b * L.Cd + co] = 0.f;
-    }
-  } else if (L.wmod) {
-    const int n = B * 3 * L.Cin;
-    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
-      const int b = i / (3 * L.Cin), r = i - b * 3 * L.Cin;
-      L.wmod[i] = L.wrgb[r] * L.s[(long)b * L.Cs + (r % L.Cin)];
-    }
-  }
-}
-
-// ---- ops.py:161-165, the FP16 pre-normalisation of a demodulated convolution ("Pre-normalize inputs to avoid FP16 overflow"):
-//   weight = weight / (amax |weight| over (ci, ky, kx) per output channel * sqrt(Ci k k));  styles = styles / amax |styles| per sample
-// Demodulation makes the layer's output invariant to both factors (up to its 1e-8); what they buy is range: with |s| <= 1 the
-// modulated activation x * s, which this library rounds to the network dtype, cannot leave the half range when x did not.
-// One workgroup per output channel
-__global__ __launch_bounds__(256) void f16_prenorm_weights_kernel(const float* __restrict__ w, float* __restrict__ out, int row,
-                                                                  float rsqrt_fan) {
-  __shared__ float red[4];
-  const float* src = w + (long)blockIdx.x * row;
-  float m = 0.f;
-  for (int i = threadIdx.x; i < row; i += 256) m = fmaxf(m, fabsf(src[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float k = rsqrt_fan / m;   // (an all-zero channel divides by zero, as the reference does)
-  for (int i = threadIdx.x; i < row; i += 256) out[(long)blockIdx.x * row + i] = src[i] * k;
-}
-int launch_f16_prenorm_weights(hipStream_t stream, const float* w, float* out, int Co, int Ci, int kk) {
-  if (Co == 0) return MAUA_OK;
-  hipLaunchKernelGGL(f16_prenorm_weights_kernel, dim3(Co), dim3(256), 0, stream, w, out, Ci * kk, 1.f / sqrtf((float)(Ci * kk)));
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-// one wave per (layer, sample): s[b][0 .. Cin) /= max |s[b][.]|, for the layers that demodulate (L.d != NULL)
-__global__ __launch_bounds__(64) void f16_prenorm_styles_kernel(const StyleLayer* __restrict__ layers, int B) {
-  const StyleLayer L = layers[blockIdx.x];
-  if (!L.d) return;
-  float* sp = L.s + (long)blockIdx.y * L.Cs;
-  float m = 0.f;
-  for (int i = threadIdx.x; i < L.Cin; i += 64) m = fmaxf(m, fabsf(sp[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  for (int i = threadIdx.x; i < L.Cin; i += 64) sp[i] = sp[i] / m;
-}
-// the same for one plain styles tensor [B][Cs] (operator-level entry point)
-__global__ __launch_bounds__(64) void f16_prenorm_styles_plain_kernel(float* __restrict__ s, int Cs, int Cin) {
-  float* sp = s + (long)blockIdx.x * Cs;
-  float m = 0.f;
-  for (int i = threadIdx.x; i < Cin; i += 64) m = fmaxf(m, fabsf(sp[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  for (int i = threadIdx.x; i < Cin; i += 64) sp[i] = sp[i] / m;
-}
-int launch_f16_prenorm_styles(hipStream_t stream, float* s, int B, int Cs, int Cin) {
-  if (B == 0) return MAUA_OK;
-  hipLaunchKernelGGL(f16_prenorm_styles_plain_kernel, dim3(B), dim3(64), 0, stream, s, Cs, Cin);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-int launch_styles(hipStream_t stream, const StyleLayer* layers_dev, int n_layers, const float* ws, int num_ws,
-                  int w_dim, int B, int max_channels, int f16_prenorm) {
-  if (B == 0 || n_layers == 0) return MAUA_OK;
-  MAUA_REQUIRE(w_dim % 4 == 0 && max_channels % 4 == 0, "styles: w_dim and channel counts must be multiples of 4");
-  const int ny = cdiv(std::max(max_channels, 32), 32);
-  hipLaunchKernelGGL(styles_affine_kernel, dim3(n_layers, ny), dim3(256), 0, stream, layers_dev, ws, num_ws, w_dim, B);
-  if (f16_prenorm) hipLaunchKernelGGL(f16_prenorm_styles_kernel, dim3(n_layers, B), dim3(64), 0, stream, layers_dev, B);
-  hipLaunchKernelGGL(styles_demod_kernel, dim3(n_layers, ny), dim3(256), 0, stream, layers_dev, B);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ toRGB + skip
-// stylegan2.py:268-272 (1x1 modulated conv without demodulation, bias, clamp) fused with SynthesisBlock's
-// img = upsample2d(img) + y (stylegan2.py:372-378; ops.py:117-133).  HBM-bound: x is read once in 16-byte
-// pieces, LP lanes cooperate on one pixel and reduce with wave shuffles.
-// bias + clamp of one pixel's RGB, the FIR-upsampled skip of the previous image, planar f32 store
-__device__ __forceinline__ void torgb_finish(const RgbArgs& a, int b, long p, float r0, float r1, float r2) {
-  const long HW = (long)a.H * a.W;
-  const int Hp = a.H >> 1, Wp = a.W >> 1;
-  int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
-  float o3[3] = {r0 + a.bias[0], r1 + a.bias[1], r2 + a.bias[2]};
-#pragma unroll
-  for (int c = 0; c < 3; c++)
-    if (a.clamp >= 0.f) o3[c] = fminf(fmaxf(o3[c], -a.clamp), a.clamp);
-  if (a.prev) {
-    // upsample2d: zero-insert x2, pad (2,1,2,1), correlate with 4f
-    const float* pv = a.prev + (long)b * 3 * Hp * Wp;
-    // upsample2d (zero-insert x2, pad (2,1,2,1), 4x4 FIR) in its branch-free 2x2 form: only the taps whose
-    // parity hits a real sample are non-zero -> rows {iy0, iy0+1}, cols {ix0, ix0+1}, filter index
-    // u = 2*iy - y + 2 (same products, same u-major order as the 16-tap correlation)
-    const int iy0 = (y - 1) >> 1, ix0 = (x - 1) >> 1;
-    float u3[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dy = 0; dy < 2; dy++) {
-      const int iy = iy0 + dy, u = 2 * iy - y + 2;
-      const bool oky = iy >= 0 && iy < Hp;
-#pragma unroll
-      for (int dx = 0; dx < 2; dx++) {
-        const int ix = ix0 + dx, v = 2 * ix - x + 2;
-        const bool ok = oky && ix >= 0 && ix < Wp;
-        const bool uh = u == 1 || u == 2, vh = v == 1 || v == 2;  // fir[u][v] takes 3 distinct values
-        const float f = !ok ? 0.f : uh ? (vh ? a.fir[5] : a.fir[4]) : (vh ? a.fir[1] : a.fir[0]);
-        const long o = ok ? (long)iy * Wp + ix : 0;
-        u3[0] += pv[o] * f;
-        u3[1] += pv[(long)Hp * Wp + o] * f;
-        u3[2] += pv[2L * Hp * Wp + o] * f;
-      }
-    }
-    o3[0] = u3[0] + o3[0]; o3[1] = u3[1] + o3[1]; o3[2] = u3[2] + o3[2];
-  }
-  float* ob = a.out + (long)b * 3 * HW + p;
-  ob[0] = o3[0]; ob[HW] = o3[1]; ob[2 * HW] = o3[2];
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void torgb_kernel(RgbArgs a, int lp_log2) {
-  constexpr int EPC = 16 / (int)sizeof(T);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* wm = reinterpret_cast<float*>(smem);  // [3][C]
-  const int b = blockIdx.y;
-  for (int i = threadIdx.x; i < 3 * a.C; i += blockDim.x) wm[i] = a.wmod[(long)b * 3 * a.C + i];
-  __syncthreads();
-  const int LP = 1 << lp_log2;
-  const int sub = threadIdx.x & (LP - 1);
-  const int ppb = blockDim.x >> lp_log2;  // pixels per block-iteration
-  const long HW = (long)a.H * a.W;
-  const T* xb = reinterpret_cast<const T*>(a.x) + (long)b * HW * a.C;
-  const int pieces = a.C / EPC;
-  const int Hp = a.H >> 1, Wp = a.W >> 1;
-  for (long p = (long)blockIdx.x * ppb + (threadIdx.x >> lp_log2); p < HW; p += (long)gridDim.x * ppb) {
-    float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-    for (int pc = sub; pc < pieces; pc += LP) {
-      uint4 v = *reinterpret_cast<const uint4*>(xb + p * a.C + pc * EPC);
-      float xv[EPC];
-      if constexpr (sizeof(T) == 2) {
-        xv[0] = Fmt16<T>::lo(v.x); xv[1] = Fmt16<T>::hi(v.x);
-        xv[2] = Fmt16<T>::lo(v.y); xv[3] = Fmt16<T>::hi(v.y);
-        xv[4] = Fmt16<T>::lo(v.z); xv[5] = Fmt16<T>::hi(v.z);
-        xv[6] = Fmt16<T>::lo(v.w); xv[7] = Fmt16<T>::hi(v.w);
-      } else {
-        xv[0] = __uint_as_float(v.x); xv[1] = __uint_as_float(v.y);
-        xv[2] = __uint_as_float(v.z); xv[3] = __uint_as_float(v.w);
-      }
-      // the lane's EPC weights of each row as 16-byte LDS reads (scalar reads at a 32-byte lane stride conflicted: lds_conf 0.65)
-      float wv[3][EPC];
-#pragma unroll
-      for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int q4 = 0; q4 < EPC / 4; q4++) {
-          const f32x4 t = *reinterpret_cast<const f32x4*>(wm + c * a.C + pc * EPC + q4 * 4);
-          wv[c][q4 * 4] = t[0]; wv[c][q4 * 4 + 1] = t[1]; wv[c][q4 * 4 + 2] = t[2]; wv[c][q4 * 4 + 3] = t[3];
-        }
-#pragma unroll
-      for (int e = 0; e < EPC; e++) {
-        r0 += xv[e] * wv[0][e];
-        r1 += xv[e] * wv[1][e];
-        r2 += xv[e] * wv[2][e];
-      }
-    }
-    for (int o = LP >> 1; o > 0; o >>= 1) {
-      r0 += __shfl_xor(r0, o);
-      r1 += __shfl_xor(r1, o);
-      r2 += __shfl_xor(r2, o);
-    }
-    if (sub == 0) torgb_finish(a, b, p, r0, r1, r2);
-  }
-}
-
-// bf16 inputs: the 1x1 convolution itself on the matrix cores.  out[3][px] = Wmod[3][C] x X^T[C][px] per 32 pixels:
-// A = pre-modulated weights split into bf16 hi (rows 0..2) + lo remainder (rows 8..10; w = hi + lo to ~2^-17, the
-// same trick as the fused toRGB of modconv_hires.hip), resident in registers; B = the pixels' channel pieces, loaded
-// straight from HBM in the MFMA operand layout (lane = pixel, 16 bytes = 8 channels) — no LDS, no cross-lane
-// reduction, ~1 VALU op per 16 bytes instead of 24 FMAs + shuffles.
-template <int NF>
-__global__ __launch_bounds__(256) void torgb_mfma_kernel(RgbArgs a) {
-  constexpr int C = NF * 16;
-  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-  const int b = blockIdx.y;
-  u32x4 wf[NF];
-  {
-    const int c_rgb = r < 3 ? r : (r >= 8 && r < 11 ? r - 8 : -1);
-#pragma unroll
-    for (int ks = 0; ks < NF; ks++) {
-      u32x4 o = u32x4{0u, 0u, 0u, 0u};
-      if (c_rgb >= 0) {
-        const float* src = a.wmod + ((long)b * 3 + c_rgb) * C + ks * 16 + 8 * h;
-        const float4 s0 = *reinterpret_cast<const float4*>(src), s1 = *reinterpret_cast<const float4*>(src + 4);
-        const float sv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          float w0 = sv[2 * k], w1 = sv[2 * k + 1];
-          const float h0 = bf2f(f2bf(w0)), h1 = bf2f(f2bf(w1));
-          if (r >= 8) { w0 -= h0; w1 -= h1; }
-          o[k] = pack2bf(w0, w1);
-        }
-      }
-      wf[ks] = o;
-    }
-  }
-  const long HW = (long)a.H * a.W;
-  const bf16_t* xb = reinterpret_cast<const bf16_t*>(a.x) + (long)b * HW * C;
-  const long n_groups = (HW + 31) / 32;
-  for (long gi = (long)blockIdx.x * 4 + (threadIdx.x >> 6); gi < n_groups; gi += (long)gridDim.x * 4) {
-    const long p = gi * 32 + r;
-    const bf16_t* px = xb + (p < HW ? p : HW - 1) * C + 8 * h;
-    u32x4 xv[NF];
-#pragma unroll
-    for (int ks = 0; ks < NF; ks++) xv[ks] = *reinterpret_cast<const u32x4*>(px + ks * 16);
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; e++) acc[e] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < NF; ks++)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[ks]), __builtin_bit_cast(bf16x8, xv[ks]),
-                                                    acc, 0, 0, 0);
-    // D rows 0..2 (hi) and 8..10 (lo) of pixel r live in the h == 0 lane: acc[0..2] and acc[4..6]
-    if (h == 0 && p < HW) torgb_finish(a, b, p, acc[0] + acc[4], acc[1] + acc[5], acc[2] + acc[6]);
-  }
-}
-
-int launch_torgb(hipStream_t stream, int dtype, const RgbArgs& a) {
-  if (a.B == 0) return MAUA_OK;
-  const int epc = dtype == MAUA_F32 ? 4 : 8;
-  MAUA_REQUIRE(a.C % epc == 0, "torgb: C must be a multiple of the 16-byte piece");
-  // (C = 512 layers are <= 64^2: the fragment set-up of 32 k-steps costs more than it saves there)
-  if (dtype == MAUA_BF16 && (a.C == 32 || a.C == 64 || a.C == 128 || a.C == 256) && ((uintptr_t)a.wmod % 16) == 0) {
-    const long groups = ((long)a.H * a.W + 31) / 32;
-    const dim3 grid((unsigned)std::min<long>((groups + 3) / 4, 1024), a.B);
-    switch (a.C / 16) {
-      case 2: hipLaunchKernelGGL(torgb_mfma_kernel<2>, grid, dim3(256), 0, stream, a); break;
-      case 4: hipLaunchKernelGGL(torgb_mfma_kernel<4>, grid, dim3(256), 0, stream, a); break;
-      case 8: hipLaunchKernelGGL(torgb_mfma_kernel<8>, grid, dim3(256), 0, stream, a); break;
-      default: hipLaunchKernelGGL(torgb_mfma_kernel<16>, grid, dim3(256), 0, stream, a); break;
-    }
-    MAUA_HIP_CHECK(hipGetLastError());
-    return MAUA_OK;
-  }
-  int pieces = a.C / epc;
-  int lp_log2 = 0;
-  while ((1 << (lp_log2 + 1)) <= pieces && lp_log2 < 4) lp_log2++;
-  long HW = (long)a.H * a.W;
-  int ppb = 256 >> lp_log2;
-  int gx = (int)std::min<long>((HW + ppb - 1) / ppb, 2048);
-  size_t smem = (size_t)3 * a.C * sizeof(float);
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(torgb_kernel<bf16_t>, dim3(gx, a.B), dim3(256), smem, stream, a, lp_log2);
-  else if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(torgb_kernel<f16_t>, dim3(gx, a.B), dim3(256), smem, stream, a, lp_log2);
-  else if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(torgb_kernel<float>, dim3(gx, a.B), dim3(256), smem, stream, a, lp_log2);
-  else
-    return fail("torgb: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
 }
 
 }  // namespace maua

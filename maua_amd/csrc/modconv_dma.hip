@@ -23,6 +23,7 @@
 // rows are zeroed once before the loop.  Layout of the 149 KB (BN = 256): W[0] | W[1] | H[0] | H[1]; the epilogue tile reuses it.
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 // K-loop schedule experiments (bit mask; results do not depend on it - scripts/experiments/README.md, round 5):
 //   1  static priority for the second-dispatched half of the workgroup (waves >= NW / 2: the younger wave of every SIMD)
@@ -39,23 +40,6 @@ namespace {
 constexpr int TH = 8, TW = 32, HW2 = TW + 2, HALO_PX = (TH + 2) * HW2;  // 8 x 32 output pixels, 10 x 34 halo
 // K bytes per LDS row (KB, template parameter): 128 (64 bf16 channels; one workgroup per CU) or 64 (32 channels: half
 // the halo, two workgroups per CU - the short-K layers, whose per-tile prologue / epilogue otherwise idles the CU)
-
-__device__ __forceinline__ unsigned lds_off(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-// LDS-direct loads; lds_dst must be wave-uniform (SGPR).  M0 is written in the same statement that uses it.
-__device__ __forceinline__ void dma16_v(const void* gptr, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gptr), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory");
-}
-
-template <typename F>
-__device__ __forceinline__ void mma(f32x16& acc, const u32x4& a, const u32x4& b) {
-  Mma16<F>::step(acc, a, b);
-}
 
 }  // namespace
 
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, KB == 64 ? 4 : 2) void modco
   }
 #define MAUA_MMA(AF_, BF_)                                                                               \
   _Pragma("unroll") for (int i = 0; i < WM; i++) _Pragma("unroll") for (int j = 0; j < WN; j++)         \
-      mma<F>(acc[i][j], BF_[j], AF_[i]);  /* rows = channels, columns = pixels */
+      Mma<F>::step(acc[i][j], BF_[j], AF_[i]);  /* rows = channels, columns = pixels */
 
   f32x16 acc[WM][WN];
 #pragma unroll
@@ -452,7 +436,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, KB == 64 ? 4 : 2) void modco
 #pragma unroll
       for (int k = 0; k < 4; k++) wf[k] = Fmt16<F>::pack2(wv[2 * k], wv[2 * k + 1]);
       const u32x4 av = *reinterpret_cast<const u32x4*>(epi + mrow * ES + (ks * 16 + 8 * h) * 2);
-      Mma16<F>::step(racc, wf, av);
+      Mma<F>::step(racc, wf, av);
     }
     if (px_ok) {
       float o3[3] = {racc[0] + racc[4] + rb0, racc[1] + racc[5] + rb1, racc[2] + racc[6] + rb2};

@@ -14,6 +14,7 @@
 // (stylegan2.py:372-378) on the epilogue tile while it is still in LDS: the 1x1 conv then never re-reads x from HBM.
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 namespace maua {
 
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(256, CI == 64 ? 2 : 3) void modconv_hires_kernel(Hi
 #pragma unroll
           for (int i = 0; i < PAIR; i++) {
             const u32x4 av = *reinterpret_cast<const u32x4*>(ap + i * HW2 * RSH);
-            Mma16<F>::step(acc[i], wv, av);
+            Mma<F>::step(acc[i], wv, av);
           }
         }
       }
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(256, CI == 64 ? 2 : 3) void modconv_hires_kernel(Hi
 #pragma unroll
           for (int ks = 0; ks < CO / 16; ks++) {
             const u32x4 av = *reinterpret_cast<const u32x4*>(epi + (row_m * 32 + r) * ES + (ks * 16 + 8 * h) * 2);
-            Mma16<F>::step(racc, rf_s[ks * 64 + lane], av);
+            Mma<F>::step(racc, rf_s[ks * 64 + lane], av);
           }
           if (rw == 0 || h == rw) { o3[0] = racc[0] + racc[4]; o3[1] = racc[1] + racc[5]; o3[2] = racc[2] + racc[6]; }
         }

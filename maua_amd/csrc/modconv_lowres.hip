@@ -17,40 +17,11 @@
 //                         the NHWC store with the parity decode of the up-layers.
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 namespace maua {
 
 namespace {
-
-template <typename T> struct LMma;
-template <> struct LMma<bf16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0,
-                                                  0, 0);
-  }
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    u32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      o[k] = pack2bf(bf2f((bf16_t)(v[k] & 0xffff)) * sv[2 * k], bf2f((bf16_t)(v[k] >> 16)) * sv[2 * k + 1]);
-    return o;
-  }
-};
-template <> struct LMma<float> {
-  // lane half h holds k = 8j+4h+e (e = 0..3): MFMA e consumes element e of both operands (same K permutation for A, B)
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& a, const u32x4& b) {
-    f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0], bf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1], bf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[2], bf[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[3], bf[3], acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    f32x4 f = __builtin_bit_cast(f32x4, v);
-    f[0] *= sv[0]; f[1] *= sv[1]; f[2] *= sv[2]; f[3] *= sv[3];
-    return __builtin_bit_cast(u32x4, f);
-  }
-};
 
 constexpr int LKCB = 128, LRS = LKCB + 16;  // bytes of K per stage and LDS row stride (conflict-free ds_read_b128)
 constexpr int LBM = 64, LBN = 128;
@@ -75,7 +46,7 @@ __global__ __launch_bounds__(256) void lowres_premod_kernel(const T* __restrict_
 #pragma unroll
   for (int e = 0; e < EPC; e++) sv[e] = s[(long)b * Ci + pc * EPC + e];
   const u32x4 v = *reinterpret_cast<const u32x4*>(x + (long)b * x_bstride + (long)p * Ci + pc * EPC);
-  *reinterpret_cast<u32x4*>(xm + bp * Ci + pc * EPC) = LMma<T>::scale(v, sv);
+  *reinterpret_cast<u32x4*>(xm + bp * Ci + pc * EPC) = Mma<T>::scale(v, sv);
 }
 
 // ---- 2. one K slice of a 64 x 128 tile
@@ -140,8 +111,8 @@ __global__ __launch_bounds__(256) void lowres_conv_kernel(const T* __restrict__ 
       const u32x4 bf = *reinterpret_cast<const u32x4*>(b_s + (wave * 32 + r) * LRS + ks * 32 + h * 16);
       const u32x4 a0 = *reinterpret_cast<const u32x4*>(a_s + r * LRS + ks * 32 + h * 16);
       const u32x4 a1 = *reinterpret_cast<const u32x4*>(a_s + (32 + r) * LRS + ks * 32 + h * 16);
-      LMma<T>::step(acc[0], bf, a0);  // rows = channels, cols = pixels: a lane owns one pixel and 4-channel runs
-      LMma<T>::step(acc[1], bf, a1);
+      Mma<T>::step(acc[0], bf, a0);  // rows = channels, cols = pixels: a lane owns one pixel and 4-channel runs
+      Mma<T>::step(acc[1], bf, a1);
     }
   }
 #undef LOWRES_LOAD

@@ -12,50 +12,12 @@
 // power-of-two tiles on H x W.
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
+#include "modconv_tconv.h"
 
 namespace maua {
 
 constexpr int TKCB = 64, TRS = TKCB + 16, TPR = TKCB / 16;  // K chunk bytes, LDS row stride, pieces per row
-
-template <typename T> struct TMma;
-template <> struct TMma<bf16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& w, const u32x4& x) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0,
-                                                  0, 0);
-  }
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    u32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      o[k] = pack2bf(bf2f((bf16_t)(v[k] & 0xffff)) * sv[2 * k], bf2f((bf16_t)(v[k] >> 16)) * sv[2 * k + 1]);
-    return o;
-  }
-};
-template <> struct TMma<f16_t> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& w, const u32x4& x) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    u32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; k++) o[k] = pack2h(Fmt16<f16_t>::lo(v[k]) * sv[2 * k], Fmt16<f16_t>::hi(v[k]) * sv[2 * k + 1]);
-    return o;
-  }
-};
-template <> struct TMma<float> {
-  __device__ static __forceinline__ void step(f32x16& acc, const u32x4& w, const u32x4& x) {
-    f32x4 wf = __builtin_bit_cast(f32x4, w), xf = __builtin_bit_cast(f32x4, x);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[0], xf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[1], xf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[2], xf[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[3], xf[3], acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ u32x4 scale(const u32x4& v, const float* sv) {
-    f32x4 f = __builtin_bit_cast(f32x4, v);
-    f[0] *= sv[0]; f[1] *= sv[1]; f[2] *= sv[2]; f[3] *= sv[3];
-    return __builtin_bit_cast(u32x4, f);
-  }
-};
 
 struct TconvGeom {
   int tw_log2, th, tiles_x, hw1, halo_px;
@@ -67,10 +29,6 @@ struct TconvRegions {
   TconvGeom r[3];        // main H x W block, last column (n = W), last row (m = H)
   int halo_max;          // LDS carve: max halo_px over the regions
 };
-
-// weight block k of a stage: (shift slot, class).  slot s: (p,q) = (1,1), (1,0), (0,1), (0,0); class = 2a' + b'.
-__device__ __constant__ const int kTconvSlot[9] = {0, 1, 1, 2, 2, 3, 3, 3, 3};
-__device__ __constant__ const int kTconvCls[9] = {0, 0, 1, 0, 2, 0, 1, 2, 3};
 
 template <typename T>
 __global__ __launch_bounds__(512, 4) void tconv2_kernel(ConvArgs a, TconvRegions regs) {
@@ -105,9 +63,8 @@ __global__ __launch_bounds__(512, 4) void tconv2_kernel(ConvArgs a, TconvRegions
   const int m = wave * 32 + r;
   const int pty = m >> g.tw_log2, ptx = m & (tw - 1);
   const int offa = ((pty + 1) * g.hw1 + (ptx + 1)) * TRS + h * 16;
-  // B fragments: the 16-byte piece p of weight row n sits at piece p ^ ((n >> 2) & 3) - with 64-byte rows this
-  // XOR makes a quarter-wave's ds_read_b128 hit 16 distinct bank groups (the padding trick needs a non-linear fill)
-  const int swz = (r >> 2) & 3;
+  // B fragments: the 16-byte piece p of weight row n sits at piece p ^ tconv_swz(n)
+  const int swz = tconv_swz(r);
   const int offb0 = r * WROW + ((h ^ swz) << 4), offb1 = r * WROW + (((h ^ swz) ^ 2) << 4);
 
   f32x16 acc[4];
@@ -132,14 +89,14 @@ __global__ __launch_bounds__(512, 4) void tconv2_kernel(ConvArgs a, TconvRegions
   u32x4 hreg[HREGS];
   float sv[EPC];
   // weights travel global -> LDS directly: instruction ii (0..17) fills the 1 KB slot of rows 16 ii .. 16 ii + 15, lane
-  // l supplies row 16 ii + (l >> 2), LDS piece l & 3 = logical piece (l & 3) ^ ((row >> 2) & 3); wave w issues ii = w + 8 j
+  // l supplies row 16 ii + (l >> 2), LDS piece l & 3 = logical piece (l & 3) ^ tconv_swz(row); wave w issues ii = w + 8 j
   int woff[WDMA];
 #pragma unroll
   for (int j = 0; j < WDMA; j++) {
     const int ii = wave + 8 * j;
     const int row = std::min(16 * ii + (lane >> 2), 9 * 32 - 1);
     const int k = row >> 5, n = row & 31;
-    const int piece = (lane & 3) ^ ((row >> 2) & 3);
+    const int piece = (lane & 3) ^ tconv_swz(row);
     woff[j] = (((kTconvSlot[k] * CB + cb) * 4 + kTconvCls[k]) * 32 + n) * a.Ci + piece * EPC;
   }
 #define TC_DMA_W(C0, BUF)                                                                                \
@@ -170,7 +127,7 @@ __global__ __launch_bounds__(512, 4) void tconv2_kernel(ConvArgs a, TconvRegions
 #pragma unroll
     for (int i = 0; i < HREGS; i++) {
       const int p = rq + i * (NT / TPR);
-      if (p < g.halo_px) *reinterpret_cast<u32x4*>(halo + p * TRS + q * 16) = TMma<T>::scale(hreg[i], sv);
+      if (p < g.halo_px) *reinterpret_cast<u32x4*>(halo + p * TRS + q * 16) = Mma<T>::scale(hreg[i], sv);
     }
     __syncthreads();
     if (c + 1 < n_chunks) {
@@ -185,24 +142,24 @@ __global__ __launch_bounds__(512, 4) void tconv2_kernel(ConvArgs a, TconvRegions
 #define TC_B(K) (*reinterpret_cast<const u32x4*>(wtb + (K) * 32 * WROW + (ks == 0 ? offb0 : offb1)))
       {
         const u32x4 a0 = TC_A(-g.hw1 - 1);
-        TMma<T>::step(acc[0], TC_B(0), a0);
+        Mma<T>::step(acc[0], TC_B(0), a0);
       }
       {
         const u32x4 a1 = TC_A(-g.hw1);
-        TMma<T>::step(acc[1], TC_B(2), a1);
-        TMma<T>::step(acc[0], TC_B(1), a1);
+        Mma<T>::step(acc[1], TC_B(2), a1);
+        Mma<T>::step(acc[0], TC_B(1), a1);
       }
       {
         const u32x4 a2 = TC_A(-1);
-        TMma<T>::step(acc[2], TC_B(4), a2);
-        TMma<T>::step(acc[0], TC_B(3), a2);
+        Mma<T>::step(acc[2], TC_B(4), a2);
+        Mma<T>::step(acc[0], TC_B(3), a2);
       }
       {
         const u32x4 a3 = TC_A(0);
-        TMma<T>::step(acc[3], TC_B(8), a3);
-        TMma<T>::step(acc[1], TC_B(6), a3);
-        TMma<T>::step(acc[2], TC_B(7), a3);
-        TMma<T>::step(acc[0], TC_B(5), a3);
+        Mma<T>::step(acc[3], TC_B(8), a3);
+        Mma<T>::step(acc[1], TC_B(6), a3);
+        Mma<T>::step(acc[2], TC_B(7), a3);
+        Mma<T>::step(acc[0], TC_B(5), a3);
       }
 #undef TC_A
 #undef TC_B

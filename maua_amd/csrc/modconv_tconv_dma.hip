@@ -16,6 +16,8 @@
 //   * 4 waves / 75 KB of LDS per workgroup: two workgroups per CU run out of phase.
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
+#include "modconv_tconv.h"
 
 namespace maua {
 
@@ -31,22 +33,6 @@ constexpr int OFF_H = 2 * WBUF;
 constexpr int NW = 4, NT = NW * 64;
 constexpr int WJ = (WBUF / 1024 + NW - 1) / NW;    // 5 weight instructions per wave per chunk (18 in all)
 constexpr int HJ = (HPX * 4 + NT - 1) / NT;        // 5 halo instructions per wave per chunk (1188 pieces)
-
-__device__ __constant__ const int kSlot[9] = {0, 1, 1, 2, 2, 3, 3, 3, 3};  // as modconv_tconv.hip
-__device__ __constant__ const int kCls[9] = {0, 0, 1, 0, 2, 0, 1, 2, 3};
-
-__device__ __forceinline__ unsigned lds_off(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-__device__ __forceinline__ void dma16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory");
-}
-template <typename F>
-__device__ __forceinline__ void mma(f32x16& acc, const u32x4& w, const u32x4& x) {
-  Mma16<F>::step(acc, w, x);
-}
-__device__ __forceinline__ int swz(int n) { return (n >> 2) & 3; }
 
 }  // namespace
 
@@ -79,7 +65,7 @@ __global__ __launch_bounds__(NT, 2) void tconv_dma_kernel(ConvArgs a) {
 #pragma unroll
   for (int j = 0; j < HJ; j++) {
     const int P = (wave + NW * j) * 64 + lane;
-    const int hp = P >> 2, q = (P & 3) ^ swz(hp);
+    const int hp = P >> 2, q = (P & 3) ^ tconv_swz(hp);
     const int py = (hp * 1986) >> 16;  // hp / 33 for hp < 297
     const int px = hp - py * HW1;
     const int gy = ty0 - 1 + py, gx = tx0 - 1 + px;
@@ -100,8 +86,8 @@ __global__ __launch_bounds__(NT, 2) void tconv_dma_kernel(ConvArgs a) {
     const int ii = wave + NW * j;
     const int R = min(16 * ii + (lane >> 2), WROWS - 1);
     const int k = R >> 5, n = R & 31;
-    const int q = (lane & 3) ^ swz(R);
-    woff[j] = (unsigned)((((((kSlot[k] * CB + cb) * 4 + kCls[k]) * 32 + n) * a.Ci) + q * 8) * 2);
+    const int q = (lane & 3) ^ tconv_swz(R);
+    woff[j] = (unsigned)((((((kTconvSlot[k] * CB + cb) * 4 + kTconvCls[k]) * 32 + n) * a.Ci) + q * 8) * 2);
   }
 #define TD_ISSUE(C_, BUF_)                                                                               \
   {                                                                                                      \
@@ -115,11 +101,11 @@ __global__ __launch_bounds__(NT, 2) void tconv_dma_kernel(ConvArgs a) {
 
   // fragment addresses.  A: halo pixel of (local row 2 wave + R, column r) under shift (p, q) = row + 1 - p, r + 1 - q
   const int hp00 = (2 * wave) * HW1 + r;   // halo row 2 wave, halo column r  (= shift (1,1) of the wave's first row)
-  const unsigned b0 = (unsigned)(r * KB + ((swz(r) ^ h) << 4));
-#define TD_A(HR_, Q1_, KS_, BUF_)                                                                        \
-  ({                                                                                                     \
-    const int hp_ = hpv + (HR_) * HW1 + (Q1_);                                                           \
-    *reinterpret_cast<const u32x4*>(smem + ((OFF_H + (BUF_) * HBUF + hp_ * KB + ((swz(hp_) ^ h) << 4)) ^ ((KS_) << 5))); \
+  const unsigned b0 = (unsigned)(r * KB + ((tconv_swz(r) ^ h) << 4));
+#define TD_A(HR_, Q1_, KS_, BUF_)                                                                                              \
+  ({                                                                                                                           \
+    const int hp_ = hpv + (HR_) * HW1 + (Q1_);                                                                                 \
+    *reinterpret_cast<const u32x4*>(smem + ((OFF_H + (BUF_) * HBUF + hp_ * KB + ((tconv_swz(hp_) ^ h) << 4)) ^ ((KS_) << 5))); \
   })
 #define TD_B(K_, KS_, BUF_) (*reinterpret_cast<const u32x4*>(smem + (BUF_) * WBUF + (K_) * 32 * KB + (b0 ^ ((KS_) << 5))))
 
@@ -139,29 +125,29 @@ __global__ __launch_bounds__(NT, 2) void tconv_dma_kernel(ConvArgs a) {
   int hpv = hp00;
   // one k-step: 6 halo fragments (rows 2w .. 2w+2 of the halo x column shifts q = 1, 0), 9 weight fragments, 18 MFMAs;
   // per class the taps accumulate in the order of tconv2_kernel (shift slots 0, 1, 2, 3)
-#define TD_STEP(KS_, BUF_)                                                                               \
-  {                                                                                                      \
-    u32x4 A00 = TD_A(0, 0, KS_, BUF_), A01 = TD_A(0, 1, KS_, BUF_);   /* halo row 2w:   q = 1, q = 0 */   \
-    u32x4 A10 = TD_A(1, 0, KS_, BUF_), A11 = TD_A(1, 1, KS_, BUF_);   /* halo row 2w+1 */                 \
-    u32x4 A20 = TD_A(2, 0, KS_, BUF_), A21 = TD_A(2, 1, KS_, BUF_);   /* halo row 2w+2 */                 \
-    {                                                                                                    \
-      const u32x4 B0 = TD_B(0, KS_, BUF_), B1 = TD_B(1, KS_, BUF_), B2 = TD_B(2, KS_, BUF_);              \
-      mma<F>(acc[0][0], B0, A00); mma<F>(acc[1][0], B0, A10);            /* shift (1,1) */                     \
-      mma<F>(acc[0][1], B2, A01); mma<F>(acc[1][1], B2, A11);            /* shift (1,0), class 1 */            \
-      mma<F>(acc[0][0], B1, A01); mma<F>(acc[1][0], B1, A11);            /* shift (1,0), class 0 */            \
-    }                                                                                                    \
-    {                                                                                                    \
-      const u32x4 B3 = TD_B(3, KS_, BUF_), B4 = TD_B(4, KS_, BUF_);                                       \
-      mma<F>(acc[0][2], B4, A10); mma<F>(acc[1][2], B4, A20);            /* shift (0,1), class 2 */            \
-      mma<F>(acc[0][0], B3, A10); mma<F>(acc[1][0], B3, A20);            /* shift (0,1), class 0 */            \
-    }                                                                                                    \
-    {                                                                                                    \
+#define TD_STEP(KS_, BUF_)                                                                                            \
+  {                                                                                                                   \
+    u32x4 A00 = TD_A(0, 0, KS_, BUF_), A01 = TD_A(0, 1, KS_, BUF_);   /* halo row 2w:   q = 1, q = 0 */               \
+    u32x4 A10 = TD_A(1, 0, KS_, BUF_), A11 = TD_A(1, 1, KS_, BUF_);   /* halo row 2w+1 */                             \
+    u32x4 A20 = TD_A(2, 0, KS_, BUF_), A21 = TD_A(2, 1, KS_, BUF_);   /* halo row 2w+2 */                             \
+    {                                                                                                                 \
+      const u32x4 B0 = TD_B(0, KS_, BUF_), B1 = TD_B(1, KS_, BUF_), B2 = TD_B(2, KS_, BUF_);                          \
+      Mma<F>::step(acc[0][0], B0, A00); Mma<F>::step(acc[1][0], B0, A10);   /* shift (1,1) */                         \
+      Mma<F>::step(acc[0][1], B2, A01); Mma<F>::step(acc[1][1], B2, A11);   /* shift (1,0), class 1 */                \
+      Mma<F>::step(acc[0][0], B1, A01); Mma<F>::step(acc[1][0], B1, A11);   /* shift (1,0), class 0 */                \
+    }                                                                                                                 \
+    {                                                                                                                 \
+      const u32x4 B3 = TD_B(3, KS_, BUF_), B4 = TD_B(4, KS_, BUF_);                                                   \
+      Mma<F>::step(acc[0][2], B4, A10); Mma<F>::step(acc[1][2], B4, A20);   /* shift (0,1), class 2 */                \
+      Mma<F>::step(acc[0][0], B3, A10); Mma<F>::step(acc[1][0], B3, A20);   /* shift (0,1), class 0 */                \
+    }                                                                                                                 \
+    {                                                                                                                 \
       const u32x4 B5 = TD_B(5, KS_, BUF_), B6 = TD_B(6, KS_, BUF_), B7 = TD_B(7, KS_, BUF_), B8 = TD_B(8, KS_, BUF_); \
-      mma<F>(acc[0][3], B8, A11); mma<F>(acc[1][3], B8, A21);            /* shift (0,0) */                     \
-      mma<F>(acc[0][1], B6, A11); mma<F>(acc[1][1], B6, A21);                                                  \
-      mma<F>(acc[0][2], B7, A11); mma<F>(acc[1][2], B7, A21);                                                  \
-      mma<F>(acc[0][0], B5, A11); mma<F>(acc[1][0], B5, A21);                                                  \
-    }                                                                                                    \
+      Mma<F>::step(acc[0][3], B8, A11); Mma<F>::step(acc[1][3], B8, A21);   /* shift (0,0) */                         \
+      Mma<F>::step(acc[0][1], B6, A11); Mma<F>::step(acc[1][1], B6, A21);                                             \
+      Mma<F>::step(acc[0][2], B7, A11); Mma<F>::step(acc[1][2], B7, A21);                                             \
+      Mma<F>::step(acc[0][0], B5, A11); Mma<F>::step(acc[1][0], B5, A21);                                             \
+    }                                                                                                                 \
   }
   for (int c = 0; c < n_chunks; c++) {
     const int buf = c & 1;
@@ -177,15 +163,15 @@ __global__ __launch_bounds__(NT, 2) void tconv_dma_kernel(ConvArgs a) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // chunk c+1 (issued one chunk ago) has landed
       __syncthreads();                                  // ... for everybody; chunk c's buffers are free
       if (c + 2 < n_chunks) TD_ISSUE(c + 2, buf)
-      mma<F>(acc[0][0], B0, A00); mma<F>(acc[1][0], B0, A10);
-      mma<F>(acc[0][1], B2, A01); mma<F>(acc[1][1], B2, A11);
-      mma<F>(acc[0][0], B1, A01); mma<F>(acc[1][0], B1, A11);
-      mma<F>(acc[0][2], B4, A10); mma<F>(acc[1][2], B4, A20);
-      mma<F>(acc[0][0], B3, A10); mma<F>(acc[1][0], B3, A20);
-      mma<F>(acc[0][3], B8, A11); mma<F>(acc[1][3], B8, A21);
-      mma<F>(acc[0][1], B6, A11); mma<F>(acc[1][1], B6, A21);
-      mma<F>(acc[0][2], B7, A11); mma<F>(acc[1][2], B7, A21);
-      mma<F>(acc[0][0], B5, A11); mma<F>(acc[1][0], B5, A21);
+      Mma<F>::step(acc[0][0], B0, A00); Mma<F>::step(acc[1][0], B0, A10);
+      Mma<F>::step(acc[0][1], B2, A01); Mma<F>::step(acc[1][1], B2, A11);
+      Mma<F>::step(acc[0][0], B1, A01); Mma<F>::step(acc[1][0], B1, A11);
+      Mma<F>::step(acc[0][2], B4, A10); Mma<F>::step(acc[1][2], B4, A20);
+      Mma<F>::step(acc[0][0], B3, A10); Mma<F>::step(acc[1][0], B3, A20);
+      Mma<F>::step(acc[0][3], B8, A11); Mma<F>::step(acc[1][3], B8, A21);
+      Mma<F>::step(acc[0][1], B6, A11); Mma<F>::step(acc[1][1], B6, A21);
+      Mma<F>::step(acc[0][2], B7, A11); Mma<F>::step(acc[1][2], B7, A21);
+      Mma<F>::step(acc[0][0], B5, A11); Mma<F>::step(acc[1][0], B5, A21);
     }
   }
 #undef TD_ISSUE
@@ -259,9 +245,9 @@ __global__ __launch_bounds__(64) void tconv_edges_kernel(ConvArgs a, int row_til
                 A2 = *reinterpret_cast<const u32x4*>(w2 + k);
     const u32x4 X0 = x0 >= 0 ? *reinterpret_cast<const u32x4*>(xb + x0 + k + 8 * h) : zero;
     const u32x4 X1 = x1 >= 0 ? *reinterpret_cast<const u32x4*>(xb + x1 + k + 8 * h) : zero;
-    mma<F>(acc0, A0, X0);
-    mma<F>(acc1, A2, X1);
-    mma<F>(acc0, A1, X1);
+    Mma<F>::step(acc0, A0, X0);
+    Mma<F>::step(acc1, A2, X1);
+    Mma<F>::step(acc0, A1, X1);
   }
   const int Wt = 2 * a.W + 1, Ht = 2 * a.H + 1;
   uint16_t* yb = reinterpret_cast<uint16_t*>(a.y) + (long)b * Ht * Wt * a.Co + cb * 32 + 4 * h;

@@ -24,19 +24,12 @@
 
 #include "common.h"
 #include "internal.h"
+#include "mma.h"
 
 namespace maua {
 
 namespace {
 constexpr int UW_TW = 64;  // positions per strip
-}
-
-// the 32x32x16 matrix instruction of the kernel's 16-bit format on operands held as any 16-byte register type
-template <typename F, typename A, typename B>
-__device__ __forceinline__ f32x16 mfma16(const A& a, const B& b, const f32x16& c) {
-  f32x16 r = c;
-  Mma16<F>::step(r, __builtin_bit_cast(u32x4, a), __builtin_bit_cast(u32x4, b));
-  return r;
 }
 
 template <int CI, int CO, typename F>
@@ -165,11 +158,11 @@ __global__ __launch_bounds__(256, 2) void upwalk_kernel(HiresArgs a, int seg_row
     for (int kx = 0; kx < 3; kx++)
 #pragma unroll
       for (int cs = 0; cs < KS; cs++) {
-        const bf16x8 av = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(abase + kx * RSH + cs * 32));
-        const bf16x8 wo = __builtin_bit_cast(bf16x8, wl[((pb * 3 + kx) * KS + cs) * 64 + lane]);
-        ecur = mfma16<F>(__builtin_bit_cast(bf16x8, wf[(1 * 3 + kx) * KS + cs]), av, ecur);
-        o = mfma16<F>(wo, av, o);
-        enext = mfma16<F>(__builtin_bit_cast(bf16x8, wf[(0 * 3 + kx) * KS + cs]), av, enext);
+        const u32x4 av = *reinterpret_cast<const u32x4*>(abase + kx * RSH + cs * 32);
+        const u32x4 wo = wl[((pb * 3 + kx) * KS + cs) * 64 + lane];
+        Mma<F>::step(ecur, wf[(1 * 3 + kx) * KS + cs], av);
+        Mma<F>::step(o, wo, av);
+        Mma<F>::step(enext, wf[(0 * 3 + kx) * KS + cs], av);
       }
     // ---- vertical FIR on the accumulators + epilogue: lane = position jbase + r, 16 channels in 4 quads
     // (each lane finishes both rows of its pixel: the other row's noise sits in the lane 32 away)
@@ -245,13 +238,6 @@ __global__ __launch_bounds__(256, 2) void upwalk_kernel(HiresArgs a, int seg_row
 struct WalkFusedArgs {
   HiresArgs up, c1;
 };
-
-__device__ __forceinline__ void lds_dma_b32(const void* sbase, unsigned voff_bytes, void* lds_wave_base) {
-  const unsigned base =
-      __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_wave_base);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff_bytes), "s"(sbase), "s"(base)
-               : "memory");
-}
 
 template <int CI, int CM, bool DBG, typename F>
 __global__ __launch_bounds__(512, 1) void upwalk_fused_kernel(WalkFusedArgs A, int seg_rows, int nseg, int strips,
@@ -452,10 +438,10 @@ __global__ __launch_bounds__(512, 1) void upwalk_fused_kernel(WalkFusedArgs A, i
         for (int it = 0; it < 3 * KS; it++) {
           if (it + PD - 1 < 3 * KS) MAUA_UWF_PLOAD(it + PD - 1)
           __builtin_amdgcn_sched_barrier(0);
-          const bf16x8 av = __builtin_bit_cast(bf16x8, pa[it % PD]);
-          ecur = mfma16<F>(__builtin_bit_cast(bf16x8, pw2[it % PD]), av, ecur);
-          o = mfma16<F>(__builtin_bit_cast(bf16x8, pw1[it % PD]), av, o);
-          enext = mfma16<F>(__builtin_bit_cast(bf16x8, pw0[it % PD]), av, enext);
+          const u32x4 av = pa[it % PD];
+          Mma<F>::step(ecur, pw2[it % PD], av);
+          Mma<F>::step(o, pw1[it % PD], av);
+          Mma<F>::step(enext, pw0[it % PD], av);
           __builtin_amdgcn_sched_barrier(0);
         }
 #undef MAUA_UWF_PLOAD
@@ -654,22 +640,22 @@ __global__ __launch_bounds__(512, 1) void upwalk_fused_kernel(WalkFusedArgs A, i
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < 3 * KS1; i++) {   // taps dy = -1 of accA / dy = +1 of accB
-          accA = mfma16<F>(__builtin_bit_cast(bf16x8, w1[i]), __builtin_bit_cast(bf16x8, f0[i]), accA);
-          accB = mfma16<F>(__builtin_bit_cast(bf16x8, w1[2 * 3 * KS1 + i]), __builtin_bit_cast(bf16x8, f3[i]), accB);
+          Mma<F>::step(accA, w1[i], f0[i]);
+          Mma<F>::step(accB, w1[2 * 3 * KS1 + i], f3[i]);
         }
         __builtin_amdgcn_sched_barrier(0);
         MAUA_UWF_CLOAD(f0, s1)               // ring row arow
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < 3 * KS1; i++) {   // ring row arow - 1: dy = 0 of accA, dy = -1 of accB
-          accA = mfma16<F>(__builtin_bit_cast(bf16x8, w1[3 * KS1 + i]), __builtin_bit_cast(bf16x8, f1[i]), accA);
-          accB = mfma16<F>(__builtin_bit_cast(bf16x8, w1[i]), __builtin_bit_cast(bf16x8, f1[i]), accB);
+          Mma<F>::step(accA, w1[3 * KS1 + i], f1[i]);
+          Mma<F>::step(accB, w1[i], f1[i]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < 3 * KS1; i++) {   // ring row arow: dy = +1 of accA, dy = 0 of accB
-          accA = mfma16<F>(__builtin_bit_cast(bf16x8, w1[2 * 3 * KS1 + i]), __builtin_bit_cast(bf16x8, f0[i]), accA);
-          accB = mfma16<F>(__builtin_bit_cast(bf16x8, w1[3 * KS1 + i]), __builtin_bit_cast(bf16x8, f0[i]), accB);
+          Mma<F>::step(accA, w1[2 * 3 * KS1 + i], f0[i]);
+          Mma<F>::step(accB, w1[3 * KS1 + i], f0[i]);
         }
 #undef MAUA_UWF_CLOAD
         const long long tc = MAUA_NOW();
@@ -691,8 +677,8 @@ __global__ __launch_bounds__(512, 1) void upwalk_fused_kernel(WalkFusedArgs A, i
         for (int e = 0; e < 16; e++) { ra[e] = 0.f; rb[e] = 0.f; }
 #pragma unroll
         for (int ks = 0; ks < KS1; ks++) {
-          ra = mfma16<F>(__builtin_bit_cast(bf16x8, rf[ks]), __builtin_bit_cast(bf16x8, fa[ks]), ra);
-          rb = mfma16<F>(__builtin_bit_cast(bf16x8, rf[ks]), __builtin_bit_cast(bf16x8, fb[ks]), rb);
+          Mma<F>::step(ra, rf[ks], fa[ks]);
+          Mma<F>::step(rb, rf[ks], fb[ks]);
         }
         // ---- B: skip = rows m - 1 (staged at step k - 2) and m (step k - 1) of the previous image, m = rho - 2
         const int oy = arow - 1 + h;
