@@ -556,20 +556,28 @@ int ensure_ws(maua_vgg* n, int B, int H, int W) {
       if (hipMalloc(&o.hg, e * n->esize) != hipSuccess) return fail("maua_vgg: out of device memory (head gradients)");
     }
     const int mc = max_c(n);
-    // gram partials: B * ceil(hw / 256) * C^2 floats per tap (largest at the first tap or the widest one); per-pixel values: B * H * W
-    size_t fb = (size_t)B * H * W * 4;
-    for (auto& o : n->ops) {
-      const long hw = (long)(H >> o.shift) * (W >> o.shift);
-      fb = std::max(fb, (size_t)B * ((hw + GRAM_PX - 1) / GRAM_PX) * o.C * o.C * 4);
-    }
     if (hipMalloc(&n->ga, widest * n->esize) != hipSuccess || hipMalloc(&n->gb, widest * n->esize) != hipSuccess ||
-        hipMalloc((void**)&n->fbuf, fb) != hipSuccess || hipMalloc((void**)&n->gram, (size_t)B * mc * mc * 4) != hipSuccess ||
+        hipMalloc((void**)&n->gram, (size_t)B * mc * mc * 4) != hipSuccess ||
         hipMalloc(&n->sym, (size_t)B * mc * mc * n->esize) != hipSuccess || hipMalloc((void**)&n->loss_dev, (size_t)B * 4) != hipSuccess ||
         hipMalloc((void**)&n->part, (size_t)B * STYLE_CHUNKS * 2 * 4) != hipSuccess)
       return fail("maua_vgg: out of device memory (workspaces)");
-    n->fbuf_bytes = fb;
     n->cap_key = key;
     n->loss_cap = B;
+  }
+  // gram partials: B * ceil(hw / 256) * C^2 floats per tap (largest at the first tap or the widest one); per-pixel values: B * H * W.
+  // The slice count rounds up per image, so a shape with no more pixels in all can still need more: sized from this shape, on its own
+  size_t fb = (size_t)B * H * W * 4;
+  for (auto& o : n->ops) {
+    const long hw = (long)(H >> o.shift) * (W >> o.shift);
+    fb = std::max(fb, (size_t)B * ((hw + GRAM_PX - 1) / GRAM_PX) * o.C * o.C * 4);
+  }
+  if (fb > n->fbuf_bytes) {
+    MAUA_HIP_CHECK(hipStreamSynchronize(st));
+    if (n->fbuf) hipFree(n->fbuf);
+    n->fbuf = nullptr; n->fbuf_bytes = 0;
+    n->epoch++;
+    if (hipMalloc((void**)&n->fbuf, fb) != hipSuccess) return fail("maua_vgg: out of device memory (workspaces)");
+    n->fbuf_bytes = fb;
   }
   if (B > n->ones_b) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
