@@ -879,6 +879,11 @@ int maua_vgg_lpips_features(maua_vgg* net, int op, float* out);
  * pointers to f32 [C][C] (target_bstride NULL / 0) or [B][C][C] (target_bstride[k] = C * C); loss optional device f32 [B] */
 int maua_vgg_style_grad(maua_vgg* net, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
                         const long* target_bstride, float strength, float* grad, float* loss);
+/* The NCA style loss (maua/nca/train.py:122-142, 228-229): G_b = F_b^T F_b / (h w) per tap, L = sum_taps mean((mean_b G_b - T)^2);
+ * grad = dL / d img [B][3][H][W], loss one optional device f32.  taps / targets as above, every target one f32 [C][C] in the same
+ * normalisation (maua_vgg_gram's output divided by h w) */
+int maua_vgg_gram_mean_grad(maua_vgg* net, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
+                            float* grad, float* loss);
 /* LPIPSGrads.forward (maua/grad.py:189-193) at the network's own size: grad = d (scale * sum_b lpips(img_b, target)) / d img;
  * targets: HOST array of DEVICE pointers to the target's unit-normalised tap features (maua_vgg_lpips_features: [hw][C], shared, or
  * [B][hw][C] with target_bstride[k] = hw * C), lins: DEVICE pointers to the lin layers' weights [C]; dist optional device f32 [B] */
@@ -1075,6 +1080,55 @@ int maua_philox_normal(maua_ctx* ctx, unsigned long long seed, unsigned long lon
 /* The benchmark clip's waveform on the device (0.3 sin(2 pi 220 t) + 0.2 (u - 0.5) [(2t mod 1) < 0.05] + 0.01 n; u / n =
  * streams 0 / 1 of `seed`): out device f32 [n].  No reference counterpart (synthetic input); host twin oracle/rng.py clip_audio. */
 int maua_philox_clip_audio(maua_ctx* ctx, unsigned long long seed, long n, double sample_rate, float* out);
+
+/* ---- neural cellular automaton (maua/nca/train.py:152-193, after znah's gitart_kunstformen_ca) ------------------------------------
+ * One update of the f32 state x [B][chn][H][W]:  x += w2 . relu(w1 . perception(x) + b1) . mask
+ *   perception: per channel, the circular 3 x 3 stencils {identity, sobel_x, sobel_x^T, laplacian} with the reference's un-normalised
+ *               integer taps (train.py:153-169); feature 4 c + f (channel-major, what its reshape(b, -1, h, w) produces)
+ *   mask:       floorf(u + rate) per pixel, shared by the channels; rate a scalar, or rate_map [H][W] (generate.py:57) when not NULL
+ *   u:          the caller's device tensor u [n_steps][B][H][W], or (u == NULL) unit23 of word ((t B + b) H + y) W + x of the Philox
+ *               stream (seed, stream) in maua_philox_u32's addressing, t = step0 + the step's index in this call: a run split into
+ *               several calls, or into windows, draws the same masks.  oracle/rng.py u32 is the host twin.
+ * One launch per step (steps_per_launch = 2, 4: per that many steps, on a halo advanced inside the workgroup, same bits) does perception, both products, bias, ReLU, mask and residual; nothing between them goes to memory.  Neighbours
+ * read the old state, so the steps alternate between x and a buffer the handle owns and the result ends in x.  The parameters are read at
+ * every call from the caller's device f32 tensors w1 [hidden][4 chn], b1 [hidden], w2 [chn][hidden] and staged into the operand layout
+ * by the step kernel itself.  dtype selects the PRODUCTS, not the state: MAUA_F32 = exact v_mfma_f32_32x32x2_f32 (an f32 fma chain, the
+ * parity mode), MAUA_F32_SPLIT = hi/lo bf16 operands and three products per k-step (lo x lo, <= 2^-16 of a product, is dropped).
+ * Limits: chn a multiple of 4 up to 16, hidden a multiple of 32 up to 128; H, W >= 3; steps_per_launch 1, 2 or 4.
+ * Window mode (W_sub > 0; generate.py:25-36's checkpoint grid): columns [col0, col0 + W_sub) of every row are a torus of width W_sub, and
+ * only window columns [margin, W_sub - margin) are written back; W stays the row length of x, of rate_map and of u, and the Philox word
+ * is addressed with the column in the whole row, so overlapping windows see one mask per pixel and step. */
+/* perception alone (train.py:167-169), for callers that want the features: x [B][C][H][W] f32 -> out [B][4 C][H][W]; any C; H, W >= 3 */
+int maua_nca_perception(maua_ctx* ctx, const float* x, int B, int C, int H, int W, float* out);
+typedef struct maua_nca maua_nca;
+typedef struct {
+  float* x; int B, H, W;
+  const float *w1, *b1, *w2;
+  int n_steps;
+  float rate; const float* rate_map;
+  const float* u;
+  unsigned long long seed, stream, step0;
+  int col0, W_sub, margin;   /* W_sub = 0: the whole grid */
+  int steps_per_launch;      /* 0 = 1; 2, 4: that many steps per launch (same bits; not in window mode or forward_keep) */
+} maua_nca_desc;
+int maua_nca_create(maua_ctx* ctx, int chn, int hidden, int dtype, maua_nca** out);
+int maua_nca_destroy(maua_nca* handle);
+/* host only, no device needed (handle may be NULL: then chn, hidden and dtype describe it): MAUA_OK, or MAUA_ERR + maua_last_error() with
+ * maua_nca_step's own refusal.  Pointers are only checked, never dereferenced. */
+int maua_nca_check(const maua_nca* handle, int chn, int hidden, int dtype, const maua_nca_desc* d);
+/* n_steps updates of d->x in place, on the context's stream */
+int maua_nca_step(maua_nca* handle, const maua_nca_desc* d);
+/* the same steps from d->x (left as it is), every state kept: states [n_steps + 1][B][chn][H][W], states[0] = x.  No window mode. */
+int maua_nca_forward_keep(maua_nca* handle, const maua_nca_desc* d, float* states);
+/* The gradient of those n_steps updates: from the kept states and g_last = dL/dx_N [B][chn][H][W] to g_first = dL/dx_0 and the parameter
+ * gradients dw1 [hidden][4 chn], db1 [hidden], dw2 [chn][hidden] (all written, not added to), walking the steps backwards.  d gives the
+ * parameters, the rate and the masks' source exactly as it did to maua_nca_forward_keep (d->x is not read); no window mode.  Per step the
+ * hidden layer is recomputed from the stored state with the forward's own summation (ReLU's mask is the forward's), g is masked,
+ * dW2 += gy h^T, gh = (w2^T gy) [h > 0], dW1 += gh p^T, db1 += sum gh, g += perception^T(w1^T gh) (the circular stencils with flipped
+ * taps).  Sums over pixels and steps run in a fixed order - per-workgroup partials carried across the steps, then one ordered reduce - so
+ * two runs give identical bits.  Products are exact f32 whatever the handle's dtype.  g_first may not alias g_last. */
+int maua_nca_vjp(maua_nca* handle, const maua_nca_desc* d, const float* states, const float* g_last, float* g_first, float* dw1, float* db1,
+                 float* dw2);
 
 /* ---- multi-GPU: the one exchange step of the frame-sharded render ------------------------------------
  * One process per GPU; frames are sharded by contiguous range (no data-path collective).  maua_gather_frames moves every

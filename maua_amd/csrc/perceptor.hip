@@ -422,6 +422,37 @@ __global__ __launch_bounds__(256) void style_dgram_kernel(const float* __restric
   if (loss && blockIdx.x == 0 && threadIdx.x == 0) loss[b] += k * Q / A;
 }
 
+// batch-mean Gram head (maua/nca/train.py:122-142, 228-229): D = inv * sum_b G_b - T with inv = 1 / (B h w), G_b the raw F_b^T F_b;
+// Sym = k (D + D^T) with k = 2 / (C^2 B h w), one [C][C] operand in the network dtype shared by every image of the batch;
+// qpart[workgroup] = sum of its 256 D^2 (fixed order).  gram_mean_loss adds the partials in order: loss[0] += sum / C^2
+template <typename T>
+__global__ __launch_bounds__(256) void gram_mean_dsym_kernel(const float* __restrict__ G, const float* __restrict__ Tg, int C, int B, float inv,
+                                                             float k, T* __restrict__ Sym, float* __restrict__ qpart) {
+  __shared__ float red[4];
+  const long CC = (long)C * C;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  float q = 0.f;
+  if (i < CC) {
+    const int r = (int)(i / C), c = (int)(i - (long)r * C);
+    const long j = (long)c * C + r;
+    float s1 = 0.f, s2 = 0.f;
+    for (int b = 0; b < B; b++) { s1 += G[(long)b * CC + i]; s2 += G[(long)b * CC + j]; }
+    const float d1 = s1 * inv - Tg[i], d2 = s2 * inv - Tg[j];
+    Elem<T>::store(Sym + i, k * (d1 + d2));
+    q = d1 * d1;
+  }
+  const float Q = block_sum_1024(q, red);
+  if (threadIdx.x == 0) qpart[blockIdx.x] = Q;
+}
+
+__global__ __launch_bounds__(256) void gram_mean_loss_kernel(const float* __restrict__ qpart, int n, float mul, float* __restrict__ loss) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += qpart[i];
+  const float t = block_sum_1024(s, red);
+  if (threadIdx.x == 0) loss[0] += mul * t;
+}
+
 // ---------------------------------------------------------------------------------------------- lpips head: one wave per pixel
 // F [B][HW][C] (T), nt = unit-normalised target features [Bt][HW][C] f32 (nt_bstride 0: shared), lin [C]
 // val[b][p] = sum_c lin_c (n_c - nt_c)^2;  hg = d (coef sum_p val) / dF  (coef = scale / HW)
@@ -746,6 +777,43 @@ int style_grad_t(maua_vgg* n, const float* img, int B, int H, int W, const int* 
   return MAUA_OK;
 }
 
+// L = sum_taps mean((mean_b F_b^T F_b / (h w) - T)^2): the style head's launches with one head operand for the whole batch
+template <typename T>
+int gram_mean_grad_t(maua_vgg* n, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets, float* grad,
+                     float* loss) {
+  hipStream_t st = n->ctx->stream;
+  if (int rc = forward_t<T>(n, img, B, H, W)) return rc;
+  hipLaunchKernelGGL(zero_f32_kernel, dim3(1), dim3(256), 0, st, n->loss_dev, 1L);
+  for (int k = 0; k < n_taps; k++) {
+    if (int rc = check_tap(n, taps[k], "maua_vgg_gram_mean_grad")) return rc;
+    POp& o = n->ops[taps[k]];
+    const int C = o.C;
+    const long hw = (long)(H >> o.shift) * (W >> o.shift);
+    if (int rc = gram_t<T>(n, taps[k], n->gram)) return rc;
+    const long CC = (long)C * C;
+    const int blocks = (int)((CC + 255) / 256);
+    const float bhw = (float)B * (float)hw;
+    hipLaunchKernelGGL(gram_mean_dsym_kernel<T>, dim3(blocks), dim3(256), 0, st, (const float*)n->gram, targets[k], C, B, 1.f / bhw,
+                       2.f / ((float)CC * bhw), (T*)n->sym, n->fbuf);   // (the Gram partials in fbuf are spent once gram_t has reduced them)
+    MAUA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(gram_mean_loss_kernel, dim3(1), dim3(256), 0, st, (const float*)n->fbuf, blocks, 1.f / (float)CC, n->loss_dev);
+    MAUA_HIP_CHECK(hipGetLastError());
+    {                                      // d L / d F_b = F_b Sym: [hw][C] x [C][C]^T, one operand for every image
+      GemmArgs g{};
+      g.a0 = o.act; g.lda0 = C; g.K0 = C;
+      g.w = n->sym;
+      g.c = o.hg; g.ldc = C;
+      g.M = hw; g.N = C;
+      g.batch = B; g.a_bstride = hw * C; g.w_bstride = 0; g.c_bstride = hw * C;
+      if (int rc = launch_gemm_nt(st, n->dtype, g)) return rc;
+    }
+    o.hg_set = true;
+  }
+  if (int rc = backward_t<T>(n, grad)) return rc;
+  if (loss) MAUA_HIP_CHECK(hipMemcpyAsync(loss, n->loss_dev, 4, hipMemcpyDeviceToDevice, st));
+  return MAUA_OK;
+}
+
 template <typename T>
 int lpips_grad_t(maua_vgg* n, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
                  const long* t_bstride, const float* const* lins, float scale, float* grad, float* dist) {
@@ -949,6 +1017,15 @@ int maua_vgg_style_grad(maua_vgg* n, const float* img, int B, int H, int W, cons
   if (B == 0) return MAUA_OK;
   return n->dtype == MAUA_BF16 ? style_grad_t<bf16_t>(n, img, B, H, W, taps, n_taps, targets, target_bstride, strength, grad, loss)
                                : style_grad_t<float>(n, img, B, H, W, taps, n_taps, targets, target_bstride, strength, grad, loss);
+}
+
+int maua_vgg_gram_mean_grad(maua_vgg* n, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
+                            float* grad, float* loss) {
+  MAUA_REQUIRE(n && img && taps && targets && grad && n_taps > 0, "maua_vgg_gram_mean_grad: NULL argument");
+  if (int rc = check_image(n, B, H, W, "maua_vgg_gram_mean_grad")) return rc;
+  MAUA_REQUIRE(B > 0, "maua_vgg_gram_mean_grad: the mean over an empty batch is undefined (B must be at least 1)");
+  return n->dtype == MAUA_BF16 ? gram_mean_grad_t<bf16_t>(n, img, B, H, W, taps, n_taps, targets, grad, loss)
+                               : gram_mean_grad_t<float>(n, img, B, H, W, taps, n_taps, targets, grad, loss);
 }
 
 int maua_vgg_lpips_grad(maua_vgg* n, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
