@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "plain_conv.h"
 
 namespace maua {
 namespace {
@@ -64,11 +65,6 @@ int conv_plan(const maua_conv_desc* d, int dtype, int sel, ConvArgs* a, ConvPlan
   return MAUA_OK;
 }
 
-__global__ __launch_bounds__(256) void fill_ones_kernel(float* __restrict__ p, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 1.f;
-}
-
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -108,9 +104,7 @@ extern "C" int maua_conv3x3_ex(maua_ctx* ctx, const maua_conv_desc* d, int dtype
     if (int rc = launch_f32_split_inplace(st, base + o_w, (long)9 * d->Co * d->Ci)) return rc;
   a.w = base + o_w;
   if (p.kernel == 1) {   // the generic kernel multiplies its input by styles: all ones, as every plain network passes
-    const long n = (long)d->B * d->Ci;
-    hipLaunchKernelGGL(fill_ones_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float*)(base + o_s), n);
-    MAUA_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_fill_ones(st, (float*)(base + o_s), (long)d->B * d->Ci)) return rc;
     a.s = (const float*)(base + o_s);
     return launch_modconv3x3(st, dtype, a);
   }

@@ -157,6 +157,8 @@ int launch_upwalk_fused(hipStream_t stream, const HiresArgs& up, const HiresArgs
 // modconv_prep.hip - weight preparation: f32 [Co][Ci][k][k] -> T [phases][k*k][Cop][Cip] (+ Wsq f32 [Co][Ci] = sum_k W^2)
 int launch_prep_weights(hipStream_t stream, int dtype, const float* w, void* wt, float* wsq, int Co, int Ci, int k,
                         int up, int flip, int Cop, int Cip);
+// the weight of a layer's input gradient: f32 [Co][Ci][kk] -> f32 [Ci][Co][kk] with the taps reversed (a pure permutation)
+int launch_transpose_flip(hipStream_t stream, const float* w, float* w_t, int Co, int Ci, int kk);
 // MAUA_F32_SPLIT: a float32 weight buffer prepared by launch_prep_weights(MAUA_F32, ...) -> [hi x 8 | lo x 8] bf16 per 8 floats (one 32-byte
 // group per lane half of modconv.hip's k-step: mma.h), in place; n_floats % 8 == 0
 int launch_f32_split_inplace(hipStream_t stream, void* w, long n_floats);

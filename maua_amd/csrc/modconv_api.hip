@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "plain_conv.h"
 
 namespace maua {
 namespace {
@@ -127,11 +128,6 @@ int modconv_plan(const maua_modconv_desc* d, const maua_modconv_desc* d1, int dt
   return MAUA_OK;
 }
 
-__global__ __launch_bounds__(256) void modconv_fill_ones_kernel(float* __restrict__ p, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 1.f;
-}
-
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -190,11 +186,8 @@ extern "C" int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const 
     x = base + o_xm;
     x_bstride = (long)d->H * d->W * d->Ci;
   }
-  if (ones_bytes) {
-    const long n = (long)d->B * d->Ci;
-    hipLaunchKernelGGL(modconv_fill_ones_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (float*)(base + o_ones), n);
-    MAUA_HIP_CHECK(hipGetLastError());
-  }
+  if (ones_bytes)
+    if (int rc = launch_fill_ones(st, (float*)(base + o_ones), (long)d->B * d->Ci)) return rc;
   switch (route) {
     case R_LOWRES:
     case R_GENERIC:

@@ -86,6 +86,23 @@ int launch_prep_weights(hipStream_t stream, int dtype, const float* w, void* wt,
   return MAUA_OK;
 }
 
+// dst[i][o][k] = src[o][i][kk - 1 - k]: a convolution's (kk = 9) / linear layer's (kk = 1) weight for its input gradient
+__global__ __launch_bounds__(256) void transpose_flip_kernel(const float* __restrict__ src, float* __restrict__ dst, int Co, int Ci, int kk) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)Co * Ci * kk) return;
+  const int k = (int)(idx % kk);
+  const long oi = idx / kk;
+  const int i = (int)(oi % Ci), o = (int)(oi / Ci);
+  dst[((long)i * Co + o) * kk + (kk - 1 - k)] = src[idx];
+}
+int launch_transpose_flip(hipStream_t stream, const float* w, float* w_t, int Co, int Ci, int kk) {
+  const long n = (long)Co * Ci * kk;
+  if (n == 0) return MAUA_OK;
+  hipLaunchKernelGGL(transpose_flip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, w_t, Co, Ci, kk);
+  MAUA_HIP_CHECK(hipGetLastError());
+  return MAUA_OK;
+}
+
 // a prepared float32 weight buffer (launch_prep_weights, MAUA_F32) -> the split form above, in place: n floats, n % 8 == 0 (K, the
 // innermost dimension, is a multiple of 32 channels)
 __global__ __launch_bounds__(256) void f32_split_inplace_kernel(float* __restrict__ w, long n8) {

@@ -30,18 +30,11 @@
 
 #include "common.h"
 #include "internal.h"
+#include "plain_conv.h"
 
 using namespace maua;
 
 namespace {
-
-struct PConv {
-  int Ci = 0, Co = 0;
-  void *wt = nullptr, *wt_t = nullptr;   // prepared [9][Co][Ci] and the transposed network's [9][Ci][Co] (not for conv0)
-  float* bias = nullptr;                 // [Co]
-  float* zero_bias = nullptr;            // [max(Ci, Co)]
-  float* w0 = nullptr;                   // conv0 only: [27][Co] float32, row = c * 9 + ky * 3 + kx
-};
 
 struct POp {
   int kind = 0;        // 0 conv + ReLU, 1 MaxPool2d(2)
@@ -533,12 +526,13 @@ struct maua_vgg {
   int dtype = MAUA_BF16;
   size_t esize = 2;
   std::vector<POp> ops;
-  std::vector<PConv> convs;
+  // unpadded (channels are multiples of 64), each with its transposed copy - but convs[0], the 27-tap direct kernel's: float32,
+  // no transposed copy, and wt holds w0 [27][Co], row = c * 9 + ky * 3 + kx
+  std::vector<PlainConv> convs;
   int pad0 = 0;
   int use_dma = 1;                 // bf16 convolutions on modconv_dma.hip where the shape allows (MAUA_VGG_NO_DMA=1: the generic kernel)
   float in_mul = 1.f, in_add = 0.f, mean[3] = {0, 0, 0}, istd[3] = {1, 1, 1};
-  float* ones = nullptr;
-  int ones_b = 0;
+  UnitStyles ones;                 // [bcap][512]
   int B = 0, H = 0, W = 0;         // shape of the kept forward (0: none)
   size_t cap_key = 0;              // B * H * W the buffers were sized for
   void *ga = nullptr, *gb = nullptr;
@@ -610,23 +604,17 @@ int ensure_ws(maua_vgg* n, int B, int H, int W) {
     if (hipMalloc((void**)&n->fbuf, fb) != hipSuccess) return fail("maua_vgg: out of device memory (workspaces)");
     n->fbuf_bytes = fb;
   }
-  if (B > n->ones_b) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->ones) hipFree(n->ones);
-    n->epoch++;
-    std::vector<float> h((size_t)B * 512, 1.f);
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->ones, h.size() * 4));
-    MAUA_HIP_CHECK(hipMemcpy(n->ones, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    n->ones_b = B;
-  }
-  return MAUA_OK;
+  bool moved = false;
+  const int rc = n->ones.ensure(st, B, 512, &moved);
+  if (moved) n->epoch++;
+  return rc;
 }
 
 // y = act(conv3x3(x) + bias) on dense NHWC tensors; transposed: the input-gradient convolution (Co -> Ci, no bias, no activation)
-int run_conv(maua_vgg* n, const PConv& c, bool transposed, const void* x, void* y, int B, int h, int w) {
+int run_conv(maua_vgg* n, const PlainConv& c, bool transposed, const void* x, void* y, int B, int h, int w) {
   ConvArgs a{};
   const int Ci = transposed ? c.Co : c.Ci, Co = transposed ? c.Ci : c.Co;
-  a.x = x; a.x_bstride = (long)h * w * Ci; a.w = transposed ? c.wt_t : c.wt; a.s = n->ones; a.d = nullptr;
+  a.x = x; a.x_bstride = (long)h * w * Ci; a.w = transposed ? c.wt_t : c.wt; a.s = n->ones.p; a.d = nullptr;
   a.noise = nullptr; a.bias = transposed ? c.zero_bias : c.bias; a.y = y;
   a.B = B; a.H = h; a.W = w; a.Ci = Ci; a.Co = Co; a.up = 1;
   a.act = transposed ? MAUA_ACT_LINEAR : MAUA_ACT_LRELU; a.alpha = transposed ? 1.f : 0.f; a.gain = 1.f; a.clamp = -1.f;
@@ -653,9 +641,9 @@ int forward_t(maua_vgg* n, const float* img, int B, int H, int W) {
   constexpr int E = 16 / (int)sizeof(T);
   for (auto& o : n->ops) o.hg_set = false;
   {
-    const PConv& c = n->convs[0];
+    const PlainConv& c = n->convs[0];
     const long total = (long)B * H * W * (c.Co / 16);
-    hipLaunchKernelGGL(vgg_conv0_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)27 * c.Co * 4, st, img, c.w0, c.bias,
+    hipLaunchKernelGGL(vgg_conv0_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)27 * c.Co * 4, st, img, (const float*)c.wt, c.bias,
                        (T*)n->ops[0].act, B, H, W, c.Co, n->pad0, n->in_mul, n->in_add, n->mean[0], n->mean[1], n->mean[2], n->istd[0],
                        n->istd[1], n->istd[2]);
     MAUA_HIP_CHECK(hipGetLastError());
@@ -693,15 +681,15 @@ int backward_t(maua_vgg* n, float* grad) {
     if (o.kind == 0) {
       T* gpre = (g == bufa) ? bufb : bufa;
       VGG_LAUNCH(mask_add_kernel<T>, (ne + 7) / 8, (const T*)g, (const T*)(o.hg_set ? o.hg : nullptr), (const T*)o.act, gpre, ne);
-      const PConv& c = n->convs[o.conv];
+      const PlainConv& c = n->convs[o.conv];
       if (i == 0) {
         const long total = (long)B * H * W;
         if (c.Co == 64)
-          hipLaunchKernelGGL(vgg_conv0_vjp64_kernel<T>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, (const T*)gpre, c.w0, grad, B, H, W,
+          hipLaunchKernelGGL(vgg_conv0_vjp64_kernel<T>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, (const T*)gpre, (const float*)c.wt, grad, B, H, W,
                              n->pad0, n->in_mul * n->istd[0], n->in_mul * n->istd[1], n->in_mul * n->istd[2]);
         else
           hipLaunchKernelGGL(vgg_conv0_vjp_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)27 * c.Co * 4, st, (const T*)gpre,
-                             c.w0, grad, B, H, W, c.Co, n->pad0, n->in_mul * n->istd[0], n->in_mul * n->istd[1], n->in_mul * n->istd[2]);
+                             (const float*)c.wt, grad, B, H, W, c.Co, n->pad0, n->in_mul * n->istd[0], n->in_mul * n->istd[1], n->in_mul * n->istd[2]);
         MAUA_HIP_CHECK(hipGetLastError());
       } else {
         T* gprev = (gpre == bufa) ? bufb : bufa;
@@ -871,7 +859,7 @@ int maua_vgg_create(maua_ctx* ctx, int dtype, const int* plan, int n_ops, int re
     if (plan[i] > 0) {
       if (plan[i] % 64 != 0 || plan[i] > 512) { maua_vgg_destroy(n); return fail("maua_vgg_create: channels must be multiples of 64, at most 512"); }
       o.kind = 0; o.conv = (int)n->convs.size(); o.C = plan[i];
-      PConv c; c.Ci = cin; c.Co = plan[i];
+      PlainConv c; c.Ci = cin; c.Co = plan[i];
       n->convs.push_back(c);
       cin = plan[i];
     } else {
@@ -882,19 +870,8 @@ int maua_vgg_create(maua_ctx* ctx, int dtype, const int* plan, int n_ops, int re
     n->ops.push_back(o);
   }
   for (size_t i = 0; i < n->convs.size(); i++) {
-    PConv& c = n->convs[i];
-    bool ok = hipMalloc((void**)&c.bias, (size_t)c.Co * 4) == hipSuccess &&
-              hipMalloc((void**)&c.zero_bias, (size_t)std::max(c.Ci, c.Co) * 4) == hipSuccess;
-    if (ok) { hipMemset(c.bias, 0, (size_t)c.Co * 4); hipMemset(c.zero_bias, 0, (size_t)std::max(c.Ci, c.Co) * 4); }
-    if (ok && i == 0) {
-      ok = hipMalloc((void**)&c.w0, (size_t)27 * c.Co * 4) == hipSuccess;
-      if (ok) hipMemset(c.w0, 0, (size_t)27 * c.Co * 4);
-    } else if (ok) {
-      const size_t we = (size_t)9 * c.Co * c.Ci * n->esize;
-      ok = hipMalloc(&c.wt, we) == hipSuccess && hipMalloc(&c.wt_t, we) == hipSuccess;
-      if (ok) { hipMemset(c.wt, 0, we); hipMemset(c.wt_t, 0, we); }
-    }
-    if (!ok) { maua_vgg_destroy(n); return fail("maua_vgg_create: out of device memory"); }
+    PlainConv& c = n->convs[i];
+    if (c.alloc(c.Ci, c.Co, c.Ci, c.Co, i == 0 ? 4 : n->esize, i != 0)) { maua_vgg_destroy(n); return fail("maua_vgg_create: out of device memory"); }
   }
   *out = n;
   return MAUA_OK;
@@ -904,14 +881,8 @@ void maua_vgg_destroy(maua_vgg* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
   free_ws(n);
-  for (auto& c : n->convs) {
-    if (c.wt) hipFree(c.wt);
-    if (c.wt_t) hipFree(c.wt_t);
-    if (c.bias) hipFree(c.bias);
-    if (c.zero_bias) hipFree(c.zero_bias);
-    if (c.w0) hipFree(c.w0);
-  }
-  if (n->ones) hipFree(n->ones);
+  for (auto& c : n->convs) c.free();
+  n->ones.free();
   delete n;
 }
 
@@ -929,12 +900,10 @@ int maua_vgg_load(maua_vgg* n, int index, int what, const float* host, size_t co
   MAUA_REQUIRE(n && host, "maua_vgg_load: NULL argument");
   MAUA_REQUIRE(index >= 0 && index < (int)n->convs.size(), "maua_vgg_load: no such convolution");
   hipStream_t st = n->ctx->stream;
-  PConv& c = n->convs[index];
+  PlainConv& c = n->convs[index];
   if (what == 1) {
     MAUA_REQUIRE(count == (size_t)c.Co, "maua_vgg_load: bias: wrong size");
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    MAUA_HIP_CHECK(hipMemcpy(c.bias, host, count * 4, hipMemcpyHostToDevice));
-    return MAUA_OK;
+    return c.load_bias(st, host);
   }
   MAUA_REQUIRE(what == 0, "maua_vgg_load: what must be 0 or 1");
   MAUA_REQUIRE(count == (size_t)c.Co * c.Ci * 9, "maua_vgg_load: weight: wrong size");
@@ -944,26 +913,10 @@ int maua_vgg_load(maua_vgg* n, int index, int what, const float* host, size_t co
     for (int o = 0; o < c.Co; o++)
       for (int i = 0; i < 3; i++)
         for (int k = 0; k < 9; k++) w0[((size_t)i * 9 + k) * c.Co + o] = host[((size_t)o * 3 + i) * 9 + k];
-    MAUA_HIP_CHECK(hipMemcpy(c.w0, w0.data(), w0.size() * 4, hipMemcpyHostToDevice));
+    MAUA_HIP_CHECK(hipMemcpy(c.wt, w0.data(), w0.size() * 4, hipMemcpyHostToDevice));
     return MAUA_OK;
   }
-  // the input-gradient convolution: Wt[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]
-  std::vector<float> wt(count);
-  for (int o = 0; o < c.Co; o++)
-    for (int i = 0; i < c.Ci; i++)
-      for (int k = 0; k < 9; k++) wt[((size_t)i * c.Co + o) * 9 + k] = host[((size_t)o * c.Ci + i) * 9 + (8 - k)];
-  float* tmp;
-  MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-  MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, hipMemcpyHostToDevice));
-  int rc = launch_prep_weights(st, n->dtype, tmp, c.wt, nullptr, c.Co, c.Ci, 3, 1, 0, c.Co, c.Ci);
-  hipStreamSynchronize(st);
-  if (!rc) {
-    hipMemcpy(tmp, wt.data(), count * 4, hipMemcpyHostToDevice);
-    rc = launch_prep_weights(st, n->dtype, tmp, c.wt_t, nullptr, c.Ci, c.Co, 3, 1, 0, c.Ci, c.Co);
-    hipStreamSynchronize(st);
-  }
-  hipFree(tmp);
-  return rc;
+  return c.load_weight(st, n->dtype, host, true);
 }
 
 int maua_vgg_forward(maua_vgg* n, const float* img, int B, int H, int W) {

@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "plain_conv.h"
 
 using namespace maua;
 
@@ -34,13 +35,6 @@ namespace {
 
 constexpr int NCONV = 24;
 constexpr int CS[6] = {64, 128, 128, 256, 256, 512};
-
-struct SConv {
-  int Ci, Co, Cip, Cop;     // real / padded-to-32 channels
-  void *wt = nullptr, *wt_t = nullptr;   // prepared [9][Cop][Cip] and the transposed network's [9][Cip][Cop]
-  float* bias = nullptr;    // [Cop], zero padded
-  float* zero_bias = nullptr;
-};
 
 __device__ __forceinline__ void bil_src(int o, int n, int& i0, int& i1, float& f) {
   // F.interpolate(scale_factor=2, mode="bilinear", align_corners=False): src = (o + 0.5) / 2 - 0.5, clamped at 0
@@ -262,10 +256,9 @@ struct maua_secondary {
   int dtype;
   int conv_dtype;
   size_t esize;
-  SConv conv[NCONV];
+  PlainConv conv[NCONV];   // padded to 32 channels, each with its transposed copy
   float* wemb = nullptr;   // [8] FourierFeatures weight
-  float* ones = nullptr;   // unit styles [bcap][512]
-  int ones_b = 0;
+  UnitStyles ones;         // [bcap][512]
   // activations of the last forward (grow-only): see forward_t for the layout
   size_t cap_px = 0;       // B * H * W
   int B = 0, H = 0, W = 0; // shape of the last forward (0: none)
@@ -340,25 +333,19 @@ int ensure_ws(maua_secondary* n, int B, int H, int W) {
     if (rc) return rc;
     n->cap_px = px;
   }
-  if (B > n->ones_b) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->ones) hipFree(n->ones);
-    n->epoch++;
-    std::vector<float> h((size_t)B * 512, 1.f);
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->ones, h.size() * 4));
-    MAUA_HIP_CHECK(hipMemcpy(n->ones, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    n->ones_b = B;
-  }
-  return MAUA_OK;
+  bool moved = false;
+  const int rc = n->ones.ensure(st, B, 512, &moved);
+  if (moved) n->epoch++;
+  return rc;
 }
 
 // y slice = act(conv3x3(x) + bias): x = all Cip channels of a buffer with xps channels per pixel, y = Cop channels at offset ycoff of
 // a buffer with yps per pixel.  transposed: the input-gradient convolution of the same layer (Cop -> Cip, no bias, no activation)
-int run_conv(maua_secondary* n, const SConv& c, bool transposed, const void* x, int xps, void* y, int yps, int ycoff, int B, int h, int w,
+int run_conv(maua_secondary* n, const PlainConv& c, bool transposed, const void* x, int xps, void* y, int yps, int ycoff, int B, int h, int w,
              bool relu) {
   ConvArgs a{};
   const int Ci = transposed ? c.Cop : c.Cip, Co = transposed ? c.Cip : c.Cop;
-  a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = transposed ? c.wt_t : c.wt; a.s = n->ones; a.d = nullptr;
+  a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = transposed ? c.wt_t : c.wt; a.s = n->ones.p; a.d = nullptr;
   a.noise = nullptr; a.bias = transposed ? c.zero_bias : c.bias; a.y = y; a.y_pstride = yps; a.y_coff = ycoff; a.y_bstride = (long)h * w * yps;
   a.B = B; a.H = h; a.W = w; a.Ci = Ci; a.Co = Co; a.up = 1;
   a.act = relu ? MAUA_ACT_LRELU : MAUA_ACT_LINEAR; a.alpha = relu ? 0.f : 1.f; a.gain = 1.f; a.clamp = -1.f;
@@ -516,19 +503,11 @@ int maua_secondary_create(maua_ctx* ctx, int dtype, maua_secondary** out) {
   n->ctx = ctx; n->conv_dtype = dtype; n->dtype = dtype == MAUA_F32_SPLIT ? MAUA_F32 : dtype; n->esize = n->dtype == MAUA_BF16 ? 2 : 4;
   int ci[NCONV], co[NCONV];
   conv_plan(ci, co);
-  for (int i = 0; i < NCONV; i++) {
-    SConv& c = n->conv[i];
-    c.Ci = ci[i]; c.Co = co[i]; c.Cip = (ci[i] + 31) / 32 * 32; c.Cop = (co[i] + 31) / 32 * 32;
-    const size_t we = (size_t)9 * c.Cop * c.Cip * n->esize;
-    if (hipMalloc(&c.wt, we) != hipSuccess || hipMalloc(&c.wt_t, we) != hipSuccess ||
-        hipMalloc((void**)&c.bias, (size_t)c.Cop * 4) != hipSuccess ||
-        hipMalloc((void**)&c.zero_bias, (size_t)std::max(c.Cop, c.Cip) * 4) != hipSuccess) {
+  for (int i = 0; i < NCONV; i++)
+    if (n->conv[i].alloc(ci[i], co[i], (ci[i] + 31) / 32 * 32, (co[i] + 31) / 32 * 32, n->esize, true)) {
       maua_secondary_destroy(n);
       return fail("maua_secondary_create: out of device memory");
     }
-    hipMemset(c.wt, 0, we); hipMemset(c.wt_t, 0, we);
-    hipMemset(c.bias, 0, (size_t)c.Cop * 4); hipMemset(c.zero_bias, 0, (size_t)std::max(c.Cop, c.Cip) * 4);
-  }
   if (hipMalloc((void**)&n->wemb, 32) != hipSuccess) {
     maua_secondary_destroy(n);
     return fail("maua_secondary_create: out of device memory");
@@ -542,14 +521,9 @@ void maua_secondary_destroy(maua_secondary* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
   free_ws(n);
-  for (auto& c : n->conv) {
-    if (c.wt) hipFree(c.wt);
-    if (c.wt_t) hipFree(c.wt_t);
-    if (c.bias) hipFree(c.bias);
-    if (c.zero_bias) hipFree(c.zero_bias);
-  }
+  for (auto& c : n->conv) c.free();
   if (n->wemb) hipFree(n->wemb);
-  if (n->ones) hipFree(n->ones);
+  n->ones.free();
   delete n;
 }
 
@@ -573,38 +547,14 @@ int maua_secondary_load(maua_secondary* n, int index, int what, const float* hos
     return MAUA_OK;
   }
   MAUA_REQUIRE(index >= 0 && index < NCONV, "maua_secondary_load: no such convolution");
-  SConv& c = n->conv[index];
+  PlainConv& c = n->conv[index];
   if (what == 1) {
     MAUA_REQUIRE(count == (size_t)c.Co, "maua_secondary_load: bias: wrong size");
-    MAUA_HIP_CHECK(hipMemcpy(c.bias, host, count * 4, hipMemcpyHostToDevice));
-    return MAUA_OK;
+    return c.load_bias(st, host);
   }
   MAUA_REQUIRE(what == 0, "maua_secondary_load: what must be 0, 1 or 2");
   MAUA_REQUIRE(count == (size_t)c.Co * c.Ci * 9, "maua_secondary_load: weight: wrong size");
-  // the input-gradient convolution: Wt[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]
-  std::vector<float> wt(count);
-  for (int o = 0; o < c.Co; o++)
-    for (int i = 0; i < c.Ci; i++)
-      for (int k = 0; k < 9; k++) wt[((size_t)i * c.Co + o) * 9 + k] = host[((size_t)o * c.Ci + i) * 9 + (8 - k)];
-  float* tmp;
-  MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-  const size_t we = (size_t)9 * c.Cop * c.Cip * n->esize;
-  MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, hipMemcpyHostToDevice));
-  MAUA_HIP_CHECK(hipMemsetAsync(c.wt, 0, we, st));
-  int rc = launch_prep_weights(st, n->dtype, tmp, c.wt, nullptr, c.Co, c.Ci, 3, 1, 0, c.Cop, c.Cip);
-  hipStreamSynchronize(st);
-  if (!rc) {
-    MAUA_HIP_CHECK(hipMemcpy(tmp, wt.data(), count * 4, hipMemcpyHostToDevice));
-    MAUA_HIP_CHECK(hipMemsetAsync(c.wt_t, 0, we, st));
-    rc = launch_prep_weights(st, n->dtype, tmp, c.wt_t, nullptr, c.Ci, c.Co, 3, 1, 0, c.Cip, c.Cop);
-    if (!rc && n->conv_dtype == MAUA_F32_SPLIT) {   // both copies in the split form the matrix cores read
-      rc = launch_f32_split_inplace(st, c.wt, (long)9 * c.Cop * c.Cip);
-      if (!rc) rc = launch_f32_split_inplace(st, c.wt_t, (long)9 * c.Cop * c.Cip);
-    }
-    hipStreamSynchronize(st);
-  }
-  hipFree(tmp);
-  return rc;
+  return c.load_weight(st, n->dtype, host, true, n->conv_dtype == MAUA_F32_SPLIT);
 }
 
 int maua_secondary_forward(maua_secondary* n, const float* x, const float* t, int B, int H, int W, float* v_out, float* pred_out,

@@ -26,16 +26,11 @@
 
 #include "common.h"
 #include "internal.h"
+#include "plain_conv.h"
 
 using namespace maua;
 
 namespace {
-
-struct PlainConv {
-  int Ci, Co, Cip, Cop;   // real / padded-to-32 channel counts
-  void* wt = nullptr;     // prepared [9][Cop][Cip]
-  float* bias = nullptr;  // [Cop] (zero padded)
-};
 
 // dst[p][c] = a * x[p][c] + b * y[p][c] over n_pix pixels x C channels (16-byte pieces), each operand with its own pixel
 // stride; y may be NULL (b ignored).  The RRDB-level residual and the block-input copy.
@@ -123,8 +118,7 @@ struct maua_rrdbnet {
   PlainConv conv_first, conv_body, conv_up1, conv_up2, conv_hr, conv_last;
   std::vector<PlainConv> rdb;  // [block][3 rdb][5 conv]
   int use_dma = 1;             // bf16 trunk convolutions on the LDS-direct kernel (MAUA_RRDB_DMA=0: the generic kernel)
-  float* ones = nullptr;       // unit styles [bcap][max Ci]
-  int ones_b = 0;
+  UnitStyles ones;             // [bcap][max Ci]
   // workspace (grow-only)
   size_t cap_px = 0;           // B * H * W the buffers were sized for
   void *in32 = nullptr, *feat0 = nullptr, *dense[3] = {nullptr, nullptr, nullptr}, *f1 = nullptr, *up1 = nullptr,
@@ -132,26 +126,26 @@ struct maua_rrdbnet {
 };
 
 static int alloc_conv(PlainConv& c, int Ci, int Co, size_t esize) {
-  c.Ci = Ci; c.Co = Co; c.Cip = (Ci + 31) / 32 * 32; c.Cop = (Co + 31) / 32 * 32;
+  int Cip = (Ci + 31) / 32 * 32;
+  const int Cop = (Co + 31) / 32 * 32;
   // bf16: K in whole 64-channel chunks (zero weights beyond Ci) so that the trunk runs on the LDS-direct kernel; the
   // channels read beyond Ci belong to the same dense-block buffer (zero-initialised, only ever finite)
   // (32 output channels: the narrow tile also takes an odd number of 32-channel chunks, so 96 / 160-channel layers are not padded)
-  if (esize == 2 && Ci >= 64 && !(c.Cop == 32 && Ci >= 96)) c.Cip = (Ci + 63) / 64 * 64;
-  MAUA_HIP_CHECK(hipMalloc(&c.wt, (size_t)9 * c.Cop * c.Cip * esize));
-  MAUA_HIP_CHECK(hipMemset(c.wt, 0, (size_t)9 * c.Cop * c.Cip * esize));
-  MAUA_HIP_CHECK(hipMalloc((void**)&c.bias, (size_t)c.Cop * 4));
-  MAUA_HIP_CHECK(hipMemset(c.bias, 0, (size_t)c.Cop * 4));
-  return MAUA_OK;
+  if (esize == 2 && Ci >= 64 && !(Cop == 32 && Ci >= 96)) Cip = (Ci + 63) / 64 * 64;
+  return c.alloc(Ci, Co, Cip, Cop, esize, false);
 }
 
-static void free_ws(maua_rrdbnet* n) {
-  void** ps[] = {&n->in32, &n->feat0, &n->dense[0], &n->dense[1], &n->dense[2], &n->f1, &n->up1, &n->f2, &n->up2, &n->f3,
-                 &n->f4, &n->f5};
+// both up-scalers: the capacity goes first, so that a growth that fails half-way leaves "nothing allocated" behind it
+static void free_ws(size_t& cap_px, std::initializer_list<void**> ps) {
+  cap_px = 0;
   for (void** p : ps) {
-    if (*p) hipFree(*p);
+    hipFree(*p);
     *p = nullptr;
   }
-  n->cap_px = 0;
+}
+static void free_ws(maua_rrdbnet* n) {
+  free_ws(n->cap_px, {&n->in32, &n->feat0, &n->dense[0], &n->dense[1], &n->dense[2], &n->f1, &n->up1, &n->f2, &n->up2, &n->f3,
+                      &n->f4, &n->f5});
 }
 
 extern "C" {
@@ -192,13 +186,9 @@ void maua_rrdb_destroy(maua_rrdbnet* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
   free_ws(n);
-  auto fc = [](PlainConv& c) {
-    if (c.wt) hipFree(c.wt);
-    if (c.bias) hipFree(c.bias);
-  };
-  fc(n->conv_first); fc(n->conv_body); fc(n->conv_up1); fc(n->conv_up2); fc(n->conv_hr); fc(n->conv_last);
-  for (auto& c : n->rdb) fc(c);
-  if (n->ones) hipFree(n->ones);
+  for (PlainConv* c : {&n->conv_first, &n->conv_body, &n->conv_up1, &n->conv_up2, &n->conv_hr, &n->conv_last}) c->free();
+  for (auto& c : n->rdb) c.free();
+  n->ones.free();
   delete n;
 }
 
@@ -225,19 +215,11 @@ int maua_rrdb_load(maua_rrdbnet* n, const char* name, const float* host, size_t 
   hipStream_t st = n->ctx->stream;
   if (par == "bias") {
     if (count != (size_t)c->Co) return fail("maua_rrdb_load: " + s + ": wrong size");
-    MAUA_HIP_CHECK(hipMemcpy(c->bias, host, count * 4, hipMemcpyHostToDevice));
-    return MAUA_OK;
+    return c->load_bias(st, host);
   }
   if (par != "weight") return fail("maua_rrdb_load: unknown parameter name: " + s);
   if (count != (size_t)c->Co * c->Ci * 9) return fail("maua_rrdb_load: " + s + ": wrong size");
-  float* tmp;
-  MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-  MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, hipMemcpyHostToDevice));
-  MAUA_HIP_CHECK(hipMemsetAsync(c->wt, 0, (size_t)9 * c->Cop * c->Cip * n->esize, st));
-  int rc = launch_prep_weights(st, n->dtype, tmp, c->wt, nullptr, c->Co, c->Ci, 3, 1, 0, c->Cop, c->Cip);
-  hipStreamSynchronize(st);
-  hipFree(tmp);
-  return rc;
+  return c->load_weight(st, n->dtype, host, false);
 }
 
 }  // extern "C"
@@ -266,20 +248,13 @@ int forward_t(maua_rrdbnet* n, const float* img, int B, int H, int W, int do_cla
     MAUA_HIP_CHECK(hipMalloc(&n->f4, px * 16 * F * es));
     n->cap_px = px;
   }
-  if (B > n->ones_b) {  // unit styles: [B][D] floats of 1
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->ones) hipFree(n->ones);
-    std::vector<float> h((size_t)B * D, 1.f);
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->ones, h.size() * 4));
-    MAUA_HIP_CHECK(hipMemcpy(n->ones, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    n->ones_b = B;
-  }
+  if (int rc = n->ones.ensure(st, B, D)) return rc;
   // a plain 3x3 convolution on channel slices: x = first c.Cip channels of a buffer with xps channels per pixel,
   // y = c.Cop channels at channel offset ycoff of a buffer with yps per pixel (+ optional residual, yps-strided source)
   auto conv = [&](const PlainConv& c, const void* x, int xps, void* y, int yps, int ycoff, int h, int w, bool lrelu,
                   float gain, const void* res, int rps, const void* res2 = nullptr, int r2ps = 0, float res_gain = 1.f) -> int {
     ConvArgs a{};
-    a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = c.wt; a.s = n->ones; a.d = nullptr;
+    a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = c.wt; a.s = n->ones.p; a.d = nullptr;
     a.noise = nullptr; a.bias = c.bias; a.y = y; a.y_pstride = yps; a.y_coff = ycoff; a.y_bstride = (long)h * w * yps;
     a.B = B; a.H = h; a.W = w; a.Ci = c.Cip; a.Co = c.Cop; a.up = 1;
     a.act = lrelu ? MAUA_ACT_LRELU : MAUA_ACT_LINEAR; a.alpha = 0.2f; a.gain = gain; a.clamp = -1.f;
@@ -347,7 +322,7 @@ int forward_t(maua_rrdbnet* n, const float* img, int B, int H, int W, int do_cla
   auto conv_up = [&](const PlainConv& c, const void* src, void** tmp, void* dst, int h, int w) -> int {   // h, w: source size
     if (n->use_dma && dma_conv_narrow_supported(n->dtype, c.Cip, c.Cop, 2 * h, 2 * w)) {
       ConvArgs a{};
-      a.x = src; a.x_bstride = (long)h * w * F; a.x_pstride = F; a.x_up2 = 1; a.w = c.wt; a.s = n->ones; a.bias = c.bias;
+      a.x = src; a.x_bstride = (long)h * w * F; a.x_pstride = F; a.x_up2 = 1; a.w = c.wt; a.s = n->ones.p; a.bias = c.bias;
       a.y = dst; a.y_pstride = F; a.y_bstride = (long)4 * h * w * F;
       a.B = B; a.H = 2 * h; a.W = 2 * w; a.Ci = c.Cip; a.Co = c.Cop; a.up = 1;
       a.act = MAUA_ACT_LRELU; a.alpha = 0.2f; a.gain = 1.f; a.clamp = -1.f;
@@ -365,7 +340,7 @@ int forward_t(maua_rrdbnet* n, const float* img, int B, int H, int W, int do_cla
     // conv_last writes the image itself (clamp, f32 planes / u8 frame in its epilogue): no 32-channel tensor, no output pass
     const PlainConv& c = n->conv_last;
     ConvArgs a{};
-    a.x = n->f4; a.x_bstride = (long)16 * H * W * F; a.x_pstride = F; a.w = c.wt; a.s = n->ones; a.bias = c.bias;
+    a.x = n->f4; a.x_bstride = (long)16 * H * W * F; a.x_pstride = F; a.w = c.wt; a.s = n->ones.p; a.bias = c.bias;
     a.B = B; a.H = 4 * H; a.W = 4 * W; a.Ci = c.Cip; a.Co = 32; a.up = 1;
     a.act = MAUA_ACT_LINEAR; a.alpha = 0.2f; a.gain = 1.f; a.clamp = -1.f;
     a.img_f32 = out_f32; a.img_u8 = out_u8; a.img_clamp = do_clamp; a.img_h = oh; a.img_w = ow;
@@ -447,11 +422,12 @@ struct maua_srvgg {
   size_t esize;
   std::vector<PlainConv> convs;   // num_conv + 2
   std::vector<float*> slopes;     // num_conv + 1 PReLU vectors [num_feat]
-  float* ones = nullptr;
-  int ones_b = 0;
+  UnitStyles ones;
   size_t cap_px = 0;
   void *in32 = nullptr, *fa = nullptr, *fb = nullptr, *flast = nullptr;
 };
+
+static void free_ws(maua_srvgg* n) { free_ws(n->cap_px, {&n->in32, &n->fa, &n->fb, &n->flast}); }
 
 extern "C" {
 
@@ -486,14 +462,10 @@ int maua_srvgg_create(maua_ctx* ctx, int num_feat, int num_conv, int upscale, in
 void maua_srvgg_destroy(maua_srvgg* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  for (auto& c : n->convs) {
-    if (c.wt) hipFree(c.wt);
-    if (c.bias) hipFree(c.bias);
-  }
-  for (float* p : n->slopes)
-    if (p) hipFree(p);
-  for (void* p : {n->in32, n->fa, n->fb, n->flast, (void*)n->ones})
-    if (p) hipFree(p);
+  free_ws(n);
+  for (auto& c : n->convs) c.free();
+  for (float* p : n->slopes) hipFree(p);
+  n->ones.free();
   delete n;
 }
 
@@ -514,19 +486,11 @@ int maua_srvgg_load(maua_srvgg* n, const char* name, const float* host, size_t c
   PlainConv& c = n->convs[idx / 2];
   if (!strcmp(par, "bias")) {
     if (count != (size_t)c.Co) return fail(std::string("maua_srvgg_load: ") + name + ": wrong size");
-    MAUA_HIP_CHECK(hipMemcpy(c.bias, host, count * 4, hipMemcpyHostToDevice));
-    return MAUA_OK;
+    return c.load_bias(st, host);
   }
   if (strcmp(par, "weight")) return fail(std::string("maua_srvgg_load: unknown parameter name: ") + name);
   if (count != (size_t)c.Co * c.Ci * 9) return fail(std::string("maua_srvgg_load: ") + name + ": wrong size");
-  float* tmp;
-  MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-  MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, hipMemcpyHostToDevice));
-  MAUA_HIP_CHECK(hipMemsetAsync(c.wt, 0, (size_t)9 * c.Cop * c.Cip * n->esize, st));
-  int rc = launch_prep_weights(st, n->dtype, tmp, c.wt, nullptr, c.Co, c.Ci, 3, 1, 0, c.Cop, c.Cip);
-  hipStreamSynchronize(st);
-  hipFree(tmp);
-  return rc;
+  return c.load_weight(st, n->dtype, host, false);
 }
 
 }  // extern "C"
@@ -541,24 +505,17 @@ int srvgg_forward_t(maua_srvgg* n, const float* img, int B, int H, int W, int do
   const int CL = n->convs.back().Cop;
   if (px > n->cap_px) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    for (void** p : {&n->in32, &n->fa, &n->fb, &n->flast}) { if (*p) hipFree(*p); *p = nullptr; }
+    free_ws(n);
     MAUA_HIP_CHECK(hipMalloc(&n->in32, px * 32 * es));
     MAUA_HIP_CHECK(hipMalloc(&n->fa, px * F * es));
     MAUA_HIP_CHECK(hipMalloc(&n->fb, px * F * es));
     MAUA_HIP_CHECK(hipMalloc(&n->flast, px * CL * es));
     n->cap_px = px;
   }
-  if (B > n->ones_b) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->ones) hipFree(n->ones);
-    std::vector<float> h((size_t)B * std::max(F, 32), 1.f);
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->ones, h.size() * 4));
-    MAUA_HIP_CHECK(hipMemcpy(n->ones, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    n->ones_b = B;
-  }
+  if (int rc = n->ones.ensure(st, B, std::max(F, 32))) return rc;
   auto conv = [&](const PlainConv& c, const void* x, void* y, const float* slopes, bool activated) -> int {
     ConvArgs a{};
-    a.x = x; a.x_bstride = (long)H * W * c.Cip; a.w = c.wt; a.s = n->ones; a.bias = c.bias; a.y = y;
+    a.x = x; a.x_bstride = (long)H * W * c.Cip; a.w = c.wt; a.s = n->ones.p; a.bias = c.bias; a.y = y;
     a.B = B; a.H = H; a.W = W; a.Ci = c.Cip; a.Co = c.Cop; a.up = 1; a.gain = 1.f; a.clamp = -1.f; a.alpha = 0.1f;
     a.act = !activated ? MAUA_ACT_LINEAR : (n->act == 1 ? MAUA_ACT_RELU : MAUA_ACT_LRELU);
     a.prelu = activated && n->act == 0 ? slopes : nullptr;

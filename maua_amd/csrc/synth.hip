@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "plain_conv.h"
 
 using namespace maua;
 
@@ -82,7 +83,7 @@ struct maua_synth {
   int dual_store = 1;  // ... whose toRGB is a separate pass (512 channels): plain + style-scaled output in one epilogue (no premod pass)
   int tconv_dma = 1;   // the up-layers' transposed conv on LDS-direct loads (main block; pre-modulated input) + the dedicated
                        // edge kernel for the last row / column (0: the register-staged transposed conv)
-  float* ones = nullptr;   // [Bcap][max channels] unit styles (kernels that take already-modulated input)
+  UnitStyles ones;         // [Bcap][max channels] (kernels that take already-modulated input)
   void* xm = nullptr;      // [Bcap] pre-modulated copy of an up-layer's input when its producer could not scale it
   void* tbuf = nullptr;  // [Bcap] transposed-conv tensor of the largest up-layer
   void* lowres_xm = nullptr;   // [Bcap] modconv_lowres workspaces (premodulated input, split-K partial sums)
@@ -166,7 +167,7 @@ static int free_workspace(maua_synth* n) {
   for (int i = 0; i < 2; i++) {
     release(n->act[i]); release(n->img[i]); release(n->rgb_tmp[i]);
   }
-  release(n->style_table_dev); release(n->tbuf); release(n->ones); release(n->xm);
+  release(n->style_table_dev); release(n->tbuf); n->ones.free(); release(n->xm);
   release(n->lowres_xm); release(n->lowres_ws); release(n->const_rs);
   n->bcap = 0;
   return MAUA_OK;
@@ -217,9 +218,7 @@ static int ensure_workspace(maua_synth* n, int B) {
       //  sized for any up-layer so that hooks / options can fall back to it)
       if (tconv_dma_fits(n, c)) xm_elems = std::max(xm_elems, (size_t)c.ih * c.iw * c.Ci);
     }
-    std::vector<float> h1((size_t)B * maxc, 1.f);
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->ones, h1.size() * sizeof(float)));
-    MAUA_HIP_CHECK(hipMemcpy(n->ones, h1.data(), h1.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = n->ones.ensure(n->ctx->stream, B, maxc)) return rc;
     if (xm_elems) MAUA_HIP_CHECK(hipMalloc(&n->xm, (size_t)B * xm_elems * n->esize));
   }
   if (lx) MAUA_HIP_CHECK(hipMalloc(&n->lowres_xm, lx));
@@ -628,14 +627,12 @@ int maua_synth_load(maua_synth* n, const char* name, const float* host, size_t c
     if (blk != 0) return fail("maua_synth_load: only block 0 has a const input");
     int C = n->convs[0].Ci;
     if (count != (size_t)C * 16) return fail("maua_synth_load: bs.0.const: wrong size");
-    float* tmp;
-    MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-    MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, g_load_kind));
-    int rc = n->dtype == MAUA_BF16   ? launch_nchw_to_nhwc<float, bf16_t>(st, tmp, n->const_x, 1, C, 16, C)
-             : n->dtype == MAUA_F16 ? launch_nchw_to_nhwc<float, f16_t>(st, tmp, n->const_x, 1, C, 16, C)
-                                    : launch_nchw_to_nhwc<float, float>(st, tmp, n->const_x, 1, C, 16, C);
+    DevTemp tmp;
+    if (int rc = tmp.stage(host, count, g_load_kind)) return rc;
+    int rc = n->dtype == MAUA_BF16   ? launch_nchw_to_nhwc<float, bf16_t>(st, tmp.p, n->const_x, 1, C, 16, C)
+             : n->dtype == MAUA_F16 ? launch_nchw_to_nhwc<float, f16_t>(st, tmp.p, n->const_x, 1, C, 16, C)
+                                    : launch_nchw_to_nhwc<float, float>(st, tmp.p, n->const_x, 1, C, 16, C);
     hipStreamSynchronize(st);
-    hipFree(tmp);
     return rc;
   }
   size_t dot = rest.find('.');
@@ -666,20 +663,18 @@ int maua_synth_load(maua_synth* n, const char* name, const float* host, size_t c
   if (par == "weight") {
     size_t expect = (size_t)c->Co * c->Ci * 9;
     if (count != expect) return fail("maua_synth_load: " + s + ": wrong size");
-    float* tmp;
-    MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-    MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, g_load_kind));
+    DevTemp tmp;
+    if (int rc = tmp.stage(host, count, g_load_kind)) return rc;
     // F16 networks: the reference's FP16 pre-normalisation of the weight (ops.py:161-163; every convolution of the synthesis
     // network demodulates) - the styles' half is applied per batch (launch_styles)
-    if (n->dtype == MAUA_F16)
-      if (int rc0 = launch_f16_prenorm_weights(st, tmp, tmp, c->Co, c->Ci, 9)) { hipFree(tmp); return rc0; }
-    int rc = launch_prep_weights(st, n->dtype, tmp, c->wt, c->wsq, c->Co, c->Ci, 3, c->up,
-                                 (c->up == 2) ? (n->nv_compat & 1) : 0, c->Co, c->Ci);
+    int rc = n->dtype == MAUA_F16 ? launch_f16_prenorm_weights(st, tmp.p, tmp.p, c->Co, c->Ci, 9) : MAUA_OK;
+    if (!rc)
+      rc = launch_prep_weights(st, n->dtype, tmp.p, c->wt, c->wsq, c->Co, c->Ci, 3, c->up, (c->up == 2) ? (n->nv_compat & 1) : 0,
+                               c->Co, c->Ci);
     if (!rc && c->up == 2)
-      rc = launch_prep_tconv_weights(st, n->dtype, tmp, c->wt_t, c->Co, c->Ci, n->nv_compat & 1);
-    if (!rc && c->wt_h) rc = launch_prep_upwalk_weights(st, tmp, c->wt_h, c->Co, c->Ci, n->nv_compat & 1, n->dtype);
+      rc = launch_prep_tconv_weights(st, n->dtype, tmp.p, c->wt_t, c->Co, c->Ci, n->nv_compat & 1);
+    if (!rc && c->wt_h) rc = launch_prep_upwalk_weights(st, tmp.p, c->wt_h, c->Co, c->Ci, n->nv_compat & 1, n->dtype);
     hipStreamSynchronize(st);
-    hipFree(tmp);
     return rc;
   }
   return fail("maua_synth_load: unknown parameter name: " + s);
@@ -816,7 +811,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
             a.x = n->xm;
             a.x_bstride = (long)c.ih * c.iw * c.Ci;
           }
-          if (reads_premod(s.route)) a.s = n->ones;
+          if (reads_premod(s.route)) a.s = n->ones.p;
           if (s.route == Route::TconvFir) {  // the whole layer in one kernel: t never leaves LDS (bit-identical output)
             if (int rc = launch_tconv_fir(st, a, u, n->dtype, n->tconv_walk, 0)) return rc;
             prof_mark(n);  // (two profile slots like the two-launch path: the second measures ~0)

@@ -93,16 +93,6 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restric
   }
 }
 
-// dst[i][o][k] = src[o][i][kk - 1 - k]: a convolution's (kk = 9) / linear layer's (kk = 1) weight for its input gradient
-__global__ __launch_bounds__(256) void transpose_flip_kernel(const float* __restrict__ src, float* __restrict__ dst, int Co, int Ci, int kk) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long)Co * Ci * kk) return;
-  const int k = (int)(idx % kk);
-  const long oi = idx / kk;
-  const int i = (int)(oi % Ci), o = (int)(oi / Ci);
-  dst[((long)i * Co + o) * kk + (kk - 1 - k)] = src[idx];
-}
-
 }  // namespace
 
 namespace {
@@ -123,10 +113,8 @@ int make_gn(maua_unet* n, UGN& g, int C, const std::string& name) {
   n->params[name + ".bias"] = PRef{P_GN_B, &g};
   return MAUA_OK;
 }
-int make_conv(maua_unet* n, UConv& c, int Ci, int Co, const std::string& name) {
-  c.Ci = Ci; c.Co = Co; c.Cip = (Ci + 31) / 32 * 32; c.Cop = (Co + 31) / 32 * 32;
-  if (int rc = dev_alloc(n, &c.wt, (size_t)9 * c.Cop * c.Cip * n->esize)) return rc;
-  if (int rc = dev_alloc(n, &c.bias, (size_t)c.Cop * 4)) return rc;
+int make_conv(maua_unet* n, PlainConv& c, int Ci, int Co, const std::string& name) {
+  if (int rc = c.alloc(Ci, Co, (Ci + 31) / 32 * 32, (Co + 31) / 32 * 32, n->esize, false)) return rc;   // (freed by maua_unet_destroy)
   n->params[name + ".weight"] = PRef{P_CONV_W, &c};
   n->params[name + ".bias"] = PRef{P_CONV_B, &c};
   return MAUA_OK;
@@ -322,7 +310,7 @@ struct Runner {
   }
 
   // y = conv3x3(x) + bias (+ res); x, y, res dense NHWC [B][H][W][.]
-  int conv(const UConv& c, const T* x, T* y, int H, int W, const T* res, float* psum = nullptr) {
+  int conv(const PlainConv& c, const T* x, T* y, int H, int W, const T* res, float* psum = nullptr) {
     const size_t ws_need = gather_conv_supported(n->dtype, c.Cip, c.Cop, H, W) ? gather_conv_workspace(n->dtype, B, H, W, c.Cip, c.Cop) : 0;
     if (plan) {
       if (ws_need > gather_ws_bytes) gather_ws_bytes = ws_need;
@@ -344,7 +332,7 @@ struct Runner {
       return launch_modconv_dma(st, a);
     }
     if (r.kernel == 3) return launch_conv_gather(st, n->dtype, a, gather_ws);
-    a.s = n->ones;
+    a.s = n->ones.p;
     return launch_modconv3x3(st, n->dtype, a);
   }
 
@@ -540,10 +528,10 @@ struct Runner {
   size_t n_gather_bytes = 0;
 
   // ------------------------------------------------------------------------------------------ input gradient (guided.py:250-272)
-  // dx = conv3x3(dy) with the transposed, spatially flipped kernel (UConv.wt_t), no bias, optional residual
-  int conv_t(const UConv& c, const T* dy, T* dx, int H, int W, const T* res) {
-    UConv v;
-    v.Ci = c.Co; v.Co = c.Ci; v.Cip = c.Cop; v.Cop = c.Cip; v.wt = c.wt_t; v.bias = n->zero_bias;
+  // dx = conv3x3(dy) with the transposed, spatially flipped kernel (PlainConv.wt_t), no bias, optional residual
+  int conv_t(const PlainConv& c, const T* dy, T* dx, int H, int W, const T* res) {
+    PlainConv v;
+    v.Ci = c.Co; v.Co = c.Ci; v.Cip = c.Cop; v.Cop = c.Cip; v.wt = c.wt_t; v.bias = c.zero_bias;
     return conv(v, dy, dx, H, W, res);
   }
   // c [M][N] = a [M][K] w_t^T (+ res), w_t rows [n0, n0 + N) of a transposed linear weight [Kin][Nout]
@@ -694,15 +682,7 @@ int run_forward(maua_unet* n, const float* x, const float* t, int B, int H, int 
     n->gather_bytes = pr.gather_ws_bytes;
     n->planned_key = key;
   }
-  if (B > n->ones_b) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    std::vector<float> h((size_t)B * n->max_ch, 1.f);
-    float* p;
-    MAUA_HIP_CHECK(hipMalloc((void**)&p, h.size() * 4));
-    MAUA_HIP_CHECK(hipMemcpy(p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    if (n->ones) hipFree(n->ones);
-    n->ones = p; n->ones_b = B;
-  }
+  if (int rc = n->ones.ensure(st, B, n->max_ch)) return rc;
   n->arena.plan = false; n->arena.top = 0;
   Runner<T> r(n, st, B, false, keep);
   r.n_gather_bytes = n->gather_bytes;
@@ -749,7 +729,7 @@ int maua::unet_emb_rows(maua_unet* n, hipStream_t st, const float* t, int rows, 
   return MAUA_OK;
 }
 
-bool maua::unet_planned(const maua_unet* n, int B, int H, int W) { return n->planned_key == shape_key(B, H, W) && B <= n->ones_b; }
+bool maua::unet_planned(const maua_unet* n, int B, int H, int W) { return n->planned_key == shape_key(B, H, W) && B <= n->ones.b; }
 
 extern "C" {
 
@@ -787,8 +767,10 @@ void maua_unet_destroy(maua_unet* n) {
   hipStreamSynchronize(n->ctx->stream);
   n->smp.release();
   for (void* p : n->owned) hipFree(p);
+  n->conv_in.free(); n->conv_out.free();
+  for (auto& r : n->res) { r.c1.free(); r.c2.free(); }
   if (n->arena.base) hipFree(n->arena.base);
-  if (n->ones) hipFree(n->ones);
+  n->ones.free();
   delete n;
 }
 
@@ -814,11 +796,6 @@ int maua_unet_set_option(maua_unet* n, const char* key, int value) {
   }
   if (!strcmp(key, "vjp")) {   // 1: maua_unet_load also prepares the transposed weights maua_unet_vjp convolves / multiplies with
     MAUA_REQUIRE(value == 0 || value == 1, "maua_unet_set_option: vjp is 0 or 1");
-    if (value && !n->zero_bias) {
-      int mp = 32;
-      for (auto& r : n->res) mp = std::max(mp, std::max(r.c1.Cip, r.c1.Cop));
-      if (int rc = dev_alloc(n, &n->zero_bias, (size_t)mp * 4)) return rc;
-    }
     n->vjp = value;
     return MAUA_OK;
   }
@@ -848,10 +825,9 @@ int maua_unet_load(maua_unet* n, const char* name, const float* host, size_t cou
       return MAUA_OK;
     }
     case P_CONV_B: {
-      UConv* c = (UConv*)p.obj;
+      PlainConv* c = (PlainConv*)p.obj;
       if (count != (size_t)c->Co) return wrong();
-      MAUA_HIP_CHECK(hipMemcpy(c->bias, host, count * 4, hipMemcpyHostToDevice));
-      return MAUA_OK;
+      return c->load_bias(st, host);
     }
     case P_LIN_B: {
       ULin* l = (ULin*)p.obj;
@@ -866,52 +842,17 @@ int maua_unet_load(maua_unet* n, const char* name, const float* host, size_t cou
       return MAUA_OK;
     }
     case P_CONV_W: {
-      UConv* c = (UConv*)p.obj;
+      PlainConv* c = (PlainConv*)p.obj;
       if (count != (size_t)c->Co * c->Ci * 9) return wrong();
-      float* tmp;
-      MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-      MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, hipMemcpyHostToDevice));
-      MAUA_HIP_CHECK(hipMemsetAsync(c->wt, 0, (size_t)9 * c->Cop * c->Cip * n->esize, st));
-      int rc = launch_prep_weights(st, n->dtype, tmp, c->wt, nullptr, c->Co, c->Ci, 3, 1, 0, c->Cop, c->Cip);
-      if (!rc && n->vjp) {
-        // the input-gradient convolution: Wt[ci][co][ky][kx] = W[co][ci][2 - ky][2 - kx]
-        float* tt = nullptr;
-        if (hipMalloc((void**)&tt, count * 4) != hipSuccess) { hipFree(tmp); return fail("maua_unet_load: out of device memory"); }
-        if (!c->wt_t) rc = dev_alloc(n, &c->wt_t, (size_t)9 * c->Cop * c->Cip * n->esize);
-        if (!rc) {
-          hipLaunchKernelGGL(transpose_flip_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, tmp, tt, c->Co, c->Ci, 9);
-          hipMemsetAsync(c->wt_t, 0, (size_t)9 * c->Cop * c->Cip * n->esize, st);
-          rc = launch_prep_weights(st, n->dtype, tt, c->wt_t, nullptr, c->Ci, c->Co, 3, 1, 0, c->Cip, c->Cop);
-        }
-        hipStreamSynchronize(st);
-        hipFree(tt);
-      }
-      hipStreamSynchronize(st);
-      hipFree(tmp);
-      return rc;
+      return c->load_weight(st, n->dtype, host, n->vjp != 0);
     }
     case P_LIN_W: {
       ULin* l = (ULin*)p.obj;
       if (count != (size_t)l->N * l->K) return wrong();
-      float* tmp;
-      MAUA_HIP_CHECK(hipMalloc((void**)&tmp, count * 4));
-      MAUA_HIP_CHECK(hipMemcpy(tmp, host, count * 4, hipMemcpyHostToDevice));
-      // a k = 1 "convolution": [N][K] rows, converted to the network dtype
-      int rc = launch_prep_weights(st, n->dtype, tmp, l->w, nullptr, l->N, l->K, 1, 1, 0, l->N, l->K);
-      if (!rc && n->vjp) {
-        float* tt = nullptr;
-        if (hipMalloc((void**)&tt, count * 4) != hipSuccess) { hipFree(tmp); return fail("maua_unet_load: out of device memory"); }
-        if (!l->w_t) rc = dev_alloc(n, &l->w_t, (size_t)l->N * l->K * n->esize);
-        if (!rc) {
-          hipLaunchKernelGGL(transpose_flip_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, tmp, tt, l->N, l->K, 1);
-          rc = launch_prep_weights(st, n->dtype, tt, l->w_t, nullptr, l->K, l->N, 1, 1, 0, l->K, l->N);
-        }
-        hipStreamSynchronize(st);
-        hipFree(tt);
-      }
-      hipStreamSynchronize(st);
-      hipFree(tmp);
-      return rc;
+      if (n->vjp && !l->w_t)
+        if (int rc = dev_alloc(n, &l->w_t, (size_t)l->N * l->K * n->esize)) return rc;
+      // a k = 1 "convolution": [N][K] rows, converted to the network dtype (and [K][N] for the input-gradient GEMM)
+      return load_weight(st, n->dtype, host, l->N, l->K, 1, l->N, l->K, l->w, n->vjp ? l->w_t : nullptr, false);
     }
   }
   return MAUA_ERR;

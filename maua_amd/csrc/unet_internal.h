@@ -6,14 +6,15 @@
 
 #include "common.h"
 #include "internal.h"
+#include "plain_conv.h"
 
 namespace maua {
 
 // ----------------------------------------------------------------------------------------------------- parameters
 struct UGN { int C = 0; float* gamma = nullptr; float* beta = nullptr; };
-struct UConv { int Ci = 0, Co = 0, Cip = 0, Cop = 0; void* wt = nullptr; float* bias = nullptr; void* wt_t = nullptr; };   // wt_t: the input-gradient convolution (option "vjp")
-struct ULin { int K = 0, N = 0; void* w = nullptr; float* bias = nullptr; void* w_t = nullptr; };   // w_t [K][N]: the input-gradient GEMM
-struct URes { int Cin, Cout, updown; UGN n1; UConv c1; int emb_off; UGN n2; UConv c2; bool skip; ULin sk; };
+// (the 3x3 convolutions are PlainConv, padded to 32 channels; wt_t exists once a weight was loaded under option "vjp")
+struct ULin{ int K = 0, N = 0; void* w = nullptr; float* bias = nullptr; void* w_t = nullptr; };   // w_t [K][N]: the input-gradient GEMM
+struct URes { int Cin, Cout, updown; UGN n1; PlainConv c1; int emb_off; UGN n2; PlainConv c2; bool skip; ULin sk; };
 struct UAttn { int C, heads; UGN n; ULin qkv, proj; };
 struct ULayer { int kind; int idx; };  // 0 conv_in, 1 res, 2 attn
 struct UBlock { std::vector<ULayer> layers; int out_ch = 0; };
@@ -56,7 +57,7 @@ struct maua_unet {
   std::vector<float> mult;
   std::vector<int> attn_ds;
   int emb_dim;
-  maua::UConv conv_in, conv_out;
+  maua::PlainConv conv_in, conv_out;
   maua::UGN out_norm;
   std::vector<maua::URes> res;
   std::vector<maua::UAttn> attn;
@@ -70,8 +71,8 @@ struct maua_unet {
   int emb_total = 0;
   std::unordered_map<std::string, maua::PRef> params;
   std::vector<void*> owned;
-  float* ones = nullptr;
-  int ones_b = 0, max_ch = 0;
+  maua::UnitStyles ones;   // [bcap][max_ch]
+  int max_ch = 0;
   maua::Arena arena;
   size_t planned_key = 0;  // B, H, W the arena was planned for
   size_t gather_bytes = 0; // split-K workspace of the gather GEMM at that shape
@@ -80,7 +81,6 @@ struct maua_unet {
   const float* emb_row = nullptr;    // non-NULL during a sampler-loop forward: this step's row (all samples share the timestep)
   // input gradient (maua_unet_forward_keep + maua_unet_vjp; option "vjp" = 1 before the weights are loaded)
   int vjp = 0;
-  float* zero_bias = nullptr;        // [max padded channels] zeros: the gradient convolutions have no bias
   std::vector<maua::TapeOp> tape;
   bool tape_valid = false;           // the arena still holds the kept forward the tape describes
   int tape_B = 0, tape_H = 0, tape_W = 0;

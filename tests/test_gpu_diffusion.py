@@ -437,6 +437,38 @@ def test_secondary_model_vjp_matches_autograd_on_the_oracle():
         net.vjp(torch.zeros(1, 3, 32, 32))     # not the shape of the last forward
 
 
+@pytest.mark.parametrize("dt,exact", [(torch.float32, False), (torch.bfloat16, True)])
+def test_secondary_reload_writes_in_place(dt, exact):
+    """MAUA_F32_SPLIT and bf16, B = 1 at 32 x 32 (first layer Ci 19 -> 32, last layer Co 3 -> 32: both padded): weights A, weights B,
+    weights A again loaded into ONE handle back to back (maua_secondary_load on the live handle), forward and vjp after each.  The
+    third v and gradient are the first bit for bit - every load zeroes both prepared buffers and rewrites them whole (the forward's
+    and the transposed network's, split again where the dtype asks), and one load's staging leaves nothing for the next - and
+    the second differ."""
+    from maua_amd import _lib as L
+    from maua_amd.diffusion import SecondaryDiffusionImageNet2
+    pa, pb = OD.secondary_random_params(21), OD.secondary_random_params(22)
+    net = SecondaryDiffusionImageNet2(dtype=dt, exact=exact)
+    net.load_state_dict(pa)
+    g = torch.Generator().manual_seed(23)
+    x, t, gv = torch.randn(1, 3, 32, 32, generator=g), torch.rand(1, generator=g), torch.randn(1, 3, 32, 32, generator=g)
+
+    def load(p):
+        h = net._handle()
+        for i, k in enumerate(net._keys):
+            for what, a in ((0, p[k + ".weight"]), (1, p[k + ".bias"])):
+                a = a.contiguous().float()
+                L.check(L.lib().maua_secondary_load(h, i, what, C.c_void_p(a.data_ptr()), C.c_size_t(a.numel())))
+
+    outs = []
+    for p in (pa, pb, pa):
+        load(p)
+        outs.append((net(x, t).v.cpu(), net.vjp(gv).cpu()))
+    for k in range(2):
+        assert float(outs[0][k].std()) > 0
+        assert torch.equal(outs[2][k], outs[0][k]), k
+        assert not torch.equal(outs[1][k], outs[0][k]), k
+
+
 def test_fast_conditioning_matches_the_reference_gradient(golden):
     """GradientGuidedConditioning(speed="fast") - the reference's default - against g28's cond_grad, which the REFERENCE's own
     GradientGuidedConditioning.forward computed with torch.autograd through its secondary model (guided.py:236-272): same weights,

@@ -468,6 +468,30 @@ def test_one_handle_through_several_shapes(dt):
     one.close()
 
 
+def test_unit_styles_grow_with_the_batch():
+    """float32, plan (64, 64): the second convolution and its gradient run on the generic kernel, which multiplies its input by the
+    handle's unit styles [B][512].  One handle at B = 1, 3, 1 (16 x 16): the buffer is filled at the first forward, regrown at the
+    second, kept at the third - features and style gradient are bit for bit a fresh handle's each time.  (The shapes above stop at
+    conv0, which reads no styles.)"""
+    plan = (64, 64)
+    ref_net = (list(plan), R.gaussian_params(plan, "f32", 6), R.GAUSS_PRE, False)
+    assert conv_route("f32", 64, 64, 16, 16, False) == "generic"
+    one = Net(ref_net, "f32")
+    for j, B in enumerate((1, 3, 1)):
+        img = R.gaussian_image(B, 16, 16, 70 + j)
+        fresh = Net(ref_net, "f32")
+        outs = []
+        for net in (one, fresh):
+            net.forward(img)
+            acts = net.acts()
+            outs.append((acts[1], *net.style_grad(img, [1], style_targets(acts, [1], B, j), 2.5)))
+        fresh.close()
+        for k, (a, b) in enumerate(zip(*outs)):
+            assert np.array_equal(a, b), f"B = {B} (step {j}): result {k} differs from a fresh handle's"
+        assert np.abs(outs[0][0]).max() > 0 and np.abs(outs[0][1]).max() > 0
+    one.close()
+
+
 def test_refusals_write_nothing():
     """a pooling entry is no tap; H, W must divide by the pooling; B == 0 returns at once: grad and loss stay untouched"""
     ref_net = ([64, 0, 64], R.gaussian_params((64, 0, 64), "f32", 1), R.GAUSS_PRE, False)

@@ -145,6 +145,47 @@ def test_srvgg_compact_matches_oracle(dt):
         assert int((u8.cpu().int() - want8.int()).abs().max()) <= 1
 
 
+def _srvgg_load_into(net, params):
+    """maua_srvgg_load on the module's LIVE handle (load_state_dict would destroy it and build a new one)"""
+    import ctypes as C
+    from maua_amd import _lib as L
+    h = net._handle()
+    for k, v in params.items():
+        a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
+        L.check(L.lib().maua_srvgg_load(h, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+
+
+def test_srvgg_reload_writes_in_place():
+    """bf16, num_feat 32 (first layer Ci 3 -> 32, last layer Co 48 -> 64: both padded), B = 1 at 8 x 8: weights A, weights B, weights A
+    again loaded into ONE handle back to back.  The third result is the first bit for bit (every load zeroes the prepared buffer and
+    rewrites all of it, the staging buffer of one load leaves nothing behind for the next), the second differs."""
+    from maua_amd.super import SRVGGNetCompact, init_srvgg_params
+    net = SRVGGNetCompact(num_feat=32, num_conv=2, upscale=4, dtype=torch.bfloat16, generator=torch.Generator().manual_seed(11))
+    pa = net.state_dict()
+    pb = init_srvgg_params(32, 2, 4, torch.Generator().manual_seed(12))
+    x = torch.rand(1, 3, 8, 8, generator=torch.Generator().manual_seed(13))
+    outs = []
+    for p in (pa, pb, pa):
+        _srvgg_load_into(net, p)
+        outs.append(net(x, clamp=False).cpu())
+    assert outs[0].shape == (1, 3, 32, 32) and float(outs[0].std()) > 0
+    assert torch.equal(outs[2], outs[0])
+    assert not torch.equal(outs[1], outs[0])
+
+
+def test_srvgg_unit_styles_grow_with_the_batch():
+    """float32 at 16 x 16: every convolution on the generic kernel, which reads the handle's unit styles.  One handle at B = 1, 3, 1
+    (filled, regrown, kept): each result is a fresh handle's bit for bit."""
+    from maua_amd.super import SRVGGNetCompact
+    mk = lambda: SRVGGNetCompact(num_feat=32, num_conv=2, upscale=4, dtype=torch.float32, generator=torch.Generator().manual_seed(14))   # noqa: E731
+    one = mk()
+    for j, B in enumerate((1, 3, 1)):
+        x = torch.rand(B, 3, 16, 16, generator=torch.Generator().manual_seed(20 + j))
+        got, want = one(x, clamp=False).cpu(), mk()(x, clamp=False).cpu()
+        assert float(want.std()) > 0
+        assert torch.equal(got, want), f"B = {B} (step {j})"
+
+
 def test_rrdb_trunk_on_lds_direct_kernel_matches_generic_and_oracle(monkeypatch):
     """bf16, image sizes the LDS-direct kernel takes (H % 8 == 0, W % 32 == 0): every 3x3 convolution of the trunk and the
     up-sampling tail runs on modconv_dma's narrow N tiles (32 / 64 output channels, channel-sliced dense-block operands,
