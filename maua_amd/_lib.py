@@ -4,6 +4,7 @@ There is NO CPU fallback: if the shared library is missing or no HIP device is v
 operator raises.  (The CPU oracle lives under /oracle and is test infrastructure only.)
 """
 import ctypes as C
+import functools
 import os
 import re
 import threading
@@ -19,6 +20,8 @@ F32, BF16, F16 = 0, 1, 2
 F32_SPLIT = 3   # float32 tensors, products as bf16 split products (maua_secondary_create only)
 ACTS = {"linear": 0, "relu": 1, "lrelu": 2, "tanh": 3, "sigmoid": 4, "elu": 5, "selu": 6, "softplus": 7, "swish": 8}
 PAD_MODES = {"circular": 0, "reflect": 1, "replicate": 2, "constant": 3}
+VFEAT_LAYOUTS = {"u8_hwc": 0, "u8_chw": 1, "f32_chw": 2}
+CORR_METRICS = {"pearson": 0, "concordance": 1, "autocorrcorr": 2, "rv": 3, "rv2": 4, "r1": 5}
 
 
 class MauaHipError(RuntimeError):
@@ -29,12 +32,76 @@ _lib = None
 _lock = threading.Lock()
 _ctxs = {}
 
+# ---- the binding: include/maua_hip.h is the one place a signature is written -----------------------------------------------------------
+_CTYPES = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+           "unsigned long long": C.c_ulonglong, "const char*": C.c_char_p}
+
+
+def ctype_of(ctype, where):
+    """A C type of the header as ctypes.  Every pointer but ``const char*`` is c_void_p: it takes ptr(t), None, byref(x), ctypes arrays,
+    integer addresses and bytes alike.  An unknown scalar is an error, never an int."""
+    t = " ".join(ctype.replace("*", " * ").split()).replace(" *", "*")
+    if t not in _CTYPES and not t.endswith("*"):
+        raise MauaHipError(f"{where}: no ctypes type for the C type '{t}' (include/maua_hip.h)")
+    return _CTYPES.get(t, C.c_void_p)
+
+
+def declaration(header, name):
+    """One function's declaration as the header writes it: (return type, [parameter, ...]).  It is looked up, not tabulated - the first
+    ` name(` outside a comment, its return type in front of it on the same line, its parameters up to the `;` - so a process pays for the
+    functions it calls and not for the 114 KB header: preprocessor lines, enum blocks and struct bodies are never looked at.  The header is
+    searched as bytes, because decoding all of it costs more than the lookups of a whole run."""
+    if isinstance(header, str):
+        header = header.encode()
+    key, at = b" %s(" % name.encode(), -1
+    while True:
+        at = header.find(key, at + 1)
+        if at < 0:
+            raise MauaHipError(f"{name} is not declared in include/maua_hip.h")
+        if header.rfind(b"/*", 0, at) <= header.rfind(b"*/", 0, at):      # not a mention inside a comment
+            break
+    ret = header[header.rfind(b"\n", 0, at) + 1:at].decode()
+    rest = header[at + len(key):header.find(b";", at)]
+    params = b" ".join([piece.partition(b"/*")[0] for piece in rest.split(b"*/")]).decode().rstrip()   # `int aggregate /* 0 = mean */, float* env`
+    if not ret.strip() or not params.endswith(")") or "(" in params:
+        raise MauaHipError(f"include/maua_hip.h: cannot parse the declaration of {name}: '{ret} {name}({params};'")
+    return ret, [] if params[:-1].strip() == "void" else params[:-1].split(",")
+
+
+def signature(header, name):
+    """(restype, [argtypes]) of a function the header (bytes or str) declares; a parameter's type is what stands in front of its name."""
+    ret, params = declaration(header, name)
+    restype = None if ret.strip() == "void" else ctype_of(ret, name)
+    return restype, [ctype_of(p.replace("*", "* ").rsplit(None, 1)[0], name) for p in params]
+
+
+def declared_names(text):
+    """every maua_* name that stands in front of a `(` outside a comment"""
+    return sorted(set(re.findall(r"\b(maua_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S))))
+
+
+def parse_header(text):
+    """name -> (restype, [argtypes]) for every function the header text declares"""
+    header = text.encode()
+    return {name: signature(header, name) for name in declared_names(text)}
+
+
+_header = functools.lru_cache(maxsize=None)(lambda: HEADER.read_bytes())
+
 
 def declared_symbols():
     """Every function the C header declares (used by the export test)."""
-    text = HEADER.read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(maua_[a-z0-9_]+)\s*\(", text)))
+    return declared_names(_header().decode())
+
+
+class _Library(C.CDLL):
+    """libmaua_hip.so; a function gets its restype and argtypes from the header when it is first looked up (ctypes keeps it from then on)."""
+
+    def __getitem__(self, name):
+        restype, argtypes = signature(_header(), name)
+        fn = super().__getitem__(name)
+        fn.restype, fn.argtypes = restype, argtypes
+        return fn
 
 
 def lib():
@@ -46,48 +113,8 @@ def lib():
                     raise MauaHipError(
                         f"{LIB_PATH} not found: build it with `python -m maua_amd.build` (hipcc, gfx950). "
                         "maua_amd has no CPU fallback.")
-                l = C.CDLL(str(LIB_PATH))
-                l.maua_last_error.restype = C.c_char_p
-                l.maua_version.restype = C.c_char_p
-                _declare_flow(l)
-                _declare_video_features(l)
-                _lib = l
+                _lib = _Library(str(LIB_PATH))
     return _lib
-
-
-def _declare_flow(l):
-    """csrc/flow.hip's entry points (include/maua_hip.h: optical-flow operators of the video pipeline)."""
-    p, i, f = C.c_void_p, C.c_int, C.c_float
-    l.maua_flow_warp.argtypes = [p, p, p, f, i, i, i, i, p]
-    l.maua_flow_consistency.argtypes = [p, p, p, i, i, i, f, p, p]
-    l.maua_flow_resize_bilinear.argtypes = [p, p, i, i, i, i, p, i, i, f, f]
-    l.maua_flow_compose.argtypes = [p, p, p, p, p, p, i, i, i, f, f, f, f, f, C.c_ulonglong, p]
-    l.maua_flow_turbo.argtypes = [p, p, p, p, i, i, i, f, i, f, p, p, p]
-    l.maua_farneback_levels.argtypes = [i, i]
-    l.maua_farneback_create.argtypes = [p, i, i, C.POINTER(p)]
-    l.maua_farneback_destroy.argtypes = [p]
-    l.maua_farneback_pair.argtypes = [p, p, p, p, i, i, p, p]
-    l.maua_farneback_level_size.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
-    l.maua_farneback_check.argtypes = [p, p]
-    l.maua_farneback_pair_ex.argtypes = [p, p, p]
-
-
-VFEAT_LAYOUTS = {"u8_hwc": 0, "u8_chw": 1, "f32_chw": 2}
-CORR_METRICS = {"pearson": 0, "concordance": 1, "autocorrcorr": 2, "rv": 3, "rv2": 4, "r1": 5}
-
-
-def _declare_video_features(l):
-    """csrc/video_features.hip's entry points (include/maua_hip.h: audio-reactivity instruments)."""
-    p, i, g = C.c_void_p, C.c_int, C.c_long
-    l.maua_vfeat_create.argtypes = [p, i, i, i, i, C.POINTER(p)]
-    l.maua_vfeat_destroy.argtypes = [p]
-    l.maua_vfeat_reset.argtypes = [p]
-    l.maua_vfeat_check.argtypes = [p, i, i, i, i, p, i, i, p, p, p, p]
-    l.maua_vfeat_push.argtypes = [p, p, p, i, i, i, i, p, p, p, p]
-    l.maua_correlation_workspace.argtypes = [i, i, i]
-    l.maua_correlation_workspace.restype = g
-    l.maua_correlation_check.argtypes = [p, p, i, i, i, i, p, g, p]
-    l.maua_correlation.argtypes = [p, p, p, i, i, i, i, p, g, p]
 
 
 class host_threads:
@@ -144,10 +171,10 @@ def ctx(device=None):
     c = _ctxs.get(dev)
     if c is None:
         p = C.c_void_p()
-        check(lib().maua_ctx_create(C.c_int(dev), C.c_void_p(stream), C.byref(p)))
+        check(lib().maua_ctx_create(dev, stream, C.byref(p)))
         c = _ctxs[dev] = p
     else:
-        check(lib().maua_ctx_set_stream(c, C.c_void_p(stream)))
+        check(lib().maua_ctx_set_stream(c, stream))
     return c
 
 
@@ -257,6 +284,15 @@ class FbDesc(C.Structure):
                 ("init_ab", C.c_void_p), ("init_ba", C.c_void_p),
                 ("gray", C.c_void_p), ("blur", C.c_void_p), ("level", C.c_void_p), ("coef", C.c_void_p), ("flow_in", C.c_void_p),
                 ("mat", C.c_void_p)]
+
+
+class NcaDesc(C.Structure):
+    """maua_nca_desc (include/maua_hip.h); pointers as integers."""
+    _fields_ = [("x", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p),
+                ("n_steps", C.c_int), ("rate", C.c_float), ("rate_map", C.c_void_p), ("u", C.c_void_p),
+                ("seed", C.c_ulonglong), ("stream", C.c_ulonglong), ("step0", C.c_ulonglong),
+                ("col0", C.c_int), ("W_sub", C.c_int), ("margin", C.c_int), ("steps_per_launch", C.c_int)]
 
 
 # routes of maua_modconv_route / maua_modconv_ex and of maua_synth_get_plan (csrc/synth.hip's Route enum; UPFIR: the FIR / epilogue pass alone)

@@ -12,7 +12,6 @@ Inputs may be CPU or device tensors; results live on the HIP device.  n_fft = 20
 framing the reference's features use).  Every function goes through libmaua_hip.so; small constant tables (mel
 basis, Gaussian taps, linspace grids) are built on the host exactly as the reference builds them.
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -87,15 +86,14 @@ def spectrogram(y, n_fft=2048, hop_length=1024, power=1, window=torch.hann_windo
     D = stft(y, n_fft, hop_length, center, window, pad_mode)[:, :-1]
     buf = _frame_major(D)
     mag = torch.empty(buf.shape[:2], dtype=torch.float32, device=buf.device)
-    L.check(L.lib().maua_magnitude(L.ctx(buf.device), L.ptr(buf), C.c_long(mag.numel()), C.c_float(float(power)),
-                                   L.ptr(mag)))
+    L.check(L.lib().maua_magnitude(L.ctx(buf.device), L.ptr(buf), mag.numel(), float(power), L.ptr(mag)))
     return mag.T
 
 
 def magphase(D, power=1.0):
     buf = _frame_major(D)
     mag = torch.empty(buf.shape[:2], dtype=torch.float32, device=buf.device)
-    L.check(L.lib().maua_magnitude(L.ctx(buf.device), L.ptr(buf), C.c_long(mag.numel()), C.c_float(1.0), L.ptr(mag)))
+    L.check(L.lib().maua_magnitude(L.ctx(buf.device), L.ptr(buf), mag.numel(), 1.0, L.ptr(mag)))
     mag = mag.T
     phase = torch.where(mag > 0, D / mag.clamp_min(1e-38), torch.ones_like(D))
     return mag ** power, phase
@@ -194,8 +192,7 @@ def onset_strength(y, sr, hop_length=1024, n_fft=2048, aggregate=torch.mean, fma
         agg = 1
     else:
         raise NotImplementedError("onset_strength: aggregate must be torch.mean or 'median'")
-    L.check(L.lib().maua_onset_from_mel(L.ctx(S.device), L.ptr(S), n_mels, T, C.c_float(1e-10), C.c_float(80.0),
-                                        pad_width, agg, L.ptr(env)))
+    L.check(L.lib().maua_onset_from_mel(L.ctx(S.device), L.ptr(S), n_mels, T, 1e-10, 80.0, pad_width, agg, L.ptr(env)))
     return env
 
 
@@ -212,8 +209,7 @@ def hpss(S, ks=31, power=2.0, margin=1.0):
         raise ValueError("expected 1025 frequency bins")
     h = torch.empty_like(buf)
     p = torch.empty_like(buf)
-    L.check(L.lib().maua_hpss(L.ctx(buf.device), L.ptr(buf), frames, C.c_float(float(margin)), C.c_float(float(power)),
-                              L.ptr(h), L.ptr(p)))
+    L.check(L.lib().maua_hpss(L.ctx(buf.device), L.ptr(buf), frames, float(margin), float(power), L.ptr(h), L.ptr(p)))
     return torch.view_as_complex(h).T, torch.view_as_complex(p).T
 
 
@@ -251,7 +247,7 @@ def normalize(array, eps=1e-8):
     """processing.py:53-56: (x - min) / (max(x - min) + 1e-8)."""
     x = _f32(array)
     y = torch.empty_like(x)
-    L.check(L.lib().maua_normalize(L.ctx(x.device), L.ptr(x), C.c_long(x.numel()), C.c_float(eps), L.ptr(y)))
+    L.check(L.lib().maua_normalize(L.ctx(x.device), L.ptr(x), x.numel(), eps, L.ptr(y)))
     return y
 
 
@@ -293,7 +289,7 @@ def gaussian_filter(x, sigma, mode="circular", causal=1, _classic=False):
         print(f"WARNING: Gaussian filter radius ({int(sigma * 4)}) is larger than number of frames ({T}).\n\t "
               f"Filter size has been lowered to ({radius}). You might want to consider lowering sigma ({sigma}).")
     y = torch.empty_like(x)
-    L.check(L.lib().maua_gaussian_filter1d(L.ctx(x.device), L.ptr(x), L.ptr(_f32(taps)), radius, T, C.c_long(Cn),
+    L.check(L.lib().maua_gaussian_filter1d(L.ctx(x.device), L.ptr(x), L.ptr(_f32(taps)), radius, T, Cn,
                                            L.PAD_MODES[mode], L.ptr(y)))
     if x.dim() < 3:  # the reference lifts to 3-D and then squeezes EVERY singleton axis (processing.py:46-48):
         y = y.reshape(shape + (1,) * (3 - x.dim())).squeeze()  # [T, 1] comes back as [T]
@@ -307,8 +303,8 @@ def order_stat(x, mode, q=0.0, k=1, mask=None):
     ranks = torch.empty((2,), dtype=torch.int64, device=x.device)
     if mask is not None:
         mask = mask.to(device=x.device, dtype=torch.uint8).contiguous()
-    L.check(L.lib().maua_order_stat(L.ctx(x.device), L.ptr(x), L.ptr(mask), C.c_long(x.numel()), mode,
-                                    C.c_float(float(q)), C.c_long(int(k)), L.ptr(out), L.ptr(ranks)))
+    L.check(L.lib().maua_order_stat(L.ctx(x.device), L.ptr(x), L.ptr(mask), x.numel(), mode,
+                                    float(q), int(k), L.ptr(out), L.ptr(ranks)))
     return out, ranks
 
 
@@ -323,8 +319,7 @@ def standardize(array):
     lo, _ = order_stat(x, 0, q=0.25)
     hi, _ = order_stat(x, 0, q=0.75)
     y = torch.empty_like(x)
-    L.check(L.lib().maua_clamp(L.ctx(x.device), L.ptr(x), L.ptr(lo), L.ptr(hi), C.c_float(0), C.c_float(1e-10),
-                               C.c_long(x.numel()), L.ptr(y)))
+    L.check(L.lib().maua_clamp(L.ctx(x.device), L.ptr(x), L.ptr(lo), L.ptr(hi), 0, 1e-10, x.numel(), L.ptr(y)))
     return normalize(y)
 
 
@@ -350,12 +345,12 @@ def emphasize(envs, strength, percentile):
     x = x.reshape(-1)
     lib, ctx = L.lib(), L.ctx(x.device)
     mm = torch.empty((2,), dtype=torch.float32, device=x.device)
-    L.check(lib.maua_minmax(ctx, L.ptr(x), C.c_long(x.numel()), L.ptr(mm)))
+    L.check(lib.maua_minmax(ctx, L.ptr(x), x.numel(), L.ptr(mm)))
     xn = torch.empty_like(x)
-    L.check(lib.maua_normalize(ctx, L.ptr(x), C.c_long(x.numel()), C.c_float(0.0), L.ptr(xn)))
+    L.check(lib.maua_normalize(ctx, L.ptr(x), x.numel(), 0.0, L.ptr(xn)))
     q, _ = order_stat(xn, 2, q=percentile / 100)
     y = torch.empty_like(x)
-    L.check(lib.maua_emphasize(ctx, L.ptr(xn), C.c_long(x.numel()), L.ptr(mm), L.ptr(q), C.c_float(float(strength)), L.ptr(y)))
+    L.check(lib.maua_emphasize(ctx, L.ptr(xn), x.numel(), L.ptr(mm), L.ptr(q), float(strength), L.ptr(y)))
     return y.reshape(shape)
 
 
@@ -369,8 +364,7 @@ def _biquad(waveform, b, a):
     out = torch.empty_like(x)
     one = torch.ones((1,), dtype=torch.float32, device=x.device)
     y32 = y.float()
-    L.check(L.lib().maua_clamp(L.ctx(x.device), L.ptr(y32), None, L.ptr(one), C.c_float(-1.0), C.c_float(0.0),
-                               C.c_long(x.numel()), L.ptr(out)))
+    L.check(L.lib().maua_clamp(L.ctx(x.device), L.ptr(y32), None, L.ptr(one), -1.0, 0.0, x.numel(), L.ptr(out)))
     return out
 
 
@@ -399,7 +393,7 @@ def contrast_enhance(audio, sr, strength=75):
     """processing.py:154-155: torchaudio.functional.contrast(audio, strength)."""
     x = _f32(audio)
     y = torch.empty_like(x)
-    L.check(L.lib().maua_contrast(L.ctx(x.device), L.ptr(x), C.c_long(x.numel()), C.c_float(float(strength)), L.ptr(y)))
+    L.check(L.lib().maua_contrast(L.ctx(x.device), L.ptr(x), x.numel(), float(strength), L.ptr(y)))
     return y
 
 
@@ -414,7 +408,7 @@ def _clamp_columns(signal, bound):
         lo, hi = bound(col)
         y = torch.empty_like(col)
         L.check(L.lib().maua_clamp(L.ctx(x.device), L.ptr(col), L.ptr(lo), L.ptr(inf if hi is None else hi),
-                                   C.c_float(float("-inf")), C.c_float(0.0), C.c_long(col.numel()), L.ptr(y)))
+                                   float("-inf"), 0.0, col.numel(), L.ptr(y)))
         out.append(y)
     return torch.stack(out, dim=1).reshape(x.shape)
 
@@ -508,8 +502,7 @@ def spectral_flatness(y, sr=None, n_fft=2048, hop_length=1024, window=torch.hann
     buf = _frame_major(stft(y, n_fft, hop_length, center, window, pad_mode))
     T = buf.shape[0] - 1                                         # spectrogram drops the last column
     out = torch.empty((T,), dtype=torch.float32, device=buf.device)
-    L.check(L.lib().maua_spectral_flatness(L.ctx(buf.device), L.ptr(buf), T, buf.shape[1], C.c_float(amin),
-                                           C.c_float(power), L.ptr(out)))
+    L.check(L.lib().maua_spectral_flatness(L.ctx(buf.device), L.ptr(buf), T, buf.shape[1], amin, power, L.ptr(out)))
     return out.unsqueeze(-1)
 
 
@@ -636,8 +629,8 @@ def _istft_dft(buf, n_fft, hop_length, length, win):
     frames = torch.empty((F_, n_fft), dtype=torch.float32, device=buf.device)
     L.check(L.lib().maua_matmul_nt(L.ctx(buf.device), L.ptr(buf), L.ptr(inv), L.ptr(frames), F_, n_fft, 2 * buf.shape[1]))
     y = torch.empty((int(length),), dtype=torch.float32, device=buf.device)
-    L.check(L.lib().maua_overlap_add(L.ctx(buf.device), L.ptr(frames), F_, n_fft, hop_length, L.ptr(win), C.c_long(n_fft // 2),
-                                     C.c_long(int(length)), L.ptr(y)))
+    L.check(L.lib().maua_overlap_add(L.ctx(buf.device), L.ptr(frames), F_, n_fft, hop_length, L.ptr(win), n_fft // 2,
+                                     int(length), L.ptr(y)))
     return y
 
 
@@ -669,14 +662,13 @@ def plp(y, sr, hop_length=1024, win_length=1024, tempo_min=60, tempo_max=180):
     buf = _frame_major(ft)                                      # [T + 1, W/2 + 1, 2], owns its memory
     freqs = _f32(fourier_tempo_frequencies(sr, W, hop_length))
     L.check(L.lib().maua_plp_select(L.ctx(buf.device), L.ptr(buf), buf.shape[0], buf.shape[1], L.ptr(freqs),
-                                    C.c_float(-1e30 if tempo_min is None else tempo_min),
-                                    C.c_float(1e30 if tempo_max is None else tempo_max)))
+                                    -1e30 if tempo_min is None else tempo_min,
+                                    1e30 if tempo_max is None else tempo_max))
     pulse = istft_general(torch.view_as_complex(buf).T, W, 1, T)
     mm = torch.empty((2,), dtype=torch.float32, device=pulse.device)
-    L.check(L.lib().maua_minmax(L.ctx(pulse.device), L.ptr(pulse), C.c_long(T), L.ptr(mm)))
+    L.check(L.lib().maua_minmax(L.ctx(pulse.device), L.ptr(pulse), T, L.ptr(mm)))
     clamped = torch.empty_like(pulse)
-    L.check(L.lib().maua_clamp(L.ctx(pulse.device), L.ptr(pulse), None, L.ptr(mm[1:]), C.c_float(0.0), C.c_float(0.0),
-                               C.c_long(T), L.ptr(clamped)))
+    L.check(L.lib().maua_clamp(L.ctx(pulse.device), L.ptr(pulse), None, L.ptr(mm[1:]), 0.0, 0.0, T, L.ptr(clamped)))
     return normalize(clamped)
 
 

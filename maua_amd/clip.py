@@ -160,14 +160,14 @@ class VisionTransformer(torch.nn.Module):
         if self._dirty:
             for k, v in self._params.items():
                 a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
-                L.check(L.lib().maua_clip_load(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+                L.check(L.lib().maua_clip_load(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), a.size))
             self._dirty = False
         return self._h
 
     def set_workspace_limit(self, nbytes=0):
         """Bytes one pass through the tower may take in a guidance call (kept activations, workspace, cutout scratch): the cutouts of
         a call go through in groups that fit.  0 (default): from the device's free memory.  ``maua_clip_set_workspace_limit``."""
-        L.check(L.lib().maua_clip_set_workspace_limit(self._handle(), C.c_size_t(int(nbytes))))
+        L.check(L.lib().maua_clip_set_workspace_limit(self._handle(), int(nbytes)))
 
     # ------------------------------------------------------------------ forward / input gradient
     def forward(self, x, keep=False):
@@ -309,7 +309,7 @@ class TextTransformer(torch.nn.Module):
         if self._dirty:
             for k, v in self._params.items():
                 a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
-                L.check(L.lib().maua_clip_text_load(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+                L.check(L.lib().maua_clip_text_load(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), a.size))
             self._dirty = False
         return self._h
 

@@ -17,10 +17,9 @@ SQUARE_ONLY = ("pearson", "concordance", "r1")   # need Fx == Fy (column pairs /
 
 def check_metric(name, T, Fx, Fy):
     """maua_correlation's refusals for such a call, without a device (maua_correlation_check): raises MauaHipError with its own message."""
-    import ctypes as C
     if name not in L.CORR_METRICS:
         raise ValueError(f"unknown correlation metric {name!r}: the metrics are {list(METRICS)}")
-    one = C.c_void_p(256)
+    one = 256
     nbytes = L.lib().maua_correlation_workspace(int(T), int(Fx), int(Fy))
     L.check(L.lib().maua_correlation_check(one, one, int(T), int(Fx), int(Fy), L.CORR_METRICS[name], one, max(nbytes, 1 << 40), one))
 

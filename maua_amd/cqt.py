@@ -11,7 +11,6 @@ smoothing are kernels (``maua_piptrack``, ``maua_spline_step``, ``maua_gaussian_
 per call on the host (set-up, not data path): the 36 complex filters and their FFT, the cq→chroma matrix, the spline
 coefficients.  torchaudio and torchcubicspline are un-vendored: their published algorithms are restated (oracle/cqt.py has
 the same restatements for the CPU side; everything the reference itself can run is pinned by tests/golden/g21_cqt.npz)."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -116,8 +115,8 @@ def resample_half(y):
     n_out = (y.numel() + 1) // 2
     out = torch.empty((n_out,), dtype=torch.float32, device=y.device)
     td = L.dev_tensor(taps, torch.float32)
-    L.check(L.lib().maua_fir_decimate(L.ctx(y.device), L.ptr(y), C.c_long(y.numel()), L.ptr(td), len(taps), 2, width,
-                                      C.c_float(math.sqrt(2.0)), L.ptr(out), C.c_long(n_out)))
+    L.check(L.lib().maua_fir_decimate(L.ctx(y.device), L.ptr(y), y.numel(), L.ptr(td), len(taps), 2, width,
+                                      math.sqrt(2.0), L.ptr(out), n_out))
     return out
 
 
@@ -134,13 +133,13 @@ def piptrack(y, sr, n_fft=2048, hop_length=None, fmin=150.0, fmax=4000.0, thresh
     buf = _frame_major(D)
     T, nb = buf.shape[0], buf.shape[1]
     S = torch.empty((T, nb), dtype=torch.float32, device=buf.device)
-    L.check(L.lib().maua_magnitude(L.ctx(buf.device), L.ptr(buf), C.c_long(S.numel()), C.c_float(1.0), L.ptr(S)))
+    L.check(L.lib().maua_magnitude(L.ctx(buf.device), L.ptr(buf), S.numel(), 1.0, L.ptr(S)))
     fmax = min(fmax, float(sr) / 2)
     freqs = L.dev_tensor(torch.linspace(0, float(sr) / 2, nb), torch.float32)
     frame_max = S.amax(1).contiguous()
     pitch, mag = torch.empty_like(S), torch.empty_like(S)
-    L.check(L.lib().maua_piptrack(L.ctx(S.device), L.ptr(S), T, nb, L.ptr(frame_max), C.c_float(threshold), L.ptr(freqs),
-                                  C.c_float(float(sr) / n_fft), C.c_float(max(fmin, 0)), C.c_float(fmax), L.ptr(pitch),
+    L.check(L.lib().maua_piptrack(L.ctx(S.device), L.ptr(S), T, nb, L.ptr(frame_max), threshold, L.ptr(freqs),
+                                  float(sr) / n_fft, max(fmin, 0), fmax, L.ptr(pitch),
                                   L.ptr(mag)))
     return pitch.T, mag.T
 
@@ -235,7 +234,7 @@ def vqt(y, sr, hop_length=1024, fmin=None, n_bins=84, gamma=None, bins_per_octav
     if not magnitude:
         return torch.view_as_complex(out).T
     mag = torch.empty((T, n_bins), dtype=torch.float32, device=dev)
-    L.check(L.lib().maua_magnitude(L.ctx(dev), L.ptr(out), C.c_long(mag.numel()), C.c_float(1.0), L.ptr(mag)))
+    L.check(L.lib().maua_magnitude(L.ctx(dev), L.ptr(out), mag.numel(), 1.0, L.ptr(mag)))
     return mag.T
 
 
@@ -295,8 +294,8 @@ def spline_quantize(chroma, h=0.25, alpha=20):
     xs, coef = _quantiser()
     xs_d, coef_d = L.dev_tensor(xs, torch.float32), L.dev_tensor(coef.contiguous(), torch.float32)
     out = torch.empty_like(x)
-    L.check(L.lib().maua_spline_step(L.ctx(x.device), L.ptr(x), C.c_long(x.numel()), L.ptr(xs_d), L.ptr(coef_d), len(xs),
-                                     C.c_float(h), C.c_float(alpha), 1, L.ptr(out)))
+    L.check(L.lib().maua_spline_step(L.ctx(x.device), L.ptr(x), x.numel(), L.ptr(xs_d), L.ptr(coef_d), len(xs),
+                                     h, alpha, 1, L.ptr(out)))
     return out
 
 
@@ -313,7 +312,7 @@ def chroma_cens(y, sr, hop_length=1024, fmin=None, tuning=None, n_chroma=12, n_o
         win = L.dev_tensor(win / win.sum(), torch.float32)
         sm = torch.empty_like(q)
         L.check(L.lib().maua_gaussian_filter1d(L.ctx(q.device), L.ptr(q), L.ptr(win), (len(win) - 1) // 2, q.shape[0],
-                                               C.c_long(q.shape[1]), 3, L.ptr(sm)))
+                                               q.shape[1], 3, L.ptr(sm)))
         q = sm
     return (q / q.norm(p=2, dim=1, keepdim=True)).T
 

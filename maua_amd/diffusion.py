@@ -206,11 +206,11 @@ class UNetModel(torch.nn.Module):
                 L.check(lib.maua_unet_set_option(net, b"vjp", 1))
             for k, v in self._params.items():
                 a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
-                L.check(lib.maua_unet_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+                L.check(lib.maua_unet_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), a.size))
             # nn.py timestep_embedding's frequency table, computed on the host with the reference's own expression
             half = self.model_channels // 2
             freqs = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half).numpy()
-            L.check(lib.maua_unet_load(net, b"timestep_embedding.freqs", freqs.ctypes.data_as(C.c_void_p), C.c_size_t(half)))
+            L.check(lib.maua_unet_load(net, b"timestep_embedding.freqs", freqs.ctypes.data_as(C.c_void_p), half))
             self._net = net
         else:
             L.ctx()
@@ -382,7 +382,7 @@ class SpacedDiffusion:
         ab = L.dev_tensor(ab.contiguous(), torch.float32)
         out = torch.empty_like(x)
         L.check(L.lib().maua_axpby_rows(L.ctx(x.device), L.ptr(x), L.ptr(noise), L.ptr(ab), x.shape[0],
-                                        C.c_long(x[0].numel()), L.ptr(out)))
+                                        x[0].numel(), L.ptr(out)))
         return out
 
     def ddim_sample(self, model, x, t, clip_denoised=False, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0,
@@ -407,7 +407,7 @@ class SpacedDiffusion:
         B, Cc = x.shape[0], x.shape[1]
         L.check(L.lib().maua_ddim_step(L.ctx(x.device), L.ptr(x), L.ptr(out), L.ptr(grad),
                                        L.ptr(noise if eta != 0.0 else None), L.ptr(cf), B, Cc, out.shape[1],
-                                       C.c_long(x[0, 0].numel()), L.ptr(sample), L.ptr(pred)))
+                                       x[0, 0].numel(), L.ptr(sample), L.ptr(pred)))
         return {"sample": sample, "pred_xstart": pred}
 
     def p_sample(self, model, x, t, clip_denoised=False, denoised_fn=None, cond_fn=None, model_kwargs=None, noise=None):
@@ -435,7 +435,7 @@ class SpacedDiffusion:
         cf = L.dev_tensor(cf, torch.float32)
         sample, pred = torch.empty_like(x), torch.empty_like(x)
         L.check(L.lib().maua_p_sample_step(L.ctx(x.device), L.ptr(x), L.ptr(out), L.ptr(grad), L.ptr(noise), L.ptr(cf), B, Cc,
-                                           C.c_long(x[0, 0].numel()), L.ptr(sample), L.ptr(pred)))
+                                           x[0, 0].numel(), L.ptr(sample), L.ptr(pred)))
         return {"sample": sample, "pred_xstart": pred}
 
     def _plms_model_output(self, model, x, t, cond_fn):
@@ -446,7 +446,7 @@ class SpacedDiffusion:
         cf = L.dev_tensor(self.step_coefficients(t), torch.float32)
         eps, pred, pred_orig = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         L.check(L.lib().maua_plms_eps(L.ctx(x.device), L.ptr(x), L.ptr(out), L.ptr(grad), L.ptr(cf), x.shape[0], x.shape[1],
-                                      out.shape[1], C.c_long(x[0, 0].numel()), L.ptr(eps), L.ptr(pred), L.ptr(pred_orig)))
+                                      out.shape[1], x[0, 0].numel(), L.ptr(eps), L.ptr(pred), L.ptr(pred_orig)))
         return eps, pred, pred_orig
 
     def _plms_update(self, x, t, eps_list, weights, divisor, pred):
@@ -462,8 +462,8 @@ class SpacedDiffusion:
         ptrs = (C.c_void_p * len(eps_list))(*[e.data_ptr() for e in eps_list])
         ws = (C.c_float * len(weights))(*weights)
         sample = torch.empty_like(x)
-        L.check(L.lib().maua_plms_update(L.ctx(x.device), L.ptr(x), ptrs, ws, len(eps_list), C.c_float(divisor), L.ptr(pred),
-                                         L.ptr(cf), x.shape[0], C.c_long(x[0].numel()), L.ptr(sample)))
+        L.check(L.lib().maua_plms_update(L.ctx(x.device), L.ptr(x), ptrs, ws, len(eps_list), divisor, L.ptr(pred),
+                                         L.ptr(cf), x.shape[0], x[0].numel(), L.ptr(sample)))
         return sample
 
     def plms_sample(self, model, x, t, clip_denoised=False, denoised_fn=None, cond_fn=None, model_kwargs=None,
@@ -488,7 +488,7 @@ class SpacedDiffusion:
             ab2 = L.dev_tensor(torch.stack([torch.sqrt(abp), torch.sqrt(1 - abp)], 1).contiguous(), torch.float32)
             mean_pred = torch.empty_like(x)
             L.check(L.lib().maua_axpby_rows(L.ctx(x.device), L.ptr(pred), L.ptr(eps), L.ptr(ab2), x.shape[0],
-                                            C.c_long(x[0].numel()), L.ptr(mean_pred)))
+                                            x[0].numel(), L.ptr(mean_pred)))
             eps_2, _, _ = self._plms_model_output(model, mean_pred, t - 1, cond_fn)
             sample = self._plms_update(x, t, [eps, eps_2], [1.0, 1.0], 2.0, pred)
         else:
@@ -552,7 +552,7 @@ class SpacedDiffusion:
             rects = np.ascontiguousarray(rects, dtype=np.int32)
             L.check(L.lib().maua_unet_set_clip_guide(model._handle(), spec["clip"]._handle(), rects.ctypes.data_as(C.c_void_p),
                                                      None if mult is None else mult.ctypes.data_as(C.c_void_p), n_steps,
-                                                     rects.shape[2], spec["batches"], C.c_float(spec["scale"]), C.c_float(spec["clamp"])))
+                                                     rects.shape[2], spec["batches"], spec["scale"], spec["clamp"]))
             tgt, tstride, mse_k = None, 0, 0.0
             # a text-guided step is ~2 500 launches (8 cutout batches x ~200 for the tower's forward + backward): 250 000 for a
             # 100-step loop.  The loop still runs inside the library in one call, but launch by launch - the launches' host cost
@@ -561,10 +561,10 @@ class SpacedDiffusion:
             if n_steps * spec["batches"] > 64:
                 use_graph = False
         elif guides:
-            L.check(L.lib().maua_unet_set_clip_guide(model._handle(), None, None, None, 0, 0, 0, C.c_float(0.0), C.c_float(0.0)))
+            L.check(L.lib().maua_unet_set_clip_guide(model._handle(), None, None, None, 0, 0, 0, 0.0, 0.0))
             tgt, tstride, mse_k = None, 0, 0.0
         else:
-            L.check(L.lib().maua_unet_set_clip_guide(model._handle(), None, None, None, 0, 0, 0, C.c_float(0.0), C.c_float(0.0)))
+            L.check(L.lib().maua_unet_set_clip_guide(model._handle(), None, None, None, 0, 0, 0, 0.0, 0.0))
             tgt = L.dev_tensor(gm.target, torch.float32)
             mse_k = gm.factor(x[0].numel())
             if tuple(tgt.shape) == tuple(x.shape[1:]):
@@ -583,8 +583,8 @@ class SpacedDiffusion:
             second = None
         L.check(L.lib().maua_ddim_guided_loop(model._handle(), second, L.ptr(x), B, H, W,
                                               mt.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p),
-                                              gc.ctypes.data_as(C.c_void_p), n_steps, L.ptr(tgt), C.c_long(tstride),
-                                              C.c_float(mse_k), int(bool(use_graph)), L.ptr(pred)))
+                                              gc.ctypes.data_as(C.c_void_p), n_steps, L.ptr(tgt), tstride,
+                                              mse_k, int(bool(use_graph)), L.ptr(pred)))
         return x, pred
 
 
@@ -752,7 +752,7 @@ class SecondaryDiffusionImageNet2(torch.nn.Module):
 
             def up(i, what, t):
                 t = t.contiguous().float()
-                L.check(lib.maua_secondary_load(net, i, what, C.c_void_p(t.data_ptr()), C.c_size_t(t.numel())))
+                L.check(lib.maua_secondary_load(net, i, what, L.ptr(t), t.numel()))
             up(0, 2, self._params["timestep_embed.weight"].reshape(-1))
             for i, k in enumerate(self._keys):
                 up(i, 0, self._params[k + ".weight"])
@@ -833,7 +833,7 @@ class GradientGuidedConditioning(torch.nn.Module):
         lib, ctx = L.lib(), L.ctx(img.device)
         for k, gm in enumerate(self.grad_modules):
             sub = L.dev_tensor(gm(img, ot), torch.float32)
-            L.check(lib.maua_grad_accumulate(ctx, L.ptr(sub), L.ptr(img_grad), C.c_long(img.numel()), int(k == 0)))
+            L.check(lib.maua_grad_accumulate(ctx, L.ptr(sub), L.ptr(img_grad), img.numel(), int(k == 0)))
         return img_grad
 
     def guide_coefficients(self, t):
@@ -872,7 +872,7 @@ class GradientGuidedConditioning(torch.nn.Module):
         idx = torch.tensor([self.timestep_map.index(int(v)) for v in t.long().cpu()])
         alpha, sigma = self.sqrt_alphas_cumprod[idx], self.sqrt_one_minus_alphas_cumprod[idx]
         x = L.dev_tensor(x, torch.float32)
-        B, row = x.shape[0], C.c_long(x[0].numel())
+        B, row = x.shape[0], x[0].numel()
         lib, ctx = L.lib(), L.ctx(x.device)
         img = torch.empty_like(x)
         if self.speed == "hyper":
@@ -949,8 +949,8 @@ class MSEGuide:
             raise ValueError(f"MSEGuide: target shape {tuple(tgt.shape)} does not fit images of shape {tuple(img.shape)}")
         row = img[0].numel()
         out = torch.empty_like(img)
-        L.check(L.lib().maua_mse_guide_grad(L.ctx(img.device), L.ptr(img), L.ptr(tgt), C.c_long(row if tgt.dim() == img.dim() else 0),
-                                            C.c_float(self.factor(row)), img.shape[0], C.c_long(row), L.ptr(out)))
+        L.check(L.lib().maua_mse_guide_grad(L.ctx(img.device), L.ptr(img), L.ptr(tgt), row if tgt.dim() == img.dim() else 0,
+                                            self.factor(row), img.shape[0], row, L.ptr(out)))
         return out
 
 

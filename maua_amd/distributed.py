@@ -243,7 +243,6 @@ class StreamingGather:
         self._reqs = []
         self._side = None
         if self.device.type == "cuda" and world > 1:
-            import ctypes as C
             from . import _lib as L
             self._side = torch.cuda.Stream(device=self.device)
             # every rank takes the same transport: the library's RCCL rounds, or - if any rank has no communicator (or the
@@ -259,7 +258,7 @@ class StreamingGather:
                     warnings.warn(f"StreamingGather: the library's RCCL communicator is unavailable ({err}); using torch.distributed isend / irecv")
             if self._comm is not None:
                 # this communicator's transfers run on the side stream from here on (finish() hands it back)
-                L.check(L.lib().maua_comm_set_stream(self._comm, C.c_void_p(self._side.cuda_stream), 0))
+                L.check(L.lib().maua_comm_set_stream(self._comm, self._side.cuda_stream, 0))
         # the exchange's rank count as the TRANSPORT reports it (read back, not echoed): RCCL's ncclCommCount for the library's
         # communicator, torch.distributed's group size otherwise
         self.nranks = 1
@@ -268,7 +267,7 @@ class StreamingGather:
             if getattr(self, "_comm", None) is not None:
                 import ctypes as C
                 from . import _lib as L
-                nr = C.c_int(0)
+                nr = C.c_int()
                 L.check(L.lib().maua_comm_count(self._comm, C.byref(nr), None))
                 self.nranks = int(nr.value)
         self.transport = ("none (one rank)" if world == 1 else "torch.distributed isend / irecv" if self._side is None or

@@ -87,7 +87,7 @@ def warp_flow(x, flow, flow_exaggeration=1.0, out=None):
         raise ValueError(f"warp_flow: flow {tuple(f.shape)} does not match the image {tuple(x.shape)}")
     if out is None:
         out = torch.empty_like(x)
-    L.check(L.lib().maua_flow_warp(L.ctx(x.device), L.ptr(x), L.ptr(f), C.c_float(flow_exaggeration), B, Cn, H, W, L.ptr(out)))
+    L.check(L.lib().maua_flow_warp(L.ctx(x.device), L.ptr(x), L.ptr(f), flow_exaggeration, B, Cn, H, W, L.ptr(out)))
     return out
 
 
@@ -110,7 +110,7 @@ def check_consistency(flow_forward, flow_backward, clamp=INF, out=None):
     B, H, W, _ = ff.shape
     buf = torch.empty((2, B, H, W), dtype=torch.float32, device=ff.device) if out is None else None
     classes, res = (buf[0], buf[1]) if out is None else out
-    L.check(L.lib().maua_flow_consistency(L.ctx(ff.device), L.ptr(ff), L.ptr(fb), B, H, W, C.c_float(clamp), L.ptr(classes), L.ptr(res)))
+    L.check(L.lib().maua_flow_consistency(L.ctx(ff.device), L.ptr(ff), L.ptr(fb), B, H, W, clamp, L.ptr(classes), L.ptr(res)))
     return res
 
 
@@ -140,7 +140,7 @@ def resize_bilinear(x, size, multiplier=1.0, clamp=INF, out=None):
     Ho, Wo = int(size[0]), int(size[1])
     if out is None:
         out = torch.empty((B, Ho, Wo, Cn), dtype=torch.float32, device=x.device)
-    L.check(L.lib().maua_flow_resize_bilinear(L.ctx(x.device), L.ptr(x), B, H, W, Cn, L.ptr(out), Ho, Wo, C.c_float(multiplier), C.c_float(clamp)))
+    L.check(L.lib().maua_flow_resize_bilinear(L.ctx(x.device), L.ptr(x), B, H, W, Cn, L.ptr(out), Ho, Wo, multiplier, clamp))
     return out.squeeze(-1) if squeeze else out
 
 
@@ -177,8 +177,8 @@ def compose(frame, prev=None, flow=None, consistency=None, cached=None, flow_exa
     if out is None:
         out = torch.empty_like(x)
     L.check(L.lib().maua_flow_compose(L.ctx(x.device), L.ptr(x), L.ptr(prev), L.ptr(flow), L.ptr(consistency), L.ptr(cached), B, H, W,
-                                      C.c_float(flow_exaggeration), C.c_float(consistency_trust), C.c_float(blend), C.c_float(fade),
-                                      C.c_float(noise_injection), C.c_ulonglong(int(seed)), L.ptr(out)))
+                                      flow_exaggeration, consistency_trust, blend, fade,
+                                      noise_injection, int(seed), L.ptr(out)))
     return out
 
 
@@ -192,8 +192,8 @@ def turbo_step(prev, nxt, flow, flow_exaggeration, warp_next, blend_t, out=None)
     prev_out = new(0) if prev is not None else None
     next_out = new(1) if warp_next else None
     img = new(2)
-    L.check(L.lib().maua_flow_turbo(L.ctx(nxt.device), L.ptr(prev), L.ptr(nxt), L.ptr(f), B, H, W, C.c_float(flow_exaggeration), int(bool(warp_next)),
-                                    C.c_float(blend_t), L.ptr(prev_out), L.ptr(next_out), L.ptr(img)))
+    L.check(L.lib().maua_flow_turbo(L.ctx(nxt.device), L.ptr(prev), L.ptr(nxt), L.ptr(f), B, H, W, flow_exaggeration, int(bool(warp_next)),
+                                    blend_t, L.ptr(prev_out), L.ptr(next_out), L.ptr(img)))
     return prev_out, (next_out if warp_next else nxt), img
 
 

@@ -114,7 +114,7 @@ def resize(img, out_shape, interp_method="cubic", out=None, accumulate=False, ad
     ly, wy, ty = _device_tables(H, Ho, interp_method, x.device) if H != Ho else (None, None, 0)
     lx, wx, tx = _device_tables(W, Wo, interp_method, x.device) if W != Wo else (None, None, 0)
     L.check(L.lib().maua_image_resize(L.ctx(x.device), L.ptr(x), planes, H, W, L.ptr(out), Ho, Wo, L.ptr(ly), L.ptr(wy), ty, L.ptr(lx),
-                                      L.ptr(wx), tx, int(bool(accumulate)), C.c_float(add)))
+                                      L.ptr(wx), tx, int(bool(accumulate)), add))
     return out
 
 
@@ -198,7 +198,7 @@ def sharpen(img, strength):
     x = _image(img, "sharpen")
     B, _, H, W = x.shape
     out = torch.empty_like(x)
-    L.check(L.lib().maua_image_sharpen(L.ctx(x.device), L.ptr(x), B, H, W, C.c_float(strength), L.ptr(out)))
+    L.check(L.lib().maua_image_sharpen(L.ctx(x.device), L.ptr(x), B, H, W, strength, L.ptr(out)))
     return out
 
 
@@ -206,9 +206,9 @@ def _moments(x, navg, noise, noise_scale):
     """-> per frame (mean [3], second moment [3, 3], min, max) in float64 from the kernel's float32 slice sums."""
     frames = x.shape[0] // navg
     HW = x.shape[2] * x.shape[3]
-    slices = L.lib().maua_image_moments_slices(C.c_long(HW))
+    slices = L.lib().maua_image_moments_slices(HW)
     part = torch.empty((frames, slices, 11), dtype=torch.float32, device=x.device)
-    L.check(L.lib().maua_image_moments(L.ctx(x.device), L.ptr(x), frames, navg, C.c_long(HW), L.ptr(noise), C.c_float(noise_scale), L.ptr(part)))
+    L.check(L.lib().maua_image_moments(L.ctx(x.device), L.ptr(x), frames, navg, HW, L.ptr(noise), noise_scale, L.ptr(part)))
     p = part.cpu().numpy().astype(np.float64)     # (the one device -> host copy of the operator: 44 bytes per 4096 pixels)
     s = p[:, :, :9].sum(1) / HW
     out = []
@@ -288,9 +288,9 @@ def match_histogram(target_tensor, source_tensor, mode="avg", noise=None, seed=N
             plan.append((nt, frames))
         for k, (nt, frames) in enumerate(plan):
             for b, (M, mu_t, mu_s) in enumerate(frames):
-                L.check(lib.maua_image_match_apply(ctx, L.ptr(x[b]), L.ptr(nt[b]), C.c_float(1e-3), C.c_long(HW), f3(M.ravel()), f3(mu_t),
-                                                   f3(mu_s), C.c_float(1.0 / len(plan)), int(k > 0), int(k == len(plan) - 1),
-                                                   C.c_float(lo), C.c_float(hi), L.ptr(out[b])))
+                L.check(lib.maua_image_match_apply(ctx, L.ptr(x[b]), L.ptr(nt[b]), 1e-3, HW, f3(M.ravel()), f3(mu_t),
+                                                   f3(mu_s), 1.0 / len(plan), int(k > 0), int(k == len(plan) - 1),
+                                                   lo, hi, L.ptr(out[b])))
     except RuntimeError as e:
         if isinstance(e, L.MauaHipError):
             raise
@@ -299,8 +299,8 @@ def match_histogram(target_tensor, source_tensor, mode="avg", noise=None, seed=N
         print("Skipping histogram matching...")
         ident, zero = f3(np.eye(3).ravel()), f3([0, 0, 0])
         for b in range(B):
-            L.check(lib.maua_image_match_apply(ctx, L.ptr(x[b]), None, C.c_float(0.0), C.c_long(HW), ident, zero, zero, C.c_float(1.0), 0, 1,
-                                               C.c_float(lo), C.c_float(hi), L.ptr(out[b])))
+            L.check(lib.maua_image_match_apply(ctx, L.ptr(x[b]), None, 0.0, HW, ident, zero, zero, 1.0, 0, 1,
+                                               lo, hi, L.ptr(out[b])))
     return out
 
 

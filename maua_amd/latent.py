@@ -22,7 +22,7 @@ def _spline(knots, t_in, t_out):
     ti = np.ascontiguousarray(t_in.double().numpy())
     to = np.ascontiguousarray(t_out.double().numpy())
     out = torch.empty((len(to), *y.shape[1:]), dtype=torch.float32, device=y.device)
-    L.check(L.lib().maua_spline_natural(L.ctx(y.device), ti.ctypes.data_as(C.c_void_p), n, L.ptr(y), C.c_long(Cn),
+    L.check(L.lib().maua_spline_natural(L.ctx(y.device), ti.ctypes.data_as(C.c_void_p), n, L.ptr(y), Cn,
                                         to.ctypes.data_as(C.c_void_p), len(to), L.ptr(out)))
     return out
 
@@ -41,8 +41,7 @@ def spline_loop_latents(y, size, n_loops=1):
 
 def _blend(a, a_ts, b, b_ts, env, T, Cn, shape):
     out = torch.empty((T, *shape), dtype=torch.float32, device=env.device)
-    L.check(L.lib().maua_latent_blend(L.ctx(env.device), L.ptr(a), C.c_long(a_ts), L.ptr(b), C.c_long(b_ts), L.ptr(env),
-                                      T, C.c_long(Cn), L.ptr(out)))
+    L.check(L.lib().maua_latent_blend(L.ctx(env.device), L.ptr(a), a_ts, L.ptr(b), b_ts, L.ptr(env), T, Cn, L.ptr(out)))
     return out
 
 
@@ -63,8 +62,7 @@ def multi_weighted(latents, envelopes):
     T, An = env.shape
     Cn = lat.numel() // lat.shape[0]
     out = torch.empty((T, *lat.shape[1:]), dtype=torch.float32, device=lat.device)
-    L.check(L.lib().maua_weighted_sum(L.ctx(lat.device), L.ptr(env), L.ptr(lat), T, An, lat.shape[0], C.c_long(Cn),
-                                      L.ptr(out)))
+    L.check(L.lib().maua_weighted_sum(L.ctx(lat.device), L.ptr(env), L.ptr(lat), T, An, lat.shape[0], Cn, L.ptr(out)))
     return out
 
 
@@ -74,12 +72,10 @@ def select_modulo_indices(n_latents, envelope):
     lo, _ = A.order_stat(env, 2, q=0.25)
     hi, _ = A.order_stat(env, 2, q=0.75)
     y = torch.empty_like(env)
-    L.check(L.lib().maua_clamp(L.ctx(env.device), L.ptr(env), L.ptr(lo), L.ptr(hi), C.c_float(0), C.c_float(0),
-                               C.c_long(env.numel()), L.ptr(y)))
+    L.check(L.lib().maua_clamp(L.ctx(env.device), L.ptr(env), L.ptr(lo), L.ptr(hi), 0, 0, env.numel(), L.ptr(y)))
     y = S.normalize(y)
     idx = torch.empty((env.numel(),), dtype=torch.int64, device=env.device)
-    L.check(L.lib().maua_scale_round_index(L.ctx(env.device), L.ptr(y), C.c_float(float(n_latents - 1)),
-                                           C.c_long(env.numel()), L.ptr(idx)))
+    L.check(L.lib().maua_scale_round_index(L.ctx(env.device), L.ptr(y), float(n_latents - 1), env.numel(), L.ptr(idx)))
     return idx
 
 
@@ -88,7 +84,7 @@ def select_modulo(latents, envelope, smooth=2):
     idx = select_modulo_indices(len(lat), envelope)
     Cn = lat.numel() // lat.shape[0]
     out = torch.empty((idx.numel(), *lat.shape[1:]), dtype=torch.float32, device=lat.device)
-    L.check(L.lib().maua_gather_rows(L.ctx(lat.device), L.ptr(lat), L.ptr(idx), lat.shape[0], idx.numel(), C.c_long(Cn),
+    L.check(L.lib().maua_gather_rows(L.ctx(lat.device), L.ptr(lat), L.ptr(idx), lat.shape[0], idx.numel(), Cn,
                                      L.ptr(out)))
     return S.gaussian_filter(out, smooth, causal=0)
 
@@ -179,7 +175,7 @@ def _eerp(a, b, t, mode):
     a, b, t = torch.broadcast_tensors(a, b, t)
     a, b, t = a.contiguous(), b.contiguous(), t.contiguous()
     y = torch.empty_like(a)
-    L.check(L.lib().maua_eerp(L.ctx(a.device), L.ptr(a), L.ptr(b), L.ptr(t), C.c_long(a.numel()), mode, L.ptr(y)))
+    L.check(L.lib().maua_eerp(L.ctx(a.device), L.ptr(a), L.ptr(b), L.ptr(t), a.numel(), mode, L.ptr(y)))
     return y
 
 

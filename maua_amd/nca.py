@@ -23,32 +23,7 @@ STEP_DTYPES = {"f32": L.F32, "split": L.F32_SPLIT}
 RENDER_STEPS_PER_LAUNCH = {"f32": 1, "split": 2}      # generate()'s default per product mode, as measured (scripts/bench_nca.py)
 
 
-class NcaDesc(C.Structure):
-    """maua_nca_desc (include/maua_hip.h); pointers as integers."""
-    _fields_ = [("x", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
-                ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p),
-                ("n_steps", C.c_int), ("rate", C.c_float), ("rate_map", C.c_void_p), ("u", C.c_void_p),
-                ("seed", C.c_ulonglong), ("stream", C.c_ulonglong), ("step0", C.c_ulonglong),
-                ("col0", C.c_int), ("W_sub", C.c_int), ("margin", C.c_int), ("steps_per_launch", C.c_int)]
-
-
-_declared = False
-
-
-def _lib():
-    global _declared
-    l = L.lib()
-    if not _declared:
-        p, i = C.c_void_p, C.c_int
-        l.maua_nca_perception.argtypes = [p, p, i, i, i, i, p]
-        l.maua_nca_create.argtypes = [p, i, i, i, C.POINTER(p)]
-        l.maua_nca_destroy.argtypes = [p]
-        l.maua_nca_check.argtypes = [p, i, i, i, C.POINTER(NcaDesc)]
-        l.maua_nca_step.argtypes = [p, C.POINTER(NcaDesc)]
-        l.maua_nca_forward_keep.argtypes = [p, C.POINTER(NcaDesc), p]
-        l.maua_nca_vjp.argtypes = [p, C.POINTER(NcaDesc), p, p, p, p, p, p]
-        _declared = True
-    return l
+NcaDesc = L.NcaDesc
 
 
 def perception(x):
@@ -59,7 +34,7 @@ def perception(x):
         raise ValueError("perception expects a [B, C, H, W] tensor")
     b, c, h, w = x.shape
     out = torch.empty(b, 4 * c, h, w, dtype=torch.float32, device=x.device)
-    L.check(_lib().maua_nca_perception(L.ctx(x.device), L.ptr(x), b, c, h, w, L.ptr(out)))
+    L.check(L.lib().maua_nca_perception(L.ctx(x.device), L.ptr(x), b, c, h, w, L.ptr(out)))
     return out
 
 
@@ -94,12 +69,12 @@ class _Handle:
     def __init__(self, chn, hidden, dtype, device):
         self.p = C.c_void_p()
         self.device = device
-        L.check(_lib().maua_nca_create(L.ctx(device), chn, hidden, dtype, C.byref(self.p)))
+        L.check(L.lib().maua_nca_create(L.ctx(device), chn, hidden, dtype, C.byref(self.p)))
 
     def __del__(self):
         try:
             if self.p:
-                _lib().maua_nca_destroy(self.p)
+                L.lib().maua_nca_destroy(self.p)
         except Exception:
             pass
 
@@ -173,7 +148,7 @@ class CA(torch.nn.Module):
         d, keep = self._desc(x, n, update_rate, u, step0, window)
         if window is None:
             d.steps_per_launch = self.steps_per_launch
-        L.check(_lib().maua_nca_step(self._handle(x.device).p, C.byref(d)))
+        L.check(L.lib().maua_nca_step(self._handle(x.device).p, C.byref(d)))
         if step0 is None:
             self.steps_done += n
         return x
@@ -188,7 +163,7 @@ class CA(torch.nn.Module):
         """[n + 1, B, chn, H, W]: x and the state after each of n updates (what the gradient walks back through)"""
         d, keep = self._desc(x, n, update_rate, u, step0, None)
         states = torch.empty((n + 1,) + tuple(x.shape), dtype=torch.float32, device=x.device)
-        L.check(_lib().maua_nca_forward_keep(self._handle(x.device).p, C.byref(d), L.ptr(states)))
+        L.check(L.lib().maua_nca_forward_keep(self._handle(x.device).p, C.byref(d), L.ptr(states)))
         if step0 is None:
             self.steps_done += n
         return states
@@ -210,8 +185,8 @@ class CA(torch.nn.Module):
         d, keep = self._desc(states[0], n, update_rate, u, step0, None)
         g_first = torch.empty_like(g_last)
         dw1, db1, dw2 = (torch.empty_like(p, dtype=torch.float32, device=states.device) for p in (self.w1.weight, self.w1.bias, self.w2.weight))
-        L.check(_lib().maua_nca_vjp(self._handle(states.device).p, C.byref(d), L.ptr(states), L.ptr(g_last), L.ptr(g_first), L.ptr(dw1),
-                                    L.ptr(db1), L.ptr(dw2)))
+        L.check(L.lib().maua_nca_vjp(self._handle(states.device).p, C.byref(d), L.ptr(states), L.ptr(g_last), L.ptr(g_first), L.ptr(dw1),
+                                     L.ptr(db1), L.ptr(dw2)))
         return g_first, dw1, db1, dw2
 
 

@@ -48,7 +48,7 @@ class Loop(Noise):
         planes, idx = self._resident()
         out = self._out(b)
         L.check(L.lib().maua_noise_loop(L.ctx(), L.ptr(planes), L.ptr(idx), int(i), int(b), self.size[0], self.size[1],
-                                        C.c_float(float(self.sigma)), L.ptr(out)))
+                                        float(self.sigma), L.ptr(out)))
         return out
 
 
@@ -149,8 +149,7 @@ class Multiply(_Mix):
 def _combine(x, y, mod, mode, scale=1.0, bias=0.0):
     out = torch.empty_like(x)
     b, h, w = x.shape
-    L.check(L.lib().maua_noise_combine(L.ctx(), L.ptr(x), L.ptr(y), L.ptr(mod), mode, C.c_float(scale),
-                                       C.c_float(bias), b, h, w, L.ptr(out)))
+    L.check(L.lib().maua_noise_combine(L.ctx(), L.ptr(x), L.ptr(y), L.ptr(mod), mode, scale, bias, b, h, w, L.ptr(out)))
     return out
 
 

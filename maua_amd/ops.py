@@ -6,7 +6,6 @@ setup_filter :236-256.  Scalars may be Python numbers or 0-dim tensors (the refe
 Tensors are NCHW; float32 and bfloat16 are supported.  Every op raises MauaHipError when the HIP
 library or device is missing — there is no CPU path here.
 """
-import ctypes as C
 from math import sqrt
 
 import torch
@@ -60,7 +59,7 @@ def bias_act(x, b=None, act="linear", alpha=None, gain=None, clamp=None):
             raise ValueError("bias must have one entry per channel")
     y = torch.empty_like(x)
     L.check(L.lib().maua_bias_act(L.ctx(x.device), L.ptr(x), L.ptr(b), L.ptr(y), n, c, h, w, L.dtype_id(x),
-                                  L.ACTS[act], C.c_float(alpha), C.c_float(gain), C.c_float(clamp)))
+                                  L.ACTS[act], alpha, gain, clamp))
     return y
 
 
@@ -101,7 +100,7 @@ def upfirdn2d(x, f, up=1, down=1, padding=(0, 0, 0, 0), gain=1):
     y = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device)
     fd = L.dev_tensor(f2, torch.float32)
     L.check(L.lib().maua_upfirdn2d(L.ctx(x.device), L.ptr(x), L.ptr(fd), fh, fw, L.ptr(y), n, c, h, w, L.dtype_id(x),
-                                   up, down, px0, px1, py0, py1, C.c_float(g)))
+                                   up, down, px0, px1, py0, py1, g))
     return y
 
 
@@ -138,7 +137,7 @@ def add(a, b, out=None):
     if a.shape != b.shape:
         raise ValueError(f"add: shapes differ, {tuple(a.shape)} vs {tuple(b.shape)}")
     out = torch.empty_like(a) if out is None else out
-    L.check(L.lib().maua_add(L.ctx(a.device), L.ptr(a), L.ptr(b), L.ptr(out), C.c_long(a.numel()), L.dtype_id(a)))
+    L.check(L.lib().maua_add(L.ctx(a.device), L.ptr(a), L.ptr(b), L.ptr(out), a.numel(), L.dtype_id(a)))
     return out
 
 
@@ -148,7 +147,7 @@ def normalize_2nd_moment(x, dim=1, eps=1e-8):
         return x / ((x * x).mean(dim=dim, keepdim=True) + eps).sqrt()
     x = L.dev_tensor(x, torch.float32)
     y = torch.empty_like(x)
-    L.check(L.lib().maua_normalize_2nd_moment(L.ctx(x.device), L.ptr(x), x.shape[0], x.shape[1], C.c_float(eps), L.ptr(y)))
+    L.check(L.lib().maua_normalize_2nd_moment(L.ctx(x.device), L.ptr(x), x.shape[0], x.shape[1], eps, L.ptr(y)))
     return y
 
 
@@ -248,9 +247,9 @@ def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, res
     clamp = -1.0 if clamp is None else _num(clamp)
     y = torch.empty((n, co, h * up, w * up), dtype=x.dtype, device=x.device)
     L.check(L.lib().maua_modconv2d(L.ctx(x.device), L.ptr(x), L.ptr(weight), L.ptr(styles), L.ptr(noise),
-                                   C.c_long(nstride), C.c_float(_num(noise_strength)), L.ptr(bias), L.ptr(y), n, ci,
+                                   nstride, _num(noise_strength), L.ptr(bias), L.ptr(y), n, ci,
                                    co, h, w, kh, up, int(bool(demodulate)), int(bool(flip_weight)), L.ACTS[act],
-                                   C.c_float(alpha), C.c_float(gain), C.c_float(clamp), L.dtype_id(x)))
+                                   alpha, gain, clamp, L.dtype_id(x)))
     return y
 
 
@@ -305,7 +304,7 @@ def interpolate_bicubic(x, size):
     n, c, h, w = x.shape
     oh, ow = int(size[0]), int(size[1])
     y = torch.empty((n, c, oh, ow), dtype=x.dtype, device=x.device)
-    L.check(L.lib().maua_resize2d(L.ctx(x.device), L.ptr(x), L.ptr(y), n, c, h, w, oh, ow, 0, 0, 0, 3, C.c_float(0.0),
+    L.check(L.lib().maua_resize2d(L.ctx(x.device), L.ptr(x), L.ptr(y), n, c, h, w, oh, ow, 0, 0, 0, 3, 0.0,
                                   L.dtype_id(x)))
     return y
 
@@ -319,7 +318,7 @@ def pad2d(x, padding, mode="constant", value=0.0):
     oh, ow = h + pt + pb, w + pl + pr
     y = torch.empty((n, c, oh, ow), dtype=x.dtype, device=x.device)
     L.check(L.lib().maua_resize2d(L.ctx(x.device), L.ptr(x), L.ptr(y), n, c, h, w, oh, ow, 1, pl, pt, _PAD_HOW[mode],
-                                  C.c_float(float(value)), L.dtype_id(x)))
+                                  float(value), L.dtype_id(x)))
     return y
 
 
@@ -356,11 +355,11 @@ def resample(input, size, align_corners=True):
             taps = L.dev_tensor(_lanczos_taps(d / s, 2), torch.float32)
             y = torch.empty_like(x)
             L.check(lib.maua_conv1d_reflect(ctx, L.ptr(x), L.ptr(y), L.ptr(taps), (taps.numel() - 1) // 2, axis,
-                                            C.c_long(n * c), h, w))
+                                            n * c, h, w))
             x = y
     out = torch.empty((n, c, dh, dw), dtype=torch.float32, device=x.device)
     L.check(lib.maua_resize2d(ctx, L.ptr(x), L.ptr(out), n, c, h, w, dh, dw, 2 if align_corners else 0, 0, 0, 3,
-                              C.c_float(0.0), L.dtype_id(x)))
+                              0.0, L.dtype_id(x)))
     return out
 
 
@@ -389,6 +388,6 @@ def resample_vjp(grad_out, in_shape, align_corners=True):
         if d < s:
             taps = L.dev_tensor(_lanczos_taps(d / s, 2), torch.float32)
             y = torch.empty_like(x)
-            L.check(lib.maua_conv1d_reflect_vjp(ctx, L.ptr(x), L.ptr(y), L.ptr(taps), (taps.numel() - 1) // 2, axis, C.c_long(n * c), h, w))
+            L.check(lib.maua_conv1d_reflect_vjp(ctx, L.ptr(x), L.ptr(y), L.ptr(taps), (taps.numel() - 1) // 2, axis, n * c, h, w))
             x = y
     return x

@@ -141,8 +141,8 @@ class VGGFeatures(torch.nn.Module):
             h = C.c_void_p()
             plan = (C.c_int * len(self.plan))(*self.plan)
             mul, add, mean, std = self.pre
-            L.check(L.lib().maua_vgg_create(L.ctx(), L.dtype_id(self.dtype), plan, len(self.plan), int(self.replicate_first), C.c_float(mul),
-                                            C.c_float(add), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), C.byref(h)))
+            L.check(L.lib().maua_vgg_create(L.ctx(), L.dtype_id(self.dtype), plan, len(self.plan), int(self.replicate_first), mul,
+                                            add, (C.c_float * 3)(*mean), (C.c_float * 3)(*std), C.byref(h)))
             self._h = h
             self._dirty = True
         else:
@@ -152,7 +152,7 @@ class VGGFeatures(torch.nn.Module):
                 key, what = k.split(".")
                 a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
                 L.check(L.lib().maua_vgg_load(self._h, self.conv_of_key[key], 0 if what == "weight" else 1, a.ctypes.data_as(C.c_void_p),
-                                              C.c_size_t(a.size)))
+                                              a.size))
             self._dirty = False
         return self._h
 
@@ -272,7 +272,7 @@ class Perceptor(torch.nn.Module):
         grad = torch.empty_like(img)
         loss = torch.empty(B, dtype=torch.float32, device=img.device)
         L.check(L.lib().maua_vgg_style_grad(self.net._handle(), L.ptr(img), B, H, W, taps, len(tg), _ptr_array(tg),
-                                            (C.c_long * len(tg))(*strides), C.c_float(float(self.style_strength)), L.ptr(grad), L.ptr(loss)))
+                                            (C.c_long * len(tg))(*strides), float(self.style_strength), L.ptr(grad), L.ptr(loss)))
         self.net._shape = tuple(img.shape)
         if from_unit_range:
             grad = grad * 2.0       # d img / d x = 2
@@ -373,7 +373,7 @@ class LPIPS(torch.nn.Module):
         grad = torch.empty_like(x)
         dist = torch.empty(B, dtype=torch.float32, device=x.device)
         L.check(L.lib().maua_vgg_lpips_grad(self.net._handle(), L.ptr(x), B, H, W, taps, 5, _ptr_array(target_feats), (C.c_long * 5)(*strides),
-                                            _ptr_array(self._lins()), C.c_float(float(scale)), L.ptr(grad), L.ptr(dist)))
+                                            _ptr_array(self._lins()), float(scale), L.ptr(grad), L.ptr(dist)))
         self.net._shape = tuple(x.shape)
         return dist, grad
 

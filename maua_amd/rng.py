@@ -2,7 +2,6 @@
 ``csrc/rng.hip`` through ``maua_philox_*``.  Same numbers on every rank and device, and in the oracle twin (oracle/rng.py, pinned
 to the published known-answer vectors), without anything being exchanged or uploaded.  No reference counterpart: the reference
 draws its random-init weights and noise planes from torch's host generator (inference/stylegan2.py:216-227, noise.py:42-53)."""
-import ctypes as C
 
 import torch
 
@@ -12,8 +11,7 @@ from . import _lib as L
 def philox_u32(seed, stream, n, offset=0, device=None):
     L.require_device()
     out = torch.empty((int(n),), dtype=torch.int32, device="cuda" if device is None else device)
-    L.check(L.lib().maua_philox_u32(L.ctx(out.device), C.c_ulonglong(int(seed)), C.c_ulonglong(int(stream)), C.c_ulonglong(int(offset)),
-                                    L.ptr(out), C.c_long(int(n))))
+    L.check(L.lib().maua_philox_u32(L.ctx(out.device), int(seed), int(stream), int(offset), L.ptr(out), int(n)))
     return out
 
 
@@ -21,8 +19,8 @@ def philox_normal(shape, seed, stream, offset=0, mean=0.0, std=1.0, device=None)
     """float32 N(mean, std^2) tensor of ``shape`` on the device: elements offset .. of stream (seed, stream), row-major."""
     L.require_device()
     out = torch.empty(tuple(int(s) for s in shape), dtype=torch.float32, device="cuda" if device is None else device)
-    L.check(L.lib().maua_philox_normal(L.ctx(out.device), C.c_ulonglong(int(seed)), C.c_ulonglong(int(stream)), C.c_ulonglong(int(offset)),
-                                       L.ptr(out), C.c_long(out.numel()), C.c_float(mean), C.c_float(std)))
+    L.check(L.lib().maua_philox_normal(L.ctx(out.device), int(seed), int(stream), int(offset),
+                                       L.ptr(out), out.numel(), mean, std))
     return out
 
 
@@ -30,8 +28,7 @@ def clip_audio(n_samples, sr, seed=1234, device=None):
     """SURVEY 8(d)'s synthetic clip (tone + 2 Hz clicks + noise floor) drawn on the device: float32 [n_samples]."""
     L.require_device()
     out = torch.empty((int(n_samples),), dtype=torch.float32, device="cuda" if device is None else device)
-    L.check(L.lib().maua_philox_clip_audio(L.ctx(out.device), C.c_ulonglong(int(seed)), C.c_long(int(n_samples)), C.c_double(float(sr)),
-                                           L.ptr(out)))
+    L.check(L.lib().maua_philox_clip_audio(L.ctx(out.device), int(seed), int(n_samples), float(sr), L.ptr(out)))
     return out
 
 

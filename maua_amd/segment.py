@@ -16,7 +16,6 @@ maua_median_filter_rows, maua_soft_kmeans (csrc/segment.hip); the symmetric eige
 Laplacian is the one library call (torch.linalg.eigh on the device, as in the reference).  Host work is what the
 reference also does on the host: the k-means++ seeding with numpy's RandomState (segment.py:85-103) and the backtrace
 through the beat links."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -44,7 +43,7 @@ def beat_track(onset_envelope, bpm, sr=22050, hop_length=1024, tightness=100.0, 
     local = torch.empty(T, dtype=torch.float64, device=env.device)
     cum = torch.empty(T, dtype=torch.float64, device=env.device)
     back = torch.empty(T, dtype=torch.int32, device=env.device)
-    L.check(L.lib().maua_beat_dp(L.ctx(env.device), L.ptr(env), T, period, C.c_double(tightness), L.ptr(local), L.ptr(cum),
+    L.check(L.lib().maua_beat_dp(L.ctx(env.device), L.ptr(env), T, period, tightness, L.ptr(local), L.ptr(cum),
                                  L.ptr(back)))
     return beats_from_links(local.cpu().numpy(), cum.cpu().numpy(), back.cpu().numpy(), trim)
 
@@ -143,7 +142,7 @@ def differentiable_k_means(data, k, num_iter, cluster_temp=5):
     mu0 = torch.from_numpy(init_plus_plus(x.cpu().numpy(), k)).to(x.device).contiguous()
     r = torch.empty((n, k), dtype=torch.float32, device=x.device)
     mu = torch.empty((k, k), dtype=torch.float32, device=x.device)
-    L.check(L.lib().maua_soft_kmeans(L.ctx(x.device), L.ptr(x), n, k, L.ptr(mu0), num_iter, C.c_float(cluster_temp), L.ptr(r),
+    L.check(L.lib().maua_soft_kmeans(L.ctx(x.device), L.ptr(x), n, k, L.ptr(mu0), num_iter, cluster_temp, L.ptr(r),
                                      L.ptr(mu)))
     return mu, r, x @ mu.t()
 

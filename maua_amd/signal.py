@@ -17,7 +17,7 @@ def resample(x, size):
     n = y.shape[0]
     Cn = y.numel() // n
     out = torch.empty((size, *y.shape[1:]), dtype=torch.float32, device=y.device)
-    L.check(L.lib().maua_resample_linear(L.ctx(y.device), L.ptr(y.contiguous()), n, C.c_long(Cn), int(size), L.ptr(out)))
+    L.check(L.lib().maua_resample_linear(L.ctx(y.device), L.ptr(y.contiguous()), n, Cn, int(size), L.ptr(out)))
     return out.squeeze()
 
 
@@ -45,8 +45,7 @@ def percentile_clip(signal, percent):
         k = 1 + round(0.01 * float(percent) * (n_peaks - 1))
         hi, _ = A.order_stat(col, 1, k=k, mask=mask)
         y = torch.empty_like(col)
-        L.check(L.lib().maua_clamp(L.ctx(col.device), L.ptr(col), None, L.ptr(hi), C.c_float(0.0), C.c_float(0.0),
-                                   C.c_long(n), L.ptr(y)))
+        L.check(L.lib().maua_clamp(L.ctx(col.device), L.ptr(col), None, L.ptr(hi), 0.0, 0.0, n, L.ptr(y)))
         cols.append(y / y.max())
     return torch.stack(cols, dim=1)
 
@@ -60,8 +59,8 @@ def compress(signal, threshold, ratio, invert=False):
     (The reference scales its argument in place; this returns a new tensor.)"""
     x = A._f32(signal)
     y = torch.empty_like(x)
-    L.check(L.lib().maua_threshold_scale(L.ctx(x.device), L.ptr(x), C.c_long(x.numel()), C.c_float(float(threshold)),
-                                         C.c_float(float(ratio)), int(bool(invert)), L.ptr(y)))
+    L.check(L.lib().maua_threshold_scale(L.ctx(x.device), L.ptr(x), x.numel(), float(threshold),
+                                         float(ratio), int(bool(invert)), L.ptr(y)))
     return normalize(y)
 
 
@@ -85,5 +84,5 @@ def sosfilt(sos, x):
     rows_in, rows_out = xd.reshape(-1, n) if n else xd.reshape(0, 0), y.reshape(-1, n) if n else y.reshape(0, 0)
     for r in range(rows_in.shape[0]):
         L.check(L.lib().maua_sosfilt(L.ctx(xd.device), sos.ctypes.data_as(C.c_void_p), sos.shape[0], L.ptr(rows_in[r]),
-                                     C.c_long(n), L.ptr(rows_out[r])))
+                                     n, L.ptr(rows_out[r])))
     return y.cpu().numpy() if as_numpy else y

@@ -223,10 +223,10 @@ class SynthesisNetwork(torch.nn.Module):
             for k, v in self._params.items():
                 if v.is_cuda:   # drawn on the device (rng.PhiloxStreams): no host round trip
                     v = v.to(device=dev, dtype=torch.float32).contiguous()
-                    L.check(lib.maua_synth_load_device(net, k.encode(), L.ptr(v), C.c_size_t(v.numel())))
+                    L.check(lib.maua_synth_load_device(net, k.encode(), L.ptr(v), v.numel()))
                     continue
                 a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
-                L.check(lib.maua_synth_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+                L.check(lib.maua_synth_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), a.size))
             L.check(lib.maua_synth_set_option(net, b"keep_features", int(self._keep_features)))
             self._net, self._net_device = net, dev
             if self._resize is not None:
@@ -250,7 +250,7 @@ class SynthesisNetwork(torch.nn.Module):
             self._resize = None
             self._resized_noise = {}
             if self._net is not None:
-                L.check(L.lib().maua_synth_set_resize(self._net, -1, 0, 0, 0, 0, 0, 0, 0, 3, C.c_float(0.0), None))
+                L.check(L.lib().maua_synth_set_resize(self._net, -1, 0, 0, 0, 0, 0, 0, 0, 3, 0.0, None))
                 self._upload_noise(None)  # the device re-allocated (zeroed) the buffers whose size changed back
             return
         fn = None if fill_noise is None else np.ascontiguousarray(fill_noise.detach().float().cpu().numpy())
@@ -282,10 +282,10 @@ class SynthesisNetwork(torch.nn.Module):
                     self._resized_noise[key] = nz
             if nz.is_cuda:
                 nz = nz.to(dtype=torch.float32).contiguous()
-                L.check(L.lib().maua_synth_load_device(self._net, key.encode(), L.ptr(nz), C.c_size_t(nz.numel())))
+                L.check(L.lib().maua_synth_load_device(self._net, key.encode(), L.ptr(nz), nz.numel()))
                 continue
             a = np.ascontiguousarray(nz.numpy(), dtype=np.float32)
-            L.check(L.lib().maua_synth_load(self._net, key.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+            L.check(L.lib().maua_synth_load(self._net, key.encode(), a.ctypes.data_as(C.c_void_p), a.size))
 
     def clone(self):
         """An independent network with the same parameters (own device object, own resize state): what every wrapper
@@ -299,7 +299,7 @@ class SynthesisNetwork(torch.nn.Module):
         fill = None if r["fill"] is None else r["fill"].ctypes.data_as(C.c_void_p)
         pl, pr, pt, pb = r["padding"]
         L.check(L.lib().maua_synth_set_resize(self._net, r["layer"], r["mode"], r["th"], r["tw"], pl, pr, pt, pb,
-                                              r["how"], C.c_float(r["value"]), fill))
+                                              r["how"], r["value"], fill))
 
     def layer_size(self, layer):
         """(h, w) of synthesis layer ``layer``'s output (= its noise size); layer -1: the final image."""
@@ -372,7 +372,7 @@ class SynthesisNetwork(torch.nn.Module):
                 raise ValueError(f"noise scales must be [{self.num_layers}, >= {B}], got {None if sc is None else tuple(sc.shape)}")
         ptrs, strides, keep = self._noise_args(noise, B)
         # (the factors apply to the NEXT render call only: the library forgets them when that call returns)
-        L.check(L.lib().maua_synth_set_noise_scale(net, L.ptr(sc), C.c_long(0 if sc is None else sc.stride(0))))
+        L.check(L.lib().maua_synth_set_noise_scale(net, L.ptr(sc), 0 if sc is None else sc.stride(0)))
         L.check(L.lib().maua_synth_render_rgb8(net, L.ptr(ws), ptrs, strides, B, L.ptr(out), L.ptr(rgb8_out)))
         del keep
         return out if out is not None else rgb8_out

@@ -88,7 +88,7 @@ class RRDBNet(torch.nn.Module):
                                              L.dtype_id(self.dtype), C.byref(net)))
             for k, v in _flipped(self._params, "conv_first", "conv_last", self._flip).items():
                 a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
-                L.check(L.lib().maua_rrdb_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+                L.check(L.lib().maua_rrdb_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), a.size))
             self._net = net
         else:
             L.ctx()
@@ -196,7 +196,7 @@ class SRVGGNetCompact(torch.nn.Module):
             last = f"body.{2 * (self.num_conv + 1)}"
             for k, v in _flipped(self._params, "body.0", last, self._flip).items():
                 a = np.ascontiguousarray(v.numpy(), dtype=np.float32)
-                L.check(L.lib().maua_srvgg_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), C.c_size_t(a.size)))
+                L.check(L.lib().maua_srvgg_load(net, k.encode(), a.ctypes.data_as(C.c_void_p), a.size))
             self._net = net
         else:
             L.ctx()

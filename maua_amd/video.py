@@ -12,7 +12,6 @@ import subprocess
 import threading
 from pathlib import Path
 
-import ctypes as C
 
 import numpy as np
 import torch
@@ -31,7 +30,7 @@ def tensor2bytes_device(tensor, value_range=(0, 1)):
     mn, mx = (float(v) for v in value_range)
     b, c, h, w = x.shape
     out = torch.empty(b, h, w, c, dtype=torch.uint8, device=x.device)
-    L.check(L.lib().maua_tensor2bytes(L.ctx(x.device), L.ptr(x), L.ptr(out), b, c, h, w, C.c_double(mn), C.c_double(mx)))
+    L.check(L.lib().maua_tensor2bytes(L.ctx(x.device), L.ptr(x), L.ptr(out), b, c, h, w, mn, mx))
     return out
 
 

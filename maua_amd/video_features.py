@@ -34,7 +34,7 @@ def layout_of(frames, H, W):
 def check_push(H, W, bins, max_batch, layout, B):
     """maua_vfeat_push's refusals for such a plan and batch, without a device (maua_vfeat_check): raises MauaHipError with the launcher's own
     message.  Pointers are only checked for NULL, so any non-NULL value stands for them."""
-    one = C.c_void_p(256)
+    one = 256
     L.check(L.lib().maua_vfeat_check(None, int(H), int(W), int(bins), int(max_batch), one, int(layout), int(B), one, None, one, one))
 
 

@@ -1,5 +1,4 @@
 """GPU box: maua_linear_nt (csrc/gemm.hip) on the guided-diffusion UNet's 1x1 / attention shapes at batch 16: ms and TFLOP/s."""
-import ctypes as C
 import os
 import sys
 import time
@@ -19,7 +18,7 @@ for name, M, N, K in shapes:
     w = torch.randn(N, K, device="cuda").bfloat16()
     b = torch.randn(N, device="cuda")
     c = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-    f = lambda: L.check(lib.maua_linear_nt(ctx, L.ptr(a), L.ptr(w), L.ptr(b), None, L.ptr(c), C.c_long(M), N, K, L.BF16))
+    f = lambda: L.check(lib.maua_linear_nt(ctx, L.ptr(a), L.ptr(w), L.ptr(b), None, L.ptr(c), M, N, K, L.BF16))
     f(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(20):

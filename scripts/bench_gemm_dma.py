@@ -1,7 +1,6 @@
 """The CLIP tower's GEMM shapes (M = 1024 images x 197 tokens) through maua_linear_nt on gemm_dma.hip (ctx option "linear_dma"):
 ms and TFLOP/s per shape, checked against torch on a slice.  `python scripts/bench_gemm_dma.py [--reps 5]`"""
 import argparse
-import ctypes as C
 import os
 import sys
 import time
@@ -27,7 +26,7 @@ for (N, K, name) in ((768, 768, "conv1 / out_proj"), (2304, 768, "in_proj"), (30
     b = torch.randn(N, generator=g).cuda()
     y = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
     def run():
-        L.check(lib.maua_linear_nt(ctx, L.ptr(x), L.ptr(w), L.ptr(b), None, L.ptr(y), C.c_long(M), N, K, L.BF16))
+        L.check(lib.maua_linear_nt(ctx, L.ptr(x), L.ptr(w), L.ptr(b), None, L.ptr(y), M, N, K, L.BF16))
     run()
     torch.cuda.synchronize()
     ref = x[:512].float() @ w.float().t() + b

@@ -14,7 +14,7 @@ x = m.net._check(a)
 for k in range(5):
     taps = (C.c_int * 1)(m.net.op_of(LPIPS_TAPS[k]))
     grad = torch.empty_like(x); dist = torch.empty(2, device='cuda')
-    L.check(L.lib().maua_vgg_lpips_grad(m.net._handle(), L.ptr(x), 2, 64, 64, taps, 1, _ptr_array([feats[k]]), (C.c_long*1)(0), _ptr_array([m._lins()[k]]), C.c_float(3.0), L.ptr(grad), L.ptr(dist)))
+    L.check(L.lib().maua_vgg_lpips_grad(m.net._handle(), L.ptr(x), 2, 64, 64, taps, 1, _ptr_array([feats[k]]), (C.c_long*1)(0), _ptr_array([m._lins()[k]]), 3.0, L.ptr(grad), L.ptr(dist)))
     with torch.enable_grad():
         xx = a.clone().requires_grad_()
         f0 = OG.vgg_features(p, OG.VGG16_CFG, OG.normalize_img(xx, OG.LPIPS_SHIFT, OG.LPIPS_SCALE), (LPIPS_TAPS[k],))[0]

@@ -14,7 +14,7 @@ for _ in range(3): net(ws, rgb8_out=u8)
 L.check(lib.maua_synth_set_option(h, b"profile", 1))
 for _ in range(5): net(ws, rgb8_out=u8)
 import ctypes as C
-n = C.c_int(0)
+n = C.c_int()
 L.check(lib.maua_synth_get_profile(h, None, 0, C.byref(n)))
 ms = (C.c_float * n.value)()
 L.check(lib.maua_synth_get_profile(h, ms, n.value, C.byref(n)))

@@ -37,11 +37,11 @@ d = torch.randn_like(ref)
 r = np.ascontiguousarray(np.asarray(rects, dtype=np.int32))
 s3 = (C.c_float * 3)(1.0, 1.0, 1.0)
 ga, gb = torch.empty_like(img), torch.empty_like(img)
-L.check(L.lib().maua_cutouts_vjp(L.ctx(), L.ptr(d), B, 256, 256, r.ctypes.data_as(C.c_void_p), len(r), 224, C.c_float(0.5), s3, L.ptr(ga)))
+L.check(L.lib().maua_cutouts_vjp(L.ctx(), L.ptr(d), B, 256, 256, r.ctypes.data_as(C.c_void_p), len(r), 224, 0.5, s3, L.ptr(ga)))
 b = 0
 for _ in range(N):
     b += int(not torch.equal(_run_cutouts(img, rects, 224, 0.5, 0.5), ref))
-    L.check(L.lib().maua_cutouts_vjp(L.ctx(), L.ptr(d), B, 256, 256, r.ctypes.data_as(C.c_void_p), len(r), 224, C.c_float(0.5), s3, L.ptr(gb)))
+    L.check(L.lib().maua_cutouts_vjp(L.ctx(), L.ptr(d), B, 256, 256, r.ctypes.data_as(C.c_void_p), len(r), 224, 0.5, s3, L.ptr(gb)))
     b += int(not torch.equal(ga, gb))
 print(f"flagged cutouts + adjoint (16 cutouts of 224^2), {N} re-runs: mismatching runs {b}")
 bad += b

@@ -201,7 +201,7 @@ def test_step_refusals_name_the_limit():
     """maua_nca_check is host only: the sizes the kernel is built for, and the window's geometry"""
     import ctypes as C
     from maua_amd import _lib as L, nca
-    l = nca._lib()
+    l = L.lib()
 
     def check(chn, hidden, dtype, **kw):
         f = dict(x=64, B=1, H=8, W=8, w1=64, b1=64, w2=64, n_steps=1, rate=0.5)
