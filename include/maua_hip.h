@@ -1068,6 +1068,49 @@ long maua_correlation_workspace(int T, int Fx, int Fy);
 int maua_correlation_check(const float* x, const float* y, int T, int Fx, int Fy, int metric, const void* ws, long ws_bytes, const float* out);
 int maua_correlation(maua_ctx* ctx, const float* x, const float* y, int T, int Fx, int Fy, int metric, void* ws, long ws_bytes, float* out);
 
+/* ---- GAN evaluation metrics on a float64 matrix-core GEMM (maua/GAN/metrics/{frechet,kernel,prdc}.py; csrc/gemm_f64.hip) ------------
+ * Everything here is float64 on v_mfma_f64_16x16x4_f64.  Feature matrices are device memory, row-major [rows][d], float32 (f64 = 0, widened
+ * on load) or float64 (f64 = 1).  Workspaces are device memory, 256-byte aligned, sized by the _workspace call beside each entry point
+ * (nothing is allocated).  Sums are trees of a fixed shape and counts are integer atomics: a rerun is bit-identical.
+ *
+ * maua_gemm_f64: row-major C = alpha op(A) op(B) + beta C, op(A) [M][K], op(B) [K][N]; transa / transb != 0: the operand is stored
+ * transposed ([K][M] / [N][K]).  Any M, N, K >= 1, leading dimensions at least a stored row; beta == 0 never reads C. */
+int maua_gemm_f64(maua_ctx* ctx, int transa, int transb, int M, int N, int K, double alpha, const double* a, long lda, const double* b, long ldb,
+                  double beta, double* c, long ldc);
+/* frechet.py:73-74: mean [d] = torch.mean(feats, axis=0) and cov [d][d] = torch.cov(feats.T): centred before the product, denominator N - 1
+ * (N >= 2). */
+long maua_metrics_moments_workspace(int N, int d);
+int maua_metrics_moments(maua_ctx* ctx, const void* feats, int f64, int N, int d, void* ws, long ws_bytes, double* mean, double* cov);
+/* frechet.py:4-46, the Newton-Schulz square root of m [d][d]: Y = m / |m|_F, Z = I; T = (3 I - Z Y) / 2, Y <- Y T, Z <- T Z;
+ * s = Y sqrt(|m|_F), error = |m - s s|_F / |m|_F; stops once error <= 1e-5 or error > the previous one, and s [d][d] (device) is the S of
+ * the iteration that stopped, the diverged one included, as the reference returns it.  errors [num_iters] and iters [1] are HOST memory
+ * (either may be NULL): the error of every iteration run and their number.  Synchronises the stream once per iteration. */
+long maua_sqrtm_workspace(int d);
+int maua_sqrtm_newton_schulz(maua_ctx* ctx, const double* m, int d, int num_iters, void* ws, long ws_bytes, double* s, double* errors, int* iters);
+/* frechet.py:61-94: |mu1 - mu2|^2 + tr sigma1 + tr sigma2 - 2 tr sqrtm(sigma1 sigma2); on a non-finite root the one retry with eps on both
+ * diagonals (:82-85).  distance [1], errors [num_iters], iters [1], retried [1]: HOST memory (the last three may be NULL). */
+long maua_frechet_workspace(int N1, int N2, int d);
+int maua_frechet_distance(maua_ctx* ctx, const void* feats1, int N1, const void* feats2, int N2, int d, int f64, double eps, int num_iters,
+                          void* ws, long ws_bytes, double* distance, double* errors, int* iters, int* retried);
+/* kernel.py:4-18 with n = d.  idx [S][2][m] (device): for subset s the rows of feats2 that make x, then the rows of feats1 that make y,
+ * drawn by the host in that order (an index outside its set yields NaN, never a read).  raw [S][3][2] (device): sum and trace of
+ * (x x^T / n + 1)^3, (y y^T / n + 1)^3, (x y^T / n + 1)^3; sums [S][3] (device): sum a, tr a, sum b of :14-15; kid [1] (device): :16-17.
+ * 2 <= m <= min(N1, N2). */
+long maua_kernel_distance_workspace(int m, int d);
+int maua_kernel_distance(maua_ctx* ctx, const void* feats1, int N1, const void* feats2, int N2, int d, int f64, const long* idx, int S, int m,
+                         void* ws, long ws_bytes, double* kid, double* sums, double* raw);
+/* prdc.py:10-24: dist [N][M] (device) = max(|x_i|^2 + |y_j|^2 - 2 x_i . y_j, 0), NaN -> 0.  The one call that writes the matrix. */
+long maua_prdc_workspace(int N, int M, int d);
+int maua_pairwise_distances(maua_ctx* ctx, const void* x, int N, const void* y, int M, int d, int f64, void* ws, long ws_bytes, double* dist);
+/* prdc.py:27-37: radii [N] (device) = the (nearest_k + 1)-th smallest distance of every row to its own set, the self distance included.
+ * nearest_k in 1 .. 15, N >= nearest_k + 1; ws: maua_prdc_workspace(N, 1, d) bytes. */
+int maua_knn_radii(maua_ctx* ctx, const void* feats, int N, int d, int f64, int nearest_k, void* ws, long ws_bytes, double* radii);
+/* prdc.py:40-61 as integers: counts [4] (device) = fakes inside some real ball, reals inside some fake ball, sum over the fakes of the real
+ * balls they lie in, reals whose nearest fake lies inside their own ball; r_real [N], r_fake [M] (device): the two radius vectors.
+ * precision = counts[0] / M, recall = counts[1] / N, density = counts[2] / (nearest_k M), coverage = counts[3] / N. */
+int maua_prdc(maua_ctx* ctx, const void* real, int N, const void* fake, int M, int d, int f64, int nearest_k, void* ws, long ws_bytes,
+              unsigned long long* counts, double* r_real, double* r_fake);
+
 /* ---- build-owned counter RNG: Philox4x32-10, identical on every device / rank and in the oracle twin (oracle/rng.py,
  * pinned to the published known-answer vectors).  No reference counterpart: the reference's random-init generator and noise planes
  * come from torch's host generator (inference/stylegan2.py:216-227, selfsupervised/noise.py:42-53); the benchmark's synthetic
