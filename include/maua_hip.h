@@ -196,6 +196,18 @@ int maua_synth_get_profile(maua_synth* net, float* ms_out, int capacity, int* co
 int maua_synth_set_noise_scale(maua_synth* net, const float* scales, long layer_stride);
 /* debug/parity (what a torch forward hook on SynthesisLayer would capture): copy layer l's activation (NHWC, net dtype) converted to f32 NCHW [B,C,h,w] after a forward. */
 int maua_synth_get_feature(maua_synth* net, int layer, int B, float* out_nchw);
+/* The gradient of the network to its latents, for the last forward that ran with option "keep_features" = 1 at this batch size
+ * (that mode keeps every layer's output in its own buffer; the styles and demodulation coefficients of that forward are still in
+ * the layers' buffers).  noise / noise_batch_stride: what that forward was given.  g_img: device f32 [B,3,R,R] = d loss / d img;
+ * g_ws: device f32 [B,num_ws,w_dim] = d loss / d ws (overwritten).  The walk goes from the last block to the first through the
+ * layer gradients below; gradients to noise, biases and weights are not computed.  The gradient convolutions' weights are made
+ * from the loaded ones on the first call: a network that only runs forwards allocates nothing for this.  Two calls give the same
+ * bits.  No reference counterpart in code (the reference uses torch.autograd, sampling/langevin.py:100-127). */
+int maua_synth_vjp(maua_synth* net, const float* const* noise, const long* noise_batch_stride, int B, const float* g_img, float* g_ws);
+/* host only: MAUA_OK if maua_synth_vjp would run; else MAUA_ERR and in maua_last_error() the cause - no kept forward of this batch
+ * size; an option, a weight load or a resize after it; a resize or warp hook installed; an MAUA_F16 network; a forward that ran with
+ * per-sample noise scales (maua_synth_set_noise_scale) */
+int maua_synth_vjp_check(const maua_synth* net, int B);
 
 /* ---- audio pre-pass (once per clip).  n_fft = 2048, hop = 1024, periodic Hann, centre/reflect padding ---- */
 /* Spectra are FRAME-major: spec[frame][bin] complex64 (re, im interleaved), 1025 bins. */
@@ -657,6 +669,23 @@ int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const maua_modcon
  * x NHWC [B][H][W][C] in dtype, wmod [B][3][C], bias [3], prev [B][3][H / 2][W / 2] or NULL, out [B][3][H][W] float32 */
 int maua_torgb_ex(maua_ctx* ctx, const void* x, const float* wmod, const float* bias, const float* prev, float* out, int B, int H,
                   int W, int C, float clamp, int dtype);
+/* The gradient of one such layer to its input and its styles.  fwd: the layer exactly as maua_modconv_ex took it, with y = the output
+ * that call left (the activation mask and the convolution result are recovered from it; the latter is not kept); act linear or
+ * lrelu, no noise_scale / out_scale / y_scaled / fused toRGB.  g_y: d loss / d y, NHWC in `dtype` like y; g_x: d loss / d x
+ * [B][H][W][Ci] in `dtype` (may be NULL); g_s: d loss / d s, DEVICE float32 [B][Ci], through the modulation and through d as the
+ * demodulation coefficients of s (d[b][co] = rsqrt(sum_ci s^2 sum_taps W^2 + 1e-8); d == NULL: no such term).  The input-gradient
+ * convolution runs on the matrix cores (bf16, or exact float32), up == 2 as a stride-2 implicit GEMM over the FIR adjoint of g_y.
+ * Reductions run in a fixed order.  dtype: MAUA_F32 or MAUA_BF16 (MAUA_F16 is refused: its pre-normalisation is not differentiated). */
+int maua_modconv_vjp_ex(maua_ctx* ctx, const maua_modconv_desc* fwd, const void* g_y, void* g_x, float* g_s, int dtype);
+/* host only, no device needed: every refusal of maua_modconv_vjp_ex, with the same message.  Pointers are only checked. */
+int maua_modconv_vjp_check(const maua_modconv_desc* fwd, const void* g_y, float* g_s, int dtype);
+/* the gradient of maua_torgb_ex's y = clamp(x . wmod + bias, clamp) (recomputed for the clamp's mask; the skip image passes g_img
+ * on unchanged): g_x [B][H][W][C] in `dtype` = (accumulate ? g_x : 0) + sum_c wmod[b][c][.] g_img[b][c][p] where |y| < clamp,
+ * g_wmod DEVICE float32 [B][3][C] = sum_p x[b][p][.] g_img[b][c][p]; g_img DEVICE float32 [B][3][H][W]; C a multiple of 32 */
+int maua_torgb_vjp_ex(maua_ctx* ctx, const void* x, const float* wmod, const float* bias, const float* g_img, void* g_x, float* g_wmod,
+                      int B, int H, int W, int C, float clamp, int accumulate, int dtype);
+int maua_torgb_vjp_check(const void* x, const float* wmod, const float* bias, const float* g_img, void* g_x, float* g_wmod, int B, int H,
+                         int W, int C, int dtype);
 /* the plan of the next forward (host only, no launch): per conv layer 7 ints {route, src (0 Kernel, 1 Producer, 2 Xm, 3 PremodPass),
  * scale_next, dual, rgb, rgb8, skip_store} into conv_out [capacity][7], per block its toRGB route (0 Separate, 1 Fused, 2 Hook) into
  * rgb_out [blocks]; *pack: the u8 frame is packed by its own launch.  Returns the number of conv layers through *n_layers. */

@@ -316,6 +316,69 @@ struct RgbArgs {
 };
 int launch_torgb(hipStream_t stream, int dtype, const RgbArgs& a);
 
+// ---- modconv_vjp.hip: the gradient of one modulated 3x3 layer (and of toRGB, and of the skip image's up-sampling) to its input and
+// its styles.  Forward, as layer_args describes it: u = conv(W, s x), v = d u + noise strength + bias, y = clamp(lrelu(v) gain).
+struct ModconvVjpArgs {
+  const void* x;        // the layer's input, NHWC [B][H][W][Ci] (T)
+  long x_bstride;       // elements between samples (0: one sample for all - the learned const input)
+  const void* y;        // the kept output [B][H up][W up][Co] (T): the activation mask and u are recovered from it
+  const void* g_y;      // d loss / d y, same shape (T)
+  const void* wg;       // launch_prep_vjp_weights / launch_vjp_weights_from_prepared: T [9][Ci][Co]
+  const float* wsq;     // [Co][Ci] (unused when d == NULL)
+  const float* s;       // [B][Ci]
+  const float* d;       // [B][Co] or NULL
+  const float* noise;   // [B|1][H up][W up] or NULL
+  long noise_bstride;
+  float noise_strength;
+  const float* bias;    // [Co] or NULL
+  void* g_x;            // d loss / d x [B][H][W][Ci] (T) or NULL (nobody wants it: the const input)
+  int accumulate;       // g_x += instead of g_x =
+  float* g_s;           // d loss / d s [B][Ci], through the modulation AND the demodulation coefficients
+  int B, H, W, Ci, Co, up;
+  int act;              // MAUA_ACT_LINEAR / MAUA_ACT_LRELU
+  float alpha, gain, clamp;
+  // workspaces (modconv_vjp_workspace): g_u T [B][H up][W up][Co]; g_t T [B][2H + 1][2W + 1][Co] (up == 2); g_xm f32 [B][H][W][Ci];
+  // part f32 (the chunk sums of both reductions); g_d f32 [B][Co]
+  void* g_u;
+  void* g_t;
+  float* g_xm;
+  float* part;
+  float* g_d;
+};
+struct ModconvVjpWorkspace { size_t g_u, g_t, g_xm, part, g_d; };   // bytes
+ModconvVjpWorkspace modconv_vjp_workspace(int dtype, int B, int H, int W, int Ci, int Co, int up);
+int modconv_vjp_check(int dtype, const ModconvVjpArgs& a);   // host only: launch_modconv_vjp's refusals (everything but the workspaces)
+int launch_modconv_vjp(hipStream_t st, int dtype, const ModconvVjpArgs& a);
+// wg [t][ci][co] = W[co][ci][t] (up == 2 with flip: W[co][ci][8 - t]) from the float32 weights [Co][Ci][3][3]; wsq (optional) [Co][Ci]
+int launch_prep_vjp_weights(hipStream_t st, int dtype, const float* w, void* wg, float* wsq, int Co, int Ci, int flip);
+// the same weights from what a network already holds in `dtype`: up == 1 launch_prep_weights' [9][Co][Ci], up == 2
+// launch_prep_tconv_weights' class form (the flip is already in it) - the gradient sees the forward's rounded weights
+int launch_vjp_weights_from_prepared(hipStream_t st, int dtype, const void* prepared, void* wg, int Co, int Ci, int up);
+// toRGB: y = clamp(x . wmod + bias, clamp) recomputed for its mask; g_x (+)= wmod^T g_y, g_wmod [B][3][C] = sum_p x g_y.
+// part: torgb_vjp_part_bytes() of scratch
+struct RgbVjpArgs {
+  const void* x;        // NHWC [B][H][W][C] (T)
+  const float* wmod;    // [B][3][C]
+  const float* bias;    // [3]
+  const float* g_img;   // [B][3][H][W]
+  void* g_x;            // [B][H][W][C] (T)
+  int accumulate;
+  float* g_wmod;        // [B][3][C]
+  float* part;
+  int B, H, W, C;
+  float clamp;
+};
+size_t torgb_vjp_part_bytes(int B, int H, int W, int C);
+int torgb_vjp_check(int dtype, const RgbVjpArgs& a);
+int launch_torgb_vjp(hipStream_t st, int dtype, const RgbVjpArgs& a);
+// the adjoint of upsample2d ([1, 3, 3, 1], gain 4): g_img [B][3][2h][2w] -> g_prev [B][3][h][w]
+int launch_skip_vjp(hipStream_t st, const float* g_img, float* g_prev, int B, int h, int w);
+// g_ws[b][w_index][k] += scale * sum_c g_s[b][c] A[c][k] (A [C][w_dim]: an affine layer); g_s rows are ld floats apart
+int launch_affine_vjp(hipStream_t st, const float* g_s, int ld, const float* affine_w, float scale, float* g_ws, int w_index, int num_ws,
+                      int w_dim, int B, int C);
+// toRGB's styles: g_s[b][c] = sum_k wrgb[k][c] g_wmod[b][k][c]
+int launch_rgb_styles_vjp(hipStream_t st, const float* g_wmod, const float* wrgb, float* g_s, int B, int C);
+
 // ---- gemm.hip: C[M][N] = A[M][K] x W[N][K]^T (+ bias[N]) (+ res[M][N]); A's columns may come from two tensors (K0 from
 // a0, K1 from a1: a channel concatenation that is never materialised).  T = network dtype; K0, K1 multiples of 64 bytes,
 // N % 32 == 0.  The 1x1 convolutions of the diffusion UNet (NHWC rows = pixels).

@@ -439,6 +439,24 @@ class SynthesisNetwork(torch.nn.Module):
             return out
         return img if rgb8_out is None else rgb8_out
 
+    def vjp(self, g_img, noise=None):
+        """d loss / d ws [B, num_ws, w_dim] from ``g_img`` = d loss / d img [B, 3, R, R], for the last forward - which must have run
+        with ``keep_features(True)``, at this batch size and with this ``noise`` (maua_synth_vjp: the walk back through every layer's
+        hand-written gradient kernels; 'skip' architecture, float32 or bfloat16 networks, no resize / warp hooks, no RawNoise)."""
+        net = self._handle()
+        g_img = L.dev_tensor(g_img, torch.float32)
+        B = g_img.shape[0]
+        if tuple(g_img.shape[1:]) != (3, *self.output_hw):
+            raise ValueError(f"g_img must be [B, 3, {self.output_hw[0]}, {self.output_hw[1]}], got {tuple(g_img.shape)}")
+        from .noise import RawNoise
+        if isinstance(noise, RawNoise):
+            raise NotImplementedError("un-normalised noise maps (RawNoise) are not differentiated: pass noise.normalised()")
+        ptrs, strides, keep = self._noise_args(noise, B)
+        g_ws = torch.empty((B, self.num_ws, self.w_dim), dtype=torch.float32, device=g_img.device)
+        L.check(L.lib().maua_synth_vjp(net, ptrs, strides, B, L.ptr(g_img), L.ptr(g_ws)))
+        del keep
+        return g_ws
+
     def get_feature(self, layer, B):
         shp = self.layer_shapes()[layer]
         h, w = self.layer_size(layer)
@@ -491,19 +509,28 @@ class MappingNetwork(torch.nn.Module):
             elif strict:
                 raise KeyError(k)
 
+    def _matrix(self, i):
+        """layer i's matrix as matmul_nt's second operand: y = x @ M^T (gain folded in).  F.linear(x, w) upstream; the in-tree layer
+        multiplies by the un-transposed matrix"""
+        wh = self._params[f"fcs.{i}.weight"]
+        w = wh * (self.lr_multiplier / sqrt(wh.shape[1]))
+        return w if self.nv_compat else w.T.contiguous()
+
     @L.host_threads(1)
-    def forward(self, z, c=None, truncation_psi=1.0, truncation_cutoff=None):
+    def forward(self, z, c=None, truncation_psi=1.0, truncation_cutoff=None, keep=False):
+        """``keep=True``: remember z and every layer's pre-activation for ``vjp`` (a few [P, w_dim] tensors)."""
         L.require_device()
         x = L.dev_tensor(z, torch.float32)
+        if keep:
+            self._kept = dict(z=x, pre=[], psi=truncation_psi, cutoff=truncation_cutoff)
         x = ops.normalize_2nd_moment(x)
         for i in range(self.num_layers):
             # (gain and layout of the 512 x 512 matrices are prepared on the host: the once-per-clip mapper then runs only
             #  library kernels - the first elementwise PyTorch kernel of a process costs ~0.3 s of code-object loading)
-            wh = self._params[f"fcs.{i}.weight"]
-            w = wh * (self.lr_multiplier / sqrt(wh.shape[1]))
             b = (self._params[f"fcs.{i}.bias"] * self.lr_multiplier).to(x.device)
-            # F.linear(x, w) upstream; the in-tree layer multiplies by the un-transposed matrix
-            y = ops.matmul_nt(x, (w if self.nv_compat else w.T.contiguous()).to(x.device))
+            y = ops.matmul_nt(x, self._matrix(i).to(x.device))
+            if keep:
+                self._kept["pre"].append(y + b)
             x = ops.bias_act(y[:, :, None, None], b, act="lrelu")[:, :, 0, 0]
         x = ops.repeat_rows(x, self.num_ws)
         if truncation_psi != 1:  # stylegan2.py:185-190: lerp towards w_avg, all ws or only the first `cutoff`
@@ -513,6 +540,30 @@ class MappingNetwork(torch.nn.Module):
             else:
                 x[:, :truncation_cutoff] = w_avg.lerp(x[:, :truncation_cutoff], truncation_psi)
         return x
+
+    @L.host_threads(1)
+    def vjp(self, g_ws):
+        """d loss / d z [P, z_dim] from d loss / d ws [P, num_ws, w_dim], for the last ``forward(..., keep=True)``: the sum over
+        the ws rows with the truncation lerp's factor on the rows it touched, back through the layers (lrelu' * sqrt 2 from the kept
+        pre-activations, then the transposed matrix on the library's small GEMM), and through normalize_2nd_moment."""
+        k = getattr(self, "_kept", None)
+        if k is None:
+            raise RuntimeError("MappingNetwork.vjp: no kept forward (call forward(..., keep=True) first)")
+        g_ws = L.dev_tensor(g_ws, torch.float32)
+        if g_ws.shape[0] != k["z"].shape[0] or tuple(g_ws.shape[1:]) != (self.num_ws, self.w_dim):
+            raise ValueError(f"g_ws must be [{k['z'].shape[0]}, {self.num_ws}, {self.w_dim}], got {tuple(g_ws.shape)}")
+        if k["psi"] != 1:   # w = w_avg + psi (x - w_avg) on the rows below the cutoff
+            scale = torch.ones(self.num_ws, device=g_ws.device)
+            scale[:self.num_ws if k["cutoff"] is None else k["cutoff"]] = k["psi"]
+            g = (g_ws * scale[None, :, None]).sum(1)
+        else:
+            g = g_ws.sum(1)
+        for i in reversed(range(self.num_layers)):
+            g = g * torch.where(k["pre"][i] > 0, sqrt(2.0), 0.2 * sqrt(2.0))
+            g = ops.matmul_nt(g, self._matrix(i).T.contiguous().to(g.device))      # g @ M
+        z = k["z"]
+        r = ((z * z).mean(1, keepdim=True) + 1e-8).rsqrt()                      # x0 = z r
+        return r * g - z * r ** 3 * (z * g).mean(1, keepdim=True)
 
 
 # =================================================================================================== wrappers
@@ -835,6 +886,36 @@ class StyleGAN2(MauaGenerator):
 
     def forward(self, z, *args, c=None, **kwargs):
         return self.synthesizer(self.mapper(z, c))
+
+    def latent_grad(self, latents, grad_modules, space="z", noise=None, t=None, truncation=1.0):
+        """(d loss / d latents, img): see ``latent_grad`` below"""
+        return latent_grad(self.mapper.G_map, self.synthesizer.G_synth, latents, grad_modules, space, noise, t, truncation)
+
+
+def latent_grad(G_map, G_synth, latents, grad_modules, space="z", noise=None, t=None, truncation=1.0):
+    """(d loss / d latents, img): the sum of the ``grad_modules``' image gradients (maua_amd.grad.GradModule: forward(img, t) ->
+    d loss / d img on the device) taken through the synthesis network (SynthesisNetwork.vjp) and, for ``space="z"`` (latents
+    [B, z_dim]), on through the mapper (MappingNetwork.vjp).  ``space="w"``: latents are ws [B, num_ws, w_dim].  img [B, 3, R, R] in
+    [-1, 1].  The synthesis network keeps its features for the call (left on if the caller had them on: switching frees its workspace)."""
+    if space not in ("z", "w"):
+        raise ValueError(f"space must be 'z' or 'w', got {space!r}")
+    if isinstance(grad_modules, torch.nn.Module):
+        grad_modules = [grad_modules]
+    was = G_synth._keep_features
+    G_synth.keep_features(True)
+    try:
+        ws = G_map.forward(latents, None, truncation_psi=truncation, keep=True) if space == "z" else latents
+        img = G_synth.forward(ws, noise=noise)
+        if t is None:   # (the losses' cutout schedules read a diffusion timestep: the middle of it)
+            t = torch.tensor(500.0)
+        g_img = None
+        for m in grad_modules:
+            g = m(img, t)
+            g_img = g if g_img is None else g_img + g
+        g_ws = G_synth.vjp(g_img, noise=noise)
+    finally:
+        G_synth.keep_features(was)
+    return (G_map.vjp(g_ws) if space == "z" else g_ws), img
 
 
 def get_generator_class(architecture):
