@@ -197,7 +197,7 @@ int attention_check(int dtype, const AttnArgs& a) {
   MAUA_REQUIRE(a.qkv && a.out, "attention: NULL qkv / out");
   MAUA_REQUIRE(a.B >= 0 && a.T > 0 && a.heads > 0, "attention: bad shape");
   MAUA_REQUIRE(a.B <= 65535 && a.heads <= 65535, "attention: grid too large");
-  const long es = dtype == MAUA_BF16 ? 2 : 4;
+  const long es = elem_bytes(dtype);
   MAUA_REQUIRE(((uintptr_t)a.qkv | (uintptr_t)a.out) % 16 == 0 && (uintptr_t)a.lse % 4 == 0, "attention: qkv / out must be 16-byte aligned");
   MAUA_REQUIRE(a.ld_qkv >= 3L * a.heads * a.D && a.ld_out >= (long)a.heads * a.D, "attention: row strides below the heads' channels");
   MAUA_REQUIRE(a.ld_qkv * es % 16 == 0 && a.ld_out * es % 16 == 0, "attention: row strides must be whole 16-byte pieces");
@@ -213,11 +213,9 @@ int launch_attention(hipStream_t stream, int dtype, const AttnArgs& a) {
     if (a.causal) hipLaunchKernelGGL((attention_kernel<TT, DD, true>), grid, dim3(256), 0, stream, a);  \
     else hipLaunchKernelGGL((attention_kernel<TT, DD, false>), grid, dim3(256), 0, stream, a);          \
   } while (0)
-  if (dtype == MAUA_BF16) {
-    if (a.D == 64) MAUA_ATTN(bf16_t, 64); else MAUA_ATTN(bf16_t, 32);
-  } else {
-    if (a.D == 64) MAUA_ATTN(float, 64); else MAUA_ATTN(float, 32);
-  }
+  dispatch_dtype<bf16_t, float>(dtype, "attention", [&](auto t) {
+    if (a.D == 64) MAUA_ATTN(decltype(t), 64); else MAUA_ATTN(decltype(t), 32);
+  });
 #undef MAUA_ATTN
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;

@@ -79,16 +79,19 @@ int maua_attention_legacy_vjp(maua_ctx* ctx, const void* qkv, const void* d_out,
   MAUA_REQUIRE(ctx && qkv && d_out && d_qkv, "maua_attention_legacy_vjp: NULL argument");
   MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_attention_legacy_vjp: f32 / bf16");
   if (B == 0) return MAUA_OK;
-  const size_t esize = dtype == MAUA_BF16 ? 2 : 4;
-  const size_t out_bytes = ((size_t)B * T * heads * head_ch * esize + 255) & ~(size_t)255, row_bytes = ((size_t)B * heads * T * 4 + 255) & ~(size_t)255;
-  if (int rc = scratch_reserve(ctx, out_bytes + 2 * row_bytes + 512)) return rc;
-  char* ws = (char*)ctx->scratch;
+  char* ws;
+  float *lse, *delta;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        ws = s.take<char>((size_t)B * T * heads * head_ch * elem_bytes(dtype));
+        lse = s.take<float>((size_t)B * heads * T); delta = s.take<float>((size_t)B * heads * T);
+      }))
+    return rc;
   AttnArgs f{};
   f.qkv = qkv; f.out = ws; f.B = B; f.T = T; f.heads = heads; f.D = head_ch; f.ld_qkv = 3L * heads * head_ch;
-  f.ld_out = (long)heads * head_ch; f.scale = 1.f / sqrtf((float)head_ch); f.lse = (float*)(ws + out_bytes);
+  f.ld_out = (long)heads * head_ch; f.scale = 1.f / sqrtf((float)head_ch); f.lse = lse;
   if (int rc = launch_attention(ctx->stream, dtype, f)) return rc;
   AttnVjpArgs a{};
-  a.qkv = qkv; a.out = ws; a.d_out = d_out; a.lse = f.lse; a.d_qkv = d_qkv; a.delta = (float*)(ws + out_bytes + row_bytes); a.B = B; a.T = T;
+  a.qkv = qkv; a.out = ws; a.d_out = d_out; a.lse = f.lse; a.d_qkv = d_qkv; a.delta = delta; a.B = B; a.T = T;
   a.heads = heads; a.D = head_ch; a.ld_qkv = f.ld_qkv; a.ld_out = f.ld_out; a.scale = f.scale;
   return launch_attention_vjp(ctx->stream, dtype, a);
 }

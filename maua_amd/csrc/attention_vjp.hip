@@ -269,7 +269,7 @@ int attention_vjp_check(int dtype, const AttnVjpArgs& a) {
   MAUA_REQUIRE(a.qkv && a.out && a.d_out && a.lse && a.d_qkv && a.delta, "attention_vjp: NULL argument");
   MAUA_REQUIRE(a.B >= 0 && a.T > 0 && a.heads > 0, "attention_vjp: bad shape");
   MAUA_REQUIRE(a.B <= 65535 && a.heads <= 65535, "attention_vjp: grid too large");
-  const long es = dtype == MAUA_BF16 ? 2 : 4;
+  const long es = elem_bytes(dtype);
   MAUA_REQUIRE(((uintptr_t)a.qkv | (uintptr_t)a.out | (uintptr_t)a.d_out | (uintptr_t)a.d_qkv) % 16 == 0 &&
                    ((uintptr_t)a.lse | (uintptr_t)a.delta) % 4 == 0,
                "attention_vjp: qkv / out / d_out / d_qkv must be 16-byte aligned");
@@ -281,7 +281,7 @@ int attention_vjp_check(int dtype, const AttnVjpArgs& a) {
 int launch_attention_vjp(hipStream_t stream, int dtype, const AttnVjpArgs& a) {
   if (int rc = attention_vjp_check(dtype, a)) return rc;
   if (a.B == 0) return MAUA_OK;
-  const long rows = (long)a.B * a.T * a.heads * (a.D * (dtype == MAUA_BF16 ? 2 : 4) / 16);   // 16-byte pieces of out / d_out
+  const long rows = (long)a.B * a.T * a.heads * (a.D * elem_bytes(dtype) / 16);   // 16-byte pieces of out / d_out
   dim3 grid((unsigned)((a.T + 127) / 128), (unsigned)a.heads, (unsigned)a.B);
 #define MAUA_ATTN_VJP(TT, DD)                                                                                   \
   do {                                                                                                          \
@@ -289,11 +289,9 @@ int launch_attention_vjp(hipStream_t stream, int dtype, const AttnVjpArgs& a) {
     hipLaunchKernelGGL((attention_vjp_kernel<TT, DD, 0>), grid, dim3(256), 0, stream, a);                       \
     hipLaunchKernelGGL((attention_vjp_kernel<TT, DD, 1>), grid, dim3(256), 0, stream, a);                       \
   } while (0)
-  if (dtype == MAUA_BF16) {
-    if (a.D == 64) MAUA_ATTN_VJP(bf16_t, 64); else MAUA_ATTN_VJP(bf16_t, 32);
-  } else {
-    if (a.D == 64) MAUA_ATTN_VJP(float, 64); else MAUA_ATTN_VJP(float, 32);
-  }
+  dispatch_dtype<bf16_t, float>(dtype, "attention_vjp", [&](auto t) {
+    if (a.D == 64) MAUA_ATTN_VJP(decltype(t), 64); else MAUA_ATTN_VJP(decltype(t), 32);
+  });
 #undef MAUA_ATTN_VJP
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;

@@ -725,8 +725,8 @@ int maua_istft_general(maua_ctx* ctx, const float* spec_frames_bins_complex, int
   MAUA_REQUIRE(hop >= 1 && n_frames > 0 && length > 0, "maua_istft_general: empty input");
   AudioTables t;
   if (int rc = get_tables(ctx, t)) return rc;
-  if (int rc = scratch_reserve(ctx, (size_t)n_frames * n_fft * sizeof(float))) return rc;
-  float* frames = (float*)ctx->scratch;
+  float* frames;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { frames = s.take<float>((size_t)n_frames * n_fft); })) return rc;
   const bool big = n_fft > NFFT;
   const size_t smem = (size_t)2 * n_fft * sizeof(float2);
   if (smem > 64 * 1024)
@@ -755,8 +755,8 @@ int maua_istft(maua_ctx* ctx, const float* spec_frames_bins_complex, int n_frame
   MAUA_REQUIRE(n_frames > 0 && length > 0, "maua_istft: empty input");
   AudioTables t;
   if (int rc = get_tables(ctx, t)) return rc;
-  if (int rc = scratch_reserve(ctx, (size_t)n_frames * NFFT * sizeof(float))) return rc;
-  float* frames = (float*)ctx->scratch;
+  float* frames;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { frames = s.take<float>((size_t)n_frames * NFFT); })) return rc;
   hipLaunchKernelGGL(istft_frames_kernel, dim3(n_frames), dim3(256), 0, ctx->stream,
                      (const float2*)spec_frames_bins_complex, t.win, t.tw, frames);
   MAUA_HIP_CHECK(hipGetLastError());
@@ -792,10 +792,8 @@ int maua_hpss(maua_ctx* ctx, const float* spec_complex, int n_frames, float marg
               float* perc_out) {
   MAUA_REQUIRE(ctx && spec_complex && (harm_out || perc_out), "maua_hpss: NULL argument");
   const long n = (long)n_frames * NBIN;
-  if (int rc = scratch_reserve(ctx, (size_t)3 * n * sizeof(float))) return rc;
-  float* mag = (float*)ctx->scratch;
-  float* harm = mag + n;
-  float* perc = harm + n;
+  float *mag, *harm, *perc;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { mag = s.take<float>(n); harm = s.take<float>(n); perc = s.take<float>(n); })) return rc;
   if (int rc = maua_magnitude(ctx, spec_complex, n, 1.f, mag)) return rc;
   if (int rc = maua_median31(ctx, mag, n_frames, NBIN, 0, harm)) return rc;
   if (int rc = maua_median31(ctx, mag, n_frames, NBIN, 1, perc)) return rc;
@@ -823,8 +821,8 @@ int maua_onset_from_mel(maua_ctx* ctx, float* mel_inout, int n_mels, int T, floa
   MAUA_REQUIRE(aggregate == 0 || aggregate == 1, "maua_onset_from_mel: aggregate must be 0 (mean) or 1 (median)");
   if (T == 0) return MAUA_OK;
   const long n = (long)n_mels * T;
-  if (int rc = scratch_reserve(ctx, MM_PARTS * 2 * sizeof(float))) return rc;
-  float* part = (float*)ctx->scratch;
+  float* part;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { part = s.take<float>(MM_PARTS * 2); })) return rc;
   hipLaunchKernelGGL(power_to_db_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, mel_inout, n,
                      amin);
   const int parts = grid_for(n, MM_PARTS);
@@ -839,8 +837,8 @@ int maua_normalize(maua_ctx* ctx, const float* x, long n, float eps, float* y) {
   MAUA_REQUIRE(ctx, "maua_normalize: ctx is NULL");
   if (n == 0) return MAUA_OK;
   MAUA_REQUIRE(x && y, "maua_normalize: NULL argument");
-  if (int rc = scratch_reserve(ctx, MM_PARTS * 2 * sizeof(float))) return rc;
-  float* part = (float*)ctx->scratch;
+  float* part;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { part = s.take<float>(MM_PARTS * 2); })) return rc;
   const int parts = grid_for(n, MM_PARTS);
   hipLaunchKernelGGL(minmax_partial_kernel, dim3(parts), dim3(256), 0, ctx->stream, x, n, part);
   hipLaunchKernelGGL(normalize_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, x, part, parts, eps, n, y);
@@ -878,10 +876,9 @@ int maua_order_stat(maua_ctx* ctx, const float* x, const uint8_t* mask, long n, 
   MAUA_REQUIRE(mode >= 0 && mode <= 2, "maua_order_stat: mode must be 0 (midpoint quantile), 1 (kth value), 2 (linear quantile)");
   MAUA_REQUIRE(n == 0 || x, "maua_order_stat: x is NULL");
   MAUA_REQUIRE(mode != 1 || k >= 1, "maua_order_stat: k is 1-based");
-  const size_t need = sizeof(SelectState) + 64;
-  if (int rc = scratch_reserve(ctx, need)) return rc;
-  SelectState* st = (SelectState*)ctx->scratch;
-  unsigned long long* saved = (unsigned long long*)((char*)ctx->scratch + sizeof(SelectState));
+  SelectState* st;
+  unsigned long long* saved;   // the two original ranks
+  if (int rc = carve_scratch(ctx, [&](Scratch& sc) { st = sc.take<SelectState>(1); saved = sc.take<unsigned long long>(2); })) return rc;
   hipStream_t s = ctx->stream;
   MAUA_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(SelectState), s));
   const int grid = grid_for(n, 1024);

@@ -276,10 +276,11 @@ int run_forward(maua_clip* n, long N, bool keep) {
   const long M = N * Tk, Mp = N * n->G * n->G;
   // patch embedding (conv1, no bias) -> tokens -> ln_pre
   if (int rc = block_gemm(r, n->patches, Mp, n->kpp, n->w_conv, w, nullptr, nullptr, n->pe)) return rc;
-  const long total = M * (w / (n->dtype == MAUA_BF16 ? 8 : 4));
+  const long total = M * (w / elems_per_piece(n->dtype));
   const dim3 tgrid((unsigned)((total + 255) / 256));
-  if (n->dtype == MAUA_BF16) hipLaunchKernelGGL(tokens_kernel<bf16_t>, tgrid, dim3(256), 0, r.st, (const bf16_t*)n->pe, n->cls, n->pos, (bf16_t*)n->tok, N, Tk, w);
-  else hipLaunchKernelGGL(tokens_kernel<float>, tgrid, dim3(256), 0, r.st, (const float*)n->pe, n->cls, n->pos, (float*)n->tok, N, Tk, w);
+  dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip", [&](auto t) {
+    hipLaunchKernelGGL(tokens_kernel<decltype(t)>, tgrid, dim3(256), 0, r.st, (const decltype(t)*)n->pe, n->cls, n->pos, (decltype(t)*)n->tok, N, Tk, w);
+  });
   void* x = n->K[0].x;
   launch_layer_norm(r.st, r.dtype, n->tok, n->lnpre_g, n->lnpre_b, x, n->st_pre, M, w);
   for (int i = 0; i < n->layers; i++) {
@@ -301,8 +302,9 @@ int run_head(maua_clip* n, long N, bool with_grad, const float* d_embed, int B, 
   h.Tk = n->Tk; h.w = n->width; h.E = n->E; h.P = n->P; h.B = B > 0 ? B : 1; h.coef = coef; h.mult = mult;
   const size_t smem = ((size_t)2 * n->width + 2 * n->E + std::max(n->P, 1) + 8) * 4;
   MAUA_REQUIRE(smem <= 64 * 1024, "maua_clip: too many targets / too wide a tower for the head kernel's LDS");
-  if (n->dtype == MAUA_BF16) hipLaunchKernelGGL(clip_head_kernel<bf16_t>, dim3((unsigned)N), dim3(256), smem, n->ctx->stream, h);
-  else hipLaunchKernelGGL(clip_head_kernel<float>, dim3((unsigned)N), dim3(256), smem, n->ctx->stream, h);
+  dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip", [&](auto t) {
+    hipLaunchKernelGGL(clip_head_kernel<decltype(t)>, dim3((unsigned)N), dim3(256), smem, n->ctx->stream, h);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -342,13 +344,13 @@ int maua_clip_create(maua_ctx* ctx, int input_resolution, int patch_size, int wi
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "maua_clip_create: dtype must be MAUA_BF16 or MAUA_F32");
   MAUA_REQUIRE(input_resolution > 0 && patch_size > 0 && input_resolution % patch_size == 0, "maua_clip_create: the input is a whole number of patches");
   MAUA_REQUIRE(width > 0 && heads > 0 && width % heads == 0 && attention_supported(width / heads), "maua_clip_create: head width must be 32 or 64");
-  const int epc = dtype == MAUA_BF16 ? 8 : 4, kc = dtype == MAUA_BF16 ? 32 : 16;
+  const int epc = elems_per_piece(dtype), kc = elems_per_chunk(dtype, 64);
   MAUA_REQUIRE(width % 32 == 0 && width % kc == 0 && width / epc <= 64 * LN_MAXP, "maua_clip_create: width must be a multiple of 32 (at most 4096 / 2048)");
   MAUA_REQUIRE(layers > 0 && output_dim > 0, "maua_clip_create: bad layer count / embedding size");
   maua_clip* n = new maua_clip();
   static std::atomic<unsigned long long> next_uid{1};
   n->uid = next_uid.fetch_add(1);
-  n->ctx = ctx; n->dtype = dtype; n->esize = dtype == MAUA_BF16 ? 2 : 4;
+  n->ctx = ctx; n->dtype = dtype; n->esize = elem_bytes(dtype);
   n->res = input_resolution; n->patch = patch_size; n->width = width; n->layers = layers; n->heads = heads; n->E = output_dim;
   n->G = input_resolution / patch_size; n->Tk = n->G * n->G + 1; n->kp = 3 * patch_size * patch_size;
   n->kpp = (n->kp + 63) / 64 * 64;
@@ -416,10 +418,10 @@ int maua_clip_encode_image(maua_clip* n, const float* images, int N, int keep, f
   if (int rc = ensure_ws(n, N, keep ? 1 : 0)) return rc;
   hipStream_t st = n->ctx->stream;
   const long total = (long)N * 3 * n->res * n->res;
-  if (n->dtype == MAUA_BF16)
-    hipLaunchKernelGGL(im2patch_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, images, (bf16_t*)n->patches, (long)N, n->res, n->patch, n->kpp);
-  else
-    hipLaunchKernelGGL(im2patch_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, images, (float*)n->patches, (long)N, n->res, n->patch, n->kpp);
+  dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip_encode_image", [&](auto t) {
+    hipLaunchKernelGGL(im2patch_kernel<decltype(t)>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, images, (decltype(t)*)n->patches,
+                       (long)N, n->res, n->patch, n->kpp);
+  });
   if (int rc = run_forward(n, N, keep != 0)) return rc;
   if (int rc = run_head(n, N, false, nullptr, 1, 0.f, false)) return rc;
   MAUA_HIP_CHECK(hipMemcpyAsync(embeds, n->embed, (size_t)N * n->E * 4, hipMemcpyDeviceToDevice, st));
@@ -435,10 +437,10 @@ int maua_clip_encode_image_vjp(maua_clip* n, const float* d_embeds, int N, float
   if (int rc = run_head(n, N, true, d_embeds, 1, 0.f, false)) return rc;
   if (int rc = run_backward(n, N)) return rc;
   const long total = (long)N * 3 * n->res * n->res;
-  if (n->dtype == MAUA_BF16)
-    hipLaunchKernelGGL(patch2im_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const bf16_t*)n->dwide, d_images, (long)N, n->res, n->patch, n->kpp);
-  else
-    hipLaunchKernelGGL(patch2im_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)n->dwide, d_images, (long)N, n->res, n->patch, n->kpp);
+  dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip_encode_image_vjp", [&](auto t) {
+    hipLaunchKernelGGL(patch2im_kernel<decltype(t)>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const decltype(t)*)n->dwide,
+                       d_images, (long)N, n->res, n->patch, n->kpp);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }

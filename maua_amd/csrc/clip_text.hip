@@ -117,12 +117,12 @@ int ensure_text_ws(maua_clip_text* n, long N) {
 
 int text_forward(maua_clip_text* n, const int* tokens, long N, float* embeds) {
   const int w = n->width, Tk = n->ctx_len;
-  const bool bf = n->dtype == MAUA_BF16;
   const BlockRun r{n->ctx->stream, n->dtype, w, n->heads, N, Tk, N * Tk, text_rows(n, N), 0, 1};
-  const long total = r.rows * (w / (bf ? 8 : 4));
+  const long total = r.rows * (w / elems_per_piece(n->dtype));
   const dim3 tgrid((unsigned)((total + 255) / 256));
-  if (bf) hipLaunchKernelGGL(text_tokens_kernel<bf16_t>, tgrid, dim3(256), 0, r.st, tokens, n->tok_emb, n->pos, (bf16_t*)n->xa, N, Tk, w, n->vocab);
-  else hipLaunchKernelGGL(text_tokens_kernel<float>, tgrid, dim3(256), 0, r.st, tokens, n->tok_emb, n->pos, (float*)n->xa, N, Tk, w, n->vocab);
+  dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip_text", [&](auto t) {
+    hipLaunchKernelGGL(text_tokens_kernel<decltype(t)>, tgrid, dim3(256), 0, r.st, tokens, n->tok_emb, n->pos, (decltype(t)*)n->xa, N, Tk, w, n->vocab);
+  });
   void* x = n->xa;
   void* other = n->xb;
   for (int i = 0; i < n->layers; i++) {
@@ -130,8 +130,10 @@ int text_forward(maua_clip_text* n, const int* tokens, long N, float* embeds) {
     std::swap(x, other);
   }
   const size_t smem = ((size_t)w + 8) * 4;
-  if (bf) hipLaunchKernelGGL(text_head_kernel<bf16_t>, dim3((unsigned)N), dim3(256), smem, r.st, tokens, (const bf16_t*)x, n->lnf_g, n->lnf_b, n->proj, embeds, Tk, w, n->E);
-  else hipLaunchKernelGGL(text_head_kernel<float>, dim3((unsigned)N), dim3(256), smem, r.st, tokens, (const float*)x, n->lnf_g, n->lnf_b, n->proj, embeds, Tk, w, n->E);
+  dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip_text", [&](auto t) {
+    hipLaunchKernelGGL(text_head_kernel<decltype(t)>, dim3((unsigned)N), dim3(256), smem, r.st, tokens, (const decltype(t)*)x, n->lnf_g, n->lnf_b,
+                       n->proj, embeds, Tk, w, n->E);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -147,11 +149,11 @@ int maua_clip_text_create(maua_ctx* ctx, int context_length, int vocab_size, int
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "maua_clip_text_create: dtype must be MAUA_BF16 or MAUA_F32");
   MAUA_REQUIRE(context_length > 0 && vocab_size > 0, "maua_clip_text_create: bad context length / vocabulary size");
   MAUA_REQUIRE(width > 0 && heads > 0 && width % heads == 0 && attention_supported(width / heads), "maua_clip_text_create: head width must be 32 or 64");
-  const int epc = dtype == MAUA_BF16 ? 8 : 4, kc = dtype == MAUA_BF16 ? 32 : 16;
+  const int epc = elems_per_piece(dtype), kc = elems_per_chunk(dtype, 64);
   MAUA_REQUIRE(width % 32 == 0 && width % kc == 0 && width / epc <= 64 * LN_MAXP, "maua_clip_text_create: width must be a multiple of 32 (at most 4096 / 2048)");
   MAUA_REQUIRE(layers > 0 && embed_dim > 0, "maua_clip_text_create: bad layer count / embedding size");
   maua_clip_text* n = new maua_clip_text();
-  n->ctx = ctx; n->dtype = dtype; n->esize = dtype == MAUA_BF16 ? 2 : 4;
+  n->ctx = ctx; n->dtype = dtype; n->esize = elem_bytes(dtype);
   n->ctx_len = context_length; n->vocab = vocab_size; n->width = width; n->layers = layers; n->heads = heads; n->E = embed_dim;
   n->L.resize(layers);
   *out = n;

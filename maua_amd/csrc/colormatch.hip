@@ -233,18 +233,17 @@ int hist_into(hipStream_t st, const float* img, int B, long HW, int nbins, int s
 }
 
 int run_hist(maua_ctx* ctx, const float* img, int B, long HW, int nbins, int sat_weighting, unsigned long long** fix_out, float** gr_out) {
-  const size_t fix_bytes = colormatch_fix_bytes(B, nbins);
-  if (int rc = scratch_reserve(ctx, fix_bytes + (size_t)B * nbins * 4)) return rc;
-  unsigned long long* fix = (unsigned long long*)ctx->scratch;
-  *fix_out = fix;
-  *gr_out = (float*)((char*)ctx->scratch + fix_bytes);
-  return hist_into(ctx->stream, img, B, HW, nbins, sat_weighting, fix);
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        *fix_out = s.take<unsigned long long>((size_t)B * nbins); *gr_out = s.take<float>((size_t)B * nbins);
+      }))
+    return rc;
+  return hist_into(ctx->stream, img, B, HW, nbins, sat_weighting, *fix_out);
 }
 
 }  // namespace
 
 namespace maua {
-size_t colormatch_fix_bytes(int B, int nbins) { return ((size_t)B * nbins * 8 + 255) / 256 * 256; }
+size_t colormatch_fix_bytes(int B, int nbins) { return align256((size_t)B * nbins * 8); }
 
 // ColorMatchGrads.forward on caller-owned workspaces (fix: colormatch_fix_bytes, gr: B * nbins floats) - nothing is allocated
 int colormatch_grad_into(hipStream_t st, const float* img, int B, int H, int W, int nbins, int sat_weighting, const float* target,
@@ -293,10 +292,11 @@ int maua_colormatch_grad(maua_ctx* ctx, const float* img, int B, int H, int W, i
   MAUA_REQUIRE(ctx && img && target && grad, "maua_colormatch_grad: NULL argument");
   MAUA_REQUIRE(B >= 0 && H > 0 && W > 0 && nbins >= 2 && nbins <= MAX_BINS, "maua_colormatch_grad: bad shape (2 <= bins <= 1024)");
   if (B == 0) return MAUA_OK;
-  const size_t fix_bytes = colormatch_fix_bytes(B, nbins);
-  if (int rc = scratch_reserve(ctx, fix_bytes + (size_t)B * nbins * 4)) return rc;
-  return colormatch_grad_into(ctx->stream, img, B, H, W, nbins, sat_weighting, target, target_per_sample, scale,
-                              (unsigned long long*)ctx->scratch, (float*)((char*)ctx->scratch + fix_bytes), grad, loss);
+  unsigned long long* fix;
+  float* gr;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { fix = s.take<unsigned long long>((size_t)B * nbins); gr = s.take<float>((size_t)B * nbins); }))
+    return rc;
+  return colormatch_grad_into(ctx->stream, img, B, H, W, nbins, sat_weighting, target, target_per_sample, scale, fix, gr, grad, loss);
 }
 
 // GradientGuidedConditioning's loop over its grad modules (guided.py:258-266): acc = (first ? 0 : acc) + (sub holds a NaN ? 0 : sub),
@@ -304,8 +304,9 @@ int maua_colormatch_grad(maua_ctx* ctx, const float* img, int B, int H, int W, i
 int maua_grad_accumulate(maua_ctx* ctx, const float* sub, float* acc, long n, int first) {
   MAUA_REQUIRE(ctx && sub && acc && n >= 0, "maua_grad_accumulate: bad argument");
   if (n == 0) return MAUA_OK;
-  if (int rc = scratch_reserve(ctx, 256)) return rc;
-  return screened_accumulate(ctx->stream, sub, acc, n, first, (int*)ctx->scratch);
+  int* flag;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { flag = s.take<int>(1); })) return rc;
+  return screened_accumulate(ctx->stream, sub, acc, n, first, flag);
 }
 
 }  // extern "C"

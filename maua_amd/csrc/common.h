@@ -5,6 +5,8 @@
 #include <string>
 
 #include "../../include/maua_hip.h"
+#include "dtype.h"
+#include "scratch.h"
 
 namespace maua {
 
@@ -12,8 +14,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;  // native 16-byte register quad (stays in VGPRs)
-
-typedef uint16_t bf16_t;  // raw bfloat16 bits
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // round-to-nearest-even via the gfx950 hardware conversion (v_cvt_pk_bf16_f32: one instruction per two values)
@@ -36,7 +36,6 @@ __device__ __forceinline__ uint32_t to_u8(float x) {
 // bits in a type of its own - bf16_t is a plain uint16_t - so that kernels templated on the element type can tell the two 16-bit
 // formats apart.  The fast bf16 kernels (LDS-direct convolutions, the walks) have no f16 form: an F16 network runs the generic
 // templated kernels on v_mfma_f32_32x32x16_f16.
-struct f16_t { uint16_t bits; };
 typedef _Float16 hw_f16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 __device__ __forceinline__ float h2f(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
@@ -66,7 +65,6 @@ template <> struct Elem<float> {
   __device__ static __forceinline__ void store(float* p, float v) { *p = v; }
 };
 // float32 storage whose PRODUCTS run on the bf16 matrix cores as three split products (MAUA_F32_SPLIT): same bytes as float
-struct f32s_t { float v; };
 template <> struct Elem<f32s_t> {
   static constexpr int kDtype = MAUA_F32_SPLIT;
   __device__ static __forceinline__ float load(const f32s_t* p) { return p->v; }
@@ -157,15 +155,10 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 struct maua_ctx {
   int device;
   hipStream_t stream;
-  // grow-only scratch arena for the operator-level entry points (layout conversion, prepared weights)
+  // grow-only scratch arena for the operator-level entry points (layout conversion, prepared weights): carve_scratch (scratch.h)
   void* scratch = nullptr;
   size_t scratch_bytes = 0;
   int dma_conv = 1;  // operator-level modconv: eligible shapes run the LDS-direct-load kernel (maua_ctx_set_option)
   int gemm_dma = 1;  // clip.hip (the image tower's BlockRun): large plain GEMMs on gemm_dma.hip (option "gemm_dma")
   int linear_dma = 0;  // maua_linear_nt: the same routing for operator-level callers (option "linear_dma")
 };
-
-namespace maua {
-// returns a 256-byte aligned carve-out of ctx's scratch arena; grows (synchronising) when too small
-int scratch_reserve(maua_ctx* ctx, size_t bytes);
-}

@@ -8,7 +8,8 @@ int fail(const std::string& msg) {
   g_err = msg;
   return MAUA_ERR;
 }
-int scratch_reserve(maua_ctx* ctx, size_t bytes) {
+int scratch_reserve(maua_ctx* ctx, size_t bytes, void** base) {
+  *base = ctx->scratch;
   if (bytes <= ctx->scratch_bytes) return MAUA_OK;
   MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   if (ctx->scratch) MAUA_HIP_CHECK(hipFree(ctx->scratch));
@@ -17,6 +18,7 @@ int scratch_reserve(maua_ctx* ctx, size_t bytes) {
   size_t want = bytes + bytes / 4;
   MAUA_HIP_CHECK(hipMalloc(&ctx->scratch, want));
   ctx->scratch_bytes = want;
+  *base = ctx->scratch;
   return MAUA_OK;
 }
 }  // namespace maua

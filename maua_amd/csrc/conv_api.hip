@@ -53,7 +53,7 @@ int conv_plan(const maua_conv_desc* d, int dtype, int sel, ConvArgs* a, ConvPlan
     MAUA_REQUIRE(d->Co % 32 == 0, "modconv3x3: Co must be a multiple of 32 (pad channels)");
     MAUA_REQUIRE(d->B <= 65535, "modconv3x3: grid too large");
     MAUA_REQUIRE(!a->x_up2 && !a->psum && (!a->Ci_read || a->Ci_read == a->Ci), "modconv3x3: no x_up2 / psum / Ci_read on the generic kernel");
-    p.variant = modconv_tile(dtype == MAUA_BF16 || dtype == MAUA_F16 ? 2 : 4, *a);
+    p.variant = modconv_tile(elem_bytes(dtype), *a);
   } else if (p.kernel == 2) {
     if (int rc = dma_conv_check(dtype, *a)) return rc;
     p.variant = dma_conv_tile(dtype, *a);
@@ -64,8 +64,6 @@ int conv_plan(const maua_conv_desc* d, int dtype, int sel, ConvArgs* a, ConvPlan
   *out = p;
   return MAUA_OK;
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 }  // namespace maua
@@ -89,25 +87,26 @@ extern "C" int maua_conv3x3_ex(maua_ctx* ctx, const maua_conv_desc* d, int dtype
   ConvPlan p;
   if (int rc = conv_plan(d, dtype, kernel ? 100 + kernel : 0, &a, &p)) return rc;
   if (d->B == 0) return MAUA_OK;
-  const size_t es = dtype == MAUA_BF16 || dtype == MAUA_F16 ? 2 : 4;
+  const size_t es = elem_bytes(dtype);
   const size_t wt_bytes = prepped_weight_elems(3, 1, d->Co, d->Ci) * es;
   const size_t ones_bytes = p.kernel == 1 ? (size_t)d->B * d->Ci * 4 : 0;
   const size_t ws_bytes = p.kernel == 3 ? gather_conv_workspace(dtype, d->B, d->H, d->W, d->Ci, d->Co) : 0;
-  const size_t o_w = 0, o_s = align256(wt_bytes), o_ws = o_s + align256(ones_bytes);
-  if (int rc = scratch_reserve(ctx, o_ws + align256(ws_bytes))) return rc;
-  char* base = (char*)ctx->scratch;
+  char* w;
+  float *ones, *ws;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { w = s.take<char>(wt_bytes); ones = s.take<float>(ones_bytes / 4); ws = s.take<float>(ws_bytes / 4); }))
+    return rc;
   hipStream_t st = ctx->stream;
   // weights as the networks prepare theirs: [9][Co][Ci] in the storage type, the split type's float32 copy split in place
   const int store_dtype = dtype == MAUA_F32_SPLIT ? MAUA_F32 : dtype;
-  if (int rc = launch_prep_weights(st, store_dtype, d->w, base + o_w, nullptr, d->Co, d->Ci, 3, 1, 0, d->Co, d->Ci)) return rc;
+  if (int rc = launch_prep_weights(st, store_dtype, d->w, w, nullptr, d->Co, d->Ci, 3, 1, 0, d->Co, d->Ci)) return rc;
   if (dtype == MAUA_F32_SPLIT)
-    if (int rc = launch_f32_split_inplace(st, base + o_w, (long)9 * d->Co * d->Ci)) return rc;
-  a.w = base + o_w;
+    if (int rc = launch_f32_split_inplace(st, w, (long)9 * d->Co * d->Ci)) return rc;
+  a.w = w;
   if (p.kernel == 1) {   // the generic kernel multiplies its input by styles: all ones, as every plain network passes
-    if (int rc = launch_fill_ones(st, (float*)(base + o_s), (long)d->B * d->Ci)) return rc;
-    a.s = (const float*)(base + o_s);
+    if (int rc = launch_fill_ones(st, ones, (long)d->B * d->Ci)) return rc;
+    a.s = ones;
     return launch_modconv3x3(st, dtype, a);
   }
   if (p.kernel == 2) return launch_modconv_dma(st, a, dtype);
-  return launch_conv_gather(st, dtype, a, (float*)(base + o_ws));
+  return launch_conv_gather(st, dtype, a, ws);
 }

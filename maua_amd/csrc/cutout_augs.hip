@@ -435,8 +435,8 @@ int aug_forward_out(hipStream_t st, int dtype, const void* recs, int n_rec, int 
   a.a = x1; a.out = out; a.patch = patch; a.patch_ld = patch_ld ? patch_ld : 3 * patch * patch;
   for (int c = 0; c < 3; c++) { a.mean[c] = mean3[c]; a.inv_std[c] = 1.f / std3[c]; }
   const dim3 grid((unsigned)cdiv(S, AUG_TX), (unsigned)cdiv(S, AUG_TY), (unsigned)(n_rec * nimg)), block(AUG_TX, AUG_TY);
-  if (dtype == MAUA_BF16) hipLaunchKernelGGL(aug_fwd_out_kernel<bf16_t>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(aug_fwd_out_kernel<float>, grid, block, 0, st, a);
+  auto launch = [&](auto t) { hipLaunchKernelGGL(aug_fwd_out_kernel<decltype(t)>, grid, block, 0, st, a); };
+  if (int rc = dispatch_dtype<bf16_t, float>(dtype, "cutout augmentations", launch)) return rc;
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -450,8 +450,8 @@ int aug_adjoint_out(hipStream_t st, int dtype, const void* recs, int n_rec, int 
   a.d_out = d_out; a.patch = patch; a.patch_ld = patch_ld ? patch_ld : 3 * patch * patch; a.a_out = d_a;
   for (int c = 0; c < 3; c++) a.inv_std[c] = 1.f / std3[c];
   const dim3 grid((unsigned)cdiv(S, AUG_TX), (unsigned)cdiv(S, AUG_TY), (unsigned)(n_rec * nimg)), block(AUG_TX, AUG_TY);
-  if (dtype == MAUA_BF16) hipLaunchKernelGGL(aug_adj_out_kernel<bf16_t>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(aug_adj_out_kernel<float>, grid, block, 0, st, a);
+  auto launch = [&](auto t) { hipLaunchKernelGGL(aug_adj_out_kernel<decltype(t)>, grid, block, 0, st, a); };
+  if (int rc = dispatch_dtype<bf16_t, float>(dtype, "cutout augmentations", launch)) return rc;
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -498,15 +498,14 @@ int maua_cutouts_aug(maua_ctx* ctx, const float* img, int B, int H, int W, const
   std::vector<char> recs;
   int n_rec = 0, S = 0;
   if (int rc = cutouts_aug_common(ctx, "maua_cutouts_aug", B, H, W, rects, n_cut, cut_size, augs, key, per_call, recs, n_rec, S)) return rc;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t tb = al(cutouts_table_bytes(n_cut, cut_size)), rb = al((size_t)n_cut * 24), ab = al(recs.size());
-  const size_t xb = al((size_t)n_cut * B * 3 * S * S * 4);
-  if (int rc = scratch_reserve(ctx, tb + rb + ab + 2 * xb)) return rc;
-  char* base = (char*)ctx->scratch;
-  int* rd = (int*)(base + tb);
-  void* recd = base + tb + rb;
-  float* x1 = (float*)(base + tb + rb + ab);
-  float* x2 = (float*)(base + tb + rb + ab + xb);
+  char *base, *recd;   // base: the resize tables
+  int* rd;
+  float *x1, *x2;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        base = s.take<char>(cutouts_table_bytes(n_cut, cut_size)); rd = s.take<int>((size_t)n_cut * 6); recd = s.take<char>(recs.size());
+        x1 = s.take<float>((size_t)n_cut * B * 3 * S * S); x2 = s.take<float>((size_t)n_cut * B * 3 * S * S);
+      }))
+    return rc;
   std::vector<int> slot((size_t)n_cut * 3);
   for (int i = 0; i < n_cut; i++) { slot[3 * i] = rects[3 * i] & CUT_SIZE_MASK; slot[3 * i + 1] = 0; slot[3 * i + 2] = 0; }
   MAUA_HIP_CHECK(hipMemcpyAsync(rd, rects, (size_t)n_cut * 12, hipMemcpyHostToDevice, ctx->stream));
@@ -539,16 +538,15 @@ int maua_cutouts_aug_vjp(maua_ctx* ctx, const float* d_out, int B, int H, int W,
   std::vector<char> recs;
   int n_rec = 0, S = 0;
   if (int rc = cutouts_aug_common(ctx, "maua_cutouts_aug_vjp", B, H, W, rects, n_cut, cut_size, augs, 0ull, per_call, recs, n_rec, S)) return rc;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t tb = al(cutouts_table_bytes(n_cut, cut_size)), rb = al((size_t)n_cut * 24), ab = al(recs.size());
-  const size_t xb = al((size_t)n_cut * B * 3 * S * S * 4), thb = al(cutouts_th_bytes(n_cut, B, cut_size, per_call ? std::min(H, W) : S));
-  if (int rc = scratch_reserve(ctx, tb + rb + ab + 2 * xb + thb)) return rc;
-  char* base = (char*)ctx->scratch;
-  int* rd = (int*)(base + tb);
-  void* recd = base + tb + rb;
-  float* x1 = (float*)(base + tb + rb + ab);
-  float* x2 = (float*)(base + tb + rb + ab + xb);
-  float* th = (float*)(base + tb + rb + ab + 2 * xb);
+  char *base, *recd;   // base: the resize tables
+  int* rd;
+  float *x1, *x2, *th;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        base = s.take<char>(cutouts_table_bytes(n_cut, cut_size)); rd = s.take<int>((size_t)n_cut * 6); recd = s.take<char>(recs.size());
+        x1 = s.take<float>((size_t)n_cut * B * 3 * S * S); x2 = s.take<float>((size_t)n_cut * B * 3 * S * S);
+        th = (float*)s.take<char>(cutouts_th_bytes(n_cut, B, cut_size, per_call ? std::min(H, W) : S));
+      }))
+    return rc;
   std::vector<int> slot((size_t)n_cut * 3);
   for (int i = 0; i < n_cut; i++) { slot[3 * i] = rects[3 * i] & CUT_SIZE_MASK; slot[3 * i + 1] = 0; slot[3 * i + 2] = 0; }
   MAUA_HIP_CHECK(hipMemcpyAsync(rd, rects, (size_t)n_cut * 12, hipMemcpyHostToDevice, ctx->stream));

@@ -272,15 +272,12 @@ int launch_cutouts_forward(hipStream_t stream, int dtype, const CutoutPlan& p, v
   a.out = out;
   const size_t smem = (size_t)CT_BAND * a.smax * 4;
   dim3 grid((unsigned)cdiv(p.cs, CT_BAND), 3, (unsigned)(p.n_cut * p.B));
-  if (dtype == MAUA_BF16) {
-    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)cutouts_fwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(cutouts_fwd_kernel<bf16_t>, grid, dim3(256), smem, stream, a);
-  } else {
-    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)cutouts_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(cutouts_fwd_kernel<float>, grid, dim3(256), smem, stream, a);
-  }
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, float>(dtype, "cutouts", [&](auto t) {
+    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)cutouts_fwd_kernel<decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(cutouts_fwd_kernel<decltype(t)>, grid, dim3(256), smem, stream, a);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 int launch_cutouts_vjp(hipStream_t stream, int dtype, const CutoutPlan& p, void* tables, const void* d_out, float* th, float* grad,
@@ -290,13 +287,12 @@ int launch_cutouts_vjp(hipStream_t stream, int dtype, const CutoutPlan& p, void*
   if (p.B == 0) return MAUA_OK;
   const size_t smem = (size_t)CT_BAND * p.cs * 4 + (size_t)p.cs * 4;
   dim3 grid((unsigned)cdiv(p.cs, CT_BAND), 3, (unsigned)(p.n_cut * p.B));
-  if (dtype == MAUA_BF16) {
-    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)cutouts_bwd_h_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(cutouts_bwd_h_kernel<bf16_t>, grid, dim3(256), smem, stream, a, d_out, th);
-  } else {
-    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)cutouts_bwd_h_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(cutouts_bwd_h_kernel<float>, grid, dim3(256), smem, stream, a, d_out, th);
-  }
+  if (int rc = dispatch_dtype<bf16_t, float>(dtype, "cutouts_vjp", [&](auto t) {
+        MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)cutouts_bwd_h_kernel<decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        hipLaunchKernelGGL(cutouts_bwd_h_kernel<decltype(t)>, grid, dim3(256), smem, stream, a, d_out, th);
+        return MAUA_OK;
+      }))
+    return rc;
   const long zs = (long)p.B * 3 * (p.img_stride ? p.n_cut : 1);
   MAUA_REQUIRE(zs <= 65535 && p.H <= 65535, "cutouts: image batch / height too large for one launch");
   hipLaunchKernelGGL(cutouts_bwd_v_kernel, dim3((unsigned)cdiv(p.W, 256), (unsigned)p.H, (unsigned)zs), dim3(256), 0, stream, a, th,
@@ -315,32 +311,38 @@ extern "C" {
 int maua_cutouts(maua_ctx* ctx, const float* img, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul, float add,
                  const float* mean3, const float* std3, float* out) {
   MAUA_REQUIRE(ctx && img && rects && out && mean3 && std3, "maua_cutouts: NULL argument");
-  const size_t tb = cutouts_table_bytes(n_cut, cut_size);
-  if (int rc = scratch_reserve(ctx, tb + (size_t)n_cut * 12 + 512)) return rc;
-  int* rd = (int*)((char*)ctx->scratch + ((tb + 255) & ~(size_t)255));
+  void* tables;
+  int* rd;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { tables = s.take<char>(cutouts_table_bytes(n_cut, cut_size)); rd = s.take<int>((size_t)n_cut * 3); }))
+    return rc;
   MAUA_HIP_CHECK(hipMemcpyAsync(rd, rects, (size_t)n_cut * 12, hipMemcpyHostToDevice, ctx->stream));
   MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   CutoutPlan p{};
   p.img = img; p.rects = rd; p.B = B; p.H = H; p.W = W; p.n_cut = n_cut; p.cs = cut_size; p.mul = mul; p.add = add;
   for (int c = 0; c < 3; c++) { p.mean[c] = mean3[c]; p.std[c] = std3[c]; }
-  if (int rc = launch_cutout_tables(ctx->stream, p, ctx->scratch)) return rc;
-  return launch_cutouts_forward(ctx->stream, MAUA_F32, p, ctx->scratch, out);
+  if (int rc = launch_cutout_tables(ctx->stream, p, tables)) return rc;
+  return launch_cutouts_forward(ctx->stream, MAUA_F32, p, tables, out);
 }
 
 int maua_cutouts_vjp(maua_ctx* ctx, const float* d_out, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul,
                      const float* std3, float* d_img) {
   MAUA_REQUIRE(ctx && d_out && rects && d_img && std3, "maua_cutouts_vjp: NULL argument");
-  const size_t tb = (cutouts_table_bytes(n_cut, cut_size) + 255) & ~(size_t)255;
-  const size_t thb = (cutouts_th_bytes(n_cut, B, cut_size, std::min(H, W)) + 255) & ~(size_t)255;
-  if (int rc = scratch_reserve(ctx, tb + thb + (size_t)n_cut * 12 + 512)) return rc;
-  int* rd = (int*)((char*)ctx->scratch + tb + thb);
+  void* tables;
+  float* th;
+  int* rd;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        tables = s.take<char>(cutouts_table_bytes(n_cut, cut_size));
+        th = (float*)s.take<char>(cutouts_th_bytes(n_cut, B, cut_size, std::min(H, W)));
+        rd = s.take<int>((size_t)n_cut * 3);
+      }))
+    return rc;
   MAUA_HIP_CHECK(hipMemcpyAsync(rd, rects, (size_t)n_cut * 12, hipMemcpyHostToDevice, ctx->stream));
   MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   CutoutPlan p{};
   p.img = nullptr; p.rects = rd; p.B = B; p.H = H; p.W = W; p.n_cut = n_cut; p.cs = cut_size; p.mul = mul; p.add = 0.f;
   for (int c = 0; c < 3; c++) { p.mean[c] = 0.f; p.std[c] = std3[c]; }
-  if (int rc = launch_cutout_tables(ctx->stream, p, ctx->scratch)) return rc;
-  return launch_cutouts_vjp(ctx->stream, MAUA_F32, p, ctx->scratch, d_out, (float*)((char*)ctx->scratch + tb), d_img, 0);
+  if (int rc = launch_cutout_tables(ctx->stream, p, tables)) return rc;
+  return launch_cutouts_vjp(ctx->stream, MAUA_F32, p, tables, d_out, th, d_img, 0);
 }
 
 }  // extern "C"

@@ -487,8 +487,8 @@ extern "C" int maua_sosfilt(maua_ctx* ctx, const double* sos_host, int n_section
   const int L = 128;
   const long n_chunks = (n + L - 1) / L;
   const int m = (int)((n_chunks + 255) / 256);
-  if (int rc = maua::scratch_reserve(ctx, (size_t)n_chunks * 4 * sizeof(double))) return rc;
-  double* f = (double*)ctx->scratch;
+  double* f;
+  if (int rc = maua::carve_scratch(ctx, [&](maua::Scratch& s) { f = s.take<double>((size_t)n_chunks * 4); })) return rc;
   double* S = f + 2 * n_chunks;
   const unsigned grid = (unsigned)((n_chunks + 63) / 64);
   for (int k = 0; k < n_sections; k++) {

@@ -279,8 +279,8 @@ __global__ __launch_bounds__(256) void gemm_nt128_kernel(GemmArgs g) {
 // the 128 x 128 kernel's conditions: both K parts in whole 128-byte chunks and 16-byte row pieces everywhere (correctness), and
 // M >= 128 (occupancy: below one tile the 64-row kernel wastes less)
 static bool gemm128_takes(int dtype, const GemmArgs& g, bool occupancy) {
-  const int kcw = dtype == MAUA_BF16 ? 64 : 32;   // channels per 128-byte chunk
-  const int epc = dtype == MAUA_BF16 ? 8 : 4;
+  const int kcw = elems_per_chunk(dtype, 128);   // channels per 128-byte chunk
+  const int epc = elems_per_piece(dtype);
   return !g.c_f32 && g.epi == 0 && g.K0 % kcw == 0 && g.K1 % kcw == 0 && (!occupancy || g.M >= 128) && g.ldc % epc == 0 &&
          (!g.res || g.ldr % epc == 0) && g.lda0 % epc == 0 && (g.K1 == 0 || g.lda1 % epc == 0);
 }
@@ -314,8 +314,8 @@ static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 int gemm_plan(int dtype, const GemmArgs& g, int prefer_dma, int force, GemmRoute* out) {
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "gemm_nt: unsupported dtype");
   MAUA_REQUIRE(force >= 0 && force <= 4, "gemm_nt: force must be 0 (production routing) or a kernel id 1 .. 4");
-  const int kc = dtype == MAUA_BF16 ? 32 : 16;    // channels per 64-byte chunk
-  const int epc = dtype == MAUA_BF16 ? 8 : 4;     // channels per 16-byte piece
+  const int kc = elems_per_chunk(dtype, 64);    // channels per 64-byte chunk
+  const int epc = elems_per_piece(dtype);     // channels per 16-byte piece
   MAUA_REQUIRE(g.a0 && g.w && g.c && g.K0 > 0 && g.K0 % kc == 0 && g.K1 >= 0 && g.K1 % kc == 0 && (g.K1 == 0 || g.a1),
                "gemm_nt: K parts must be multiples of 64 bytes");
   MAUA_REQUIRE(g.N % 32 == 0 && g.N > 0 && g.M >= 0, "gemm_nt: N must be a multiple of 32");
@@ -345,29 +345,25 @@ int launch_gemm_routed(hipStream_t stream, int dtype, const GemmArgs& g, GemmRou
   if (r.kernel == 3 || r.kernel == 4) return launch_gemm_dma(stream, g, r.kernel);
   const unsigned nb = g.batch > 1 ? (unsigned)g.batch : 1u;
   if (r.kernel == 2) {
-    const size_t smem = std::max<size_t>((size_t)2 * WBM * WRS, (size_t)WBM * (WBN * (dtype == MAUA_BF16 ? 2 : 4) + 16));
+    const size_t smem = std::max<size_t>((size_t)2 * WBM * WRS, (size_t)WBM * (WBN * elem_bytes(dtype) + 16));
     dim3 gridw((unsigned)((g.M + WBM - 1) / WBM), (unsigned)((g.N + WBN - 1) / WBN), nb);
     GemmArgs gr = g;
     gr.remap_nt = r.remap_nt;
     if (r.remap_nt) gridw = dim3((gridw.x + 7) / 8 * 8 * gridw.y, 1, 1);
-    if (dtype == MAUA_BF16) {
-      MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_nt128_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL(gemm_nt128_kernel<bf16_t>, gridw, dim3(256), smem, stream, gr);
-    } else {
-      MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_nt128_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      hipLaunchKernelGGL(gemm_nt128_kernel<float>, gridw, dim3(256), smem, stream, gr);
-    }
-    MAUA_HIP_CHECK(hipGetLastError());
-    return MAUA_OK;
+    return dispatch_dtype<bf16_t, float>(dtype, "gemm_nt", [&](auto t) {
+      MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_nt128_kernel<decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      hipLaunchKernelGGL(gemm_nt128_kernel<decltype(t)>, gridw, dim3(256), smem, stream, gr);
+      MAUA_HIP_CHECK(hipGetLastError());
+      return MAUA_OK;
+    });
   }
   MAUA_REQUIRE(r.kernel == 1, "gemm_nt: unknown kernel id");
   dim3 grid((unsigned)((g.M + GBM - 1) / GBM), (unsigned)((g.N + GBN - 1) / GBN), nb);
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(gemm_nt_kernel<bf16_t>, grid, dim3(256), 0, stream, g);
-  else
-    hipLaunchKernelGGL(gemm_nt_kernel<float>, grid, dim3(256), 0, stream, g);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, float>(dtype, "gemm_nt", [&](auto t) {
+    hipLaunchKernelGGL(gemm_nt_kernel<decltype(t)>, grid, dim3(256), 0, stream, g);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 int launch_gemm_nt(hipStream_t stream, int dtype, const GemmArgs& g) {

@@ -422,8 +422,6 @@ __global__ void kid_finish_kernel(const double* __restrict__ raw, int S, int m, 
 }
 
 // ---- launches ------------------------------------------------------------------------------------------------------------------------
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 template <typename K> int allow_smem(K kern, size_t bytes) {
   MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   return MAUA_OK;
@@ -474,21 +472,17 @@ int moments(hipStream_t st, const void* x, int f64, int N, int d, double* xc, do
   return gemm_f64(st, 1, 0, d, d, N, 1.0 / (N - 1), xc, d, xc, d, 0.0, cov, d);     // torch.cov: centred, N - 1
 }
 
+// the workspace layouts: each one function of a Scratch, measured by the *_workspace call and placed by the entry point beside it
+double* moments_ws(Scratch& s, int N, int d) { return s.take<double>((size_t)N * d); }
+
 struct SqrtmWs { double *Y, *Z, *T, *Y2, *Z2, *R, *tmp, *scal; };
-size_t sqrtm_ws(int d, SqrtmWs* w, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t n) { double* p = (double*)(base + off); off += align256(n * sizeof(double)); return p; };
-  const size_t dd = (size_t)d * d;
-  double* Y = take(dd); double* Z = take(dd); double* T = take(dd); double* Y2 = take(dd); double* Z2 = take(dd); double* R = take(dd);
-  double* tmp = take(kRedBlocks); double* scal = take(8);
-  if (w) *w = SqrtmWs{Y, Z, T, Y2, Z2, R, tmp, scal};
-  return off;
+SqrtmWs sqrtm_ws(Scratch& s, int d) {
+  auto mat = [&] { return s.take<double>((size_t)d * d); };
+  return SqrtmWs{mat(), mat(), mat(), mat(), mat(), mat(), s.take<double>(kRedBlocks), s.take<double>(8)};
 }
 
 // frechet.py:4-46.  errors [num_iters] and iters are host memory; s [d][d] is device memory.
-int sqrtm_ns(hipStream_t st, const double* m, int d, int num_iters, char* ws, double* s, double* errors, int* iters) {
-  SqrtmWs w;
-  sqrtm_ws(d, &w, ws);
+int sqrtm_ns(hipStream_t st, const double* m, int d, int num_iters, const SqrtmWs& w, double* s, double* errors, int* iters) {
   const long dd = (long)d * d;
   const unsigned eb = (unsigned)((dd + 255) / 256);
   double ss_m = 0.0;
@@ -526,18 +520,16 @@ int sqrtm_ns(hipStream_t st, const double* m, int d, int num_iters, char* ws, do
   return MAUA_OK;
 }
 
-struct FrechetWs { double *xc, *mu1, *mu2, *s1, *s2, *P, *S, *scal; char* sq; };
-size_t frechet_ws(int N1, int N2, int d, FrechetWs* w, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t n) { double* p = (double*)(base + off); off += align256(n * sizeof(double)); return p; };
-  const size_t dd = (size_t)d * d;
-  double* xc = take((size_t)(N1 > N2 ? N1 : N2) * d);
-  double* mu1 = take(d); double* mu2 = take(d); double* s1 = take(dd); double* s2 = take(dd); double* P = take(dd); double* S = take(dd);
-  double* scal = take(8);
-  char* sq = base + off;
-  off += sqrtm_ws(d, nullptr, nullptr);
-  if (w) *w = FrechetWs{xc, mu1, mu2, s1, s2, P, S, scal, sq};
-  return off;
+struct FrechetWs { double *xc, *mu1, *mu2, *s1, *s2, *P, *S, *scal; SqrtmWs sq; };
+FrechetWs frechet_ws(Scratch& s, int N1, int N2, int d) {
+  auto mat = [&] { return s.take<double>((size_t)d * d); };
+  return FrechetWs{s.take<double>((size_t)(N1 > N2 ? N1 : N2) * d), s.take<double>(d), s.take<double>(d), mat(), mat(), mat(), mat(),
+                   s.take<double>(8), sqrtm_ws(s, d)};
+}
+
+struct KidWs { double *x, *y, *partial; };
+KidWs kid_ws(Scratch& s, int m, int d) {
+  return KidWs{s.take<double>((size_t)m * d), s.take<double>((size_t)m * d), s.take<double>((size_t)cdiv(m, 64) * cdiv(m, 64) * 2)};
 }
 
 struct PrdcWs { double *x, *y, *xn, *yn, *lists; int *col_count, *row_any; unsigned long long* row_min; };
@@ -548,17 +540,10 @@ int dist_splits(int rows, int cols) {      // column blocks per row tile: enough
   if (splits > 64) splits = 64;
   return splits < 1 ? 1 : splits;
 }
-size_t prdc_ws(int N, int M, int d, PrdcWs* w, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base + off; off += align256(bytes); return p; };
+PrdcWs prdc_ws(Scratch& s, int N, int M, int d) {
   const size_t ln = (size_t)N * dist_splits(N, N), lm = (size_t)M * dist_splits(M, M);
-  double* x = (double*)take((size_t)N * d * 8); double* y = (double*)take((size_t)M * d * 8);
-  double* xn = (double*)take((size_t)N * 8); double* yn = (double*)take((size_t)M * 8);
-  double* lists = (double*)take((ln > lm ? ln : lm) * kTopK * 8);
-  int* col_count = (int*)take((size_t)M * 4); int* row_any = (int*)take((size_t)N * 4);
-  unsigned long long* row_min = (unsigned long long*)take((size_t)N * 8);
-  if (w) *w = PrdcWs{x, y, xn, yn, lists, col_count, row_any, row_min};
-  return off;
+  return PrdcWs{s.take<double>((size_t)N * d), s.take<double>((size_t)M * d), s.take<double>(N), s.take<double>(M),
+                s.take<double>((ln > lm ? ln : lm) * kTopK), s.take<int>(M), s.take<int>(N), s.take<unsigned long long>(N)};
 }
 
 int launch_dist(hipStream_t st, const OperandsF64& o, DistArgs g, int splits) {
@@ -611,7 +596,7 @@ int maua_gemm_f64(maua_ctx* ctx, int transa, int transb, int M, int N, int K, do
 
 long maua_metrics_moments_workspace(int N, int d) {
   if (N < 2 || d < 1) return 0;
-  return (long)align256((size_t)N * d * sizeof(double));
+  return (long)scratch_bytes(moments_ws, N, d);
 }
 
 int maua_metrics_moments(maua_ctx* ctx, const void* feats, int f64, int N, int d, void* ws, long ws_bytes, double* mean, double* cov) {
@@ -620,12 +605,13 @@ int maua_metrics_moments(maua_ctx* ctx, const void* feats, int f64, int N, int d
   MAUA_REQUIRE(feats && ws && mean && cov, "maua_metrics_moments: NULL argument");
   MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= maua_metrics_moments_workspace(N, d),
                "maua_metrics_moments: the workspace must be 256-byte aligned and hold maua_metrics_moments_workspace() bytes");
-  if (moments(ctx->stream, feats, f64, N, d, (double*)ws, mean, cov) != MAUA_OK) return MAUA_ERR;
+  Scratch s(ws);
+  if (moments(ctx->stream, feats, f64, N, d, moments_ws(s, N, d), mean, cov) != MAUA_OK) return MAUA_ERR;
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
 
-long maua_sqrtm_workspace(int d) { return d < 1 ? 0 : (long)sqrtm_ws(d, nullptr, nullptr); }
+long maua_sqrtm_workspace(int d) { return d < 1 ? 0 : (long)scratch_bytes(sqrtm_ws, d); }
 
 int maua_sqrtm_newton_schulz(maua_ctx* ctx, const double* m, int d, int num_iters, void* ws, long ws_bytes, double* s, double* errors, int* iters) {
   MAUA_REQUIRE(ctx, "maua_sqrtm_newton_schulz: ctx is NULL");
@@ -634,12 +620,13 @@ int maua_sqrtm_newton_schulz(maua_ctx* ctx, const double* m, int d, int num_iter
   MAUA_REQUIRE(m && ws && s, "maua_sqrtm_newton_schulz: NULL argument");
   MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= maua_sqrtm_workspace(d),
                "maua_sqrtm_newton_schulz: the workspace must be 256-byte aligned and hold maua_sqrtm_workspace() bytes");
-  return sqrtm_ns(ctx->stream, m, d, num_iters, (char*)ws, s, errors, iters);
+  Scratch place(ws);
+  return sqrtm_ns(ctx->stream, m, d, num_iters, sqrtm_ws(place, d), s, errors, iters);
 }
 
 long maua_frechet_workspace(int N1, int N2, int d) {
   if (N1 < 2 || N2 < 2 || d < 1) return 0;
-  return (long)frechet_ws(N1, N2, d, nullptr, nullptr);
+  return (long)scratch_bytes(frechet_ws, N1, N2, d);
 }
 
 int maua_frechet_distance(maua_ctx* ctx, const void* feats1, int N1, const void* feats2, int N2, int d, int f64, double eps, int num_iters,
@@ -651,10 +638,9 @@ int maua_frechet_distance(maua_ctx* ctx, const void* feats1, int N1, const void*
   MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= maua_frechet_workspace(N1, N2, d),
                "maua_frechet_distance: the workspace must be 256-byte aligned and hold maua_frechet_workspace() bytes");
   hipStream_t st = ctx->stream;
-  FrechetWs w;
-  frechet_ws(N1, N2, d, &w, (char*)ws);
-  SqrtmWs q;
-  sqrtm_ws(d, &q, w.sq);
+  Scratch place(ws);
+  const FrechetWs w = frechet_ws(place, N1, N2, d);
+  const SqrtmWs& q = w.sq;
   if (moments(st, feats1, f64, N1, d, w.xc, w.mu1, w.s1) != MAUA_OK) return MAUA_ERR;
   if (moments(st, feats2, f64, N2, d, w.xc, w.mu2, w.s2) != MAUA_OK) return MAUA_ERR;
   const long dd = (long)d * d;
@@ -688,8 +674,7 @@ int maua_frechet_distance(maua_ctx* ctx, const void* feats1, int N1, const void*
 
 long maua_kernel_distance_workspace(int m, int d) {
   if (m < 2 || d < 1) return 0;
-  const size_t blocks = (size_t)cdiv(m, 64) * cdiv(m, 64);
-  return (long)(2 * align256((size_t)m * d * 8) + align256(blocks * 2 * 8));
+  return (long)scratch_bytes(kid_ws, m, d);
 }
 
 int maua_kernel_distance(maua_ctx* ctx, const void* feats1, int N1, const void* feats2, int N2, int d, int f64, const long* idx, int S, int m,
@@ -701,11 +686,10 @@ int maua_kernel_distance(maua_ctx* ctx, const void* feats1, int N1, const void* 
   MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= maua_kernel_distance_workspace(m, d),
                "maua_kernel_distance: the workspace must be 256-byte aligned and hold maua_kernel_distance_workspace() bytes");
   hipStream_t st = ctx->stream;
-  char* base = (char*)ws;
-  const size_t mat = align256((size_t)m * d * 8);
+  Scratch place(ws);
+  const KidWs w = kid_ws(place, m, d);
+  double *x = w.x, *y = w.y, *partial = w.partial;
   const int blocks = cdiv(m, 64) * cdiv(m, 64);
-  double* x = (double*)base; double* y = (double*)(base + mat);
-  double* partial = (double*)(base + 2 * mat);
   const unsigned gb = (unsigned)(((long)m * d + 255) / 256);
   for (int s = 0; s < S; s++) {
     const long* ix = idx + (long)s * 2 * m;      // kernel.py:12-13: x from feats2, y from feats1
@@ -734,7 +718,7 @@ int maua_kernel_distance(maua_ctx* ctx, const void* feats1, int N1, const void* 
 
 long maua_prdc_workspace(int N, int M, int d) {
   if (N < 1 || M < 1 || d < 1) return 0;
-  return (long)prdc_ws(N, M, d, nullptr, nullptr);
+  return (long)scratch_bytes(prdc_ws, N, M, d);
 }
 
 int maua_knn_radii(maua_ctx* ctx, const void* feats, int N, int d, int f64, int nearest_k, void* ws, long ws_bytes, double* radii) {
@@ -744,8 +728,8 @@ int maua_knn_radii(maua_ctx* ctx, const void* feats, int N, int d, int f64, int 
   MAUA_REQUIRE(feats && ws && radii, "maua_knn_radii: NULL argument");
   MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= maua_prdc_workspace(N, 1, d),
                "maua_knn_radii: the workspace must be 256-byte aligned and hold maua_prdc_workspace(N, 1, d) bytes");
-  PrdcWs w;
-  prdc_ws(N, 1, d, &w, (char*)ws);
+  Scratch place(ws);
+  const PrdcWs w = prdc_ws(place, N, 1, d);
   widen(ctx->stream, feats, f64, N, d, w.x, w.xn);
   if (knn_radii(ctx->stream, w.x, w.xn, N, d, nearest_k, w.lists, radii) != MAUA_OK) return MAUA_ERR;
   MAUA_HIP_CHECK(hipGetLastError());
@@ -758,8 +742,8 @@ int maua_pairwise_distances(maua_ctx* ctx, const void* x, int N, const void* y, 
   MAUA_REQUIRE(x && y && ws && dist, "maua_pairwise_distances: NULL argument");
   MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= maua_prdc_workspace(N, M, d),
                "maua_pairwise_distances: the workspace must be 256-byte aligned and hold maua_prdc_workspace() bytes");
-  PrdcWs w;
-  prdc_ws(N, M, d, &w, (char*)ws);
+  Scratch place(ws);
+  const PrdcWs w = prdc_ws(place, N, M, d);
   widen(ctx->stream, x, f64, N, d, w.x, w.xn);
   widen(ctx->stream, y, f64, M, d, w.y, w.yn);
   const OperandsF64 o = make_operands(0, 1, N, M, d, w.x, d, w.y, d);
@@ -779,8 +763,8 @@ int maua_prdc(maua_ctx* ctx, const void* real, int N, const void* fake, int M, i
   MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= maua_prdc_workspace(N, M, d),
                "maua_prdc: the workspace must be 256-byte aligned and hold maua_prdc_workspace() bytes");
   hipStream_t st = ctx->stream;
-  PrdcWs w;
-  prdc_ws(N, M, d, &w, (char*)ws);
+  Scratch place(ws);
+  const PrdcWs w = prdc_ws(place, N, M, d);
   widen(st, real, f64, N, d, w.x, w.xn);
   widen(st, fake, f64, M, d, w.y, w.yn);
   if (knn_radii(st, w.x, w.xn, N, d, nearest_k, w.lists, r_real) != MAUA_OK) return MAUA_ERR;

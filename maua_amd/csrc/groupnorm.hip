@@ -441,7 +441,7 @@ static inline bool gn_aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
 int maua::group_norm_check(int dtype, const GnArgs& a) {
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "group_norm: unsupported dtype");
-  const int EPC = dtype == MAUA_BF16 ? 8 : 4;
+  const int EPC = elems_per_piece(dtype);
   MAUA_REQUIRE(a.x0 && a.gamma && a.beta && a.y, "group_norm: NULL argument");
   MAUA_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.C0 > 0 && a.C1 >= 0, "group_norm: bad shape");
   const long C = (long)a.C0 + a.C1;
@@ -468,7 +468,7 @@ int maua::group_norm_check(int dtype, const GnArgs& a) {
 }
 
 GnPlanInfo maua::group_norm_plan(int dtype, const GnArgs& a) {
-  const int esize = dtype == MAUA_BF16 ? 2 : 4, C = a.C0 + a.C1;
+  const int esize = elem_bytes(dtype), C = a.C0 + a.C1;
   const GnPlan p = gn_plan(a.B, C, (long)a.H * a.W, esize);
   int Ho, Wo;
   gn_out_size(a, &Ho, &Wo);
@@ -489,20 +489,21 @@ int maua::launch_group_norm(hipStream_t stream, int dtype, const GnArgs& a, doub
   MAUA_REQUIRE(part && stats, "group_norm: NULL workspace");
   if (a.B == 0) return MAUA_OK;
   const GnPlanInfo pl = group_norm_plan(dtype, a);
-  return dtype == MAUA_BF16 ? gn_launch<bf16_t>(stream, a, pl, part, stats) : gn_launch<float>(stream, a, pl, part, stats);
+  return dispatch_dtype<bf16_t, float>(dtype, "group_norm", [&](auto t) { return gn_launch<decltype(t)>(stream, a, pl, part, stats); });
 }
 
 // the statistics passes alone (per-channel kernels: any C % 32 == 0)
 int maua::launch_group_norm_stats(hipStream_t st, int dtype, const void* x, int C, int B, int H, int W, double* part, float* stats) {
-  const int esize = dtype == MAUA_BF16 ? 2 : 4, PPP = C / (16 / esize);
+  const int esize = elem_bytes(dtype), PPP = C / (16 / esize);
   const long HW = (long)H * W;
   MAUA_REQUIRE(C % 32 == 0 && PPP <= 1024, "group_norm: C % 32 == 0, at most 1024 16-byte pieces per pixel");
   const GnPlan p = gn_plan(B, C, HW, esize);
   const dim3 grid((unsigned)p.nchunk, B), block(PPP * p.RY);
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(gn_partial_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, C, (const bf16_t*)nullptr, 0, HW, p.ppc, part);
-  else
-    hipLaunchKernelGGL(gn_partial_kernel<float>, grid, block, 0, st, (const float*)x, C, (const float*)nullptr, 0, HW, p.ppc, part);
+  if (int rc = dispatch_dtype<bf16_t, float>(dtype, "group_norm", [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gn_partial_kernel<T>, grid, block, 0, st, (const T*)x, C, (const T*)nullptr, 0, HW, p.ppc, part);
+      }))
+    return rc;
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(32, B), dim3(256), 0, st, part, (int)(p.nchunk * p.RY), C, HW, 1e-5f, stats);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;

@@ -61,10 +61,11 @@ extern "C" int maua_group_norm_ex(maua_ctx* ctx, const maua_gn_desc* d) {
   const GnArgs a = gn_args(d);
   if (int rc = gn_check(d, a)) return rc;
   if (d->B == 0) return MAUA_OK;
-  const size_t part_bytes = (group_norm_workspace(d->B, d->C0 + d->C1, (long)d->H * d->W, d->dtype == MAUA_BF16 ? 2 : 4) + 255) & ~(size_t)255;
-  if (int rc = scratch_reserve(ctx, part_bytes + (size_t)d->B * 64 * 4 + 256)) return rc;
-  float* stats = d->stats_out ? d->stats_out : (float*)((char*)ctx->scratch + part_bytes);
-  return launch_group_norm(ctx->stream, d->dtype, a, (double*)ctx->scratch, stats);
+  const size_t part_bytes = group_norm_workspace(d->B, d->C0 + d->C1, (long)d->H * d->W, elem_bytes(d->dtype));
+  double* part;
+  float* stats;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { part = (double*)s.take<char>(part_bytes); stats = s.take<float>((size_t)d->B * 64); })) return rc;
+  return launch_group_norm(ctx->stream, d->dtype, a, part, d->stats_out ? d->stats_out : stats);
 }
 
 extern "C" int maua_group_norm_vjp_check(const maua_gn_vjp_desc* d) {
@@ -89,8 +90,10 @@ extern "C" int maua_group_norm_vjp_ex(maua_ctx* ctx, const maua_gn_vjp_desc* d) 
   const GnVjpArgs a = gn_vjp_args(d);
   if (int rc = group_norm_vjp_check(d->dtype, a)) return rc;
   if (d->B == 0) return MAUA_OK;
-  if (int rc = scratch_reserve(ctx, group_norm_vjp_workspace(d->B, d->C0 + d->C1, (long)d->H * d->W, d->dtype == MAUA_BF16 ? 2 : 4))) return rc;
-  return launch_group_norm_vjp(ctx->stream, d->dtype, a, ctx->scratch);
+  const size_t ws_bytes = group_norm_vjp_workspace(d->B, d->C0 + d->C1, (long)d->H * d->W, elem_bytes(d->dtype));
+  void* ws;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { ws = s.take<char>(ws_bytes); })) return rc;
+  return launch_group_norm_vjp(ctx->stream, d->dtype, a, ws);
 }
 
 // ---- operator-level entry points (NHWC tensors in the network dtype) -----------------------------------------------------------
@@ -102,10 +105,10 @@ int maua_group_norm_nhwc(maua_ctx* ctx, const void* x, const float* gamma, const
   MAUA_REQUIRE(ctx && x && gamma && beta && y, "maua_group_norm_nhwc: NULL argument");
   MAUA_REQUIRE(C % 32 == 0 && (dtype == MAUA_F32 || dtype == MAUA_BF16), "maua_group_norm_nhwc: C % 32, f32 / bf16");
   if (B == 0) return MAUA_OK;
-  const size_t part_bytes = group_norm_workspace(B, C, (long)H * W, dtype == MAUA_BF16 ? 2 : 4);
-  if (int rc = scratch_reserve(ctx, part_bytes + (size_t)B * 64 * 4 + 512)) return rc;
-  double* part = (double*)ctx->scratch;
-  float* stats = (float*)((char*)ctx->scratch + ((part_bytes + 255) & ~(size_t)255));
+  const size_t part_bytes = group_norm_workspace(B, C, (long)H * W, elem_bytes(dtype));
+  double* part;
+  float* stats;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { part = (double*)s.take<char>(part_bytes); stats = s.take<float>((size_t)B * 64); })) return rc;
   GnArgs a{};
   a.x0 = x; a.C0 = C; a.B = B; a.H = H; a.W = W; a.gamma = gamma; a.beta = beta; a.ss = scale_shift; a.ss_ld = 2L * C; a.silu = silu;
   a.y = y;
@@ -119,13 +122,15 @@ int maua_group_norm_nhwc_vjp(maua_ctx* ctx, const void* x, const float* gamma, c
   MAUA_REQUIRE(ctx && x && gamma && beta && dy && dx, "maua_group_norm_nhwc_vjp: NULL argument");
   MAUA_REQUIRE(C % 32 == 0 && (dtype == MAUA_F32 || dtype == MAUA_BF16), "maua_group_norm_nhwc_vjp: C % 32, f32 / bf16");
   if (B == 0) return MAUA_OK;
-  const int esize = dtype == MAUA_BF16 ? 2 : 4;
-  const size_t part_bytes = (group_norm_workspace(B, C, (long)H * W, esize) + 255) & ~(size_t)255;
-  const size_t vjp_bytes = group_norm_vjp_workspace(B, C, (long)H * W, esize);
-  if (int rc = scratch_reserve(ctx, part_bytes + (size_t)B * 64 * 4 + 512 + vjp_bytes)) return rc;
-  double* part = (double*)ctx->scratch;
-  float* stats = (float*)((char*)ctx->scratch + part_bytes);
-  void* ws = (char*)ctx->scratch + part_bytes + (size_t)B * 64 * 4 + 256;
+  const size_t part_bytes = group_norm_workspace(B, C, (long)H * W, elem_bytes(dtype));
+  const size_t vjp_bytes = group_norm_vjp_workspace(B, C, (long)H * W, elem_bytes(dtype));
+  double* part;
+  float* stats;
+  void* ws;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        part = (double*)s.take<char>(part_bytes); stats = s.take<float>((size_t)B * 64); ws = s.take<char>(vjp_bytes);
+      }))
+    return rc;
   // the forward's statistics (its output goes nowhere: the statistics passes only)
   if (int rc = launch_group_norm_stats(ctx->stream, dtype, x, C, B, H, W, part, stats)) return rc;
   GnVjpArgs a{};

@@ -318,7 +318,7 @@ size_t group_norm_vjp_workspace(int B, int C, long HW, int esize) {
 
 int group_norm_vjp_check(int dtype, const GnVjpArgs& a) {
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "group_norm_vjp: unsupported dtype");
-  const int esize = dtype == MAUA_BF16 ? 2 : 4, EPC = 16 / esize;
+  const int esize = elem_bytes(dtype), EPC = 16 / esize;
   MAUA_REQUIRE(a.x0 && a.stats && a.gamma && a.beta && a.dy && a.dx0, "group_norm_vjp: NULL argument");
   MAUA_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.C0 > 0 && a.C1 >= 0, "group_norm_vjp: bad shape");
   const long C = (long)a.C0 + a.C1;
@@ -335,7 +335,7 @@ int group_norm_vjp_check(int dtype, const GnVjpArgs& a) {
 }
 
 GnVjpPlanInfo group_norm_vjp_plan(int dtype, const GnVjpArgs& a) {
-  const VjpPlan p = vjp_plan(a.C0 + a.C1, (long)a.H * a.W, dtype == MAUA_BF16 ? 2 : 4);
+  const VjpPlan p = vjp_plan(a.C0 + a.C1, (long)a.H * a.W, elem_bytes(dtype));
   const int bmax = std::max(1, 65535 / a.H);
   return GnVjpPlanInfo{p.RY, p.ppc, (int)p.nchunk, (a.B + bmax - 1) / bmax};
 }
@@ -344,7 +344,7 @@ int launch_group_norm_vjp(hipStream_t stream, int dtype, const GnVjpArgs& a, voi
   if (int rc = group_norm_vjp_check(dtype, a)) return rc;
   MAUA_REQUIRE(workspace, "group_norm_vjp: NULL argument");
   if (a.B == 0) return MAUA_OK;
-  return dtype == MAUA_BF16 ? run<bf16_t>(stream, a, workspace) : run<float>(stream, a, workspace);
+  return dispatch_dtype<bf16_t, float>(dtype, "group_norm_vjp", [&](auto t) { return run<decltype(t)>(stream, a, workspace); });
 }
 
 }  // namespace maua

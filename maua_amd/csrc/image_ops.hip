@@ -489,14 +489,14 @@ extern "C" int maua_image_perlin(maua_ctx* ctx, const float* grads, const long* 
   for (int k = 0; k < n_octaves; k++) a.oct[k] = octaves[k];
   const long n = S_r * S_c;
   const int parts = (int)((n + 255) / 256);
-  const size_t q_bytes = ((size_t)a.channels * n + 255) & ~(size_t)255;
-  const size_t table_bytes = ((size_t)a.channels * parts * 8 + 255) & ~(size_t)255;
-  if (int rc = scratch_reserve(ctx, q_bytes + table_bytes + 256)) return rc;
-  uint8_t* q = (uint8_t*)ctx->scratch;
-  int* minmax = (int*)((char*)ctx->scratch + q_bytes);
+  uint8_t* q;
+  int *minmax, *lohi;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        q = s.take<uint8_t>((size_t)a.channels * n); minmax = s.take<int>((size_t)a.channels * parts * 2); lohi = s.take<int>(2 * a.channels);
+      }))
+    return rc;
   hipLaunchKernelGGL(perlin_octaves_kernel, dim3((unsigned)parts, (unsigned)a.channels), dim3(256), 0, ctx->stream, a, raw, q, minmax);
   MAUA_HIP_CHECK(hipGetLastError());
-  int* lohi = (int*)((char*)ctx->scratch + q_bytes + table_bytes);
   hipLaunchKernelGGL(perlin_extremes_kernel, dim3((unsigned)a.channels), dim3(256), 0, ctx->stream, minmax, parts, lohi);
   MAUA_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(perlin_autocontrast_kernel, dim3((unsigned)parts, 3), dim3(256), 0, ctx->stream, q, lohi, 1, a.channels, n, out);

@@ -228,27 +228,26 @@ int maua_spline_natural(maua_ctx* ctx, const double* t_knots_host, int n, const 
     hw[t] = h[i];
   }
   // scratch layout: M [n][C] f64 | h | cp | inv_den | aw | bw | hw | idx
-  size_t off = 0;
-  auto carve = [&](size_t b) { size_t o = off; off += (b + 255) & ~(size_t)255; return o; };
-  size_t oM = carve((size_t)n * C * 8), oh = carve(n * 8), ocp = carve(n * 8), oid = carve(n * 8);
-  size_t oa = carve(T * 8), ob = carve(T * 8), ohw = carve(T * 8), oix = carve(T * 4);
-  if (int rc = scratch_reserve(ctx, off)) return rc;
-  char* base = (char*)ctx->scratch;
+  double *dM, *dh, *dcp, *did, *da, *db, *dhw;
+  int* dix;
+  if (int rc = carve_scratch(ctx, [&](Scratch& sc) {
+        dM = sc.take<double>((size_t)n * C); dh = sc.take<double>(n); dcp = sc.take<double>(n); did = sc.take<double>(n);
+        da = sc.take<double>(T); db = sc.take<double>(T); dhw = sc.take<double>(T); dix = sc.take<int>(T);
+      }))
+    return rc;
   hipStream_t s = ctx->stream;
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + oh, h.data(), n * 8, hipMemcpyHostToDevice, s));
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + ocp, cp.data(), n * 8, hipMemcpyHostToDevice, s));
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + oid, inv_den.data(), n * 8, hipMemcpyHostToDevice, s));
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + oa, aw.data(), T * 8, hipMemcpyHostToDevice, s));
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + ob, bw.data(), T * 8, hipMemcpyHostToDevice, s));
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + ohw, hw.data(), T * 8, hipMemcpyHostToDevice, s));
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + oix, idx.data(), T * 4, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(dh, h.data(), n * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(dcp, cp.data(), n * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(did, inv_den.data(), n * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(da, aw.data(), T * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(db, bw.data(), T * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(dhw, hw.data(), T * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(dix, idx.data(), T * 4, hipMemcpyHostToDevice, s));
   MAUA_HIP_CHECK(hipStreamSynchronize(s));  // host staging vectors go out of scope
-  hipLaunchKernelGGL(spline_solve_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, y, n, C,
-                     (const double*)(base + oh), (const double*)(base + ocp), (const double*)(base + oid),
-                     (double*)(base + oM));
-  hipLaunchKernelGGL(spline_eval_kernel, dim3((unsigned)((C + 255) / 256), T), dim3(256), 0, s, y,
-                     (const double*)(base + oM), C, (const int*)(base + oix), (const double*)(base + oa),
-                     (const double*)(base + ob), (const double*)(base + ohw), out);
+  hipLaunchKernelGGL(spline_solve_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, y, n, C, (const double*)dh, (const double*)dcp,
+                     (const double*)did, dM);
+  hipLaunchKernelGGL(spline_eval_kernel, dim3((unsigned)((C + 255) / 256), T), dim3(256), 0, s, y, (const double*)dM, C, (const int*)dix,
+                     (const double*)da, (const double*)db, (const double*)dhw, out);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }

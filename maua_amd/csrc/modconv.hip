@@ -601,7 +601,7 @@ int modconv3x3_check(int dtype, const ConvArgs& a) {
   MAUA_REQUIRE(!a.y_scaled, "modconv3x3: no y_scaled (the dual store is the LDS-direct kernel's)");
   MAUA_REQUIRE(!a.rgb_out || !a.out_scale, "modconv3x3: fused toRGB and out_scale exclude each other");
   if (a.B == 0) return MAUA_OK;
-  const int tile = modconv_tile(dtype == MAUA_BF16 || dtype == MAUA_F16 ? 2 : 4, a);
+  const int tile = modconv_tile(elem_bytes(dtype), a);
   MAUA_REQUIRE(!a.rgb_out || ((dtype == MAUA_BF16 || dtype == MAUA_F16) && a.up == 1 && a.Co == 128 && tile >= 2 && tile <= 6 &&
                               a.rgb_wmod && a.rgb_bias),
                "modconv3x3: fused toRGB needs bf16, up == 1 and all output channels in one N tile");
@@ -611,11 +611,7 @@ int modconv3x3_check(int dtype, const ConvArgs& a) {
 
 int launch_modconv3x3(hipStream_t stream, int dtype, const ConvArgs& a) {
   if (int rc = modconv3x3_check(dtype, a)) return rc;
-  if (dtype == MAUA_BF16) return launch_modconv_t<bf16_t>(stream, a);
-  if (dtype == MAUA_F16) return launch_modconv_t<f16_t>(stream, a);
-  if (dtype == MAUA_F32) return launch_modconv_t<float>(stream, a);
-  if (dtype == MAUA_F32_SPLIT) return launch_modconv_t<f32s_t>(stream, a);
-  return fail("modconv3x3: unsupported dtype");
+  return dispatch_dtype<bf16_t, f16_t, float, f32s_t>(dtype, "modconv3x3", [&](auto t) { return launch_modconv_t<decltype(t)>(stream, a); });
 }
 
 }  // namespace maua

@@ -74,7 +74,7 @@ int modconv_plan(const maua_modconv_desc* d, const maua_modconv_desc* d1, int dt
     case R_GENERIC: {
       const ConvArgs a = conv_args(d);
       if (int rc = modconv3x3_check(dtype, a)) return rc;
-      *tile = modconv_tile(dtype == MAUA_F32 ? 4 : 2, a);
+      *tile = modconv_tile(elem_bytes(dtype), a);
       return MAUA_OK;
     }
     case R_DMA: {
@@ -128,8 +128,6 @@ int modconv_plan(const maua_modconv_desc* d, const maua_modconv_desc* d1, int dt
   return MAUA_OK;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace maua
 
@@ -149,7 +147,7 @@ extern "C" int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const 
   int tile = 0;
   if (int rc = modconv_plan(d, d1, dtype, route, &tile)) return rc;
   if (d->B == 0) return MAUA_OK;
-  const size_t es = dtype == MAUA_F32 ? 4 : 2;
+  const size_t es = elem_bytes(dtype);
   const size_t CoCi = (size_t)d->Co * d->Ci, px = (size_t)d->B * d->H * d->W;
   // workspaces from the context's scratch arena: prepared weights (two layers for the fused walk), unit styles, the pre-modulated
   // input, t, the split-K partial sums
@@ -162,40 +160,43 @@ extern "C" int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const 
   size_t xm_bytes = reads_premod(route) ? px * d->Ci * es : 0, ws_bytes = 0;
   if (route == R_LOWRES) lowres_workspace(dtype, d->B, d->H, d->W, d->Ci, d->Co, d->up, &xm_bytes, &ws_bytes);
   const size_t t_bytes = (route == R_TDMA || route == R_T2) && !d->t ? (size_t)d->B * (2 * d->H + 1) * (2 * d->W + 1) * d->Co * es : 0;
-  const size_t o_w = 0, o_w1 = o_w + align256(w_bytes), o_ones = o_w1 + align256(w1_bytes), o_xm = o_ones + align256(ones_bytes),
-               o_ws = o_xm + align256(xm_bytes), o_t = o_ws + align256(ws_bytes);
-  if (int rc = scratch_reserve(ctx, o_t + align256(t_bytes))) return rc;
-  char* base = (char*)ctx->scratch;
+  char *w, *w1, *xm, *tbuf;
+  float *ones, *ws;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        w = s.take<char>(w_bytes); w1 = s.take<char>(w1_bytes); ones = s.take<float>(ones_bytes / 4);
+        xm = s.take<char>(xm_bytes); ws = s.take<float>(ws_bytes / 4); tbuf = s.take<char>(t_bytes);
+      }))
+    return rc;
   hipStream_t st = ctx->stream;
   // weights as maua_synth_load prepares them for the route
   if (route == R_UPWALK || route == R_FUSED) {
-    if (int rc = launch_prep_upwalk_weights(st, d->w, base + o_w, d->Co, d->Ci, d->flip, dtype)) return rc;
+    if (int rc = launch_prep_upwalk_weights(st, d->w, w, d->Co, d->Ci, d->flip, dtype)) return rc;
   } else if (is_tconv(route)) {
-    if (int rc = launch_prep_tconv_weights(st, dtype, d->w, base + o_w, d->Co, d->Ci, d->flip)) return rc;
+    if (int rc = launch_prep_tconv_weights(st, dtype, d->w, w, d->Co, d->Ci, d->flip)) return rc;
   } else if (route != R_UPFIR) {
-    if (int rc = launch_prep_weights(st, dtype, d->w, base + o_w, nullptr, d->Co, d->Ci, 3, d->up, d->up == 2 ? d->flip : 0, d->Co, d->Ci))
+    if (int rc = launch_prep_weights(st, dtype, d->w, w, nullptr, d->Co, d->Ci, 3, d->up, d->up == 2 ? d->flip : 0, d->Co, d->Ci))
       return rc;
   }
   if (route == R_FUSED)
-    if (int rc = launch_prep_weights(st, dtype, d1->w, base + o_w1, nullptr, d1->Co, d1->Ci, 3, 1, 0, d1->Co, d1->Ci)) return rc;
+    if (int rc = launch_prep_weights(st, dtype, d1->w, w1, nullptr, d1->Co, d1->Ci, 3, 1, 0, d1->Co, d1->Ci)) return rc;
   // what the plan's Src does in front of a route that reads pre-modulated input: the premod pass, unit styles for the kernel
   const void* x = d->x;
   long x_bstride = d->x_bstride;
   if (reads_premod(route)) {
-    if (int rc = launch_premod_nhwc(st, d->x, d->x_bstride, d->s, base + o_xm, d->B, (long)d->H * d->W, d->Ci, dtype)) return rc;
-    x = base + o_xm;
+    if (int rc = launch_premod_nhwc(st, d->x, d->x_bstride, d->s, xm, d->B, (long)d->H * d->W, d->Ci, dtype)) return rc;
+    x = xm;
     x_bstride = (long)d->H * d->W * d->Ci;
   }
   if (ones_bytes)
-    if (int rc = launch_fill_ones(st, (float*)(base + o_ones), (long)d->B * d->Ci)) return rc;
+    if (int rc = launch_fill_ones(st, ones, (long)d->B * d->Ci)) return rc;
   switch (route) {
     case R_LOWRES:
     case R_GENERIC:
     case R_DMA: {
       ConvArgs a = conv_args(d);
-      a.x = x; a.x_bstride = x_bstride; a.w = base + o_w;
+      a.x = x; a.x_bstride = x_bstride; a.w = w;
       if (route == R_DMA) a.s = nullptr;
-      return route == R_LOWRES    ? launch_modconv_lowres(st, dtype, a, base + o_xm, (float*)(base + o_ws))
+      return route == R_LOWRES    ? launch_modconv_lowres(st, dtype, a, xm, ws)
              : route == R_GENERIC ? launch_modconv3x3(st, dtype, a)
                                   : launch_modconv_dma(st, a, dtype);
     }
@@ -203,21 +204,21 @@ extern "C" int maua_modconv_ex(maua_ctx* ctx, const maua_modconv_desc* d, const 
     case R_UPWALK:
     case R_FUSED: {
       HiresArgs a = hires_args(d);
-      a.w = base + o_w;
+      a.w = w;
       if (route == R_HIRES) return launch_modconv_hires(st, a, dtype);
       if (route == R_UPWALK) return launch_upwalk(st, a, dtype);
       HiresArgs f = hires_args(d1);
-      f.x = nullptr; f.y = nullptr; f.w = base + o_w1;
+      f.x = nullptr; f.y = nullptr; f.w = w1;
       a.y = nullptr;
       return launch_upwalk_fused(st, a, f, force_segs, narrow_ok, dtype);
     }
     case R_TFIR:
     case R_TDMA:
     case R_T2: {
-      void* t = d->t ? d->t : base + o_t;
+      void* t = d->t ? d->t : tbuf;
       ConvArgs a = tconv_args(d);
-      a.x = x; a.x_bstride = x_bstride; a.w = base + o_w; a.y = t;
-      if (route != R_T2) a.s = (const float*)(base + o_ones);
+      a.x = x; a.x_bstride = x_bstride; a.w = w; a.y = t;
+      if (route != R_T2) a.s = ones;
       UpfirArgs u = upfir_args(d);
       if (route == R_TFIR) return launch_tconv_fir(st, a, u, dtype, force_segs >= 0, force_segs);   // (force_segs < 0: the tile form)
       if (route == R_TDMA) {

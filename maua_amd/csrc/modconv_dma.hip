@@ -70,14 +70,12 @@ int launch_premod_nhwc(hipStream_t stream, const void* x, long x_bstride, const 
   MAUA_REQUIRE(Ci % 8 == 0, "premod: Ci must be a multiple of 8");
   if (B == 0) return MAUA_OK;
   const long n = (long)B * HW * (Ci / 8);
-  if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(premod_nhwc_kernel<f16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const uint16_t*)x, x_bstride, s,
+  return dispatch_dtype<bf16_t, f16_t>(dtype, "premod", [&](auto t) {
+    hipLaunchKernelGGL(premod_nhwc_kernel<decltype(t)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const uint16_t*)x, x_bstride, s,
                        (uint16_t*)y, B, HW, Ci);
-  else
-    hipLaunchKernelGGL(premod_nhwc_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const uint16_t*)x, x_bstride, s,
-                       (uint16_t*)y, B, HW, Ci);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 // PSUM: also emit ConvArgs.psum (its own instantiation: the 16 accumulators of the copy-out loop cost the 128-register

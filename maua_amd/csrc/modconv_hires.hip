@@ -399,14 +399,13 @@ int launch_modconv_hires(hipStream_t stream, const HiresArgs& a, int dtype) {
   if (a.B == 0) return MAUA_OK;
   HiresArgs b = a;
   if (a.act == MAUA_ACT_LINEAR) b.alpha = 1.f;
-  if (dtype == MAUA_F16) {   // (round 6: the reference's own render dtype on the same kernels - v_mfma_f32_32x32x16_f16, half conversions)
-    if (a.Ci == 32) return launch_hires_variant<32, 32, 1, f16_t>(stream, b);
-    if (a.up == 1) return launch_hires_variant<64, 64, 1, f16_t>(stream, b);
-    return launch_hires_variant<64, 32, 2, f16_t>(stream, b);
-  }
-  if (a.Ci == 32) return launch_hires_variant<32, 32, 1, bf16_t>(stream, b);
-  if (a.up == 1) return launch_hires_variant<64, 64, 1, bf16_t>(stream, b);
-  return launch_hires_variant<64, 32, 2, bf16_t>(stream, b);
+  // (MAUA_F16, the reference's own render dtype, runs the same kernels on v_mfma_f32_32x32x16_f16 with half conversions)
+  return dispatch_dtype<bf16_t, f16_t>(dtype, "modconv_hires", [&](auto t) {
+    using T = decltype(t);
+    if (a.Ci == 32) return launch_hires_variant<32, 32, 1, T>(stream, b);
+    if (a.up == 1) return launch_hires_variant<64, 64, 1, T>(stream, b);
+    return launch_hires_variant<64, 32, 2, T>(stream, b);
+  });
 }
 
 }  // namespace maua

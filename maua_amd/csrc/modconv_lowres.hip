@@ -243,12 +243,12 @@ int launch_lowres_t(hipStream_t stream, const ConvArgs& a, void* xm, float* ws, 
 
 bool lowres_supported(int dtype, int Ci, int Co, int up, int H, int W) {
   if (dtype != MAUA_BF16 && dtype != MAUA_F32) return false;
-  const int esize = dtype == MAUA_BF16 ? 2 : 4;
+  const int esize = elem_bytes(dtype);
   return (up == 1 || up == 2) && H * W <= 64 && Ci % (LKCB / esize) == 0 && Co % 32 == 0 && (Co * up * up) % LBN == 0;
 }
 
 void lowres_workspace(int dtype, int B, int H, int W, int Ci, int Co, int up, size_t* xm_bytes, size_t* ws_bytes) {
-  const int esize = dtype == MAUA_BF16 ? 2 : 4;
+  const int esize = elem_bytes(dtype);
   const LowresGeom g = lowres_geom(esize, B, H, W, Ci, Co, up);
   *xm_bytes = (size_t)g.M * Ci * esize;
   *ws_bytes = (size_t)g.ksplit * g.M * g.CoV * sizeof(float);
@@ -258,12 +258,12 @@ void lowres_workspace(int dtype, int B, int H, int W, int Ci, int Co, int up, si
 // the 16^2 / 8^2 levels of the diffusion UNet (unet.hip), where a per-sample tiling leaves the chip empty.
 bool gather_conv_supported(int dtype, int Ci, int Co, int H, int W) {
   if (dtype != MAUA_BF16 && dtype != MAUA_F32) return false;
-  const int esize = dtype == MAUA_BF16 ? 2 : 4;
+  const int esize = elem_bytes(dtype);
   return H * W <= 1024 && Ci % (LKCB / esize) == 0 && Co % LBN == 0;
 }
 constexpr int GATHER_TILES = 256;
 size_t gather_conv_workspace(int dtype, int B, int H, int W, int Ci, int Co) {
-  const LowresGeom g = lowres_geom(dtype == MAUA_BF16 ? 2 : 4, B, H, W, Ci, Co, 1, GATHER_TILES);
+  const LowresGeom g = lowres_geom(elem_bytes(dtype), B, H, W, Ci, Co, 1, GATHER_TILES);
   return (size_t)g.ksplit * g.M * g.CoV * sizeof(float);
 }
 // what launch_conv_gather checks before it launches (host only), and the K slices it then takes
@@ -278,13 +278,12 @@ int gather_conv_check(int dtype, const ConvArgs& a) {
   return MAUA_OK;
 }
 int gather_conv_ksplit(int dtype, int B, int H, int W, int Ci, int Co) {
-  return lowres_geom(dtype == MAUA_BF16 ? 2 : 4, B, H, W, Ci, Co, 1, GATHER_TILES).ksplit;
+  return lowres_geom(elem_bytes(dtype), B, H, W, Ci, Co, 1, GATHER_TILES).ksplit;
 }
 int launch_conv_gather(hipStream_t stream, int dtype, const ConvArgs& a, float* ws) {
   if (int rc = gather_conv_check(dtype, a)) return rc;
   if (a.B == 0) return MAUA_OK;
-  if (dtype == MAUA_BF16) return launch_lowres_t<bf16_t>(stream, a, nullptr, ws, GATHER_TILES);
-  return launch_lowres_t<float>(stream, a, nullptr, ws, GATHER_TILES);
+  return dispatch_dtype<bf16_t, float>(dtype, "conv_gather", [&](auto t) { return launch_lowres_t<decltype(t)>(stream, a, nullptr, ws, GATHER_TILES); });
 }
 
 // what launch_modconv_lowres checks before it launches (host only), and the K slices it then takes
@@ -300,15 +299,14 @@ int lowres_check(int dtype, const ConvArgs& a) {
   return MAUA_OK;
 }
 int lowres_ksplit(int dtype, int B, int H, int W, int Ci, int Co, int up) {
-  return lowres_geom(dtype == MAUA_BF16 ? 2 : 4, B, H, W, Ci, Co, up).ksplit;
+  return lowres_geom(elem_bytes(dtype), B, H, W, Ci, Co, up).ksplit;
 }
 
 int launch_modconv_lowres(hipStream_t stream, int dtype, const ConvArgs& a, void* xm, float* ws) {
   if (int rc = lowres_check(dtype, a)) return rc;
   if (a.B == 0) return MAUA_OK;
   MAUA_REQUIRE(xm && ws, "modconv_lowres: NULL workspace / styles");
-  if (dtype == MAUA_BF16) return launch_lowres_t<bf16_t>(stream, a, xm, ws);
-  return launch_lowres_t<float>(stream, a, xm, ws);
+  return dispatch_dtype<bf16_t, float>(dtype, "modconv_lowres", [&](auto t) { return launch_lowres_t<decltype(t)>(stream, a, xm, ws); });
 }
 
 }  // namespace maua

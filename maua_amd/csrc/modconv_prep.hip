@@ -71,19 +71,11 @@ int launch_prep_weights(hipStream_t stream, int dtype, const float* w, void* wt,
   MAUA_REQUIRE(up == 1 || (up == 2 && k == 3), "prep_weights: up=2 needs a 3x3 kernel");
   long n = (long)Cop * Cip;
   dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(prep_weights_kernel<bf16_t>, grid, dim3(256), 0, stream, w, (bf16_t*)wt, wsq, Co, Ci, k, up, flip,
-                       Cop, Cip);
-  else if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(prep_weights_kernel<f16_t>, grid, dim3(256), 0, stream, w, (f16_t*)wt, wsq, Co, Ci, k, up, flip,
-                       Cop, Cip);
-  else if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(prep_weights_kernel<float>, grid, dim3(256), 0, stream, w, (float*)wt, wsq, Co, Ci, k, up, flip,
-                       Cop, Cip);
-  else
-    return fail("prep_weights: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, f16_t, float>(dtype, "prep_weights", [&](auto t) {
+    hipLaunchKernelGGL(prep_weights_kernel<decltype(t)>, grid, dim3(256), 0, stream, w, (decltype(t)*)wt, wsq, Co, Ci, k, up, flip, Cop, Cip);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 // dst[i][o][k] = src[o][i][kk - 1 - k]: a convolution's (kk = 9) / linear layer's (kk = 1) weight for its input gradient

@@ -237,7 +237,7 @@ static int launch_tconv_t(hipStream_t stream, const ConvArgs& a) {
 // what launch_tconv2 checks from the shape alone (host only; the halo budget is checked where the regions are laid out)
 int tconv2_check(int dtype, const ConvArgs& a) {
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F16 || dtype == MAUA_F32, "tconv2: unsupported dtype");
-  MAUA_REQUIRE(a.Ci % (TKCB / (dtype == MAUA_F32 ? 4 : 2)) == 0 && a.Co % 32 == 0, "tconv2: channel counts must be multiples of 32");
+  MAUA_REQUIRE(a.Ci % (TKCB / elem_bytes(dtype)) == 0 && a.Co % 32 == 0, "tconv2: channel counts must be multiples of 32");
   MAUA_REQUIRE((long)a.H * a.W * a.Ci < (1L << 31) && 16L * a.Co * a.Ci < (1L << 31), "tconv2: 32-bit offsets");
   MAUA_REQUIRE(a.B <= 65535 && a.Co / 32 <= 65535, "tconv2: grid too large");
   return MAUA_OK;
@@ -245,10 +245,7 @@ int tconv2_check(int dtype, const ConvArgs& a) {
 
 int launch_tconv2(hipStream_t stream, int dtype, const ConvArgs& a) {
   if (int rc = tconv2_check(dtype, a)) return rc;
-  if (dtype == MAUA_BF16) return launch_tconv_t<bf16_t>(stream, a);
-  if (dtype == MAUA_F16) return launch_tconv_t<f16_t>(stream, a);
-  if (dtype == MAUA_F32) return launch_tconv_t<float>(stream, a);
-  return fail("tconv2: unsupported dtype");
+  return dispatch_dtype<bf16_t, f16_t, float>(dtype, "tconv2", [&](auto t) { return launch_tconv_t<decltype(t)>(stream, a); });
 }
 
 // ---- weights: f32 [Co][Ci][3][3] -> T [slot 4][Co/32][class 4][32][Ci]  (zero where a class does not use a slot)
@@ -278,16 +275,11 @@ int launch_prep_tconv_weights(hipStream_t stream, int dtype, const float* w, voi
   MAUA_REQUIRE(Co % 32 == 0, "prep_tconv_weights: Co must be a multiple of 32");
   const long n = (long)Co * Ci;
   dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(prep_tconv_weights_kernel<bf16_t>, grid, dim3(256), 0, stream, w, (bf16_t*)wt, Co, Ci, flip);
-  else if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(prep_tconv_weights_kernel<f16_t>, grid, dim3(256), 0, stream, w, (f16_t*)wt, Co, Ci, flip);
-  else if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(prep_tconv_weights_kernel<float>, grid, dim3(256), 0, stream, w, (float*)wt, Co, Ci, flip);
-  else
-    return fail("prep_tconv_weights: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, f16_t, float>(dtype, "prep_tconv_weights", [&](auto t) {
+    hipLaunchKernelGGL(prep_tconv_weights_kernel<decltype(t)>, grid, dim3(256), 0, stream, w, (decltype(t)*)wt, Co, Ci, flip);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 }  // namespace maua

@@ -289,12 +289,11 @@ int launch_tconv_edges(hipStream_t stream, const ConvArgs& a, int dtype) {
   if (int rc = tconv_edges_check(a, dtype)) return rc;
   if (a.B == 0) return MAUA_OK;
   const int row_tiles = (a.W + 1 + 31) / 32, col_tiles = (a.H + 31) / 32;
-  if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(tconv_edges_kernel<f16_t>, dim3(row_tiles + col_tiles, a.B, a.Co / 32), dim3(64), 0, stream, a, row_tiles);
-  else
-    hipLaunchKernelGGL(tconv_edges_kernel<bf16_t>, dim3(row_tiles + col_tiles, a.B, a.Co / 32), dim3(64), 0, stream, a, row_tiles);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, f16_t>(dtype, "tconv_edges", [&](auto t) {
+    hipLaunchKernelGGL(tconv_edges_kernel<decltype(t)>, dim3(row_tiles + col_tiles, a.B, a.Co / 32), dim3(64), 0, stream, a, row_tiles);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 bool tconv_dma_supported(int dtype, int Ci, int Co, int H, int W) {
@@ -310,15 +309,12 @@ int launch_tconv_dma(hipStream_t stream, const ConvArgs& a, int dtype) {
   const int tiles = (a.H / PTH) * (a.W / PTW), CB = a.Co / 32, cbg = CB < 8 ? CB : 8;
   const long n_ts = (long)tiles * a.B, grid = ((n_ts + 7) / 8) * 8 * cbg * (CB / cbg);
   const size_t smem = std::max<size_t>((size_t)2 * WBUF + 2 * HBUF, (size_t)PTH * PTW * (128 * 2 + 16));
-  if (dtype == MAUA_F16) {
-    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)tconv_dma_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(tconv_dma_kernel<f16_t>, dim3((unsigned)grid), dim3(NT), smem, stream, a);
-  } else {
-    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)tconv_dma_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(tconv_dma_kernel<bf16_t>, dim3((unsigned)grid), dim3(NT), smem, stream, a);
-  }
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, f16_t>(dtype, "tconv_dma", [&](auto t) {
+    MAUA_HIP_CHECK(hipFuncSetAttribute((const void*)tconv_dma_kernel<decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(tconv_dma_kernel<decltype(t)>, dim3((unsigned)grid), dim3(NT), smem, stream, a);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 }  // namespace maua

@@ -881,12 +881,11 @@ __global__ __launch_bounds__(256) void prep_upwalk_weights_kernel(const float* _
 
 int launch_prep_upwalk_weights(hipStream_t stream, const float* w, void* wt, int Co, int Ci, int flip, int dtype) {
   const long n = (long)Co * Ci;
-  if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(prep_upwalk_weights_kernel<f16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, (uint16_t*)wt, Co, Ci, flip);
-  else
-    hipLaunchKernelGGL(prep_upwalk_weights_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, (uint16_t*)wt, Co, Ci, flip);
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, f16_t>(dtype, "prep_upwalk_weights", [&](auto t) {
+    hipLaunchKernelGGL(prep_upwalk_weights_kernel<decltype(t)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, (uint16_t*)wt, Co, Ci, flip);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 }  // namespace maua

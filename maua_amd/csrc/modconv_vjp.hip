@@ -338,8 +338,6 @@ __global__ __launch_bounds__(256) void rgb_styles_vjp_kernel(const float* __rest
   g_s[(long)b * C + c] = (wrgb[c] * g[c] + wrgb[C + c] * g[C + c]) + wrgb[2 * C + c] * g[2 * C + c];
 }
 
-size_t esize_of(int dtype) { return dtype == MAUA_F32 ? 4 : 2; }
-
 template <typename T>
 int launch_modconv_vjp_t(hipStream_t st, const ModconvVjpArgs& a) {
   const int Ho = a.H * a.up, Wo = a.W * a.up;
@@ -388,8 +386,6 @@ int launch_torgb_vjp_t(hipStream_t st, const RgbVjpArgs& a) {
   return MAUA_OK;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the forward descriptor -> the launcher's arguments (workspaces and prepared weights are the caller's)
 ModconvVjpArgs vjp_args(const maua_modconv_desc* f, const void* g_y, void* g_x, float* g_s) {
   ModconvVjpArgs a{};
@@ -412,7 +408,7 @@ int vjp_desc_check(const maua_modconv_desc* f, const void* g_y, float* g_s, int 
 }  // namespace
 
 ModconvVjpWorkspace modconv_vjp_workspace(int dtype, int B, int H, int W, int Ci, int Co, int up) {
-  const size_t es = esize_of(dtype);
+  const size_t es = elem_bytes(dtype);
   const long Po = (long)H * up * W * up, Pi = (long)H * W;
   ModconvVjpWorkspace w;
   w.g_u = (size_t)B * Po * Co * es;
@@ -442,32 +438,27 @@ int launch_modconv_vjp(hipStream_t st, int dtype, const ModconvVjpArgs& a) {
   if (int rc = modconv_vjp_check(dtype, a)) return rc;
   MAUA_REQUIRE(a.wg && a.g_u && a.g_xm && a.part && (a.up == 1 || a.g_t) && (!a.d || (a.g_d && a.wsq)), "maua_modconv_vjp: NULL workspace");
   if (a.B == 0) return MAUA_OK;
-  return dtype == MAUA_BF16 ? launch_modconv_vjp_t<bf16_t>(st, a) : launch_modconv_vjp_t<float>(st, a);
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_modconv_vjp", [&](auto t) { return launch_modconv_vjp_t<decltype(t)>(st, a); });
 }
 
 int launch_prep_vjp_weights(hipStream_t st, int dtype, const float* w, void* wg, float* wsq, int Co, int Ci, int flip) {
   const unsigned grid = (unsigned)((9L * Ci * Co + 255) / 256);
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(prep_vjp_weights_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, w, (bf16_t*)wg, wsq, Co, Ci, flip);
-  else if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(prep_vjp_weights_kernel<float>, dim3(grid), dim3(256), 0, st, w, (float*)wg, wsq, Co, Ci, flip);
-  else
-    return fail("prep_vjp_weights: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, float>(dtype, "prep_vjp_weights", [&](auto t) {
+    hipLaunchKernelGGL(prep_vjp_weights_kernel<decltype(t)>, dim3(grid), dim3(256), 0, st, w, (decltype(t)*)wg, wsq, Co, Ci, flip);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 int launch_vjp_weights_from_prepared(hipStream_t st, int dtype, const void* prepared, void* wg, int Co, int Ci, int up) {
   MAUA_REQUIRE(Co % 32 == 0, "vjp_weights_from_prepared: Co must be a multiple of 32");
   const unsigned grid = (unsigned)((9L * Ci * Co + 255) / 256);
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(vjp_weights_from_prepared_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)prepared, (bf16_t*)wg, Co, Ci, up);
-  else if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(vjp_weights_from_prepared_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)prepared, (float*)wg, Co, Ci, up);
-  else
-    return fail("vjp_weights_from_prepared: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, float>(dtype, "vjp_weights_from_prepared", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(vjp_weights_from_prepared_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)prepared, (T*)wg, Co, Ci, up);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 size_t torgb_vjp_part_bytes(int B, int H, int W, int C) { return (size_t)B * rgb_nchunk((long)H * W) * 3 * C * 4; }
@@ -486,7 +477,7 @@ int launch_torgb_vjp(hipStream_t st, int dtype, const RgbVjpArgs& a) {
   if (int rc = torgb_vjp_check(dtype, a)) return rc;
   MAUA_REQUIRE(a.part, "maua_torgb_vjp: NULL workspace");
   if (a.B == 0) return MAUA_OK;
-  return dtype == MAUA_BF16 ? launch_torgb_vjp_t<bf16_t>(st, a) : launch_torgb_vjp_t<float>(st, a);
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_torgb_vjp", [&](auto t) { return launch_torgb_vjp_t<decltype(t)>(st, a); });
 }
 
 int launch_skip_vjp(hipStream_t st, const float* g_img, float* g_prev, int B, int h, int w) {
@@ -525,17 +516,16 @@ extern "C" int maua_modconv_vjp_ex(maua_ctx* ctx, const maua_modconv_desc* fwd, 
   if (int rc = vjp_desc_check(fwd, g_y, g_s, dtype)) return rc;
   if (fwd->B == 0) return MAUA_OK;
   const ModconvVjpWorkspace ws = modconv_vjp_workspace(dtype, fwd->B, fwd->H, fwd->W, fwd->Ci, fwd->Co, fwd->up);
-  const size_t wg_bytes = 9 * (size_t)fwd->Ci * fwd->Co * esize_of(dtype), wsq_bytes = (size_t)fwd->Ci * fwd->Co * 4;
-  const size_t o_wg = 0, o_wsq = o_wg + align256(wg_bytes), o_gu = o_wsq + align256(wsq_bytes), o_gt = o_gu + align256(ws.g_u),
-               o_gxm = o_gt + align256(ws.g_t), o_part = o_gxm + align256(ws.g_xm), o_gd = o_part + align256(ws.part);
-  if (int rc = scratch_reserve(ctx, o_gd + align256(ws.g_d))) return rc;
-  char* base = (char*)ctx->scratch;
-  if (int rc = launch_prep_vjp_weights(ctx->stream, dtype, fwd->w, base + o_wg, (float*)(base + o_wsq), fwd->Co, fwd->Ci,
-                                       fwd->up == 2 ? fwd->flip : 0))
-    return rc;
+  const size_t wg_bytes = 9 * (size_t)fwd->Ci * fwd->Co * elem_bytes(dtype), wsq_bytes = (size_t)fwd->Ci * fwd->Co * 4;
   ModconvVjpArgs a = vjp_args(fwd, g_y, g_x, g_s);
-  a.wg = base + o_wg; a.wsq = (const float*)(base + o_wsq); a.g_u = base + o_gu; a.g_t = base + o_gt;
-  a.g_xm = (float*)(base + o_gxm); a.part = (float*)(base + o_part); a.g_d = (float*)(base + o_gd);
+  char* wg;
+  float* wsq;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        a.wg = wg = s.take<char>(wg_bytes); a.wsq = wsq = s.take<float>(wsq_bytes / 4); a.g_u = s.take<char>(ws.g_u); a.g_t = s.take<char>(ws.g_t);
+        a.g_xm = s.take<float>(ws.g_xm / 4); a.part = s.take<float>(ws.part / 4); a.g_d = s.take<float>(ws.g_d / 4);
+      }))
+    return rc;
+  if (int rc = launch_prep_vjp_weights(ctx->stream, dtype, fwd->w, wg, wsq, fwd->Co, fwd->Ci, fwd->up == 2 ? fwd->flip : 0)) return rc;
   return launch_modconv_vjp(ctx->stream, dtype, a);
 }
 
@@ -558,7 +548,6 @@ extern "C" int maua_torgb_vjp_ex(maua_ctx* ctx, const void* x, const float* wmod
   RgbVjpArgs a = rgb_vjp_args(x, wmod, bias, g_img, g_x, g_wmod, B, H, W, C, clamp, accumulate);
   if (int rc = torgb_vjp_check(dtype, a)) return rc;
   if (B == 0) return MAUA_OK;
-  if (int rc = scratch_reserve(ctx, torgb_vjp_part_bytes(B, H, W, C))) return rc;
-  a.part = (float*)ctx->scratch;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { a.part = s.take<float>(torgb_vjp_part_bytes(B, H, W, C) / 4); })) return rc;
   return launch_torgb_vjp(ctx->stream, dtype, a);
 }

@@ -295,8 +295,7 @@ StepArgs make_args(const maua_nca* h, const maua_nca_desc* d) {
 }
 
 void launch(const maua_nca* h, const StepArgs& a, int k = 1) {
-  if (h->dtype == MAUA_F32) launch_step<float>(h->ctx->stream, a, k);
-  else launch_step<f32s_t>(h->ctx->stream, a, k);
+  dispatch_dtype<float, f32s_t>(h->dtype, "maua_nca", [&](auto t) { launch_step<decltype(t)>(h->ctx->stream, a, k); });
 }
 
 }  // namespace

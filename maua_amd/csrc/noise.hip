@@ -257,8 +257,8 @@ int maua_noise_loop(maua_ctx* ctx, const float* planes, const float* idx, int i0
   MAUA_REQUIRE(sigma != 0.f, "maua_noise_loop: sigma must be non-zero");
   const int hw = h * w;
   const int nblk = noise_nparts(hw);
-  if (int rc = scratch_reserve(ctx, (size_t)B * nblk * sizeof(float))) return rc;
-  float* partial = (float*)ctx->scratch;
+  float* partial;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { partial = s.take<float>((size_t)B * nblk); })) return rc;
   const float inv_s = (float)(50.0 / (double)sigma);
   hipLaunchKernelGGL(noise_loop_sumsq_kernel, dim3(nblk, B), dim3(256), 0, ctx->stream, planes, idx, i0, hw, inv_s,
                      partial);
@@ -288,8 +288,8 @@ int maua_noise_loop_batch(maua_ctx* ctx, int n, const float* const* planes, cons
     max_wblk = std::max(max_wblk, nb.wblk[l]);
   }
   nb.i0 = i0; nb.B = B;
-  if (int rc = scratch_reserve(ctx, (size_t)n * B * NZ_BLOCKS * sizeof(float))) return rc;
-  float* partial = (float*)ctx->scratch;
+  float* partial;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { partial = s.take<float>((size_t)n * B * NZ_BLOCKS); })) return rc;
   hipLaunchKernelGGL(noise_loop_batch_sumsq_kernel, dim3(NZ_BLOCKS, B, n), dim3(256), 0, ctx->stream, nb, partial);
   hipLaunchKernelGGL(noise_loop_batch_write_kernel, dim3(max_wblk, B, n), dim3(256), 0,
                      ctx->stream, nb, partial);
@@ -315,8 +315,8 @@ int maua_noise_loop_batch_raw(maua_ctx* ctx, int n, const float* const* planes, 
   }
   static_assert(NZ_RAW_BLOCKS >= 256, "noise_wblk() returns at most 256 blocks");
   nb.i0 = i0; nb.B = B;
-  if (int rc = scratch_reserve(ctx, (size_t)n * B * NZ_RAW_BLOCKS * sizeof(float))) return rc;
-  float* partial = (float*)ctx->scratch;
+  float* partial;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { partial = s.take<float>((size_t)n * B * NZ_RAW_BLOCKS); })) return rc;
   hipLaunchKernelGGL(noise_loop_batch_raw_kernel, dim3(max_wblk, B, n), dim3(256), 0, ctx->stream, nb, partial);
   hipLaunchKernelGGL(noise_loop_batch_scale_kernel, dim3((unsigned)((n * B + 255) / 256)), dim3(256), 0, ctx->stream, nb, n,
                      partial, scales);

@@ -30,8 +30,6 @@ __global__ __launch_bounds__(256) void demod_kernel(const float* __restrict__ s,
   if (lane == 0) d[(long)b * Cd + co] = dv;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace maua
 
 using namespace maua;
@@ -48,42 +46,34 @@ extern "C" int maua_modconv2d(maua_ctx* ctx, const void* x, const float* weight,
   MAUA_REQUIRE(up == 1 || (up == 2 && k == 3), "maua_modconv2d: up must be 1, or 2 with a 3x3 kernel");
   MAUA_REQUIRE(N >= 0 && Ci > 0 && Co > 0 && H > 0 && W > 0, "maua_modconv2d: bad shape");
   if (N == 0) return MAUA_OK;
-  const size_t es = dtype == MAUA_F32 ? 4 : 2;
+  const size_t es = elem_bytes(dtype);
   const int Cip = (Ci + 31) / 32 * 32, Cop = (Co + 31) / 32 * 32;
   const int Ho = H * up, Wo = W * up;
   const size_t wt_elems = prepped_weight_elems(3, up, Cop, Cip);
-  // carve the scratch arena
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off += align256(bytes);
-    return o;
-  };
-  size_t o_x = carve((size_t)N * H * W * Cip * es), o_y = carve((size_t)N * Ho * Wo * Cop * es);
-  size_t o_w = carve(wt_elems * es), o_wsq = carve((size_t)Co * Ci * 4), o_s = carve((size_t)N * Cip * 4);
-  size_t o_d = carve((size_t)N * Cop * 4), o_b = carve((size_t)Cop * 4);
   // ops.py:161-165: "if x.dtype == torch.float16 and demodulate" the weight and the styles are pre-normalised
   const bool prenorm = dtype == MAUA_F16 && demodulate;
-  size_t o_wn = prenorm ? carve((size_t)Co * Ci * k * k * 4) : 0;
   const bool dma = ctx->dma_conv && k == 3 && dma_conv_supported(dtype, Cip, Cop, up, H, W);
-  size_t o_xm = dma ? carve((size_t)N * H * W * Cip * es) : 0;
-  if (int rc = scratch_reserve(ctx, off)) return rc;
-  char* base = (char*)ctx->scratch;
+  char *xn, *yn, *wt, *xm = nullptr;
+  float *wsq, *sp, *dp, *bp, *wn = nullptr;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) {
+        xn = s.take<char>((size_t)N * H * W * Cip * es);
+        yn = s.take<char>((size_t)N * Ho * Wo * Cop * es);
+        wt = s.take<char>(wt_elems * es);
+        wsq = s.take<float>((size_t)Co * Ci);
+        sp = s.take<float>((size_t)N * Cip);
+        dp = s.take<float>((size_t)N * Cop);
+        bp = s.take<float>(Cop);
+        if (prenorm) wn = s.take<float>((size_t)Co * Ci * k * k);
+        if (dma) xm = s.take<char>((size_t)N * H * W * Cip * es);
+      }))
+    return rc;
   hipStream_t st = ctx->stream;
-  void* xn = base + o_x;
-  void* yn = base + o_y;
-  void* wt = base + o_w;
-  float* wsq = (float*)(base + o_wsq);
-  float* sp = (float*)(base + o_s);
-  float* dp = (float*)(base + o_d);
-  float* bp = (float*)(base + o_b);
 
-  int rc = dtype == MAUA_BF16   ? launch_nchw_to_nhwc<bf16_t, bf16_t>(st, x, xn, N, Ci, H * W, Cip)
-           : dtype == MAUA_F16 ? launch_nchw_to_nhwc<f16_t, f16_t>(st, x, xn, N, Ci, H * W, Cip)
-                               : launch_nchw_to_nhwc<float, float>(st, x, xn, N, Ci, H * W, Cip);
+  int rc = dispatch_dtype<float, bf16_t, f16_t>(dtype, "maua_modconv2d", [&](auto t) {
+    return launch_nchw_to_nhwc<decltype(t), decltype(t)>(st, x, xn, N, Ci, H * W, Cip);
+  });
   if (rc) return rc;
   if (prenorm) {
-    float* wn = (float*)(base + o_wn);
     if ((rc = launch_f16_prenorm_weights(st, weight, wn, Co, Ci, k * k))) return rc;
     weight = wn;
   }
@@ -110,13 +100,13 @@ extern "C" int maua_modconv2d(maua_ctx* ctx, const void* x, const float* weight,
   a.bias = bp; a.y = yn; a.B = N; a.H = H; a.W = W; a.Ci = Cip; a.Co = Cop; a.up = up;
   a.act = act; a.alpha = alpha; a.gain = gain; a.clamp = clamp;
   if (dma) {  // the hot path's kernel for this shape: styles applied to the input first (there the producer does it)
-    if ((rc = launch_premod_nhwc(st, xn, a.x_bstride, sp, base + o_xm, N, (long)H * W, Cip, dtype))) return rc;
-    a.x = base + o_xm;
+    if ((rc = launch_premod_nhwc(st, xn, a.x_bstride, sp, xm, N, (long)H * W, Cip, dtype))) return rc;
+    a.x = xm;
     if ((rc = launch_modconv_dma(st, a, dtype))) return rc;
   } else if ((rc = launch_modconv3x3(st, dtype, a))) {
     return rc;
   }
-  return dtype == MAUA_BF16   ? launch_nhwc_to_nchw<bf16_t, bf16_t>(st, yn, y, N, Co, Ho * Wo, Cop)
-         : dtype == MAUA_F16 ? launch_nhwc_to_nchw<f16_t, f16_t>(st, yn, y, N, Co, Ho * Wo, Cop)
-                             : launch_nhwc_to_nchw<float, float>(st, yn, y, N, Co, Ho * Wo, Cop);
+  return dispatch_dtype<float, bf16_t, f16_t>(dtype, "maua_modconv2d", [&](auto t) {
+    return launch_nhwc_to_nchw<decltype(t), decltype(t)>(st, yn, y, N, Co, Ho * Wo, Cop);
+  });
 }

@@ -327,10 +327,9 @@ int maua_bias_act(maua_ctx* ctx, const void* x, const float* b, void* y, int N, 
   MAUA_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0, "maua_bias_act: negative size");
   if ((long)N * C * H * W == 0) return MAUA_OK;
   MAUA_REQUIRE(x && y, "maua_bias_act: NULL argument");
-  if (dtype == MAUA_F32) return maua::launch_bias_act<float>(ctx, x, b, y, N, C, H, W, act, alpha, gain, clamp);
-  if (dtype == MAUA_BF16) return maua::launch_bias_act<maua::bf16_t>(ctx, x, b, y, N, C, H, W, act, alpha, gain, clamp);
-  if (dtype == MAUA_F16) return maua::launch_bias_act<maua::f16_t>(ctx, x, b, y, N, C, H, W, act, alpha, gain, clamp);
-  return maua::fail("maua_bias_act: unsupported dtype");
+  return maua::dispatch_dtype<float, maua::bf16_t, maua::f16_t>(dtype, "maua_bias_act", [&](auto t) {
+    return maua::launch_bias_act<decltype(t)>(ctx, x, b, y, N, C, H, W, act, alpha, gain, clamp);
+  });
 }
 
 int maua_add(maua_ctx* ctx, const void* a, const void* b, void* out, long n, int dtype) {
@@ -338,10 +337,8 @@ int maua_add(maua_ctx* ctx, const void* a, const void* b, void* out, long n, int
   MAUA_REQUIRE(n >= 0, "maua_add: negative size");
   if (n == 0) return MAUA_OK;
   MAUA_REQUIRE(a && b && out, "maua_add: NULL argument");
-  if (dtype == MAUA_F32) return maua::launch_add<float>(ctx, a, b, out, n);
-  if (dtype == MAUA_BF16) return maua::launch_add<maua::bf16_t>(ctx, a, b, out, n);
-  if (dtype == MAUA_F16) return maua::launch_add<maua::f16_t>(ctx, a, b, out, n);
-  return maua::fail("maua_add: unsupported dtype");
+  return maua::dispatch_dtype<float, maua::bf16_t, maua::f16_t>(dtype, "maua_add",
+                                                                [&](auto t) { return maua::launch_add<decltype(t)>(ctx, a, b, out, n); });
 }
 
 int maua_upfirdn2d(maua_ctx* ctx, const void* x, const float* f, int fh, int fw, void* y, int N, int C, int H, int W,
@@ -352,13 +349,9 @@ int maua_upfirdn2d(maua_ctx* ctx, const void* x, const float* f, int fh, int fw,
   MAUA_REQUIRE(up >= 1 && down >= 1, "maua_upfirdn2d: up/down must be >= 1");
   MAUA_REQUIRE(fh >= 1 && fw >= 1 && fh <= maua::UF_MAXF && fw <= maua::UF_MAXF, "maua_upfirdn2d: filter size 1..32");
   if (N * C == 0) return MAUA_OK;
-  if (dtype == MAUA_F32)
-    return maua::launch_upfirdn2d<float>(ctx, x, f, fh, fw, y, N, C, H, W, up, down, px0, px1, py0, py1, gain);
-  if (dtype == MAUA_BF16)
-    return maua::launch_upfirdn2d<maua::bf16_t>(ctx, x, f, fh, fw, y, N, C, H, W, up, down, px0, px1, py0, py1, gain);
-  if (dtype == MAUA_F16)
-    return maua::launch_upfirdn2d<maua::f16_t>(ctx, x, f, fh, fw, y, N, C, H, W, up, down, px0, px1, py0, py1, gain);
-  return maua::fail("maua_upfirdn2d: unsupported dtype");
+  return maua::dispatch_dtype<float, maua::bf16_t, maua::f16_t>(dtype, "maua_upfirdn2d", [&](auto t) {
+    return maua::launch_upfirdn2d<decltype(t)>(ctx, x, f, fh, fw, y, N, C, H, W, up, down, px0, px1, py0, py1, gain);
+  });
 }
 
 int maua_pack_rgb8(maua_ctx* ctx, const float* img, uint8_t* out_hwc, int B, int H, int W) {

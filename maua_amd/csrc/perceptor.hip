@@ -849,7 +849,7 @@ int maua_vgg_create(maua_ctx* ctx, int dtype, const int* plan, int n_ops, int re
   MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_vgg_create: dtype must be MAUA_F32 or MAUA_BF16");
   MAUA_REQUIRE(n_ops >= 1 && plan[0] > 0, "maua_vgg_create: the plan starts with a convolution");
   maua_vgg* n = new maua_vgg();
-  n->ctx = ctx; n->dtype = dtype; n->esize = dtype == MAUA_BF16 ? 2 : 4;
+  n->ctx = ctx; n->dtype = dtype; n->esize = elem_bytes(dtype);
   n->pad0 = replicate_first ? 1 : 0; n->in_mul = in_mul; n->in_add = in_add;
   if (const char* e = getenv("MAUA_VGG_NO_DMA")) n->use_dma = !(e[0] == '1');
   for (int i = 0; i < 3; i++) { n->mean[i] = mean[i]; n->istd[i] = 1.f / std3[i]; }
@@ -923,7 +923,7 @@ int maua_vgg_forward(maua_vgg* n, const float* img, int B, int H, int W) {
   MAUA_REQUIRE(n && img, "maua_vgg_forward: NULL argument");
   if (int rc = check_image(n, B, H, W, "maua_vgg_forward")) return rc;
   if (B == 0) return MAUA_OK;
-  return n->dtype == MAUA_BF16 ? forward_t<bf16_t>(n, img, B, H, W) : forward_t<float>(n, img, B, H, W);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_vgg_forward", [&](auto t) { return forward_t<decltype(t)>(n, img, B, H, W); });
 }
 
 // the kept activation of plan entry `op` as planar float32 [B][C][h][w]
@@ -934,9 +934,10 @@ int maua_vgg_features(maua_vgg* n, int op, float* out) {
   hipStream_t st = n->ctx->stream;
   const POp& o = n->ops[op];
   const long hw = (long)(n->H >> o.shift) * (n->W >> o.shift);
-  if (n->dtype == MAUA_BF16) VGG_LAUNCH(features_out_kernel<bf16_t>, (long)n->B * hw * o.C, (const bf16_t*)o.act, out, n->B, hw, o.C);
-  else VGG_LAUNCH(features_out_kernel<float>, (long)n->B * hw * o.C, (const float*)o.act, out, n->B, hw, o.C);
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_vgg_features", [&](auto t) {
+    VGG_LAUNCH(features_out_kernel<decltype(t)>, (long)n->B * hw * o.C, (const decltype(t)*)o.act, out, n->B, hw, o.C);
+    return MAUA_OK;
+  });
 }
 
 // Gram matrices of the kept activation of plan entry `op`: out [B][C][C] float32
@@ -944,7 +945,7 @@ int maua_vgg_gram(maua_vgg* n, int op, float* out) {
   MAUA_REQUIRE(n && out, "maua_vgg_gram: NULL argument");
   MAUA_REQUIRE(n->B > 0, "maua_vgg_gram: call maua_vgg_forward first");
   if (int rc = check_tap(n, op, "maua_vgg_gram")) return rc;
-  return n->dtype == MAUA_BF16 ? gram_t<bf16_t>(n, op, out) : gram_t<float>(n, op, out);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_vgg_gram", [&](auto t) { return gram_t<decltype(t)>(n, op, out); });
 }
 
 // unit-normalised features of the kept activation (what lpips compares): out [B][h * w][C] float32
@@ -955,10 +956,9 @@ int maua_vgg_lpips_features(maua_vgg* n, int op, float* out) {
   hipStream_t st = n->ctx->stream;
   const POp& o = n->ops[op];
   const long n_pix = (long)n->B * (n->H >> o.shift) * (n->W >> o.shift);
-  if (n->dtype == MAUA_BF16)
-    hipLaunchKernelGGL(lpips_norm_kernel<bf16_t>, dim3((unsigned)((n_pix + 3) / 4)), dim3(256), 0, st, (const bf16_t*)o.act, out, n_pix, o.C);
-  else
-    hipLaunchKernelGGL(lpips_norm_kernel<float>, dim3((unsigned)((n_pix + 3) / 4)), dim3(256), 0, st, (const float*)o.act, out, n_pix, o.C);
+  dispatch_dtype<bf16_t, float>(n->dtype, "maua_vgg_lpips_features", [&](auto t) {
+    hipLaunchKernelGGL(lpips_norm_kernel<decltype(t)>, dim3((unsigned)((n_pix + 3) / 4)), dim3(256), 0, st, (const decltype(t)*)o.act, out, n_pix, o.C);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -968,8 +968,9 @@ int maua_vgg_style_grad(maua_vgg* n, const float* img, int B, int H, int W, cons
   MAUA_REQUIRE(n && img && taps && targets && grad && n_taps > 0, "maua_vgg_style_grad: NULL argument");
   if (int rc = check_image(n, B, H, W, "maua_vgg_style_grad")) return rc;
   if (B == 0) return MAUA_OK;
-  return n->dtype == MAUA_BF16 ? style_grad_t<bf16_t>(n, img, B, H, W, taps, n_taps, targets, target_bstride, strength, grad, loss)
-                               : style_grad_t<float>(n, img, B, H, W, taps, n_taps, targets, target_bstride, strength, grad, loss);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_vgg_style_grad", [&](auto t) {
+    return style_grad_t<decltype(t)>(n, img, B, H, W, taps, n_taps, targets, target_bstride, strength, grad, loss);
+  });
 }
 
 int maua_vgg_gram_mean_grad(maua_vgg* n, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
@@ -977,8 +978,8 @@ int maua_vgg_gram_mean_grad(maua_vgg* n, const float* img, int B, int H, int W, 
   MAUA_REQUIRE(n && img && taps && targets && grad && n_taps > 0, "maua_vgg_gram_mean_grad: NULL argument");
   if (int rc = check_image(n, B, H, W, "maua_vgg_gram_mean_grad")) return rc;
   MAUA_REQUIRE(B > 0, "maua_vgg_gram_mean_grad: the mean over an empty batch is undefined (B must be at least 1)");
-  return n->dtype == MAUA_BF16 ? gram_mean_grad_t<bf16_t>(n, img, B, H, W, taps, n_taps, targets, grad, loss)
-                               : gram_mean_grad_t<float>(n, img, B, H, W, taps, n_taps, targets, grad, loss);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_vgg_gram_mean_grad",
+                                       [&](auto t) { return gram_mean_grad_t<decltype(t)>(n, img, B, H, W, taps, n_taps, targets, grad, loss); });
 }
 
 int maua_vgg_lpips_grad(maua_vgg* n, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
@@ -986,8 +987,9 @@ int maua_vgg_lpips_grad(maua_vgg* n, const float* img, int B, int H, int W, cons
   MAUA_REQUIRE(n && img && taps && targets && lins && grad && n_taps > 0, "maua_vgg_lpips_grad: NULL argument");
   if (int rc = check_image(n, B, H, W, "maua_vgg_lpips_grad")) return rc;
   if (B == 0) return MAUA_OK;
-  return n->dtype == MAUA_BF16 ? lpips_grad_t<bf16_t>(n, img, B, H, W, taps, n_taps, targets, target_bstride, lins, scale, grad, dist)
-                               : lpips_grad_t<float>(n, img, B, H, W, taps, n_taps, targets, target_bstride, lins, scale, grad, dist);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_vgg_lpips_grad", [&](auto t) {
+    return lpips_grad_t<decltype(t)>(n, img, B, H, W, taps, n_taps, targets, target_bstride, lins, scale, grad, dist);
+  });
 }
 
 }  // extern "C"

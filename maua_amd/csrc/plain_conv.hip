@@ -22,7 +22,7 @@ int DevTemp::stage(const float* src, size_t count, hipMemcpyKind kind) {
 
 int load_weight(hipStream_t st, int dtype, const float* host, int Co, int Ci, int k, int Cop, int Cip, void* wt, void* wt_t, bool split) {
   const size_t count = (size_t)Co * Ci * k * k;
-  const size_t elems = prepped_weight_elems(k, 1, Cop, Cip), bytes = elems * (dtype == MAUA_F32 ? 4 : 2);
+  const size_t elems = prepped_weight_elems(k, 1, Cop, Cip), bytes = elems * elem_bytes(dtype);
   DevTemp w, w_t;
   if (int rc = w.stage(host, count)) return rc;
   auto prep = [&]() -> int {

@@ -110,20 +110,13 @@ int launch_resize2d(hipStream_t stream, int dtype, bool nhwc, const ResizeArgs& 
     MAUA_REQUIRE(a.pl < a.W && a.ow - a.W - a.pl < a.W && a.pt < a.H && a.oh - a.H - a.pt < a.H,
                  "resize2d: reflect padding must be smaller than the input (as torch)");
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (dtype == MAUA_F32) {
-    if (nhwc) hipLaunchKernelGGL((resize2d_kernel<float, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((resize2d_kernel<float, false>), grid, dim3(256), 0, stream, a);
-  } else if (dtype == MAUA_BF16) {
-    if (nhwc) hipLaunchKernelGGL((resize2d_kernel<bf16_t, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((resize2d_kernel<bf16_t, false>), grid, dim3(256), 0, stream, a);
-  } else if (dtype == MAUA_F16) {
-    if (nhwc) hipLaunchKernelGGL((resize2d_kernel<f16_t, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((resize2d_kernel<f16_t, false>), grid, dim3(256), 0, stream, a);
-  } else {
-    return fail("resize2d: unsupported dtype");
-  }
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<float, bf16_t, f16_t>(dtype, "resize2d", [&](auto t) {
+    using T = decltype(t);
+    if (nhwc) hipLaunchKernelGGL((resize2d_kernel<T, true>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((resize2d_kernel<T, false>), grid, dim3(256), 0, stream, a);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 // depthwise 1-D correlation along H (axis 0) or W (axis 1) of planar f32 [planes][H][W] with reflect padding: the
@@ -268,16 +261,12 @@ int launch_warp_affine_nhwc(hipStream_t stream, int dtype, const void* x, void* 
   const long total = (long)B * H * W * C;
   if (total == 0) return MAUA_OK;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(warp_affine_nhwc_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, (float*)y, minv, H, W, C, total);
-  else if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(warp_affine_nhwc_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, minv, H, W, C, total);
-  else if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(warp_affine_nhwc_kernel<f16_t>, grid, dim3(256), 0, stream, (const f16_t*)x, (f16_t*)y, minv, H, W, C, total);
-  else
-    return fail("warp_affine: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<float, bf16_t, f16_t>(dtype, "warp_affine", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(warp_affine_nhwc_kernel<T>, grid, dim3(256), 0, stream, (const T*)x, (T*)y, minv, H, W, C, total);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 // img = upsample2d(prev) + y (stylegan2.py:372-378 with ops.py:117-133), planar f32 [B][3][H][W], prev [B][3][H/2][W/2]
@@ -362,8 +351,8 @@ int maua_resize2d_bicubic_vjp(maua_ctx* ctx, const float* gy, float* gx, int N, 
   const long planes = (long)N * C;
   if (planes * H * W == 0) return MAUA_OK;
   MAUA_REQUIRE(gy && gx && out_h > 0 && out_w > 0, "maua_resize2d_bicubic_vjp: bad argument");
-  if (int rc = scratch_reserve(ctx, (size_t)planes * out_h * W * 4)) return rc;
-  float* tmp = (float*)ctx->scratch;
+  float* tmp;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { tmp = s.take<float>((size_t)planes * out_h * W); })) return rc;
   const long t1 = planes * out_h * W, t2 = planes * H * W;
   hipLaunchKernelGGL(bicubic_axis_vjp_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, ctx->stream, gy, tmp, out_h, out_w, W, 1,
                      align_corners, t1);

@@ -442,9 +442,9 @@ int maua_mse_guide_grad(maua_ctx* ctx, const float* img, const float* target, lo
   MAUA_REQUIRE(ctx, "maua_mse_guide_grad: ctx is NULL");
   if (B == 0 || row == 0) return MAUA_OK;
   MAUA_REQUIRE(img && target && out, "maua_mse_guide_grad: NULL argument");
-  if (int rc = scratch_reserve(ctx, 256 + (size_t)B * 4)) return rc;
-  int* flag = reinterpret_cast<int*>(ctx->scratch);
-  float* kd = reinterpret_cast<float*>(reinterpret_cast<char*>(ctx->scratch) + 256);
+  int* flag;
+  float* kd;
+  if (int rc = carve_scratch(ctx, [&](Scratch& s) { flag = s.take<int>(1); kd = s.take<float>(B); })) return rc;
   std::vector<float> hk((size_t)B, k);
   MAUA_HIP_CHECK(hipMemcpyAsync(kd, hk.data(), (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
   MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // (hk lives on this call's stack)

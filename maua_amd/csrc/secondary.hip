@@ -500,7 +500,7 @@ int maua_secondary_create(maua_ctx* ctx, int dtype, maua_secondary** out) {
   static std::atomic<unsigned long long> next_uid{1};
   n->uid = next_uid.fetch_add(1);
   // MAUA_F32_SPLIT: float32 tensors everywhere (dtype below), only the convolutions' products differ (conv_dtype)
-  n->ctx = ctx; n->conv_dtype = dtype; n->dtype = dtype == MAUA_F32_SPLIT ? MAUA_F32 : dtype; n->esize = n->dtype == MAUA_BF16 ? 2 : 4;
+  n->ctx = ctx; n->conv_dtype = dtype; n->dtype = dtype == MAUA_F32_SPLIT ? MAUA_F32 : dtype; n->esize = elem_bytes(n->dtype);
   int ci[NCONV], co[NCONV];
   conv_plan(ci, co);
   for (int i = 0; i < NCONV; i++)
@@ -562,14 +562,14 @@ int maua_secondary_forward(maua_secondary* n, const float* x, const float* t, in
   MAUA_REQUIRE(n && x && t, "maua_secondary_forward: NULL argument");
   MAUA_REQUIRE(B >= 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0, "maua_secondary_forward: H and W must be positive multiples of 32");
   if (B == 0) return MAUA_OK;
-  return n->dtype == MAUA_BF16 ? forward_t<bf16_t>(n, x, t, B, H, W, v_out, pred_out, eps_out)
-                               : forward_t<float>(n, x, t, B, H, W, v_out, pred_out, eps_out);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_secondary_forward",
+                                       [&](auto e) { return forward_t<decltype(e)>(n, x, t, B, H, W, v_out, pred_out, eps_out); });
 }
 
 int maua_secondary_vjp(maua_secondary* n, const float* g_v, int B, int H, int W, float* g_x) {
   MAUA_REQUIRE(n && g_v && g_x, "maua_secondary_vjp: NULL argument");
   MAUA_REQUIRE(n->B > 0 && B == n->B && H == n->H && W == n->W, "maua_secondary_vjp: call maua_secondary_forward with the same shape first");
-  return n->dtype == MAUA_BF16 ? vjp_t<bf16_t>(n, g_v, g_x) : vjp_t<float>(n, g_v, g_x);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_secondary_vjp", [&](auto e) { return vjp_t<decltype(e)>(n, g_v, g_x); });
 }
 
 }  // extern "C"

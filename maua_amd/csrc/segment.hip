@@ -318,20 +318,17 @@ int maua_beat_dp(maua_ctx* ctx, const float* onset_norm, int T, int period, doub
     const double l = std::log(-(double)(-2 * period + j) / period);
     txwt[j] = -tightness * (l * l);
   }
-  size_t off = 0;
-  auto carve = [&](size_t b) { size_t o = off; off += (b + 255) & ~(size_t)255; return o; };
-  const size_t og = carve(gw.size() * 8), ot = carve(txwt.size() * 8), om = carve(8);
-  if (int rc = scratch_reserve(ctx, off)) return rc;
-  char* base = (char*)ctx->scratch;
+  double *dg, *dt, *dm;
+  if (int rc = carve_scratch(ctx, [&](Scratch& sc) { dg = sc.take<double>(gw.size()); dt = sc.take<double>(txwt.size()); dm = sc.take<double>(1); }))
+    return rc;
   hipStream_t s = ctx->stream;
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + og, gw.data(), gw.size() * 8, hipMemcpyHostToDevice, s));
-  MAUA_HIP_CHECK(hipMemcpyAsync(base + ot, txwt.data(), txwt.size() * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(dg, gw.data(), gw.size() * 8, hipMemcpyHostToDevice, s));
+  MAUA_HIP_CHECK(hipMemcpyAsync(dt, txwt.data(), txwt.size() * 8, hipMemcpyHostToDevice, s));
   MAUA_HIP_CHECK(hipStreamSynchronize(s));   // the host tables go out of scope
-  hipLaunchKernelGGL(beat_localscore_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, onset_norm, (const double*)(base + og), T,
-                     period, localscore);
-  hipLaunchKernelGGL(max_f64_kernel, dim3(1), dim3(256), 0, s, localscore, T, (double*)(base + om));
-  hipLaunchKernelGGL(beat_dp_kernel, dim3(1), dim3(64), 0, s, localscore, (const double*)(base + ot),
-                     (const double*)(base + om), T, period, wlen, cumscore, backlink);
+  hipLaunchKernelGGL(beat_localscore_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, onset_norm, (const double*)dg, T, period, localscore);
+  hipLaunchKernelGGL(max_f64_kernel, dim3(1), dim3(256), 0, s, localscore, T, dm);
+  hipLaunchKernelGGL(beat_dp_kernel, dim3(1), dim3(64), 0, s, localscore, (const double*)dt, (const double*)dm, T, period, wlen, cumscore,
+                     backlink);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -354,19 +351,15 @@ int maua_recurrence_affinity(maua_ctx* ctx, const float* data, int n, int d, int
   MAUA_REQUIRE(data && rec, "maua_recurrence_affinity: NULL argument");
   MAUA_REQUIRE(k >= 1 && k <= n, "maua_recurrence_affinity: k must be in [1, n]");
   MAUA_REQUIRE(n <= 16384, "maua_recurrence_affinity: too many beats");
-  size_t off = 0;
-  auto carve = [&](size_t b) { size_t o = off; off += (b + 255) & ~(size_t)255; return o; };
-  const size_t oraw = carve((size_t)n * n * 4), omax = carve((size_t)n * 4), obw = carve(4);
-  if (int rc = scratch_reserve(ctx, off)) return rc;
-  char* base = (char*)ctx->scratch;
+  float *raw, *rowmax, *bw;
+  if (int rc = carve_scratch(ctx, [&](Scratch& sc) { raw = sc.take<float>((size_t)n * n); rowmax = sc.take<float>(n); bw = sc.take<float>(1); }))
+    return rc;
   hipStream_t s = ctx->stream;
-  hipLaunchKernelGGL(recurrence_topk_kernel, dim3(n), dim3(256), (size_t)n * 4, s, data, n, d, k, width, (float*)(base + oraw));
-  hipLaunchKernelGGL(recurrence_sym_kernel, dim3(n), dim3(256), 0, s, (const float*)(base + oraw), n, rec,
-                     (float*)(base + omax));
-  hipLaunchKernelGGL(lower_median_kernel, dim3(1), dim3(256), 0, s, (const float*)(base + omax), n, 1, (float*)(base + obw));
+  hipLaunchKernelGGL(recurrence_topk_kernel, dim3(n), dim3(256), (size_t)n * 4, s, data, n, d, k, width, raw);
+  hipLaunchKernelGGL(recurrence_sym_kernel, dim3(n), dim3(256), 0, s, (const float*)raw, n, rec, rowmax);
+  hipLaunchKernelGGL(lower_median_kernel, dim3(1), dim3(256), 0, s, (const float*)rowmax, n, 1, bw);
   const long n2 = (long)n * n;
-  hipLaunchKernelGGL(recurrence_affinity_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, rec, n2,
-                     (const float*)(base + obw));
+  hipLaunchKernelGGL(recurrence_affinity_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, rec, n2, (const float*)bw);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }

@@ -162,7 +162,7 @@ int maua_rrdb_create(maua_ctx* ctx, int num_feat, int num_block, int num_grow_ch
                  "maua_rrdb_create: num_feat + k * num_grow_ch padded to 64 exceeds the dense-block width (use 64 / 32)");
   maua_rrdbnet* n = new maua_rrdbnet();
   n->ctx = ctx; n->num_feat = num_feat; n->num_block = num_block; n->grow = num_grow_ch; n->dtype = dtype;
-  n->esize = dtype == MAUA_BF16 ? 2 : 4;
+  n->esize = elem_bytes(dtype);
   if (const char* e = getenv("MAUA_RRDB_DMA")) n->use_dma = atoi(e);
   int rc = alloc_conv(n->conv_first, 3, num_feat, n->esize);
   n->rdb.resize((size_t)num_block * 15);
@@ -365,8 +365,8 @@ extern "C" int maua_rrdb_enhance_u8(maua_rrdbnet* n, const uint8_t* frames, int 
   MAUA_REQUIRE(B >= 0 && h > 0 && w > 0 && pre_pad >= 0 && pre_pad < h && pre_pad < w, "maua_rrdb_enhance_u8: bad shape (reflect padding needs pre_pad < h, w)");
   if (B == 0) return MAUA_OK;
   const int H = h + pre_pad, W = w + pre_pad;
-  return n->dtype == MAUA_BF16 ? forward_t<bf16_t>(n, nullptr, B, H, W, 1, nullptr, out_rgb8, frames, h, w)
-                               : forward_t<float>(n, nullptr, B, H, W, 1, nullptr, out_rgb8, frames, h, w);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_rrdb_enhance_u8",
+                                       [&](auto t) { return forward_t<decltype(t)>(n, nullptr, B, H, W, 1, nullptr, out_rgb8, frames, h, w); });
 }
 
 extern "C" int maua_rrdb_forward_ex(maua_rrdbnet* n, const float* img_nchw, int B, int H, int W, int clamp01, float* out_nchw,
@@ -375,8 +375,8 @@ extern "C" int maua_rrdb_forward_ex(maua_rrdbnet* n, const float* img_nchw, int 
   MAUA_REQUIRE(out_nchw || out_rgb8, "maua_rrdb_forward: no output buffer");
   MAUA_REQUIRE(B >= 0 && H > 0 && W > 0, "maua_rrdb_forward: bad shape");
   if (B == 0) return MAUA_OK;
-  return n->dtype == MAUA_BF16 ? forward_t<bf16_t>(n, img_nchw, B, H, W, clamp01, out_nchw, out_rgb8)
-                               : forward_t<float>(n, img_nchw, B, H, W, clamp01, out_nchw, out_rgb8);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_rrdb_forward",
+                                       [&](auto t) { return forward_t<decltype(t)>(n, img_nchw, B, H, W, clamp01, out_nchw, out_rgb8); });
 }
 extern "C" int maua_rrdb_forward(maua_rrdbnet* n, const float* img_nchw, int B, int H, int W, float* out_nchw,
                                  uint8_t* out_rgb8) {
@@ -439,7 +439,7 @@ int maua_srvgg_create(maua_ctx* ctx, int num_feat, int num_conv, int upscale, in
   MAUA_REQUIRE(act_type >= 0 && act_type <= 2, "maua_srvgg_create: act_type 0 prelu / 1 relu / 2 leakyrelu");
   maua_srvgg* n = new maua_srvgg();
   n->ctx = ctx; n->num_feat = num_feat; n->num_conv = num_conv; n->upscale = upscale; n->dtype = dtype; n->act = act_type;
-  n->esize = dtype == MAUA_BF16 ? 2 : 4;
+  n->esize = elem_bytes(dtype);
   n->convs.resize((size_t)num_conv + 2);
   int rc = alloc_conv(n->convs[0], 3, num_feat, n->esize);
   for (int i = 1; i <= num_conv && !rc; i++) rc = alloc_conv(n->convs[i], num_feat, num_feat, n->esize);
@@ -548,6 +548,6 @@ extern "C" int maua_srvgg_forward(maua_srvgg* n, const float* img_nchw, int B, i
   MAUA_REQUIRE(out_nchw || out_rgb8, "maua_srvgg_forward: no output buffer");
   MAUA_REQUIRE(B >= 0 && H > 0 && W > 0, "maua_srvgg_forward: bad shape");
   if (B == 0) return MAUA_OK;
-  return n->dtype == MAUA_BF16 ? srvgg_forward_t<bf16_t>(n, img_nchw, B, H, W, clamp01, out_nchw, out_rgb8)
-                               : srvgg_forward_t<float>(n, img_nchw, B, H, W, clamp01, out_nchw, out_rgb8);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_srvgg_forward",
+                                       [&](auto t) { return srvgg_forward_t<decltype(t)>(n, img_nchw, B, H, W, clamp01, out_nchw, out_rgb8); });
 }

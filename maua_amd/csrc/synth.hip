@@ -325,11 +325,11 @@ int maua_synth_create(maua_ctx* ctx, int img_resolution, int w_dim, int channel_
   MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16 || dtype == MAUA_F16,
                "maua_synth_create: dtype must be MAUA_F32, MAUA_BF16 or MAUA_F16");
   MAUA_REQUIRE(w_dim > 0 && w_dim <= 4096, "maua_synth_create: bad w_dim");
-  const int kc = dtype == MAUA_F32 ? 16 : 32;
+  const int kc = elems_per_chunk(dtype, 64);
   maua_synth* n = new maua_synth();
   n->ctx = ctx; n->res = img_resolution; n->w_dim = w_dim; n->channel_base = channel_base;
   n->channel_max = channel_max; n->dtype = dtype; n->nv_compat = nv_compat;
-  n->esize = dtype == MAUA_F32 ? 4 : 2;
+  n->esize = elem_bytes(dtype);
   int nb = 0;
   for (int r = 4; r <= img_resolution; r *= 2) nb++;
   n->nblocks = nb;
@@ -550,9 +550,8 @@ int maua_synth_load(maua_synth* n, const char* name, const float* host, size_t c
     if (count != (size_t)C * 16) return fail("maua_synth_load: bs.0.const: wrong size");
     DevTemp tmp;
     if (int rc = tmp.stage(host, count, g_load_kind)) return rc;
-    int rc = n->dtype == MAUA_BF16   ? launch_nchw_to_nhwc<float, bf16_t>(st, tmp.p, n->const_x, 1, C, 16, C)
-             : n->dtype == MAUA_F16 ? launch_nchw_to_nhwc<float, f16_t>(st, tmp.p, n->const_x, 1, C, 16, C)
-                                    : launch_nchw_to_nhwc<float, float>(st, tmp.p, n->const_x, 1, C, 16, C);
+    int rc = dispatch_dtype<bf16_t, f16_t, float>(n->dtype, "maua_synth_load",
+                                                  [&](auto t) { return launch_nchw_to_nhwc<float, decltype(t)>(st, tmp.p, n->const_x, 1, C, 16, C); });
     hipStreamSynchronize(st);
     return rc;
   }
@@ -886,9 +885,9 @@ int maua_synth_get_feature(maua_synth* n, int layer, int B, float* out_nchw) {
   MAUA_REQUIRE(B <= n->bcap, "maua_synth_get_feature: batch larger than the last forward");
   ConvLayer& c = n->convs[layer];
   hipStream_t st = n->ctx->stream;
-  if (n->dtype == MAUA_BF16) return launch_nhwc_to_nchw<bf16_t, float>(st, c.feat, out_nchw, B, c.Co, c.fh * c.fw, c.Co);
-  if (n->dtype == MAUA_F16) return launch_nhwc_to_nchw<f16_t, float>(st, c.feat, out_nchw, B, c.Co, c.fh * c.fw, c.Co);
-  return launch_nhwc_to_nchw<float, float>(st, c.feat, out_nchw, B, c.Co, c.fh * c.fw, c.Co);
+  return dispatch_dtype<bf16_t, f16_t, float>(n->dtype, "maua_synth_get_feature", [&](auto t) {
+    return launch_nhwc_to_nchw<decltype(t), float>(st, c.feat, out_nchw, B, c.Co, c.fh * c.fw, c.Co);
+  });
 }
 
 }  // extern "C"

@@ -155,7 +155,8 @@ __global__ __launch_bounds__(256) void torgb_mfma_kernel(RgbArgs a) {
 
 int launch_torgb(hipStream_t stream, int dtype, const RgbArgs& a) {
   if (a.B == 0) return MAUA_OK;
-  const int epc = dtype == MAUA_F32 ? 4 : 8;
+  const int epc = elems_per_piece(dtype);
+  MAUA_REQUIRE(epc, "torgb: unsupported dtype");
   MAUA_REQUIRE(a.C % epc == 0, "torgb: C must be a multiple of the 16-byte piece");
   // (C = 512 layers are <= 64^2: the fragment set-up of 32 k-steps costs more than it saves there)
   if (dtype == MAUA_BF16 && (a.C == 32 || a.C == 64 || a.C == 128 || a.C == 256) && ((uintptr_t)a.wmod % 16) == 0) {
@@ -177,16 +178,11 @@ int launch_torgb(hipStream_t stream, int dtype, const RgbArgs& a) {
   int ppb = 256 >> lp_log2;
   int gx = (int)std::min<long>((HW + ppb - 1) / ppb, 2048);
   size_t smem = (size_t)3 * a.C * sizeof(float);
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(torgb_kernel<bf16_t>, dim3(gx, a.B), dim3(256), smem, stream, a, lp_log2);
-  else if (dtype == MAUA_F16)
-    hipLaunchKernelGGL(torgb_kernel<f16_t>, dim3(gx, a.B), dim3(256), smem, stream, a, lp_log2);
-  else if (dtype == MAUA_F32)
-    hipLaunchKernelGGL(torgb_kernel<float>, dim3(gx, a.B), dim3(256), smem, stream, a, lp_log2);
-  else
-    return fail("torgb: unsupported dtype");
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, f16_t, float>(dtype, "torgb", [&](auto t) {
+    hipLaunchKernelGGL(torgb_kernel<decltype(t)>, dim3(gx, a.B), dim3(256), smem, stream, a, lp_log2);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 }  // namespace maua

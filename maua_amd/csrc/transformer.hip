@@ -143,31 +143,32 @@ __global__ __launch_bounds__(256) void quick_gelu_vjp_kernel(const T* __restrict
 // the one place the element type of each of these kernels is chosen
 void launch_layer_norm(hipStream_t st, int dtype, const void* x, const float* g, const float* b, void* y, float* stats, long rows, int C) {
   const dim3 grid((unsigned)((rows + 3) / 4));
-  if (dtype == MAUA_BF16) hipLaunchKernelGGL(layer_norm_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, g, b, (bf16_t*)y, stats, rows, C);
-  else hipLaunchKernelGGL(layer_norm_kernel<float>, grid, dim3(256), 0, st, (const float*)x, g, b, (float*)y, stats, rows, C);
+  dispatch_dtype<bf16_t, float>(dtype, "layer_norm", [&](auto t) {
+    hipLaunchKernelGGL(layer_norm_kernel<decltype(t)>, grid, dim3(256), 0, st, (const decltype(t)*)x, g, b, (decltype(t)*)y, stats, rows, C);
+  });
 }
 void launch_layer_norm_vjp(hipStream_t st, int dtype, const void* x, const float* stats, const float* g, const void* dy, const void* add,
                            void* dx, long rows, int C, int drop_T) {
   const dim3 grid((unsigned)((rows + 3) / 4));
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(layer_norm_vjp_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, stats, g, (const bf16_t*)dy, (const bf16_t*)add,
-                       (bf16_t*)dx, rows, C, drop_T);
-  else
-    hipLaunchKernelGGL(layer_norm_vjp_kernel<float>, grid, dim3(256), 0, st, (const float*)x, stats, g, (const float*)dy, (const float*)add,
-                       (float*)dx, rows, C, drop_T);
+  dispatch_dtype<bf16_t, float>(dtype, "layer_norm_vjp", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(layer_norm_vjp_kernel<T>, grid, dim3(256), 0, st, (const T*)x, stats, g, (const T*)dy, (const T*)add, (T*)dx, rows, C, drop_T);
+  });
 }
 void launch_quick_gelu(hipStream_t st, int dtype, const void* h, void* a, long count) {
-  const long pieces = count / (dtype == MAUA_BF16 ? 8 : 4);
+  const long pieces = count / elems_per_piece(dtype);
   const dim3 grid((unsigned)((pieces + 255) / 256));
-  if (dtype == MAUA_BF16) hipLaunchKernelGGL(quick_gelu_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)h, (bf16_t*)a, pieces);
-  else hipLaunchKernelGGL(quick_gelu_kernel<float>, grid, dim3(256), 0, st, (const float*)h, (float*)a, pieces);
+  dispatch_dtype<bf16_t, float>(dtype, "quick_gelu", [&](auto t) {
+    hipLaunchKernelGGL(quick_gelu_kernel<decltype(t)>, grid, dim3(256), 0, st, (const decltype(t)*)h, (decltype(t)*)a, pieces);
+  });
 }
 void launch_quick_gelu_vjp(hipStream_t st, int dtype, const void* h, const void* da, void* dh, long count) {
-  const long pieces = count / (dtype == MAUA_BF16 ? 8 : 4);
+  const long pieces = count / elems_per_piece(dtype);
   const dim3 grid((unsigned)((pieces + 255) / 256));
-  if (dtype == MAUA_BF16)
-    hipLaunchKernelGGL(quick_gelu_vjp_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)h, (const bf16_t*)da, (bf16_t*)dh, pieces);
-  else hipLaunchKernelGGL(quick_gelu_vjp_kernel<float>, grid, dim3(256), 0, st, (const float*)h, (const float*)da, (float*)dh, pieces);
+  dispatch_dtype<bf16_t, float>(dtype, "quick_gelu_vjp", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(quick_gelu_vjp_kernel<T>, grid, dim3(256), 0, st, (const T*)h, (const T*)da, (T*)dh, pieces);
+  });
 }
 
 int block_gemm(const BlockRun& r, const void* a, long M, int K, const void* w, int N, const float* bias, const void* res, void* c, int epi,
@@ -336,7 +337,7 @@ extern "C" {
 int maua_layer_norm(maua_ctx* ctx, const void* x, const float* gamma, const float* beta, long rows, int C, int dtype, void* y, float* stats) {
   MAUA_REQUIRE(ctx && x && gamma && beta && y, "maua_layer_norm: NULL argument");
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "maua_layer_norm: f32 / bf16");
-  const int epc = dtype == MAUA_BF16 ? 8 : 4;
+  const int epc = elems_per_piece(dtype);
   MAUA_REQUIRE(C % epc == 0 && C / epc <= 64 * LN_MAXP, "maua_layer_norm: C must be a multiple of 16 bytes and at most 4096 (bf16) / 2048 (f32)");
   if (rows == 0) return MAUA_OK;
   launch_layer_norm(ctx->stream, dtype, x, gamma, beta, y, stats, rows, C);
@@ -347,7 +348,7 @@ int maua_layer_norm_vjp(maua_ctx* ctx, const void* x, const float* stats, const 
                         int dtype, void* dx) {
   MAUA_REQUIRE(ctx && x && stats && gamma && dy && dx, "maua_layer_norm_vjp: NULL argument");
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F32, "maua_layer_norm_vjp: f32 / bf16");
-  const int epc = dtype == MAUA_BF16 ? 8 : 4;
+  const int epc = elems_per_piece(dtype);
   MAUA_REQUIRE(C % epc == 0 && C / epc <= 64 * LN_MAXP, "maua_layer_norm_vjp: C must be a multiple of 16 bytes and at most 4096 (bf16) / 2048 (f32)");
   if (rows == 0) return MAUA_OK;
   launch_layer_norm_vjp(ctx->stream, dtype, x, stats, gamma, dy, add, dx, rows, C, 0);

@@ -710,11 +710,11 @@ int run_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels) {
 
 // ---- what sampler.hip uses of the network (unet_internal.h)
 int maua::unet_forward(maua_unet* n, const float* x, const float* t, int B, int H, int W, float* out, bool keep) {
-  return n->dtype == MAUA_BF16 ? run_forward<bf16_t>(n, x, t, B, H, W, out, keep) : run_forward<float>(n, x, t, B, H, W, out, keep);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_unet", [&](auto e) { return run_forward<decltype(e)>(n, x, t, B, H, W, out, keep); });
 }
 
 int maua::unet_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels) {
-  return n->dtype == MAUA_BF16 ? run_vjp<bf16_t>(n, g_out, g_x, g_channels) : run_vjp<float>(n, g_out, g_x, g_channels);
+  return dispatch_dtype<bf16_t, float>(n->dtype, "maua_unet", [&](auto e) { return run_vjp<decltype(e)>(n, g_out, g_x, g_channels); });
 }
 
 int maua::unet_emb_rows(maua_unet* n, hipStream_t st, const float* t, int rows, float* e0, float* e1, float* e2, float* emb) {
@@ -749,7 +749,7 @@ int maua_unet_create(maua_ctx* ctx, int image_size, int in_channels, int model_c
   }
   maua_unet* n = new maua_unet();
   n->ctx = ctx; n->image_size = image_size; n->in_ch = in_channels; n->mc = model_channels; n->out_ch = out_channels;
-  n->nrb = num_res_blocks; n->head_ch = num_head_channels; n->dtype = dtype; n->esize = dtype == MAUA_BF16 ? 2 : 4;
+  n->nrb = num_res_blocks; n->head_ch = num_head_channels; n->dtype = dtype; n->esize = elem_bytes(dtype);
   n->mult.assign(channel_mult, channel_mult + n_mult);
   n->attn_ds.assign(attention_ds, attention_ds + n_attn);
   n->emb_dim = 4 * model_channels;

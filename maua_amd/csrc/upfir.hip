@@ -161,14 +161,14 @@ __global__ __launch_bounds__(256) void upfir_epilogue_kernel(UpfirArgs a) {
 int upfir_check(int dtype, const UpfirArgs& a) {
   if (a.B == 0) return MAUA_OK;
   MAUA_REQUIRE(dtype == MAUA_BF16 || dtype == MAUA_F16 || dtype == MAUA_F32, "upfir_epilogue: unsupported dtype");
-  const int epc = dtype == MAUA_F32 ? 4 : 8;
+  const int epc = elems_per_piece(dtype);
   MAUA_REQUIRE(a.Co % epc == 0, "upfir_epilogue: Co must be a multiple of the 16-byte piece");
   MAUA_REQUIRE(!a.out_scale || ((uintptr_t)a.out_scale % 16) == 0, "upfir_epilogue: out_scale must be 16-byte aligned");
   MAUA_REQUIRE((!a.d || ((uintptr_t)a.d % 16) == 0) && (!a.bias || ((uintptr_t)a.bias % 16) == 0),
                "upfir_epilogue: d and bias must be 16-byte aligned");
   MAUA_REQUIRE(!a.noise || (((uintptr_t)a.noise % 8) == 0 && a.noise_bstride % 2 == 0),
                "upfir_epilogue: noise must be 8-byte aligned");
-  MAUA_REQUIRE((long)(2 * a.H + 1) * (2 * a.W + 1) * a.Co * (dtype == MAUA_F32 ? 4 : 2) < (1L << 31),
+  MAUA_REQUIRE((long)(2 * a.H + 1) * (2 * a.W + 1) * a.Co * elem_bytes(dtype) < (1L << 31),
                "upfir_epilogue: a sample of t must stay below 2 GiB (32-bit offsets)");
   MAUA_REQUIRE(a.B <= 65535, "upfir_epilogue: grid too large");
   return MAUA_OK;
@@ -177,24 +177,17 @@ int upfir_check(int dtype, const UpfirArgs& a) {
 int launch_upfir_epilogue(hipStream_t stream, int dtype, const UpfirArgs& a) {
   if (int rc = upfir_check(dtype, a)) return rc;
   if (a.B == 0) return MAUA_OK;
-  const int epc = dtype == MAUA_F32 ? 4 : 8;
+  const int epc = elems_per_piece(dtype);
   const long total = (long)((2 * a.H + UPFIR_ROWS - 1) / UPFIR_ROWS) * a.W * (a.Co / epc);
   const dim3 grid((unsigned)((total + 255) / 256), a.B);
   const bool lr = a.act == MAUA_ACT_LRELU && a.alpha >= 0.f && a.alpha <= 1.f && a.gain > 0.f;  // folded-gain fast path
-  if (dtype == MAUA_BF16) {
-    if (lr) hipLaunchKernelGGL((upfir_epilogue_kernel<bf16_t, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((upfir_epilogue_kernel<bf16_t, false>), grid, dim3(256), 0, stream, a);
-  } else if (dtype == MAUA_F16) {
-    if (lr) hipLaunchKernelGGL((upfir_epilogue_kernel<f16_t, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((upfir_epilogue_kernel<f16_t, false>), grid, dim3(256), 0, stream, a);
-  } else if (dtype == MAUA_F32) {
-    if (lr) hipLaunchKernelGGL((upfir_epilogue_kernel<float, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((upfir_epilogue_kernel<float, false>), grid, dim3(256), 0, stream, a);
-  } else {
-    return fail("upfir_epilogue: unsupported dtype");
-  }
-  MAUA_HIP_CHECK(hipGetLastError());
-  return MAUA_OK;
+  return dispatch_dtype<bf16_t, f16_t, float>(dtype, "upfir_epilogue", [&](auto t) {
+    using T = decltype(t);
+    if (lr) hipLaunchKernelGGL((upfir_epilogue_kernel<T, true>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((upfir_epilogue_kernel<T, false>), grid, dim3(256), 0, stream, a);
+    MAUA_HIP_CHECK(hipGetLastError());
+    return MAUA_OK;
+  });
 }
 
 }  // namespace maua

@@ -321,7 +321,6 @@ __global__ __launch_bounds__(256) void vf_hist_kernel(const int* counts, int bin
   }
 }
 
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // every refusal of a push, in front of the first launch
 int vfeat_check(int H, int W, int bins, int max_batch, const void* frames, int layout, int B, const float* hist, const float* variance,
@@ -375,24 +374,22 @@ int maua_vfeat_create(maua_ctx* ctx, int H, int W, int bins, int max_batch, maua
   if (vfeat_check(H, W, bins, max_batch, nullptr, MAUA_VFEAT_U8_HWC, 0, nullptr, nullptr, nullptr) != MAUA_OK) return MAUA_ERR;
   const long P = (long)H * W;
   const int nblk = (int)((P + VF_SPAN - 1) / VF_SPAN);
-  const size_t b_mm = align256((size_t)max_batch * nblk * 12 * sizeof(float));
-  const size_t b_sum = align256((size_t)max_batch * nblk * 3 * sizeof(unsigned long long));
-  const size_t b_fr = align256((size_t)max_batch * 12 * sizeof(float));
-  const size_t b_cnt = align256((size_t)max_batch * 6 * bins * sizeof(int));
-  const size_t b_carry = align256((size_t)P * 3 * sizeof(float));
   auto* h = new maua_vfeat{ctx->device, H, W, bins, max_batch, nblk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1};
+  auto layout = [&](Scratch& s) {
+    h->part_mm = s.take<float>((size_t)max_batch * nblk * 12);
+    h->part_sum = s.take<unsigned long long>((size_t)max_batch * nblk * 3);
+    h->mm = s.take<float>((size_t)max_batch * 12);
+    h->counts = s.take<int>((size_t)max_batch * 6 * bins);
+    h->carry = s.take<char>((size_t)P * 3 * sizeof(float));
+  };
   MAUA_HIP_CHECK(hipSetDevice(ctx->device));
-  const hipError_t e = hipMalloc((void**)&h->ws, b_mm + b_sum + b_fr + b_cnt + b_carry);
+  const hipError_t e = hipMalloc((void**)&h->ws, scratch_bytes(layout));
   if (e != hipSuccess) {
     delete h;
     return fail(std::string("maua_vfeat_create: ") + hipGetErrorString(e));
   }
-  char* p = h->ws;
-  h->part_mm = (float*)p;               p += b_mm;
-  h->part_sum = (unsigned long long*)p; p += b_sum;
-  h->mm = (float*)p;                    p += b_fr;
-  h->counts = (int*)p;                  p += b_cnt;
-  h->carry = p;
+  Scratch place(h->ws);
+  layout(place);
   *out = h;
   return MAUA_OK;
 }
@@ -618,13 +615,9 @@ __global__ __launch_bounds__(256) void corr_finish_kernel(int T, int Fx, int Fy,
   if (tid == 0) out[0] = (float)val;
 }
 
-size_t corr_ws_bytes(long T, int F, CorrWs* w, char* base) {
-  size_t off = 0;
-  auto take = [&](size_t n) { double* p = (double*)(base + off); off += align256(n * sizeof(double)); return p; };
-  double* mean = take(F); double* rn = take(2 * (size_t)T); double* G = take((size_t)F * F); double* Gn = take((size_t)F * F);
-  double* cs = take(F); double* col = take(F);
-  if (w) *w = CorrWs{mean, rn, G, Gn, cs, col};
-  return off;
+CorrWs corr_ws(Scratch& s, long T, int F) {
+  return CorrWs{s.take<double>(F), s.take<double>(2 * (size_t)T), s.take<double>((size_t)F * F), s.take<double>((size_t)F * F),
+                s.take<double>(F), s.take<double>(F)};
 }
 
 int corr_check(const void* x, const void* y, int T, int Fx, int Fy, int metric, const void* ws, size_t ws_bytes, const void* out) {
@@ -635,7 +628,7 @@ int corr_check(const void* x, const void* y, int T, int Fx, int Fy, int metric, 
   MAUA_REQUIRE((metric != MAUA_CORR_PEARSON && metric != MAUA_CORR_CONCORDANCE && metric != MAUA_CORR_R1) || Fx == Fy,
                "maua_correlation: pearson, concordance and r1 need Fx == Fy");
   MAUA_REQUIRE(x && y && ws && out, "maua_correlation: NULL argument");
-  MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= corr_ws_bytes(T, Fx + Fy, nullptr, nullptr),
+  MAUA_REQUIRE(((size_t)ws & 255) == 0 && ws_bytes >= scratch_bytes(corr_ws, T, Fx + Fy),
                "maua_correlation: the workspace must be 256-byte aligned and hold maua_correlation_workspace() bytes");
   return MAUA_OK;
 }
@@ -647,7 +640,7 @@ extern "C" {
 
 long maua_correlation_workspace(int T, int Fx, int Fy) {
   if (T < 1 || Fx < 1 || Fy < 1 || Fx + Fy > CR_MAX_F) return 0;
-  return (long)corr_ws_bytes(T, Fx + Fy, nullptr, nullptr);
+  return (long)scratch_bytes(corr_ws, T, Fx + Fy);
 }
 
 int maua_correlation_check(const float* x, const float* y, int T, int Fx, int Fy, int metric, const void* ws, long ws_bytes, const float* out) {
@@ -659,8 +652,8 @@ int maua_correlation(maua_ctx* ctx, const float* x, const float* y, int T, int F
   if (corr_check(x, y, T, Fx, Fy, metric, ws, ws_bytes < 0 ? 0 : (size_t)ws_bytes, out) != MAUA_OK) return MAUA_ERR;
   hipStream_t st = ctx->stream;
   const int F = Fx + Fy;
-  CorrWs w;
-  corr_ws_bytes(T, F, &w, (char*)ws);
+  Scratch place(ws);
+  const CorrWs w = corr_ws(place, T, F);
   const dim3 tiles(cdiv(F, CR_TILE), cdiv(F, CR_TILE));
   hipLaunchKernelGGL(corr_col_kernel, dim3(F), dim3(256), 0, st, x, y, T, Fx, Fy, 0, (const double*)nullptr, (const double*)nullptr, w.mean);
   hipLaunchKernelGGL(corr_row_kernel, dim3(cdiv(T, 256)), dim3(256), 0, st, x, y, T, Fx, Fy, (const double*)w.mean, w.rn);

@@ -349,3 +349,41 @@ def test_pack_rgb8(M, golden):
     L.check(L.lib().maua_pack_rgb8(L.ctx(), L.ptr(img), L.ptr(out), 1, 1, 8))
     want = ((img + 1) / 2).clamp(0, 1).mul(255).round().byte().permute(0, 2, 3, 1)
     assert torch.equal(out, want)
+
+
+def test_modconv2d_shared_scratch_grows_and_keeps_results():
+    """The context's scratch arena through its grow path (float32): 8 x 8, then 16 x 16 - which needs more than the 1.25 x 8 x 8 bytes the
+    arena holds, so it is freed and allocated anew - then 8 x 8 again in the grown arena.  First and third outputs are bit-equal, and the
+    16 x 16 output is bit-equal to the same call on a fresh context."""
+    import ctypes as C
+
+    from maua_amd import _lib as L
+    lib, dev = L.lib(), torch.cuda.current_device()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    g = torch.Generator().manual_seed(7)
+    w = torch.randn(32, 32, 3, 3, generator=g).cuda()
+    s = torch.randn(1, 32, generator=g).cuda()
+    xs = {hw: torch.randn(1, 32, hw, hw, generator=g).cuda() for hw in (8, 16)}
+
+    def new_ctx():
+        p = C.c_void_p()
+        L.check(lib.maua_ctx_create(dev, stream, C.byref(p)))
+        return p
+
+    def run(ctx, hw):
+        y = torch.full((1, 32, hw, hw), float("nan"), device="cuda")
+        L.check(lib.maua_modconv2d(ctx, L.ptr(xs[hw]), L.ptr(w), L.ptr(s), None, 0, 0.0, None, L.ptr(y), 1, 32, 32, hw, hw, 3, 1, 1, 0,
+                                   L.ACTS["linear"], 1.0, 1.0, -1.0, L.F32))
+        torch.cuda.synchronize()
+        return y
+
+    a, b = new_ctx(), new_ctx()
+    try:
+        first, grown, third = run(a, 8), run(a, 16), run(a, 8)
+        fresh = run(b, 16)
+    finally:
+        lib.maua_ctx_destroy(a)
+        lib.maua_ctx_destroy(b)
+    assert torch.isfinite(first).all() and torch.isfinite(grown).all()
+    assert torch.equal(first, third)
+    assert torch.equal(grown, fresh)
