@@ -246,9 +246,9 @@ __device__ __forceinline__ float median_of(const float* v) {
 
 template <int K>
 __global__ __launch_bounds__(256) void median_time_kernel(const float* __restrict__ mag, int n_frames, int n_bins,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out, int f0) {
   int k = blockIdx.x * blockDim.x + threadIdx.x;
-  int f = blockIdx.y;
+  int f = f0 + blockIdx.y;   // (the grid's y extent holds at most 65535 rows: long clips come in frame ranges)
   if (k >= n_bins) return;
   float v[K];
 #pragma unroll
@@ -258,9 +258,9 @@ __global__ __launch_bounds__(256) void median_time_kernel(const float* __restric
 
 template <int K>
 __global__ __launch_bounds__(256) void median_freq_kernel(const float* __restrict__ mag, int n_frames, int n_bins,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out, int f0) {
   int k = blockIdx.x * blockDim.x + threadIdx.x;
-  int f = blockIdx.y;
+  int f = f0 + blockIdx.y;
   if (k >= n_bins) return;
   const float* row = mag + (long)f * n_bins;
   float v[K];
@@ -464,9 +464,9 @@ __device__ __forceinline__ int pad_src(int j, int T, int radius, int mode) {
 }
 
 __global__ __launch_bounds__(256) void gauss1d_kernel(const float* __restrict__ x, const float* __restrict__ taps,
-                                                      int radius, int T, long C, int mode, float* __restrict__ y) {
+                                                      int radius, int T, long C, int mode, float* __restrict__ y, int t0) {
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  int t = blockIdx.y;
+  int t = t0 + blockIdx.y;   // (at most 65535 rows per launch)
   if (c >= C) return;
   float acc = 0.f;
   for (int k = 0; k <= 2 * radius; k++) {
@@ -629,6 +629,7 @@ __global__ __launch_bounds__(256) void clamp_kernel(const float* __restrict__ x,
   }
 }
 
+constexpr int GRID_Y_MAX = 65535;   // rows of one launch whose row index rides in gridDim.y
 static int grid_for(long n, int cap = 2048) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
 constexpr int MM_PARTS = 256;
 
@@ -779,12 +780,14 @@ int maua_median31(maua_ctx* ctx, const float* mag, int n_frames, int n_bins, int
   MAUA_REQUIRE(ctx && mag && out, "maua_median31: NULL argument");
   MAUA_REQUIRE(axis == 0 || axis == 1, "maua_median31: axis must be 0 (time) or 1 (frequency)");
   MAUA_REQUIRE((axis == 0 ? n_frames : n_bins) > 15, "maua_median31: axis shorter than the reflect padding (15)");
-  dim3 grid(cdiv(n_bins, 256), n_frames);
-  if (axis == 0)
-    hipLaunchKernelGGL(median_time_kernel<31>, grid, dim3(256), 0, ctx->stream, mag, n_frames, n_bins, out);
-  else
-    hipLaunchKernelGGL(median_freq_kernel<31>, grid, dim3(256), 0, ctx->stream, mag, n_frames, n_bins, out);
-  MAUA_HIP_CHECK(hipGetLastError());
+  for (int f0 = 0; f0 < n_frames; f0 += GRID_Y_MAX) {
+    dim3 grid(cdiv(n_bins, 256), std::min(GRID_Y_MAX, n_frames - f0));
+    if (axis == 0)
+      hipLaunchKernelGGL(median_time_kernel<31>, grid, dim3(256), 0, ctx->stream, mag, n_frames, n_bins, out, f0);
+    else
+      hipLaunchKernelGGL(median_freq_kernel<31>, grid, dim3(256), 0, ctx->stream, mag, n_frames, n_bins, out, f0);
+    MAUA_HIP_CHECK(hipGetLastError());
+  }
   return MAUA_OK;
 }
 
@@ -864,9 +867,11 @@ int maua_gaussian_filter1d(maua_ctx* ctx, const float* x, const float* taps, int
   // torch's F.pad(mode="reflect") rejects a pad >= the sequence length; the reference pads min(radius, T) with `mode`
   MAUA_REQUIRE(mode != MAUA_PAD_REFLECT || std::min(radius, T) < T,
                "maua_gaussian_filter1d: reflect padding must be smaller than the sequence (lower sigma)");
-  dim3 grid((unsigned)((C + 255) / 256), T);
-  hipLaunchKernelGGL(gauss1d_kernel, grid, dim3(256), 0, ctx->stream, x, taps, radius, T, C, mode, y);
-  MAUA_HIP_CHECK(hipGetLastError());
+  for (int t0 = 0; t0 < T; t0 += GRID_Y_MAX) {
+    dim3 grid((unsigned)((C + 255) / 256), std::min(GRID_Y_MAX, T - t0));
+    hipLaunchKernelGGL(gauss1d_kernel, grid, dim3(256), 0, ctx->stream, x, taps, radius, T, C, mode, y, t0);
+    MAUA_HIP_CHECK(hipGetLastError());
+  }
   return MAUA_OK;
 }
 
