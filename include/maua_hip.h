@@ -264,7 +264,8 @@ int maua_segment_reduce(maua_ctx* ctx, const float* x, int T, int C, const int* 
 /* segment.py:23-57 recurrence_matrix(data, k, width, sym=True): rec [n][n] = exp(-d / bandwidth) on the k nearest rows of
  * every column (|i - j| < width excluded), symmetrised by the minimum, bandwidth = lower median of the row maxima */
 int maua_recurrence_affinity(maua_ctx* ctx, const float* data, int n, int d, int k, int width, float* rec);
-/* segment.py:74-82 timelag_median_filter: median of 7 along the diagonals (time-lag domain), out != rec */
+/* segment.py:74-82 timelag_median_filter: median of 7 along the diagonals (time-lag domain), out != rec, 3 < n <= 16384
+ * (the limit of maua_recurrence_affinity, which produces rec) */
 int maua_timelag_median(maua_ctx* ctx, const float* rec, int n, float* out);
 /* segment.py:60-64 median_filter1d as :193 applies it: window k (odd, <= 15) along the rows of x [n][m], reflect padding */
 int maua_median_filter_rows(maua_ctx* ctx, const float* x, int n, int m, int k, float* out);
@@ -363,13 +364,17 @@ int maua_spline_natural(maua_ctx* ctx, const double* t_knots_host, int n, const 
  * (0 broadcasts one [C] row over time). */
 int maua_latent_blend(maua_ctx* ctx, const float* a, long a_tstride, const float* b, long b_tstride, const float* env,
                       int T, long C, float* out);
-/* replaces latent.py:21-31 multi_weighted: out[t] = sum_a (env[t][a]/sum_a' env[t][a']) * latents[a % n]. */
+/* replaces latent.py:21-31 multi_weighted: out[t] = sum_a (env[t][a]/sum_a' env[t][a']) * latents[a % n].
+ * A <= 16384 (one row of env is staged in LDS), refused otherwise. */
 int maua_weighted_sum(maua_ctx* ctx, const float* env, const float* latents, int T, int A, int n, long C, float* out);
 /* latent.py:38-40: idx = int64(round_half_even(x * scale)) — the onset-bin assignment (bit-exact). */
 int maua_scale_round_index(maua_ctx* ctx, const float* x, float scale, long n, long long* idx);
-/* latent.py:41: out[t] = src[idx[t]] (rows of C floats). */
+/* latent.py:41: out[t] = src[idx[t]] (rows of C floats); a negative index counts from the end, as numpy's does.
+ * Precondition (not checked: the indices live on the device): every idx[t] lies in [-n_rows, n_rows). */
 int maua_gather_rows(maua_ctx* ctx, const float* src, const long long* idx, int n_rows, int T, long C, float* out);
-/* replaces signal.py:5-24 resample / F.interpolate(mode="linear", align_corners=False) along axis 0. */
+/* replaces signal.py:5-24 resample / F.interpolate(mode="linear", align_corners=False) along axis 0: torch's formula with every
+ * operation rounded once.  A build of torch that fuses scale * (j + 0.5) - 0.5 or the final l0 x0 + l1 x1 into multiply-adds
+ * (its CPU kernels do where the compiler contracts) differs from this by those roundings: an ulp of the source position. */
 int maua_resample_linear(maua_ctx* ctx, const float* x, int n, long C, int size, float* out);
 /* replaces latent.py:54-65 slerp: y [n_seg+1][L][D], t [k] -> out [k][n_seg][L][D] (unit-normalised, Q9). */
 int maua_slerp(maua_ctx* ctx, const float* y, const float* t, int k, int n_seg, int L, int D, float* out);
@@ -381,15 +386,22 @@ int maua_latent_merge(maua_ctx* ctx, float* latents, const float* sequence, cons
 /* ---- per-batch noise (selfsupervised patch) ----------------------------------------------------- */
 /* replaces selfsupervised/noise.py:42-53 Loop.forward(i, b): planes [3,h,w] f32 (the module's randn buffer),
  * idx [T] f32 (= linspace(0, 2*pi*n_loops, T)), frames i0..i0+B-1 ->
- * out[b] = sin(cos(idx[i0+b] + n0) / (sigma/50) + n1) * n2, divided by its per-frame RMS + eps(f32).  out [B,h,w]. */
+ * out[b] = sin(cos(idx[i0+b] + n0) / (sigma/50) + n1) * n2, divided by its per-frame RMS + eps(f32).  out [B,h,w].
+ * Alignment: when h*w is a multiple of 4 the kernels move 16 bytes at a time, so `planes` and `out` must be 16-byte aligned
+ * (every plane and every frame then is); any other h*w takes a scalar path and needs 4-byte alignment only.  This holds for
+ * all three Loop entry points, per layer.  sigma != 0; B <= 65535 and, batched, at most 24 layers per call (refused
+ * otherwise).  The sine and cosine are the library's own short forms, held to 4 x the float32 libm deviation for
+ * |argument| <= 1e4 (idx + n0 and 50 / sigma + n1 stay far below that for sigma >= 0.05). */
 int maua_noise_loop(maua_ctx* ctx, const float* planes, const float* idx, int i0, int B, int h, int w, float sigma,
                     float* out);
-/* the same for n Loop modules (one per synthesis layer) in two launches: host arrays of n device pointers / sizes;
+/* the same for n Loop modules (one per synthesis layer) in three launches (maua_noise_loop is its n = 1: the same bits);
+ * its factor 1 / (rms + eps) comes from the same partial sums as maua_noise_loop_batch_raw's scales; host arrays of n device pointers / sizes;
  * out[l] receives [B, h[l], w[l]].  What selfsupervised/sample.py:93-95 does per batch with 17 module calls. */
 int maua_noise_loop_batch(maua_ctx* ctx, int n, const float* const* planes, const float* const* idx, const int* h,
                           const int* w, const float* sigma, int i0, int B, float* const* out);
 /* replaces noise.py:11-24 Blend.forward (noise2 != NULL: sum_m noise[m]*mod[b,m] + sum_m noise2[m]*(1-mod[b,m]))
- * and :27-39 Multiply.forward (noise2 == NULL).  noise/noise2 [M,h,w], mod [B,M] (rows i..i+B of the modulator). */
+ * and :27-39 Multiply.forward (noise2 == NULL).  noise/noise2 [M,h,w], mod [B,M] (rows i..i+B of the modulator).
+ * M <= 16384 (one row of the modulator is staged in LDS) and B <= 65535, refused otherwise. */
 /* The same maps UN-NORMALISED in one pass + the per-(layer, sample) factor 1 / (rms + eps) that noise.py:52 divides by:
  * scales [n][B] f32 (device).  Hand the maps to the synthesis call as usual and the factors through maua_synth_set_noise_scale:
  * the consuming convolution epilogues multiply them into their noise strength, so the maps are written once and sin(cos(.)) is
@@ -400,7 +412,7 @@ int maua_noise_loop_batch_raw(maua_ctx* ctx, int n, const float* const* planes, 
 int maua_noise_mix(maua_ctx* ctx, const float* noise, const float* noise2, const float* mod, int M, int B, int h,
                    int w, float* out);
 /* replaces noise.py:56-63 Average (mode 0: (x+y)/2), :66-75 Modulate (mode 1: x*mod[b] + y*(1-mod[b]), mod [B]),
- * :78-86 ScaleBias (mode 2: scale*x + bias).  x, y, out [B,h,w]. */
+ * :78-86 ScaleBias (mode 2: scale*x + bias).  x, y, out [B,h,w].  B <= 65535. */
 int maua_noise_combine(maua_ctx* ctx, const float* x, const float* y, const float* mod, int mode, float scale,
                        float bias, int B, int h, int w, float* out);
 

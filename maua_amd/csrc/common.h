@@ -150,6 +150,14 @@ int fail(const std::string& msg);  // sets the thread-local error, returns MAUA_
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// A row index that rides in gridDim.y or gridDim.z: one launch holds at most 65535 of them, so longer tensors are launched in
+// row ranges and the kernel adds the first row of its range.  launch(first_row, rows_in_this_range).
+constexpr int GRID_ROWS_MAX = 65535;
+template <typename F>
+static inline void for_row_ranges(long rows, F&& launch) {
+  for (long r0 = 0; r0 < rows; r0 += GRID_ROWS_MAX) launch((int)r0, (int)(rows - r0 < GRID_ROWS_MAX ? rows - r0 : GRID_ROWS_MAX));
+}
+
 }  // namespace maua
 
 struct maua_ctx {

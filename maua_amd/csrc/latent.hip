@@ -41,9 +41,9 @@ __global__ __launch_bounds__(256) void spline_solve_kernel(const float* __restri
 __global__ __launch_bounds__(256) void spline_eval_kernel(const float* __restrict__ y, const double* __restrict__ M,
                                                           long C, const int* __restrict__ idx,
                                                           const double* __restrict__ aw, const double* __restrict__ bw,
-                                                          const double* __restrict__ hw, float* __restrict__ out) {
+                                                          const double* __restrict__ hw, float* __restrict__ out, int t0) {
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  int t = blockIdx.y;
+  int t = t0 + blockIdx.y;   // (at most 65535 rows per launch: for_row_ranges)
   if (c >= C) return;
   int i = idx[t];
   double a = aw[t], b = bw[t], h = hw[t];
@@ -54,23 +54,29 @@ __global__ __launch_bounds__(256) void spline_eval_kernel(const float* __restric
 }
 
 // ---- envelope-weighted blends ---------------------------------------------------------------------------------
+// The kernels whose operation order is their contract (blend, resample_linear, latent_merge: each operation rounded once, as
+// the reference's separate tensor operations are) switch contraction off for their body and use plain operators.  (The
+// __f*_rn intrinsics do not do that here: they are inline operators compiled with contraction allowed, and the back end fused
+// scale * (j + 0.5) - 0.5 of the resampler into one multiply-add through them.)
 // out[t] = a[t] * (1 - e[t]) + b[t] * e[t]   (a/b time strides may be 0: constants)
 __global__ __launch_bounds__(256) void blend_kernel(const float* __restrict__ a, long a_ts, const float* __restrict__ b,
                                                     long b_ts, const float* __restrict__ e, long C,
-                                                    float* __restrict__ out) {
+                                                    float* __restrict__ out, int t0) {
+#pragma clang fp contract(off)
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  int t = blockIdx.y;
+  int t = t0 + blockIdx.y;
   if (c >= C) return;
   float ev = e[t];
-  float w0 = __fsub_rn(1.f, ev);
-  out[(long)t * C + c] = __fadd_rn(__fmul_rn(a[(long)t * a_ts + c], w0), __fmul_rn(b[(long)t * b_ts + c], ev));
+  float w0 = 1.f - ev;
+  out[(long)t * C + c] = a[(long)t * a_ts + c] * w0 + b[(long)t * b_ts + c] * ev;
 }
 
 // multi_weighted: out[t][c] = sum_a (e[t][a] / sum_a' e[t][a']) * lat[a % n][c]
+constexpr int WS_MAX_A = 16384;   // es[A] in dynamic LDS: 64 KiB, what a launch gets without asking for more
 __global__ __launch_bounds__(256) void weighted_sum_kernel(const float* __restrict__ e, const float* __restrict__ lat,
-                                                           int A, int n, long C, float* __restrict__ out) {
+                                                           int A, int n, long C, float* __restrict__ out, int t0) {
   extern __shared__ float es[];
-  int t = blockIdx.y;
+  int t = t0 + blockIdx.y;
   if (threadIdx.x == 0) {
     float s = 0.f;
     for (int a = 0; a < A; a++) s += e[(long)t * A + a];
@@ -93,9 +99,9 @@ __global__ __launch_bounds__(256) void scale_round_index_kernel(const float* __r
 }
 
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, const long long* __restrict__ idx,
-                                                          int n_rows, long C, float* __restrict__ out) {
+                                                          int n_rows, long C, float* __restrict__ out, int t0) {
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  int t = blockIdx.y;
+  int t = t0 + blockIdx.y;
   if (c >= C) return;
   long long r = idx[t];
   if (r < 0) r += n_rows;  // numpy-style negative index (latent.py:41 indexes a numpy array)
@@ -104,25 +110,26 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 
 // F.interpolate(mode="linear", align_corners=False) along axis 0 of [n][C] -> [size][C]
 __global__ __launch_bounds__(256) void resample_linear_kernel(const float* __restrict__ x, int n, long C, int size,
-                                                              float* __restrict__ out) {
+                                                              float* __restrict__ out, int j0) {
+#pragma clang fp contract(off)
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  int j = blockIdx.y;
+  int j = j0 + blockIdx.y;
   if (c >= C) return;
   const float scale = (float)n / (float)size;
-  float src = __fsub_rn(__fmul_rn(scale, __fadd_rn((float)j, 0.5f)), 0.5f);
+  float src = scale * ((float)j + 0.5f) - 0.5f;
   if (src < 0.f) src = 0.f;
   int i0 = (int)src;
   if (i0 > n - 1) i0 = n - 1;
   int i1 = i0 + (i0 < n - 1 ? 1 : 0);
-  float l1 = __fsub_rn(src, (float)i0), l0 = __fsub_rn(1.f, l1);
-  out[(long)j * C + c] = __fadd_rn(__fmul_rn(l0, x[(long)i0 * C + c]), __fmul_rn(l1, x[(long)i1 * C + c]));
+  float l1 = src - (float)i0, l0 = 1.f - l1;
+  out[(long)j * C + c] = l0 * x[(long)i0 * C + c] + l1 * x[(long)i1 * C + c];
 }
 
 // slerp (latent.py:54-65): one workgroup per (t, segment, layer) vector of length D
 __global__ __launch_bounds__(256) void slerp_kernel(const float* __restrict__ y, const float* __restrict__ tv, int n_seg,
-                                                    int L, int D, float* __restrict__ out) {
+                                                    int L, int D, float* __restrict__ out, int k0) {
   __shared__ float red[3][4];
-  const int ti = blockIdx.z, seg = blockIdx.y, lay = blockIdx.x;
+  const int ti = k0 + blockIdx.z, seg = blockIdx.y, lay = blockIdx.x;
   const float* a = y + ((long)seg * L + lay) * D;
   const float* b = y + ((long)(seg + 1) * L + lay) * D;
   auto bsum = [&](float v, int slot) {
@@ -169,18 +176,19 @@ __global__ __launch_bounds__(256) void slerp_kernel(const float* __restrict__ y,
 // latent_patch merges (selfsupervised/latent.py:57-78) on layers [l0, l1) of lat [T][L][D], in place
 __global__ __launch_bounds__(256) void latent_merge_kernel(float* __restrict__ lat, const float* __restrict__ seq,
                                                            const float* __restrict__ mod, int mode, int L, int D,
-                                                           int l0, int l1) {
-  int t = blockIdx.y;
+                                                           int l0, int l1, int t0) {
+#pragma clang fp contract(off)
+  int t = t0 + blockIdx.y;
   long span = (long)(l1 - l0) * D;
   long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= span) return;
   long o = ((long)t * L + l0) * D + c;
   float a = lat[o], s = seq[o];
   float v;
-  if (mode == 0) v = __fadd_rn(a, s) / 2.f;  // average: += then /= 2
+  if (mode == 0) v = (a + s) / 2.f;          // average: += then /= 2
   else if (mode == 1) {                      // modulate: *= (1 - m); += m * seq
     float m = mod[t];
-    v = __fadd_rn(__fmul_rn(a, __fsub_rn(1.f, m)), __fmul_rn(m, s));
+    v = a * (1.f - m) + m * s;
   } else v = s;                              // overwrite
   lat[o] = v;
 }
@@ -246,8 +254,10 @@ int maua_spline_natural(maua_ctx* ctx, const double* t_knots_host, int n, const 
   MAUA_HIP_CHECK(hipStreamSynchronize(s));  // host staging vectors go out of scope
   hipLaunchKernelGGL(spline_solve_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, y, n, C, (const double*)dh, (const double*)dcp,
                      (const double*)did, dM);
-  hipLaunchKernelGGL(spline_eval_kernel, dim3((unsigned)((C + 255) / 256), T), dim3(256), 0, s, y, (const double*)dM, C, (const int*)dix,
-                     (const double*)da, (const double*)db, (const double*)dhw, out);
+  for_row_ranges(T, [&](int t0, int rows) {
+    hipLaunchKernelGGL(spline_eval_kernel, dim3((unsigned)((C + 255) / 256), rows), dim3(256), 0, s, y, (const double*)dM, C, (const int*)dix,
+                       (const double*)da, (const double*)db, (const double*)dhw, out, t0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -255,26 +265,34 @@ int maua_spline_natural(maua_ctx* ctx, const double* t_knots_host, int n, const 
 int maua_latent_blend(maua_ctx* ctx, const float* a, long a_tstride, const float* b, long b_tstride, const float* env,
                       int T, long C, float* out) {
   MAUA_REQUIRE(ctx, "maua_latent_blend: ctx is NULL");
+  MAUA_REQUIRE(T >= 0 && C >= 0, "maua_latent_blend: negative size");
   if (T == 0 || C == 0) return MAUA_OK;
   MAUA_REQUIRE(a && b && env && out, "maua_latent_blend: NULL argument");
-  hipLaunchKernelGGL(blend_kernel, dim3((unsigned)((C + 255) / 256), T), dim3(256), 0, ctx->stream, a, a_tstride, b,
-                     b_tstride, env, C, out);
+  for_row_ranges(T, [&](int t0, int rows) {
+    hipLaunchKernelGGL(blend_kernel, dim3((unsigned)((C + 255) / 256), rows), dim3(256), 0, ctx->stream, a, a_tstride, b,
+                       b_tstride, env, C, out, t0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
 
 int maua_weighted_sum(maua_ctx* ctx, const float* env, const float* latents, int T, int A, int n, long C, float* out) {
   MAUA_REQUIRE(ctx, "maua_weighted_sum: ctx is NULL");
+  MAUA_REQUIRE(T >= 0 && C >= 0, "maua_weighted_sum: negative size");
   if (T == 0 || C == 0) return MAUA_OK;
   MAUA_REQUIRE(env && latents && out && A > 0 && n > 0, "maua_weighted_sum: NULL argument");
-  hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)((C + 255) / 256), T), dim3(256), (size_t)A * sizeof(float),
-                     ctx->stream, env, latents, A, n, C, out);
+  MAUA_REQUIRE(A <= WS_MAX_A, "maua_weighted_sum: at most 16384 envelopes (one row of them is staged in LDS)");
+  for_row_ranges(T, [&](int t0, int rows) {
+    hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)((C + 255) / 256), rows), dim3(256), (size_t)A * sizeof(float),
+                       ctx->stream, env, latents, A, n, C, out, t0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
 
 int maua_scale_round_index(maua_ctx* ctx, const float* x, float scale, long n, long long* idx) {
   MAUA_REQUIRE(ctx, "maua_scale_round_index: ctx is NULL");
+  MAUA_REQUIRE(n >= 0, "maua_scale_round_index: negative size");
   if (n == 0) return MAUA_OK;
   MAUA_REQUIRE(x && idx, "maua_scale_round_index: NULL argument");
   hipLaunchKernelGGL(scale_round_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, x, scale, n,
@@ -285,29 +303,39 @@ int maua_scale_round_index(maua_ctx* ctx, const float* x, float scale, long n, l
 
 int maua_gather_rows(maua_ctx* ctx, const float* src, const long long* idx, int n_rows, int T, long C, float* out) {
   MAUA_REQUIRE(ctx, "maua_gather_rows: ctx is NULL");
+  MAUA_REQUIRE(T >= 0 && C >= 0, "maua_gather_rows: negative size");
   if (T == 0 || C == 0) return MAUA_OK;
   MAUA_REQUIRE(src && idx && out, "maua_gather_rows: NULL argument");
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((C + 255) / 256), T), dim3(256), 0, ctx->stream, src, idx,
-                     n_rows, C, out);
+  for_row_ranges(T, [&](int t0, int rows) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((C + 255) / 256), rows), dim3(256), 0, ctx->stream, src, idx,
+                       n_rows, C, out, t0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
 
 int maua_resample_linear(maua_ctx* ctx, const float* x, int n, long C, int size, float* out) {
   MAUA_REQUIRE(ctx, "maua_resample_linear: ctx is NULL");
+  MAUA_REQUIRE(size >= 0 && C >= 0, "maua_resample_linear: negative size");
   if (size == 0 || C == 0) return MAUA_OK;
   MAUA_REQUIRE(x && out && n > 0, "maua_resample_linear: NULL argument");
-  hipLaunchKernelGGL(resample_linear_kernel, dim3((unsigned)((C + 255) / 256), size), dim3(256), 0, ctx->stream, x, n, C,
-                     size, out);
+  for_row_ranges(size, [&](int j0, int rows) {
+    hipLaunchKernelGGL(resample_linear_kernel, dim3((unsigned)((C + 255) / 256), rows), dim3(256), 0, ctx->stream, x, n, C,
+                       size, out, j0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
 
 int maua_slerp(maua_ctx* ctx, const float* y, const float* t, int k, int n_seg, int L, int D, float* out) {
   MAUA_REQUIRE(ctx, "maua_slerp: ctx is NULL");
+  MAUA_REQUIRE(k >= 0 && n_seg >= 0, "maua_slerp: negative size");
   if (k == 0 || n_seg == 0) return MAUA_OK;
   MAUA_REQUIRE(y && t && out && L > 0 && D > 0, "maua_slerp: NULL argument");
-  hipLaunchKernelGGL(slerp_kernel, dim3(L, n_seg, k), dim3(256), 0, ctx->stream, y, t, n_seg, L, D, out);
+  MAUA_REQUIRE(n_seg <= GRID_ROWS_MAX, "maua_slerp: at most 65535 segments");
+  for_row_ranges(k, [&](int k0, int rows) {
+    hipLaunchKernelGGL(slerp_kernel, dim3(L, n_seg, rows), dim3(256), 0, ctx->stream, y, t, n_seg, L, D, out, k0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -315,13 +343,16 @@ int maua_slerp(maua_ctx* ctx, const float* y, const float* t, int k, int n_seg, 
 int maua_latent_merge(maua_ctx* ctx, float* latents, const float* sequence, const float* mod, int mode, int T, int L,
                       int D, int l0, int l1) {
   MAUA_REQUIRE(ctx, "maua_latent_merge: ctx is NULL");
-  if (T == 0 || l1 <= l0) return MAUA_OK;
+  MAUA_REQUIRE(T >= 0 && D >= 0, "maua_latent_merge: negative size");
+  if (T == 0 || D == 0 || l1 <= l0) return MAUA_OK;   // (D = 0: no elements, and no grid to launch)
   MAUA_REQUIRE(latents && sequence, "maua_latent_merge: NULL argument");
   MAUA_REQUIRE(mode >= 0 && mode <= 2 && (mode != 1 || mod), "maua_latent_merge: mode 0 average, 1 modulate (needs mod), 2 overwrite");
   MAUA_REQUIRE(l0 >= 0 && l1 <= L, "maua_latent_merge: layer slice out of range");
   long span = (long)(l1 - l0) * D;
-  hipLaunchKernelGGL(latent_merge_kernel, dim3((unsigned)((span + 255) / 256), T), dim3(256), 0, ctx->stream, latents,
-                     sequence, mod, mode, L, D, l0, l1);
+  for_row_ranges(T, [&](int t0, int rows) {
+    hipLaunchKernelGGL(latent_merge_kernel, dim3((unsigned)((span + 255) / 256), rows), dim3(256), 0, ctx->stream, latents,
+                       sequence, mod, mode, L, D, l0, l1, t0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }

@@ -231,8 +231,8 @@ __global__ __launch_bounds__(256) void timelag_median_kernel(const float* __rest
 // segment.py:60-64 median_filter1d along the ROWS of x [n][m] (the reference filters evecs.T along its columns), window k,
 // reflect padding k / 2
 __global__ __launch_bounds__(256) void median_rows_kernel(const float* __restrict__ x, int n, int m, int k,
-                                                          float* __restrict__ out) {
-  const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+                                                          float* __restrict__ out, int r0) {
+  const int c = blockIdx.x * 256 + threadIdx.x, r = r0 + blockIdx.y;   // (at most 65535 rows per launch: for_row_ranges)
   if (c >= m) return;
   float v[15];
   for (int t = 0; t < k; t++) v[t] = x[(long)reflect_index(r + t - k / 2, n) * m + c];
@@ -301,6 +301,7 @@ extern "C" {
 int maua_beat_dp(maua_ctx* ctx, const float* onset_norm, int T, int period, double tightness, double* localscore,
                  double* cumscore, int* backlink) {
   MAUA_REQUIRE(ctx, "maua_beat_dp: ctx is NULL");
+  MAUA_REQUIRE(T >= 0, "maua_beat_dp: negative size");
   if (T == 0) return MAUA_OK;
   MAUA_REQUIRE(onset_norm && localscore && cumscore && backlink, "maua_beat_dp: NULL argument");
   MAUA_REQUIRE(period >= 1, "maua_beat_dp: the beat period must be at least one frame (bpm too high for this frame rate)");
@@ -336,6 +337,7 @@ int maua_beat_dp(maua_ctx* ctx, const float* onset_norm, int T, int period, doub
 int maua_segment_reduce(maua_ctx* ctx, const float* x, int T, int C, const int* bounds, int n_segments, int mode,
                         float* out) {
   MAUA_REQUIRE(ctx, "maua_segment_reduce: ctx is NULL");
+  MAUA_REQUIRE(n_segments >= 0 && C >= 0, "maua_segment_reduce: negative size");
   if (n_segments == 0 || C == 0) return MAUA_OK;
   MAUA_REQUIRE(x && bounds && out, "maua_segment_reduce: NULL argument");
   MAUA_REQUIRE(mode == 0 || mode == 1, "maua_segment_reduce: mode must be 0 (median) or 1 (mean)");
@@ -347,6 +349,7 @@ int maua_segment_reduce(maua_ctx* ctx, const float* x, int T, int C, const int* 
 
 int maua_recurrence_affinity(maua_ctx* ctx, const float* data, int n, int d, int k, int width, float* rec) {
   MAUA_REQUIRE(ctx, "maua_recurrence_affinity: ctx is NULL");
+  MAUA_REQUIRE(n >= 0, "maua_recurrence_affinity: negative size");
   if (n == 0) return MAUA_OK;
   MAUA_REQUIRE(data && rec, "maua_recurrence_affinity: NULL argument");
   MAUA_REQUIRE(k >= 1 && k <= n, "maua_recurrence_affinity: k must be in [1, n]");
@@ -366,9 +369,11 @@ int maua_recurrence_affinity(maua_ctx* ctx, const float* data, int n, int d, int
 
 int maua_timelag_median(maua_ctx* ctx, const float* rec, int n, float* out) {
   MAUA_REQUIRE(ctx, "maua_timelag_median: ctx is NULL");
+  MAUA_REQUIRE(n >= 0, "maua_timelag_median: negative size");
   if (n == 0) return MAUA_OK;
   MAUA_REQUIRE(rec && out && rec != out, "maua_timelag_median: NULL or aliased argument");
   MAUA_REQUIRE(n > 3, "maua_timelag_median: reflect padding of 3 needs more than 3 beats");
+  MAUA_REQUIRE(n <= 16384, "maua_timelag_median: too many beats");   // (n rides in gridDim.y; maua_recurrence_affinity's limit)
   hipLaunchKernelGGL(timelag_median_kernel, dim3(cdiv(n, 256), n), dim3(256), 0, ctx->stream, rec, n, out);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
@@ -376,11 +381,14 @@ int maua_timelag_median(maua_ctx* ctx, const float* rec, int n, float* out) {
 
 int maua_median_filter_rows(maua_ctx* ctx, const float* x, int n, int m, int k, float* out) {
   MAUA_REQUIRE(ctx, "maua_median_filter_rows: ctx is NULL");
+  MAUA_REQUIRE(n >= 0 && m >= 0, "maua_median_filter_rows: negative size");
   if (n == 0 || m == 0) return MAUA_OK;
   MAUA_REQUIRE(x && out && x != out, "maua_median_filter_rows: NULL or aliased argument");
   MAUA_REQUIRE(k >= 1 && k <= 15 && (k & 1), "maua_median_filter_rows: the window must be odd and at most 15");
   MAUA_REQUIRE(n > k / 2, "maua_median_filter_rows: reflect padding needs more rows than half the window");
-  hipLaunchKernelGGL(median_rows_kernel, dim3(cdiv(m, 256), n), dim3(256), 0, ctx->stream, x, n, m, k, out);
+  for_row_ranges(n, [&](int r0, int rows) {
+    hipLaunchKernelGGL(median_rows_kernel, dim3(cdiv(m, 256), rows), dim3(256), 0, ctx->stream, x, n, m, k, out, r0);
+  });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }

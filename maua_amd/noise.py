@@ -79,7 +79,7 @@ class RawNoise:
 
 
 def loop_batch(modules, i, b, raw=False):
-    """forward(i, b) of a list of Loop modules in one C call (two launches for all layers) -> list of [b,h,w].
+    """forward(i, b) of a list of Loop modules in one C call (three launches for all layers; raw: two) -> list of [b,h,w].
     ``raw=True``: the maps un-normalised, written in ONE pass, as a ``RawNoise`` carrying the per-sample factors (what the
     render loops use: the normalised form evaluates sin(cos(.)) twice per value)."""
     n = len(modules)
