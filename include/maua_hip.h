@@ -156,16 +156,21 @@ int maua_synth_set_warp(maua_synth* net, int slot, int layer, const float* inv_m
 int maua_synth_layer_size(const maua_synth* net, int layer, int* h, int* w);
 /* the torch ops the hooks are made of, on NCHW tensors (dtype f32 / bf16): mode 0 = F.interpolate(x, (out_h, out_w),
  * mode="bicubic", align_corners=False); mode 1 = F.pad with left/top offsets (negative = crop), out size given;
- * mode 2 = bicubic with align_corners=True (maua/ops/image.py:240, the post-render resample). */
+ * mode 2 = bicubic with align_corners=True (maua/ops/image.py:240, the post-render resample).  dtype f32 / bf16 / f16.  Circular
+ * padding wraps as often as it takes (torch refuses a pad larger than the input; reflect padding as large as the input is refused
+ * here as there).  Checked by name: NULL or aliased x / y, any negative size, H or W of 0 with a non-empty output, mode, pad_how, dtype.
+ * N, C, out_h or out_w of 0: nothing is done. */
 int maua_resize2d(maua_ctx* ctx, const void* x, void* y, int N, int C, int H, int W, int out_h, int out_w, int mode,
                   int pad_left, int pad_top, int pad_how, float pad_value, int dtype);
 /* depthwise 1-D correlation of planar f32 [planes][H][W] along rows (axis 0) or columns (axis 1) with reflect padding
- * `radius` (taps [2*radius+1], device): the lanczos pre-filter of maua/ops/image.py:226-236 resample. */
+ * `radius` (taps [2*radius+1], device): the lanczos pre-filter of maua/ops/image.py:226-236 resample.  0 <= radius < the axis's
+ * length; x != y; a negative planes, H or W is refused, one of them 0 does nothing (the same for the vjp below). */
 int maua_conv1d_reflect(maua_ctx* ctx, const float* x, float* y, const float* taps, int radius, int axis, long planes,
                         int H, int W);
 /* the adjoints of the two steps of `resample` (maua/ops/image.py:214-240) - what autograd gives a loss taken on a resampled image
  * (LPIPSGrads, maua/grad.py:191-192): gy -> gx through the reflect-padded 1-D correlation / through the bicubic interpolation
- * (gy device f32 [N][C][out_h][out_w] -> gx [N][C][H][W]; align_corners as maua_resize2d's mode 2 / 0) */
+ * (gy device f32 [N][C][out_h][out_w] -> gx [N][C][H][W]; align_corners as maua_resize2d's mode 2 / 0; gy != gx; negative sizes are
+ * refused, N, C, H or W of 0 does nothing, out_h or out_w of 0 with a non-empty gx is refused) */
 int maua_conv1d_reflect_vjp(maua_ctx* ctx, const float* gy, float* gx, const float* taps, int radius, int axis, long planes, int H, int W);
 int maua_resize2d_bicubic_vjp(maua_ctx* ctx, const float* gy, float* gx, int N, int C, int H, int W, int out_h, int out_w, int align_corners);
 int maua_synth_set_option(maua_synth* net, const char* key, int value);
@@ -855,7 +860,11 @@ int maua_unet_set_clip_guide(maua_unet* net, maua_clip* clip, const int* rects, 
                              float scale, float clamp_gradient);
 /* operator-level pieces.  maua_cutouts: random_cutouts (cutouts.py:8-38) on HOST rectangles [n_cut][3] applied to img * mul + add,
  * resized to cut_size^2 by the `resize_right` algorithm (cubic, antialiased, zero padding), Normalize(mean3, std3) -> out device f32
- * [n_cut * B][3][cut_size][cut_size] (cutout-major, like torch.cat); maua_cutouts_vjp: d_out -> d_img [B][3][H][W] */
+ * [n_cut * B][3][cut_size][cut_size] (cutout-major, like torch.cat); maua_cutouts_vjp: d_out -> d_img [B][3][H][W].  A rectangle is
+ * (size | flags, top, left): flags MAUA's grey (1 << 30) and mirror (1 << 29) bits of DangoCutouts, no others.  Checked by name before
+ * anything is carved, copied or launched: NULL or aliased pointers, n_cut and cut_size >= 1, H and W >= 1, n_cut * B <= 65535 (the
+ * gradient also 3 * B and H <= 65535), min(H, W) <= 4 * cut_size - 1 (16 filter taps), every rectangle's size >= 1 and the rectangle
+ * inside the image.  B == 0: nothing is done. */
 int maua_cutouts(maua_ctx* ctx, const float* img, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul, float add,
                  const float* mean3, const float* std3, float* out);
 int maua_cutouts_vjp(maua_ctx* ctx, const float* d_out, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul,
@@ -888,7 +897,11 @@ int maua_layer_norm_vjp(maua_ctx* ctx, const void* x, const float* stats, const 
  *   maua_colormatch_hist : hist device f32 [B][nbins]                                   (histogram(), set_targets :65-69)
  *   maua_colormatch_grad : grad = d (scale * mse_loss(hist, target)) / d img in closed form (forward :67-70); target device f32
  *                          [nbins] (target_per_sample == 0) or [B][nbins]; loss: optional device f32 [B], the samples' shares of the
- *                          loss (their sum is the reference's scalar) */
+ *                          loss (their sum is the reference's scalar)
+ * Checked by name: NULL pointers, grad aliasing img, 2 <= nbins <= 1024, H and W >= 1, 0 <= B <= 65535 (B == 0: nothing is done) and
+ * H * W <= 2^23 (nbins - 1): a pixel adds less than 2^41 / (nbins - 1) to a 64-bit sum, beyond that the sums could pass 2^64.  An image
+ * whose weights are all zero (all grey, with saturation weighting) gives 0 / 0: a NaN histogram, as the reference does, and a gradient
+ * holding NaN, which maua_grad_accumulate drops. */
 int maua_colormatch_hist(maua_ctx* ctx, const float* img, int B, int H, int W, int nbins, int sat_weighting, float* hist);
 int maua_colormatch_grad(maua_ctx* ctx, const float* img, int B, int H, int W, int nbins, int sat_weighting, const float* target,
                          int target_per_sample, float scale, float* grad, float* loss);

@@ -35,13 +35,17 @@ struct Hsv {
   float M, delta, deltap, num, hue_raw, x, s, v, w;
 };
 
-// one pixel of ColorMatchGrads.histogram up to the histogram's inputs (x = clamped hue, w = weight)
+// one pixel of ColorMatchGrads.histogram up to the histogram's inputs (x = clamped hue, w = weight).  The order is the contract with
+// the reference (every float32 operation rounds once, kornia's order): plain operators with contraction switched off in this body
+// (the pragma is lexical) and sqrtf, which is correctly rounded - __fsqrt_rn is the hardware's approximate square root under this
+// project's flags and left the weight one ulp low (pinned by tests/test_gpu_image_kernels.py's single-pixel images)
 __device__ __forceinline__ Hsv pixel_hsv(float r, float g, float b, bool sat_weighting) {
+#pragma clang fp contract(off)
   Hsv h;
   const float in3[3] = {r, g, b};
 #pragma unroll
   for (int i = 0; i < 3; i++) {
-    const float u = __fdiv_rn(__fadd_rn(in3[i], 1.f), 2.f);
+    const float u = (in3[i] + 1.f) / 2.f;
     h.live[i] = u >= 1e-8f && u <= 1.f;
     h.c[i] = fminf(fmaxf(u, 1e-8f), 1.f);
   }
@@ -52,26 +56,29 @@ __device__ __forceinline__ Hsv pixel_hsv(float r, float g, float b, bool sat_wei
   if (h.c[2] < h.c[h.in]) h.in = 2;
   h.M = h.c[h.im];
   const float m = h.c[h.in];
-  h.delta = __fsub_rn(h.M, m);
+  h.delta = h.M - m;
   h.v = h.M;
-  h.s = __fdiv_rn(h.delta, __fadd_rn(h.M, 1e-8f));
+  h.s = h.delta / (h.M + 1e-8f);
   h.deltap = h.delta == 0.f ? 1.f : h.delta;
-  const float rc = __fsub_rn(h.M, h.c[0]), gc = __fsub_rn(h.M, h.c[1]), bc = __fsub_rn(h.M, h.c[2]);
+  const float rc = h.M - h.c[0], gc = h.M - h.c[1], bc = h.M - h.c[2];
   float hh;
-  if (h.im == 0) { h.num = __fsub_rn(bc, gc); hh = __fdiv_rn(h.num, h.deltap); }
-  else if (h.im == 1) { h.num = __fsub_rn(rc, bc); hh = __fdiv_rn(__fadd_rn(h.num, __fmul_rn(2.f, h.deltap)), h.deltap); }
-  else { h.num = __fsub_rn(gc, rc); hh = __fdiv_rn(__fadd_rn(h.num, __fmul_rn(4.f, h.deltap)), h.deltap); }
-  const float q = __fdiv_rn(hh, 6.f);
+  if (h.im == 0) { h.num = bc - gc; hh = h.num / h.deltap; }
+  else if (h.im == 1) { h.num = rc - bc; hh = (h.num + 2.f * h.deltap) / h.deltap; }
+  else { h.num = gc - rc; hh = (h.num + 4.f * h.deltap) / h.deltap; }
+  const float q = hh / 6.f;
   float fr = fmodf(q, 1.f);                       // torch's float % 1.0: fmod, then + 1 when the signs differ (a tiny negative q gives exactly 1)
-  if (fr < 0.f) fr = __fadd_rn(fr, 1.f);
-  h.hue_raw = __fmul_rn(TWO_PI, fr);
+  if (fr < 0.f) fr = fr + 1.f;
+  h.hue_raw = TWO_PI * fr;
   h.x = fminf(fmaxf(h.hue_raw, 0.f), 1.f);
   const float sc = fminf(fmaxf(h.s, 0.f), 1.f), vc = fminf(fmaxf(h.v, 0.f), 1.f);
-  h.w = sat_weighting ? __fsqrt_rn(__fmul_rn(sc, vc)) : 1.f;
+  h.w = sat_weighting ? sqrtf(sc * vc) : 1.f;
   return h;
 }
 
-__device__ __forceinline__ float edge(int j, float delta) { return __fmul_rn((float)j, delta); }
+__device__ __forceinline__ float edge(int j, float delta) {
+#pragma clang fp contract(off)
+  return (float)j * delta;
+}
 
 // k with e_k <= x < e_k+1 (x in [0, 1]: 0 <= k <= nbins - 1 because e_nbins-1 = 1 rounds to at most 1 and e_nbins > 1)
 __device__ __forceinline__ int bin_of(float x, int nbins, float delta) {
@@ -84,6 +91,7 @@ __device__ __forceinline__ int bin_of(float x, int nbins, float delta) {
 
 __global__ __launch_bounds__(256) void cm_hist_kernel(const float* __restrict__ img, long HW, int nbins, float delta, int sat_weighting,
                                                       unsigned long long* __restrict__ hist) {
+#pragma clang fp contract(off)
   __shared__ unsigned long long sh[MAX_BINS];
   const int b = blockIdx.y;
   for (int i = threadIdx.x; i < nbins; i += 256) sh[i] = 0ull;
@@ -94,10 +102,10 @@ __global__ __launch_bounds__(256) void cm_hist_kernel(const float* __restrict__ 
     const int k = bin_of(h.x, nbins, delta);
     const float lo = edge(k, delta), hi = edge(k + 1, delta);
     if (h.x >= lo && h.x < hi) {
-      const float a = __fmul_rn(__fsub_rn(hi, h.x), h.w);
+      const float a = (hi - h.x) * h.w;
       atomicAdd(&sh[k], (unsigned long long)((double)a * FIX + 0.5));
       if (k + 1 <= nbins - 1) {
-        const float c = __fmul_rn(__fsub_rn(h.x, lo), h.w);
+        const float c = (h.x - lo) * h.w;
         atomicAdd(&sh[k + 1], (unsigned long long)((double)c * FIX + 0.5));
       }
     }
@@ -232,6 +240,14 @@ int hist_into(hipStream_t st, const float* img, int B, long HW, int nbins, int s
   return MAUA_OK;
 }
 
+// B rides in gridDim.y (not split).  A pixel adds at most delta (1 + 2^-22) 2^40 + 1 < 2^41 / (nbins - 1) to one 64-bit sum (both
+// contributions are at most delta = 1 / (nbins - 1) wide times a weight <= 1), so H W <= 2^23 (nbins - 1) keeps every sum below 2^64.
+int check_extent(int B, int H, int W, int nbins, const char* who) {
+  MAUA_REQUIRE(B <= 65535, std::string(who) + ": at most 65535 images per call");
+  MAUA_REQUIRE((long)H * W <= ((long)(nbins - 1) << 23), std::string(who) + ": more than 2^23 (bins - 1) pixels overflow the 64-bit fixed-point sums");
+  return MAUA_OK;
+}
+
 int run_hist(maua_ctx* ctx, const float* img, int B, long HW, int nbins, int sat_weighting, unsigned long long** fix_out, float** gr_out) {
   if (int rc = carve_scratch(ctx, [&](Scratch& s) {
         *fix_out = s.take<unsigned long long>((size_t)B * nbins); *gr_out = s.take<float>((size_t)B * nbins);
@@ -277,6 +293,7 @@ extern "C" {
 int maua_colormatch_hist(maua_ctx* ctx, const float* img, int B, int H, int W, int nbins, int sat_weighting, float* hist) {
   MAUA_REQUIRE(ctx && img && hist, "maua_colormatch_hist: NULL argument");
   MAUA_REQUIRE(B >= 0 && H > 0 && W > 0 && nbins >= 2 && nbins <= MAX_BINS, "maua_colormatch_hist: bad shape (2 <= bins <= 1024)");
+  if (int rc = check_extent(B, H, W, nbins, "maua_colormatch_hist")) return rc;
   if (B == 0) return MAUA_OK;
   unsigned long long* fix;
   float* gr;
@@ -291,6 +308,8 @@ int maua_colormatch_grad(maua_ctx* ctx, const float* img, int B, int H, int W, i
                          int target_per_sample, float scale, float* grad, float* loss) {
   MAUA_REQUIRE(ctx && img && target && grad, "maua_colormatch_grad: NULL argument");
   MAUA_REQUIRE(B >= 0 && H > 0 && W > 0 && nbins >= 2 && nbins <= MAX_BINS, "maua_colormatch_grad: bad shape (2 <= bins <= 1024)");
+  if (int rc = check_extent(B, H, W, nbins, "maua_colormatch_grad")) return rc;
+  MAUA_REQUIRE((const void*)img != (const void*)grad, "maua_colormatch_grad: grad aliases img");
   if (B == 0) return MAUA_OK;
   unsigned long long* fix;
   float* gr;

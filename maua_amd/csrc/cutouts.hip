@@ -38,17 +38,21 @@ namespace {
 constexpr int CT_MAXT = 16;    // weights per output sample (cubic support 4 / scale: cutouts up to 4 x the perceptor's input size)
 constexpr int CT_BAND = 16;    // output rows per forward workgroup
 
+// (the order of cubic_f and of the table kernel below is the contract with the published algorithm's float32 tensor arithmetic: plain
+//  operators, contraction switched off in each body - the pragma is lexical)
 __device__ __forceinline__ float cubic_f(float x) {   // resize_right interp_methods.cubic, float32 like the tensor arithmetic there
-  const float a = fabsf(x), a2 = __fmul_rn(a, a), a3 = __fmul_rn(a2, a);
+#pragma clang fp contract(off)
+  const float a = fabsf(x), a2 = a * a, a3 = a2 * a;
   float r = 0.f;
-  if (a <= 1.f) r = __fadd_rn(__fsub_rn(__fmul_rn(1.5f, a3), __fmul_rn(2.5f, a2)), 1.f);
-  else if (a <= 2.f) r = __fadd_rn(__fsub_rn(__fadd_rn(__fmul_rn(-0.5f, a3), __fmul_rn(2.5f, a2)), __fmul_rn(4.f, a)), 2.f);
+  if (a <= 1.f) r = (1.5f * a3 - 2.5f * a2) + 1.f;
+  else if (a <= 2.f) r = ((-0.5f * a3 + 2.5f * a2) - 4.f * a) + 2.f;
   return r;
 }
 
 // one dimension of resize(out_shape = cs) for a cutout of `size` samples
 __global__ void cutout_tables_kernel(const int* __restrict__ rects, int n_cut, int cs, int* __restrict__ left, float* __restrict__ wts,
                                      int* __restrict__ taps_out) {
+#pragma clang fp contract(off)
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n_cut * cs) return;
   const int n = idx / cs, o = idx - n * cs;
@@ -56,20 +60,20 @@ __global__ void cutout_tables_kernel(const int* __restrict__ rects, int n_cut, i
   const double scale_d = (double)cs / (double)size;
   const float scale = (float)scale_d;
   float pf = (float)o / scale;
-  pf = __fadd_rn(pf, (float)((size - 1) / 2.0));
-  pf = __fsub_rn(pf, (float)((cs - 1) / (2.0 * scale_d)));
+  pf = pf + (float)((size - 1) / 2.0);
+  pf = pf - (float)((cs - 1) / (2.0 * scale_d));
   const bool aa = scale_d < 1.0;
   const double support = aa ? 4.0 / scale_d : 4.0;
   const double eps_d = 1.1920928955078125e-07;
-  const float lf = ceilf(__fsub_rn(__fsub_rn(pf, (float)(support / 2.0)), (float)eps_d));
+  const float lf = ceilf((pf - (float)(support / 2.0)) - (float)eps_d);
   const int l = (int)lf;
   int taps = (int)ceil(support - eps_d);
   if (taps > CT_MAXT) taps = CT_MAXT;   // (refused on the host before the launch)
   float w[CT_MAXT], sum = 0.f;
   for (int k = 0; k < taps; k++) {
-    const float arg = __fsub_rn(pf, (float)(l + k));
-    w[k] = aa ? __fmul_rn(scale, cubic_f(__fmul_rn(scale, arg))) : cubic_f(arg);
-    sum = __fadd_rn(sum, w[k]);
+    const float arg = pf - (float)(l + k);
+    w[k] = aa ? scale * cubic_f(scale * arg) : cubic_f(arg);
+    sum = sum + w[k];
   }
   if (sum == 0.f) sum = 1.f;
   left[idx] = l;
@@ -305,12 +309,34 @@ int launch_cutouts_vjp(hipStream_t stream, int dtype, const CutoutPlan& p, void*
 
 using namespace maua;
 
+// the host-side checks of the two entry points below, ahead of any scratch carving, copy or launch: sizes, each pass's own grid limits
+// (forward: cutout images ride in gridDim.z; gradient: also image planes in gridDim.z and rows in gridDim.y) and every HOST rectangle
+// (size >= 1, inside the image, no bits besides the two flags)
+static int check_cutout_call(const char* who, bool vjp, int B, int H, int W, const int* rects, int n_cut, int cut_size) {
+  MAUA_REQUIRE(B >= 0 && H > 0 && W > 0, std::string(who) + ": bad image shape");
+  MAUA_REQUIRE(n_cut > 0 && cut_size > 0, std::string(who) + ": n_cut and cut_size must be positive");
+  MAUA_REQUIRE((long)n_cut * B <= 65535, std::string(who) + ": at most 65535 cutout images per call");
+  if (vjp) {
+    MAUA_REQUIRE((long)B * 3 <= 65535 && H <= 65535, std::string(who) + ": at most 21845 images of at most 65535 rows per call");
+  }
+  for (int n = 0; n < n_cut; n++) {
+    const int rs = rects[3 * n], size = rs & CUT_SIZE_MASK, top = rects[3 * n + 1], left = rects[3 * n + 2];
+    MAUA_REQUIRE((rs & ~(CUT_SIZE_MASK | CUT_GREY | CUT_FLIP)) == 0 && size >= 1, std::string(who) + ": a rectangle's size is below 1 or carries unknown bits");
+    MAUA_REQUIRE(top >= 0 && left >= 0 && (long)top + size <= H && (long)left + size <= W, std::string(who) + ": a rectangle leaves the image");
+  }
+  MAUA_REQUIRE(std::min(H, W) <= 4 * (long)cut_size - 1, std::string(who) + ": images of more than 4 x the cut size need more than 16 filter taps");
+  return MAUA_OK;
+}
+
 extern "C" {
 
 // operator-level pieces (tests, other perceptors): the cutouts and their gradient on HOST rectangles [n_cut][3]
 int maua_cutouts(maua_ctx* ctx, const float* img, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul, float add,
                  const float* mean3, const float* std3, float* out) {
   MAUA_REQUIRE(ctx && img && rects && out && mean3 && std3, "maua_cutouts: NULL argument");
+  MAUA_REQUIRE((const void*)img != (const void*)out, "maua_cutouts: out aliases img");
+  if (int rc = check_cutout_call("maua_cutouts", false, B, H, W, rects, n_cut, cut_size)) return rc;
+  if (B == 0) return MAUA_OK;
   void* tables;
   int* rd;
   if (int rc = carve_scratch(ctx, [&](Scratch& s) { tables = s.take<char>(cutouts_table_bytes(n_cut, cut_size)); rd = s.take<int>((size_t)n_cut * 3); }))
@@ -327,6 +353,9 @@ int maua_cutouts(maua_ctx* ctx, const float* img, int B, int H, int W, const int
 int maua_cutouts_vjp(maua_ctx* ctx, const float* d_out, int B, int H, int W, const int* rects, int n_cut, int cut_size, float mul,
                      const float* std3, float* d_img) {
   MAUA_REQUIRE(ctx && d_out && rects && d_img && std3, "maua_cutouts_vjp: NULL argument");
+  MAUA_REQUIRE((const void*)d_out != (const void*)d_img, "maua_cutouts_vjp: d_img aliases d_out");
+  if (int rc = check_cutout_call("maua_cutouts_vjp", true, B, H, W, rects, n_cut, cut_size)) return rc;
+  if (B == 0) return MAUA_OK;
   void* tables;
   float* th;
   int* rd;

@@ -22,7 +22,7 @@
 //              tile * (wy * wx) and wy * wx exactly as the reference's in-place adds do, then divides.
 //   histogram  moments: a workgroup sums 11 numbers (3 sums, 6 products, min, max) over a fixed slice of pixels in a fixed tree; the
 //              slices' partials go to the host, which finishes mean / covariance and the two 3x3 square roots in float64.
-//   perlin     pass 1 evaluates the octave sum per pixel with individually rounded float32 operations in the reference's order and
+//   perlin     pass 1 evaluates the octave sum per pixel with individually rounded float32 operations (contraction off) in the reference's order and
 //              quantises to 8 bits (to_pil_image), writing per-workgroup min / max; pass 2 (one workgroup per channel) collapses them to
 //              the channel's extremes; pass 3 builds autocontrast's table from those and writes to_tensor's floats.  (Three
 //              launches, not one: the table needs the whole image's extremes, and every workgroup re-reducing the per-workgroup
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void image_resize_kernel(ImResizeArgs a) {
       acc = band_s[yl * a.W + x];
     }
     float* o = dst + (long)(y0 + yl) * a.Wo + x;
-    *o = a.accumulate ? __fadd_rn(__fadd_rn(*o, acc), a.add) : __fadd_rn(acc, a.add);
+    *o = a.accumulate ? (*o + acc) + a.add : acc + a.add;
   }
 }
 
@@ -120,6 +120,7 @@ __global__ __launch_bounds__(256) void destitch_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void restitch_kernel(const float* __restrict__ tiles, const float* __restrict__ wy,
                                                        const float* __restrict__ wx, float* __restrict__ out, TileGrid g, int H, int W,
                                                        int T) {
+#pragma clang fp contract(off)   // the reference's order: weight, product and both sums each round once
   const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, ch = blockIdx.z;
   if (X >= W) return;
   float acc = 0.f, norm = 0.f;
@@ -130,10 +131,10 @@ __global__ __launch_bounds__(256) void restitch_kernel(const float* __restrict__
     for (int c = 0; c < g.n_cols; c++) {
       const int x = X - g.xs[c];
       if (x < 0 || x >= T) continue;
-      const float w = __fmul_rn(vy, wx[c * T + x]);
+      const float w = vy * wx[c * T + x];
       const float t = tiles[(((long)(r * g.n_cols + c) * 3 + ch) * T + y) * T + x];
-      acc = __fadd_rn(acc, __fmul_rn(t, w));
-      norm = __fadd_rn(norm, w);
+      acc = acc + t * w;
+      norm = norm + w;
     }
   }
   out[((long)ch * H + Y) * W + X] = acc / norm;
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(256) void sharpen_kernel(const float* __restrict__ 
       for (int dx = -1; dx <= 1; dx++) acc = fmaf(dy == 0 && dx == 0 ? k5 : k1, px(y + dy, x + dx), acc);
     blur = acc;
   }
-  float r = __fadd_rn(__fmul_rn(strength, v), __fmul_rn(1.f - strength, blur));   // _blend: ratio * img + (1 - ratio) * degenerate
+  float r = strength * v + (1.f - strength) * blur;   // _blend: ratio * img + (1 - ratio) * degenerate
   r = fminf(fmaxf(r, 0.f), 1.f);
   out[(long)blockIdx.z * H * W + (long)y * W + x] = r * 2.f - 1.f;
 }
@@ -186,11 +187,11 @@ __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ 
       float sum = 0.f;
       for (int n = 0; n < navg; n++) {
         const float x = img[(((long)frame * navg + n) * 3 + c) * HW + p];
-        sum = __fadd_rn(sum, x);
+        sum = sum + x;
         s[9] = fminf(s[9], x); s[10] = fmaxf(s[10], x);
       }
       v[c] = navg > 1 ? sum / (float)navg : sum;
-      if (noise) v[c] = __fadd_rn(v[c], __fmul_rn(noise_scale, noise[((long)frame * 3 + c) * HW + p]));
+      if (noise) v[c] = v[c] + noise_scale * noise[((long)frame * 3 + c) * HW + p];
     }
     s[0] += v[0]; s[1] += v[1]; s[2] += v[2];
     s[3] = fmaf(v[0], v[0], s[3]); s[4] = fmaf(v[0], v[1], s[4]); s[5] = fmaf(v[0], v[2], s[5]);
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(256) void match_apply_kernel(const float* __restric
   float v[3];
   for (int c = 0; c < 3; c++) {
     v[c] = img[c * HW + p];
-    if (noise) v[c] = __fadd_rn(v[c], __fmul_rn(a.noise_scale, noise[c * HW + p]));
+    if (noise) v[c] = v[c] + a.noise_scale * noise[c * HW + p];
     v[c] -= a.mu_t[c];
   }
   for (int c = 0; c < 3; c++) {
@@ -245,23 +246,28 @@ struct PerlinArgs {
   int S_r, S_c;                   // width * scale0, height * scale0
 };
 
+// The order of these three functions is the contract with the reference (every operation rounds once, in ops/noise.py's order): plain
+// operators with contraction switched off in each body - the pragma is lexical, it does not reach a helper from its caller, and the
+// __f*_rn intrinsics do not stop the compiler from fusing a product into the sum that follows.
 __device__ __forceinline__ float perlin_interp(float t) {   // noise.py:90-91: 3 t^2 - 2 t^3
-  const float t2 = __fmul_rn(t, t), t3 = __fmul_rn(t2, t);
-  return __fsub_rn(__fmul_rn(3.f, t2), __fmul_rn(2.f, t3));
+#pragma clang fp contract(off)
+  const float t2 = t * t, t3 = t2 * t;
+  return 3.f * t2 - 2.f * t3;
 }
 
-// one octave's value at pixel (R, Cc): noise.py:94-106, every operation rounded on its own, in the reference's order
+// one octave's value at pixel (R, Cc): noise.py:94-106
 __device__ __forceinline__ float perlin_at(const float* gx, const float* gy, int h1, int scale, int R, int Cc) {
+#pragma clang fp contract(off)
   const int i = R / scale, a = R - i * scale, j = Cc / scale, b = Cc - j * scale;
   const float xs = (float)a / (float)scale, ys = (float)b / (float)scale;   // exact: scale is a power of two
-  const float wx = __fsub_rn(1.f, perlin_interp(xs)), wy = __fsub_rn(1.f, perlin_interp(ys));
-  const float x1 = __fsub_rn(1.f, xs), y1 = __fsub_rn(1.f, ys), wx1 = __fsub_rn(1.f, wx), wy1 = __fsub_rn(1.f, wy);
+  const float wx = 1.f - perlin_interp(xs), wy = 1.f - perlin_interp(ys);
+  const float x1 = 1.f - xs, y1 = 1.f - ys, wx1 = 1.f - wx, wy1 = 1.f - wy;
   const int i00 = i * h1 + j, i10 = (i + 1) * h1 + j, i01 = i * h1 + j + 1, i11 = (i + 1) * h1 + j + 1;
   float d = 0.f;
-  d = __fadd_rn(d, __fmul_rn(__fmul_rn(wx, wy), __fadd_rn(__fmul_rn(gx[i00], xs), __fmul_rn(gy[i00], ys))));
-  d = __fadd_rn(d, __fmul_rn(__fmul_rn(wx1, wy), __fadd_rn(__fmul_rn(-gx[i10], x1), __fmul_rn(gy[i10], ys))));
-  d = __fadd_rn(d, __fmul_rn(__fmul_rn(wx, wy1), __fsub_rn(__fmul_rn(gx[i01], xs), __fmul_rn(gy[i01], y1))));
-  d = __fadd_rn(d, __fmul_rn(__fmul_rn(wx1, wy1), __fsub_rn(__fmul_rn(-gx[i11], x1), __fmul_rn(gy[i11], y1))));
+  d = d + (wx * wy) * (gx[i00] * xs + gy[i00] * ys);
+  d = d + (wx1 * wy) * (-gx[i10] * x1 + gy[i10] * ys);
+  d = d + (wx * wy1) * (gx[i01] * xs - gy[i01] * y1);
+  d = d + (wx1 * wy1) * (-gx[i11] * x1 - gy[i11] * y1);
   return d;
 }
 
@@ -269,6 +275,7 @@ __device__ __forceinline__ float perlin_at(const float* gx, const float* gy, int
 // grid (ceil(S_r * S_c / 256), channels)
 __global__ __launch_bounds__(256) void perlin_octaves_kernel(PerlinArgs a, float* __restrict__ raw, uint8_t* __restrict__ q,
                                                              int* __restrict__ minmax) {
+#pragma clang fp contract(off)
   __shared__ int lo_s[256], hi_s[256];
   const long n = (long)a.S_r * a.S_c;
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -281,12 +288,12 @@ __global__ __launch_bounds__(256) void perlin_octaves_kernel(PerlinArgs a, float
     for (int k = 0; k < a.n_oct; k++) {
       const float* gx = a.grads + a.offs[ch * IM_MAX_OCT + k];
       const float* gy = gx + (long)(w + 1) * (h + 1);
-      v = __fadd_rn(v, __fmul_rn(perlin_at(gx, gy, h + 1, scale, R, Cc), a.oct[k]));
+      v = v + perlin_at(gx, gy, h + 1, scale, R, Cc) * a.oct[k];
       scale >>= 1; w <<= 1; h <<= 1;
     }
     if (raw) raw[ch * n + e] = v;
     const float c = fminf(fmaxf(v, 0.f), 1.f);
-    const int b = (int)__fmul_rn(c, 255.f);   // .byte(): truncation
+    const int b = (int)(c * 255.f);   // .byte(): truncation
     q[ch * n + e] = (uint8_t)b;
     lo = hi = b;
   }

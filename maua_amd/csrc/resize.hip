@@ -319,6 +319,7 @@ extern "C" {
 int maua_conv1d_reflect(maua_ctx* ctx, const float* x, float* y, const float* taps, int radius, int axis, long planes,
                         int H, int W) {
   MAUA_REQUIRE(ctx, "maua_conv1d_reflect: ctx is NULL");
+  MAUA_REQUIRE(planes >= 0 && H >= 0 && W >= 0, "maua_conv1d_reflect: negative size");
   const long total = planes * H * W;
   if (total == 0) return MAUA_OK;
   MAUA_REQUIRE(x && y && taps && x != y, "maua_conv1d_reflect: NULL or aliased argument");
@@ -333,6 +334,7 @@ int maua_conv1d_reflect(maua_ctx* ctx, const float* x, float* y, const float* ta
 // ---- adjoints (the gradient of a loss through `resample`, maua/ops/image.py:214-240: what autograd gives LPIPSGrads, grad.py:191-192)
 int maua_conv1d_reflect_vjp(maua_ctx* ctx, const float* gy, float* gx, const float* taps, int radius, int axis, long planes, int H, int W) {
   MAUA_REQUIRE(ctx, "maua_conv1d_reflect_vjp: ctx is NULL");
+  MAUA_REQUIRE(planes >= 0 && H >= 0 && W >= 0, "maua_conv1d_reflect_vjp: negative size");
   const long total = planes * H * W;
   if (total == 0) return MAUA_OK;
   MAUA_REQUIRE(gy && gx && taps && gy != gx, "maua_conv1d_reflect_vjp: NULL or aliased argument");
@@ -348,9 +350,11 @@ int maua_conv1d_reflect_vjp(maua_ctx* ctx, const float* gy, float* gx, const flo
 // 1-D gather passes (columns, then rows) over the outputs whose four clamped taps touch an input sample - no atomics
 int maua_resize2d_bicubic_vjp(maua_ctx* ctx, const float* gy, float* gx, int N, int C, int H, int W, int out_h, int out_w, int align_corners) {
   MAUA_REQUIRE(ctx, "maua_resize2d_bicubic_vjp: ctx is NULL");
+  MAUA_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0 && out_h >= 0 && out_w >= 0, "maua_resize2d_bicubic_vjp: negative size");
   const long planes = (long)N * C;
   if (planes * H * W == 0) return MAUA_OK;
-  MAUA_REQUIRE(gy && gx && out_h > 0 && out_w > 0, "maua_resize2d_bicubic_vjp: bad argument");
+  MAUA_REQUIRE(out_h > 0 && out_w > 0, "maua_resize2d_bicubic_vjp: an empty gradient image for a non-empty input");
+  MAUA_REQUIRE(gy && gx && gy != gx, "maua_resize2d_bicubic_vjp: NULL or aliased argument");
   float* tmp;
   if (int rc = carve_scratch(ctx, [&](Scratch& s) { tmp = s.take<float>((size_t)planes * out_h * W); })) return rc;
   const long t1 = planes * out_h * W, t2 = planes * H * W;
@@ -365,8 +369,10 @@ int maua_resize2d_bicubic_vjp(maua_ctx* ctx, const float* gy, float* gx, int N, 
 int maua_resize2d(maua_ctx* ctx, const void* x, void* y, int N, int C, int H, int W, int out_h, int out_w, int mode,
                   int pad_left, int pad_top, int pad_how, float pad_value, int dtype) {
   MAUA_REQUIRE(ctx, "maua_resize2d: ctx is NULL");
+  MAUA_REQUIRE(N >= 0 && C >= 0 && H >= 0 && W >= 0 && out_h >= 0 && out_w >= 0, "maua_resize2d: negative size");
   if ((long)N * C * out_h * out_w == 0) return MAUA_OK;
-  MAUA_REQUIRE(x && y, "maua_resize2d: NULL argument");
+  MAUA_REQUIRE(H > 0 && W > 0, "maua_resize2d: empty input");
+  MAUA_REQUIRE(x && y && x != y, "maua_resize2d: NULL or aliased argument");
   MAUA_REQUIRE(mode >= 0 && mode <= 2, "maua_resize2d: mode must be 0 (bicubic), 1 (pad / crop) or 2 (bicubic, align_corners)");
   ResizeArgs a{};
   a.align = mode == 2;
