@@ -534,6 +534,43 @@ int maua_secondary_load(maua_secondary* net, int index, int what, const float* h
 int maua_secondary_forward(maua_secondary* net, const float* x, const float* t, int B, int H, int W, float* v_out, float* pred_out,
                            float* eps_out);
 int maua_secondary_vjp(maua_secondary* net, const float* g_v, int B, int H, int W, float* g_x);
+/* operator-level forms of the small kernels that hold the guided-diffusion path together, for parity tests (no reference counterpart
+ * of their own): each launches the kernel the networks run, through the launcher the networks use.  Device pointers; a size of zero
+ * does nothing; refused with the entry point's name: a negative size, an unknown dtype, C that is not whole 16-byte pieces, a pixel
+ * stride below C, odd H or W where a 2 x 2 window is read, dim < 2.
+ * nn.py timestep_embedding: t [B] -> e [B][dim] = [cos(t f_i) | sin(t f_i)] (i < dim / 2; a zero last column when dim is odd), the
+ * argument t f_i a float32 product; freqs: the float32 table f_i = exp(-ln(10000) i / (dim / 2)) [dim / 2], or NULL: computed on the
+ * device. */
+int maua_timestep_embedding(maua_ctx* ctx, const float* t, const float* freqs, int B, int dim, float* e);
+/* the timestep MLP's and every ResBlock's emb_layers' row product, all f32: y [B][N] = act_out(W [N][K] . act_in(x [B][K]) + bias [N]);
+ * act 0 = none, 1 = SiLU (v / (1 + exp(-v))); bias may be NULL */
+int maua_linear_rows(maua_ctx* ctx, const float* x, const float* W, const float* bias, int B, int K, int N, int act_in, int act_out,
+                     float* y);
+/* the secondary model's glue (csrc/secondary.hip), NHWC tensors in dtype (MAUA_F32 or MAUA_BF16; a bf16 store is one round to nearest
+ * even of the f32 value), pixel strides in elements.
+ * input: x [B][3][HW] f32, t [B], wemb [8] -> out [B][HW][32] = [x | cos(2 pi t w_k) | sin(2 pi t w_k) | 13 zeros]
+ * output: vn [B][HW][32] (3 real channels), x, t -> planar f32 [B][3][HW] v, pred = x cos(t pi / 2) - v sin(t pi / 2), eps = x sin + v cos;
+ * any of the three may be NULL */
+int maua_secondary_input(maua_ctx* ctx, const float* x, const float* t, const float* wemb, int B, long HW, int dtype, void* out);
+int maua_secondary_output(maua_ctx* ctx, const void* vn, const float* x, const float* t, int B, long HW, int dtype, float* v, float* pred,
+                          float* eps);
+/* AvgPool2d(2): C channels at src (pixel stride src_stride) of the [B][H][W] grid -> dense dst [B][H / 2][W / 2][C]; H, W even */
+int maua_avgpool2_nhwc(maua_ctx* ctx, const void* src, long src_stride, int B, int H, int W, int C, int dtype, void* dst);
+/* F.interpolate(scale_factor=2, mode="bilinear", align_corners=False): dense src [B][h][w][C] -> C channels at dst (pixel stride
+ * dst_stride) of the [B][2 h][2 w] grid; and its adjoint: gout (pixel stride g_stride, [2 h][2 w]) -> dense gin [B][h][w][C], zeroed
+ * where the stored activation act (dense like gin; NULL: no mask) is not above 0.  Every product and sum rounds once. */
+int maua_bilinear_up2_nhwc(maua_ctx* ctx, const void* src, int B, int h, int w, int C, int dtype, void* dst, long dst_stride);
+int maua_bilinear_up2_nhwc_vjp(maua_ctx* ctx, const void* gout, long g_stride, const void* act, int B, int h, int w, int C, int dtype,
+                               void* gin);
+/* ReLU's gradient in place: dense g [n_pix][C] zeroed where act (pixel stride act_stride) is not above 0 */
+int maua_relu_mask_nhwc(maua_ctx* ctx, void* g, const void* act, long act_stride, long n_pix, int C, int dtype);
+/* where a skip leaves: out [B][H][W][C] (dense) = act > 0 ? gcat + 0.25 gpool[y / 2][x / 2] : 0; gcat, act: C channels at pixel stride
+ * cat_stride of the [B][H][W] grid; gpool dense [B][H / 2][W / 2][C]; H, W even */
+int maua_skip_grad_nhwc(maua_ctx* ctx, const void* gcat, const void* act, long cat_stride, const void* gpool, int B, int H, int W, int C,
+                        int dtype, void* out);
+/* the gradient's two layout kernels: to_nhwc 1: planar f32 src [B][3][HW] -> dst [B][HW][32] in dtype (channels 3.. zero); 0: src
+ * [B][HW][32] in dtype -> planar f32 dst [B][3][HW] */
+int maua_secondary_grad_layout(maua_ctx* ctx, const void* src, int B, long HW, int dtype, int to_nhwc, void* dst);
 /* operator-level forms of the UNet's building blocks, NHWC tensors in `dtype` (guided_diffusion/unet.py, nn.py):
  * QKVAttentionLegacy.forward - qkv [B][T][3 * heads * head_ch] with channel = head * 3 ch + {q | k | v} * ch + c (what
  * `qkv.reshape(bs * n_heads, ch * 3, length).split(ch, dim=1)` sees) -> out [B][T][heads * head_ch]; head_ch 32 or 64 */

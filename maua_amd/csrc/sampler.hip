@@ -18,6 +18,11 @@ using namespace maua;
 namespace {
 
 // ------------------------------------------------------------------------------------------------------ DDIM step
+// The step kernels below evaluate the reference's float32 tensor expressions in its order, every product, sum and quotient rounded
+// once: plain operators with contraction switched off in each body (the pragma is lexical).  __fmul_rn / __fadd_rn would not do: they
+// are inline operators to this compiler and the back end fuses them (latent.hip found the same); (k0 x - pred) / k1 cancels, so one
+// fused rounding is not small against the result.  expf in p_sample_step_kernel is the device library's: that sample is bounded, not exact.
+//
 // gaussian_diffusion.py ddim_sample for an epsilon-predicting model (clip_denoised False), in the reference's float32
 // operation order; coefficients per sample: cf[b] = {sqrt_recip_ac, sqrt_recipm1_ac, sqrt(1 - ac), sqrt(ac_prev),
 // sqrt(1 - ac_prev - sigma^2), sigma * nonzero_mask, 0, 0}.  model_out [B][Cm][HW] (eps = first C channels), x [B][C][HW].
@@ -25,6 +30,7 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict_
                                                         const float* __restrict__ grad, const float* __restrict__ noise,
                                                         const float* __restrict__ cf, int C, int Cm, long HW, long total,
                                                         float* __restrict__ sample, float* __restrict__ pred_out) {
+#pragma clang fp contract(off)
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const long chw = (long)C * HW;
@@ -54,6 +60,7 @@ __global__ __launch_bounds__(256) void p_sample_step_kernel(const float* __restr
                                                             const float* __restrict__ grad, const float* __restrict__ noise,
                                                             const float* __restrict__ cf, int C, long HW, long total,
                                                             float* __restrict__ sample, float* __restrict__ pred_out) {
+#pragma clang fp contract(off)
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const long chw = (long)C * HW;
@@ -79,6 +86,7 @@ __global__ __launch_bounds__(256) void plms_eps_kernel(const float* __restrict__
                                                        const float* __restrict__ grad, const float* __restrict__ cf, int C,
                                                        int Cm, long HW, long total, float* __restrict__ eps_out,
                                                        float* __restrict__ pred_out, float* __restrict__ pred_orig_out) {
+#pragma clang fp contract(off)
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const long chw = (long)C * HW;
@@ -107,13 +115,14 @@ struct PlmsEps { const float* e[4]; float w[4]; float div; int n; };
 __global__ __launch_bounds__(256) void plms_update_kernel(const float* __restrict__ x, PlmsEps pe, const float* __restrict__ pred,
                                                           const float* __restrict__ cf, long chw, long total,
                                                           float* __restrict__ sample) {
+#pragma clang fp contract(off)
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const int b = (int)(idx / chw);
   const float* k = cf + b * 8;
-  // (separately rounded products and sums, left to right, then the division: the order of the reference's expression)
-  float ep = __fmul_rn(pe.w[0], pe.e[0][idx]);
-  for (int i = 1; i < pe.n; i++) ep = __fadd_rn(ep, __fmul_rn(pe.w[i], pe.e[i][idx]));
+  // (separately rounded products and sums, left to right, then the division: the order of the reference's expression - contraction is off)
+  float ep = pe.w[0] * pe.e[0][idx];
+  for (int i = 1; i < pe.n; i++) ep = ep + pe.w[i] * pe.e[i][idx];
   ep = ep / pe.div;
   const float pp = k[0] * x[idx] - k[1] * ep;
   const float mean = pp * k[2] + k[3] * ep;
@@ -124,6 +133,7 @@ __global__ __launch_bounds__(256) void plms_update_kernel(const float* __restric
 __global__ __launch_bounds__(256) void axpby_rows_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                          const float* __restrict__ ab, long row, long total,
                                                          float* __restrict__ out) {
+#pragma clang fp contract(off)
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const int b = (int)(idx / row);
@@ -235,6 +245,7 @@ int maua_unet_graph_active(maua_unet* n, int* active) {
 int maua_ddim_step(maua_ctx* ctx, const float* x, const float* model_out, const float* cond_grad, const float* noise,
                    const float* coef, int B, int C, int Cm, long HW, float* sample, float* pred_xstart) {
   MAUA_REQUIRE(ctx, "maua_ddim_step: ctx is NULL");
+  MAUA_REQUIRE(B >= 0 && HW >= 0, "maua_ddim_step: a negative size");
   if (B == 0 || HW == 0) return MAUA_OK;
   MAUA_REQUIRE(x && model_out && coef && sample && C > 0 && Cm >= C, "maua_ddim_step: NULL argument");
   const long total = (long)B * C * HW;
@@ -251,6 +262,7 @@ int maua_ddim_step(maua_ctx* ctx, const float* x, const float* model_out, const 
 int maua_p_sample_step(maua_ctx* ctx, const float* x, const float* model_out, const float* cond_grad, const float* noise,
                        const float* coef, int B, int C, long HW, float* sample, float* pred_xstart) {
   MAUA_REQUIRE(ctx, "maua_p_sample_step: ctx is NULL");
+  MAUA_REQUIRE(B >= 0 && HW >= 0, "maua_p_sample_step: a negative size");
   if (B == 0 || HW == 0) return MAUA_OK;
   MAUA_REQUIRE(x && model_out && noise && coef && sample && C > 0, "maua_p_sample_step: NULL argument");
   const long total = (long)B * C * HW;
@@ -265,6 +277,7 @@ int maua_p_sample_step(maua_ctx* ctx, const float* x, const float* model_out, co
 int maua_plms_eps(maua_ctx* ctx, const float* x, const float* model_out, const float* cond_grad, const float* coef, int B,
                   int C, int Cm, long HW, float* eps, float* pred_xstart, float* pred_xstart_orig) {
   MAUA_REQUIRE(ctx, "maua_plms_eps: ctx is NULL");
+  MAUA_REQUIRE(B >= 0 && HW >= 0, "maua_plms_eps: a negative size");
   if (B == 0 || HW == 0) return MAUA_OK;
   MAUA_REQUIRE(x && model_out && coef && eps && C > 0 && Cm >= C, "maua_plms_eps: NULL argument");
   const long total = (long)B * C * HW;
@@ -280,6 +293,7 @@ int maua_plms_eps(maua_ctx* ctx, const float* x, const float* model_out, const f
 int maua_plms_update(maua_ctx* ctx, const float* x, const float* const* eps_list, const float* weights, int n_eps,
                      float divisor, const float* pred_xstart, const float* coef, int B, long chw, float* sample) {
   MAUA_REQUIRE(ctx, "maua_plms_update: ctx is NULL");
+  MAUA_REQUIRE(B >= 0 && chw >= 0, "maua_plms_update: a negative size");
   if (B == 0 || chw == 0) return MAUA_OK;
   MAUA_REQUIRE(x && eps_list && weights && pred_xstart && coef && sample && n_eps >= 1 && n_eps <= 4, "maua_plms_update: bad argument");
   MAUA_REQUIRE(divisor != 0.f, "maua_plms_update: divisor is zero");
@@ -299,6 +313,7 @@ int maua_plms_update(maua_ctx* ctx, const float* x, const float* const* eps_list
 // out[b] = ab[b][0] * x[b] + ab[b][1] * y[b] over rows of `row` elements (q_sample, gaussian_diffusion.py)
 int maua_axpby_rows(maua_ctx* ctx, const float* x, const float* y, const float* ab, int B, long row, float* out) {
   MAUA_REQUIRE(ctx, "maua_axpby_rows: ctx is NULL");
+  MAUA_REQUIRE(B >= 0 && row >= 0, "maua_axpby_rows: a negative size");
   if (B == 0 || row == 0) return MAUA_OK;
   MAUA_REQUIRE(x && y && ab && out, "maua_axpby_rows: NULL argument");
   const long total = (long)B * row;
@@ -440,6 +455,7 @@ static int mse_guide_grad(maua_ctx* ctx, const float* img, const float* target, 
 // (target_bstride = row) or one row for all samples (0).
 int maua_mse_guide_grad(maua_ctx* ctx, const float* img, const float* target, long target_bstride, float k, int B, long row, float* out) {
   MAUA_REQUIRE(ctx, "maua_mse_guide_grad: ctx is NULL");
+  MAUA_REQUIRE(B >= 0 && row >= 0, "maua_mse_guide_grad: a negative size");
   if (B == 0 || row == 0) return MAUA_OK;
   MAUA_REQUIRE(img && target && out, "maua_mse_guide_grad: NULL argument");
   int* flag;

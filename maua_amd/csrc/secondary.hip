@@ -37,6 +37,7 @@ constexpr int NCONV = 24;
 constexpr int CS[6] = {64, 128, 128, 256, 256, 512};
 
 __device__ __forceinline__ void bil_src(int o, int n, int& i0, int& i1, float& f) {
+#pragma clang fp contract(off)
   // F.interpolate(scale_factor=2, mode="bilinear", align_corners=False): src = (o + 0.5) / 2 - 0.5, clamped at 0
   float s = fmaxf((o + 0.5f) * 0.5f - 0.5f, 0.f);
   i0 = (int)s;
@@ -94,10 +95,13 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const T* __restrict__ src
   for (int e = 0; e < E; e++) Elem<T>::store(d + e, v[e] * 0.25f);
 }
 
-// bilinear x2: dense [h][w][C] -> C channels at dst (pixel stride dps) of the [2h][2w] grid
+// bilinear x2: dense [h][w][C] -> C channels at dst (pixel stride dps) of the [2h][2w] grid.  The order is pinned: every product and
+// sum of the expression below rounds once (plain operators, contraction off in this body - the pragma is lexical), so the map and its
+// adjoint are the same float32 numbers on every build; tests/diffusion_ref.py restates both.
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear_up2_kernel(const T* __restrict__ src, T* __restrict__ dst, int dps, int B, int h, int w,
                                                            int C) {
+#pragma clang fp contract(off)
   constexpr int E = 16 / (int)sizeof(T);
   const int ppp = C / E;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,11 +128,13 @@ __global__ __launch_bounds__(256) void bilinear_up2_kernel(const T* __restrict__
   for (int e = 0; e < E; e++) Elem<T>::store(o + e, v[e]);
 }
 
-// the adjoint of bilinear_up2: g_in[y][x] = sum over the output pixels that read (y, x) of their weight x g_out; then the ReLU
+// the adjoint of bilinear_up2: g_in[y][x] = sum over the output pixels that read (y, x) of their weight x g_out, rows then columns
+// ascending, each term (wy wx) g rounded at the product of the weights, at the product with g and at the sum; then the ReLU
 // mask of the stored activation `act` (dense [h][w][C]; NULL: none).  gout: C channels at pixel stride gps of the [2h][2w] grid.
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear_up2_adjoint_kernel(const T* __restrict__ gout, int gps, const T* __restrict__ act,
                                                                    T* __restrict__ gin, int B, int h, int w, int C) {
+#pragma clang fp contract(off)
   constexpr int E = 16 / (int)sizeof(T);
   const int ppp = C / E;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -359,14 +365,65 @@ int run_conv(maua_secondary* n, const PlainConv& c, bool transposed, const void*
     MAUA_HIP_CHECK(hipGetLastError());                                                                         \
   } while (0)
 
+// one launcher per glue kernel: the network (forward_t, vjp_t) and the operator-level entry points at the end of this file run through these
+template <typename T>
+int launch_sec_input(hipStream_t st, const float* x, const float* t, const float* wemb, int B, long HW, T* out) {
+  SEC_LAUNCH(sec_input_kernel<T>, (long)B * HW, x, t, wemb, out, B, HW);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_sec_output(hipStream_t st, const T* vn, const float* x, const float* t, int B, long HW, float* v, float* pred, float* eps) {
+  SEC_LAUNCH(sec_output_kernel<T>, (long)B * HW, vn, x, t, v, pred, eps, B, HW);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_avgpool2(hipStream_t st, const T* src, int sps, int B, int H, int W, int C, T* dst) {
+  constexpr int E = 16 / (int)sizeof(T);
+  SEC_LAUNCH(avgpool2_kernel<T>, (long)B * (H / 2) * (W / 2) * (C / E), src, sps, dst, B, H, W, C);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_bilinear_up2(hipStream_t st, const T* src, int B, int h, int w, int C, T* dst, int dps) {
+  constexpr int E = 16 / (int)sizeof(T);
+  SEC_LAUNCH(bilinear_up2_kernel<T>, (long)B * 4 * h * w * (C / E), src, dst, dps, B, h, w, C);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_bilinear_up2_adjoint(hipStream_t st, const T* gout, int gps, const T* act, int B, int h, int w, int C, T* gin) {
+  constexpr int E = 16 / (int)sizeof(T);
+  SEC_LAUNCH(bilinear_up2_adjoint_kernel<T>, (long)B * h * w * (C / E), gout, gps, act, gin, B, h, w, C);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_relu_mask(hipStream_t st, T* g, const T* act, int aps, long n_pix, int C) {
+  constexpr int E = 16 / (int)sizeof(T);
+  SEC_LAUNCH(relu_mask_kernel<T>, n_pix * (C / E), g, act, aps, n_pix, C);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_skip_grad(hipStream_t st, const T* gcat, const T* act, int cps, const T* gpool, int B, int H, int W, int C, T* out) {
+  constexpr int E = 16 / (int)sizeof(T);
+  SEC_LAUNCH(skip_grad_kernel<T>, (long)B * H * W * (C / E), gcat, act, cps, gpool, out, B, H, W, C);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_sec_grad_in(hipStream_t st, const float* g, int B, long HW, T* out) {
+  SEC_LAUNCH(sec_grad_in_kernel<T>, (long)B * HW, g, out, B, HW);
+  return MAUA_OK;
+}
+template <typename T>
+int launch_sec_grad_out(hipStream_t st, const T* g, int B, long HW, float* out) {
+  SEC_LAUNCH(sec_grad_out_kernel<T>, (long)B * HW, g, out, B, HW);
+  return MAUA_OK;
+}
+
 template <typename T>
 int forward_t(maua_secondary* n, const float* x, const float* t, int B, int H, int W, float* v_out, float* pred, float* eps) {
   hipStream_t st = n->ctx->stream;
   if (int rc = ensure_ws<T>(n, B, H, W)) return rc;
-  constexpr int E = 16 / (int)sizeof(T);
   const long HW = (long)H * W;
   int rc;
-  SEC_LAUNCH(sec_input_kernel<T>, (long)B * HW, x, t, n->wemb, (T*)n->in0, B, HW);
+  if ((rc = launch_sec_input<T>(st, x, t, n->wemb, B, HW, (T*)n->in0))) return rc;
   // encoder: level k's skip s_k lands in the upper channel slice of cat[k]
   const void* cur = n->in0;
   int cur_ps = 32;
@@ -374,7 +431,7 @@ int forward_t(maua_secondary* n, const float* x, const float* t, int B, int H, i
     const int h = H >> k, w = W >> k, cm = level_ch_main(k), csk = level_ch_skip(k), cps = cm + csk;
     if ((rc = run_conv(n, n->conv[2 * k], false, cur, cur_ps, n->a[k], CS[k], 0, B, h, w, true))) return rc;
     if ((rc = run_conv(n, n->conv[2 * k + 1], false, n->a[k], CS[k], n->cat[k], cps, cm, B, h, w, true))) return rc;
-    SEC_LAUNCH(avgpool2_kernel<T>, (long)B * (h / 2) * (w / 2) * (csk / E), (const T*)n->cat[k] + cm, cps, (T*)n->pool[k], B, h, w, csk);
+    if ((rc = launch_avgpool2<T>(st, (const T*)n->cat[k] + cm, cps, B, h, w, csk, (T*)n->pool[k]))) return rc;
     cur = n->pool[k];
     cur_ps = csk;
   }
@@ -391,7 +448,7 @@ int forward_t(maua_secondary* n, const float* x, const float* t, int B, int H, i
   // decoder: up into the lower slice of cat[k], two convolutions, k = 4 .. 1; then level 0
   for (int k = 4; k >= 0; k--) {
     const int h = H >> k, w = W >> k, cm = level_ch_main(k), cps = cm + level_ch_skip(k);
-    SEC_LAUNCH(bilinear_up2_kernel<T>, (long)B * h * w * (cm / E), (const T*)cur, (T*)n->cat[k], cps, B, h / 2, w / 2, cm);
+    if ((rc = launch_bilinear_up2<T>(st, (const T*)cur, B, h / 2, w / 2, cm, (T*)n->cat[k], cps))) return rc;
     if (k > 0) {
       const int i0 = 14 + 2 * (4 - k);
       const int c_mid = n->conv[i0].Cop, c_out = n->conv[i0 + 1].Cop;
@@ -403,7 +460,7 @@ int forward_t(maua_secondary* n, const float* x, const float* t, int B, int H, i
       if ((rc = run_conv(n, n->conv[23], false, n->dec[8], CS[0], n->vbuf, 32, 0, B, h, w, false))) return rc;
     }
   }
-  SEC_LAUNCH(sec_output_kernel<T>, (long)B * HW, (const T*)n->vbuf, x, t, v_out, pred, eps, B, HW);
+  if ((rc = launch_sec_output<T>(st, (const T*)n->vbuf, x, t, B, HW, v_out, pred, eps))) return rc;
   n->B = B; n->H = H; n->W = W;
   return MAUA_OK;
 }
@@ -411,15 +468,14 @@ int forward_t(maua_secondary* n, const float* x, const float* t, int B, int H, i
 template <typename T>
 int vjp_t(maua_secondary* n, const float* g_v, float* g_x) {
   hipStream_t st = n->ctx->stream;
-  constexpr int E = 16 / (int)sizeof(T);
   const int B = n->B, H = n->H, W = n->W;
   const long HW = (long)H * W;
   int rc;
   T *ga = (T*)n->ga, *gb = (T*)n->gb, *gcat = (T*)n->gcat, *gpool = (T*)n->gpool;
   // v = c23(d22): no ReLU on v
-  SEC_LAUNCH(sec_grad_in_kernel<T>, (long)B * HW, g_v, ga, B, HW);
+  if ((rc = launch_sec_grad_in<T>(st, g_v, B, HW, ga))) return rc;
   if ((rc = run_conv(n, n->conv[23], true, ga, 32, gb, CS[0], 0, B, H, W, false))) return rc;       // G(d22) before its mask
-  SEC_LAUNCH(relu_mask_kernel<T>, (long)B * HW * (CS[0] / E), gb, (const T*)n->dec[8], CS[0], (long)B * HW, CS[0]);
+  if ((rc = launch_relu_mask<T>(st, gb, (const T*)n->dec[8], CS[0], (long)B * HW, CS[0]))) return rc;
   // decoder backwards, level 0 .. 4: G(cat[k]) = convT(first decoder conv of the level); its lower slice goes down through the
   // up-sampling's adjoint, its upper slice waits in gcat_k for the encoder's way back.  The cat gradients of all levels are kept
   // (they are needed again on the way up): level k's lives in its own buffer - reuse the forward's bott / pool scratch? no: allocate
@@ -443,14 +499,13 @@ int vjp_t(maua_secondary* n, const float* g_v, float* g_x) {
       // gcur = G(second conv's output) -> through the second conv -> mask of the first conv's output
       const int c_mid = n->conv[i_first].Cop;
       if ((rc = run_conv(n, n->conv[i_first + 1], true, gcur, n->conv[i_first + 1].Cop, gother, c_mid, 0, B, h, w, false))) return rc;
-      SEC_LAUNCH(relu_mask_kernel<T>, lp * (c_mid / E), gother, (const T*)n->dec[2 * (4 - k)], c_mid, lp, c_mid);
+      if ((rc = launch_relu_mask<T>(st, gother, (const T*)n->dec[2 * (4 - k)], c_mid, lp, c_mid))) return rc;
       std::swap(gcur, gother);
     }
     if ((rc = run_conv(n, n->conv[i_first], true, gcur, n->conv[i_first].Cop, gcat_k[k], cps, 0, B, h, w, false))) return rc;
     // lower slice -> adjoint of the up-sampling -> G(source), masked by the source's stored activation
     const void* src_act = k == 4 ? n->bott[3] : n->dec[2 * (4 - (k + 1)) + 1];
-    SEC_LAUNCH(bilinear_up2_adjoint_kernel<T>, (long)B * (h / 2) * (w / 2) * (cm / E), (const T*)gcat_k[k], cps, (const T*)src_act, gother, B,
-               h / 2, w / 2, cm);
+    if ((rc = launch_bilinear_up2_adjoint<T>(st, (const T*)gcat_k[k], cps, (const T*)src_act, B, h / 2, w / 2, cm, gother))) return rc;
     std::swap(gcur, gother);
   }
   // bottleneck backwards: gcur = G(c13 out), masked
@@ -460,7 +515,7 @@ int vjp_t(maua_secondary* n, const float* g_v, float* g_x) {
     for (int i = 3; i >= 1; i--) {
       const int c_prev = n->conv[10 + i].Cip;
       if ((rc = run_conv(n, n->conv[10 + i], true, gcur, n->conv[10 + i].Cop, gother, c_prev, 0, B, h, w, false))) return rc;
-      SEC_LAUNCH(relu_mask_kernel<T>, lp * (c_prev / E), gother, (const T*)n->bott[i - 1], c_prev, lp, c_prev);
+      if ((rc = launch_relu_mask<T>(st, gother, (const T*)n->bott[i - 1], c_prev, lp, c_prev))) return rc;
       std::swap(gcur, gother);
     }
     if ((rc = run_conv(n, n->conv[10], true, gcur, n->conv[10].Cop, gpool, CS[4], 0, B, h, w, false))) return rc;   // G(pool[4])
@@ -469,14 +524,14 @@ int vjp_t(maua_secondary* n, const float* g_v, float* g_x) {
   for (int k = 4; k >= 0; k--) {
     const int h = H >> k, w = W >> k, cm = level_ch_main(k), csk = level_ch_skip(k), cps = cm + csk;
     const long lp = (long)B * h * w;
-    SEC_LAUNCH(skip_grad_kernel<T>, lp * (csk / E), (const T*)gcat_k[k] + cm, (const T*)n->cat[k] + cm, cps, (const T*)gpool, gcur, B, h, w, csk);
+    if ((rc = launch_skip_grad<T>(st, (const T*)gcat_k[k] + cm, (const T*)n->cat[k] + cm, cps, (const T*)gpool, B, h, w, csk, gcur))) return rc;
     if ((rc = run_conv(n, n->conv[2 * k + 1], true, gcur, csk, gother, CS[k], 0, B, h, w, false))) return rc;
-    SEC_LAUNCH(relu_mask_kernel<T>, lp * (CS[k] / E), gother, (const T*)n->a[k], CS[k], lp, CS[k]);
+    if ((rc = launch_relu_mask<T>(st, gother, (const T*)n->a[k], CS[k], lp, CS[k]))) return rc;
     // through the level's first conv: into the pool gradient of the level above (k > 0) or the network input (k = 0)
     const int cin = n->conv[2 * k].Cip;
     if ((rc = run_conv(n, n->conv[2 * k], true, gother, CS[k], k > 0 ? (void*)gpool : (void*)gcur, cin, 0, B, h, w, false))) return rc;
   }
-  SEC_LAUNCH(sec_grad_out_kernel<T>, (long)B * HW, (const T*)gcur, g_x, B, HW);
+  if ((rc = launch_sec_grad_out<T>(st, (const T*)gcur, B, HW, g_x))) return rc;
   return MAUA_OK;
 }
 
@@ -570,6 +625,112 @@ int maua_secondary_vjp(maua_secondary* n, const float* g_v, int B, int H, int W,
   MAUA_REQUIRE(n && g_v && g_x, "maua_secondary_vjp: NULL argument");
   MAUA_REQUIRE(n->B > 0 && B == n->B && H == n->H && W == n->W, "maua_secondary_vjp: call maua_secondary_forward with the same shape first");
   return dispatch_dtype<bf16_t, float>(n->dtype, "maua_secondary_vjp", [&](auto e) { return vjp_t<decltype(e)>(n, g_v, g_x); });
+}
+
+// ---- the glue kernels above as operators (include/maua_hip.h): each runs the network's own launcher
+namespace {
+// what every NHWC form checks in front of its launch: the dtype, the sizes' signs, whole 16-byte pieces per pixel, pixel strides
+int glue_check(const char* who, int dtype, int B, int H, int W, int C, long stride0, long stride1, bool even) {
+  const std::string w(who);
+  if (dtype != MAUA_F32 && dtype != MAUA_BF16) return fail(w + ": dtype must be MAUA_F32 or MAUA_BF16");
+  if (B < 0 || H < 0 || W < 0 || C < 0) return fail(w + ": a negative size");
+  if (C % elems_per_piece(dtype)) return fail(w + ": C must be whole 16-byte pieces");
+  if (even && ((H | W) & 1)) return fail(w + ": H and W must be even");
+  if (stride0 < C || stride1 < C) return fail(w + ": a pixel stride below C");
+  if (stride0 > 0x7fffffffL || stride1 > 0x7fffffffL) return fail(w + ": a pixel stride beyond int");
+  return MAUA_OK;
+}
+}  // namespace
+
+int maua_secondary_input(maua_ctx* ctx, const float* x, const float* t, const float* wemb, int B, long HW, int dtype, void* out) {
+  MAUA_REQUIRE(ctx, "maua_secondary_input: ctx is NULL");
+  MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_secondary_input: dtype must be MAUA_F32 or MAUA_BF16");
+  MAUA_REQUIRE(B >= 0 && HW >= 0, "maua_secondary_input: a negative size");
+  if (B == 0 || HW == 0) return MAUA_OK;
+  MAUA_REQUIRE(x && t && wemb && out, "maua_secondary_input: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_secondary_input",
+                                       [&](auto e) { return launch_sec_input<decltype(e)>(ctx->stream, x, t, wemb, B, HW, (decltype(e)*)out); });
+}
+
+int maua_secondary_output(maua_ctx* ctx, const void* vn, const float* x, const float* t, int B, long HW, int dtype, float* v, float* pred,
+                          float* eps) {
+  MAUA_REQUIRE(ctx, "maua_secondary_output: ctx is NULL");
+  MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_secondary_output: dtype must be MAUA_F32 or MAUA_BF16");
+  MAUA_REQUIRE(B >= 0 && HW >= 0, "maua_secondary_output: a negative size");
+  if (B == 0 || HW == 0) return MAUA_OK;
+  MAUA_REQUIRE(vn && x && t, "maua_secondary_output: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_secondary_output", [&](auto e) {
+    return launch_sec_output<decltype(e)>(ctx->stream, (const decltype(e)*)vn, x, t, B, HW, v, pred, eps);
+  });
+}
+
+int maua_avgpool2_nhwc(maua_ctx* ctx, const void* src, long src_stride, int B, int H, int W, int C, int dtype, void* dst) {
+  MAUA_REQUIRE(ctx, "maua_avgpool2_nhwc: ctx is NULL");
+  if (int rc = glue_check("maua_avgpool2_nhwc", dtype, B, H, W, C, src_stride, C, true)) return rc;
+  if (B == 0 || H == 0 || W == 0 || C == 0) return MAUA_OK;
+  MAUA_REQUIRE(src && dst, "maua_avgpool2_nhwc: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_avgpool2_nhwc", [&](auto e) {
+    return launch_avgpool2<decltype(e)>(ctx->stream, (const decltype(e)*)src, (int)src_stride, B, H, W, C, (decltype(e)*)dst);
+  });
+}
+
+int maua_bilinear_up2_nhwc(maua_ctx* ctx, const void* src, int B, int h, int w, int C, int dtype, void* dst, long dst_stride) {
+  MAUA_REQUIRE(ctx, "maua_bilinear_up2_nhwc: ctx is NULL");
+  if (int rc = glue_check("maua_bilinear_up2_nhwc", dtype, B, h, w, C, dst_stride, C, false)) return rc;
+  if (B == 0 || h == 0 || w == 0 || C == 0) return MAUA_OK;
+  MAUA_REQUIRE(src && dst, "maua_bilinear_up2_nhwc: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_bilinear_up2_nhwc", [&](auto e) {
+    return launch_bilinear_up2<decltype(e)>(ctx->stream, (const decltype(e)*)src, B, h, w, C, (decltype(e)*)dst, (int)dst_stride);
+  });
+}
+
+int maua_bilinear_up2_nhwc_vjp(maua_ctx* ctx, const void* gout, long g_stride, const void* act, int B, int h, int w, int C, int dtype,
+                               void* gin) {
+  MAUA_REQUIRE(ctx, "maua_bilinear_up2_nhwc_vjp: ctx is NULL");
+  if (int rc = glue_check("maua_bilinear_up2_nhwc_vjp", dtype, B, h, w, C, g_stride, C, false)) return rc;
+  if (B == 0 || h == 0 || w == 0 || C == 0) return MAUA_OK;
+  MAUA_REQUIRE(gout && gin, "maua_bilinear_up2_nhwc_vjp: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_bilinear_up2_nhwc_vjp", [&](auto e) {
+    return launch_bilinear_up2_adjoint<decltype(e)>(ctx->stream, (const decltype(e)*)gout, (int)g_stride, (const decltype(e)*)act, B, h, w, C,
+                                                    (decltype(e)*)gin);
+  });
+}
+
+int maua_relu_mask_nhwc(maua_ctx* ctx, void* g, const void* act, long act_stride, long n_pix, int C, int dtype) {
+  MAUA_REQUIRE(ctx, "maua_relu_mask_nhwc: ctx is NULL");
+  MAUA_REQUIRE(n_pix >= 0, "maua_relu_mask_nhwc: a negative size");
+  if (int rc = glue_check("maua_relu_mask_nhwc", dtype, 0, 0, 0, C, act_stride, C, false)) return rc;
+  if (n_pix == 0 || C == 0) return MAUA_OK;
+  MAUA_REQUIRE(g && act, "maua_relu_mask_nhwc: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_relu_mask_nhwc", [&](auto e) {
+    return launch_relu_mask<decltype(e)>(ctx->stream, (decltype(e)*)g, (const decltype(e)*)act, (int)act_stride, n_pix, C);
+  });
+}
+
+int maua_skip_grad_nhwc(maua_ctx* ctx, const void* gcat, const void* act, long cat_stride, const void* gpool, int B, int H, int W, int C,
+                        int dtype, void* out) {
+  MAUA_REQUIRE(ctx, "maua_skip_grad_nhwc: ctx is NULL");
+  if (int rc = glue_check("maua_skip_grad_nhwc", dtype, B, H, W, C, cat_stride, C, true)) return rc;
+  if (B == 0 || H == 0 || W == 0 || C == 0) return MAUA_OK;
+  MAUA_REQUIRE(gcat && act && gpool && out, "maua_skip_grad_nhwc: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_skip_grad_nhwc", [&](auto e) {
+    return launch_skip_grad<decltype(e)>(ctx->stream, (const decltype(e)*)gcat, (const decltype(e)*)act, (int)cat_stride,
+                                         (const decltype(e)*)gpool, B, H, W, C, (decltype(e)*)out);
+  });
+}
+
+int maua_secondary_grad_layout(maua_ctx* ctx, const void* src, int B, long HW, int dtype, int to_nhwc, void* dst) {
+  MAUA_REQUIRE(ctx, "maua_secondary_grad_layout: ctx is NULL");
+  MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_secondary_grad_layout: dtype must be MAUA_F32 or MAUA_BF16");
+  MAUA_REQUIRE(B >= 0 && HW >= 0, "maua_secondary_grad_layout: a negative size");
+  MAUA_REQUIRE(to_nhwc == 0 || to_nhwc == 1, "maua_secondary_grad_layout: to_nhwc is 0 or 1");
+  if (B == 0 || HW == 0) return MAUA_OK;
+  MAUA_REQUIRE(src && dst, "maua_secondary_grad_layout: NULL argument");
+  return dispatch_dtype<bf16_t, float>(dtype, "maua_secondary_grad_layout", [&](auto e) {
+    using T = decltype(e);
+    return to_nhwc ? launch_sec_grad_in<T>(ctx->stream, (const float*)src, B, HW, (T*)dst)
+                   : launch_sec_grad_out<T>(ctx->stream, (const T*)src, B, HW, (float*)dst);
+  });
 }
 
 }  // extern "C"

@@ -55,7 +55,7 @@ __global__ void timestep_embedding_kernel(const float* __restrict__ t, const flo
 }
 
 // y[b][n] = act_out(W[n] . act_in(x[b]) + bias[n]); one wave per output row n (W streamed once, coalesced), all B
-// samples per row (B <= 16 per pass).  act: 0 none, 1 SiLU.  The timestep MLP and every ResBlock's emb_layers (all in
+// samples per row (8 samples per pass; W is read again for every further 8).  act: 0 none, 1 SiLU.  The timestep MLP and every ResBlock's emb_layers (all in
 // f32 like the reference, whose convert_to_fp16 leaves nn.Linear alone).
 __global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                           const float* __restrict__ bias, float* __restrict__ y, int B, int K,
@@ -717,21 +717,54 @@ int maua::unet_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels)
   return dispatch_dtype<bf16_t, float>(n->dtype, "maua_unet", [&](auto e) { return run_vjp<decltype(e)>(n, g_out, g_x, g_channels); });
 }
 
-int maua::unet_emb_rows(maua_unet* n, hipStream_t st, const float* t, int rows, float* e0, float* e1, float* e2, float* emb) {
-  const int E = n->emb_dim, mc = n->mc, half = mc / 2;
-  hipLaunchKernelGGL(timestep_embedding_kernel, dim3((rows * half + 255) / 256), dim3(256), 0, st, t,
-                     n->freqs_loaded ? n->freqs : nullptr, e0, rows, mc);
-  hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e0, n->te0_w, n->te0_b, e1, rows, mc, E, 0, 1);
-  hipLaunchKernelGGL(linear_rows_kernel, dim3((E + 3) / 4), dim3(256), 0, st, e1, n->te2_w, n->te2_b, e2, rows, E, E, 0, 0);
-  hipLaunchKernelGGL(linear_rows_kernel, dim3((n->emb_total + 3) / 4), dim3(256), 0, st, e2, n->embw, n->embb, emb, rows, E,
-                     n->emb_total, 1, 0);
+// the launchers of the two small f32 kernels: the network's timestep path and the operator-level entry points run through these
+int maua::launch_timestep_embedding(hipStream_t st, const float* t, const float* freqs, int B, int dim, float* e) {
+  const long work = (long)B * (dim / 2);
+  MAUA_REQUIRE(work <= 0x7fffffffL - 256, "timestep_embedding: B * (dim / 2) does not fit the kernel's int index");
+  hipLaunchKernelGGL(timestep_embedding_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, t, freqs, e, B, dim);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
+}
+
+int maua::launch_linear_rows(hipStream_t st, const float* x, const float* W, const float* bias, int B, int K, int N, int act_in, int act_out,
+                             float* y) {
+  hipLaunchKernelGGL(linear_rows_kernel, dim3((N + 3) / 4), dim3(256), 0, st, x, W, bias, y, B, K, N, act_in, act_out);
+  MAUA_HIP_CHECK(hipGetLastError());
+  return MAUA_OK;
+}
+
+int maua::unet_emb_rows(maua_unet* n, hipStream_t st, const float* t, int rows, float* e0, float* e1, float* e2, float* emb) {
+  const int E = n->emb_dim, mc = n->mc;
+  if (int rc = launch_timestep_embedding(st, t, n->freqs_loaded ? n->freqs : nullptr, rows, mc, e0)) return rc;
+  if (int rc = launch_linear_rows(st, e0, n->te0_w, n->te0_b, rows, mc, E, 0, 1, e1)) return rc;
+  if (int rc = launch_linear_rows(st, e1, n->te2_w, n->te2_b, rows, E, E, 0, 0, e2)) return rc;
+  return launch_linear_rows(st, e2, n->embw, n->embb, rows, E, n->emb_total, 1, 0, emb);
 }
 
 bool maua::unet_planned(const maua_unet* n, int B, int H, int W) { return n->planned_key == shape_key(B, H, W) && B <= n->ones.b; }
 
 extern "C" {
+
+// nn.py timestep_embedding as an operator: t [B] -> e [B][dim] = [cos(t f_i) | sin(t f_i) | 0 if dim is odd], f_i = freqs[i] (a float32
+// table of dim / 2 values) or, freqs NULL, computed on the device
+int maua_timestep_embedding(maua_ctx* ctx, const float* t, const float* freqs, int B, int dim, float* e) {
+  MAUA_REQUIRE(ctx, "maua_timestep_embedding: ctx is NULL");
+  MAUA_REQUIRE(B >= 0, "maua_timestep_embedding: B is negative");
+  MAUA_REQUIRE(dim >= 2, "maua_timestep_embedding: dim must be at least 2");
+  if (B == 0) return MAUA_OK;
+  MAUA_REQUIRE(t && e, "maua_timestep_embedding: NULL argument");
+  return launch_timestep_embedding(ctx->stream, t, freqs, B, dim, e);
+}
+
+// y [B][N] = act_out(W [N][K] . act_in(x [B][K]) + bias [N]); act: 0 none, 1 SiLU; bias may be NULL
+int maua_linear_rows(maua_ctx* ctx, const float* x, const float* W, const float* bias, int B, int K, int N, int act_in, int act_out, float* y) {
+  MAUA_REQUIRE(ctx, "maua_linear_rows: ctx is NULL");
+  MAUA_REQUIRE(B >= 0 && K >= 0 && N >= 0, "maua_linear_rows: B, K or N is negative");
+  MAUA_REQUIRE((act_in == 0 || act_in == 1) && (act_out == 0 || act_out == 1), "maua_linear_rows: an activation is 0 (none) or 1 (SiLU)");
+  if (B == 0 || N == 0) return MAUA_OK;
+  MAUA_REQUIRE(y && (K == 0 || (x && W)), "maua_linear_rows: NULL argument");
+  return launch_linear_rows(ctx->stream, x, W, bias, B, K, N, act_in, act_out, y);
+}
 
 int maua_unet_create(maua_ctx* ctx, int image_size, int in_channels, int model_channels, int out_channels, int num_res_blocks,
                      const float* channel_mult, int n_mult, const int* attention_ds, int n_attn, int num_head_channels,

@@ -151,6 +151,10 @@ int unet_vjp(maua_unet* n, const float* g_out, float* g_x, int g_channels);
 // the timestep path: t [rows] (device) -> emb [rows][emb_total], every ResBlock's emb_layers output; e0 [rows][mc], e1 and e2
 // [rows][emb_dim]: scratch
 int unet_emb_rows(maua_unet* n, hipStream_t st, const float* t, int rows, float* e0, float* e1, float* e2, float* emb);
+// the two small f32 kernels at the top of unet.hip on a stream: e [B][dim] = timestep_embedding(t) (freqs: a float32 table or NULL);
+// y [B][N] = act_out(W [N][K] . act_in(x) + bias) (act: 0 none, 1 SiLU; bias or NULL).  Sizes are the caller's to check.
+int launch_timestep_embedding(hipStream_t st, const float* t, const float* freqs, int B, int dim, float* e);
+int launch_linear_rows(hipStream_t st, const float* x, const float* W, const float* bias, int B, int K, int N, int act_in, int act_out, float* y);
 // the arena is planned for an ordinary forward of this shape and `ones` covers B: such a forward allocates nothing (capturable)
 bool unet_planned(const maua_unet* n, int B, int H, int W);
 

@@ -374,6 +374,32 @@ class SpacedDiffusion:
         cf[:, 5] = sigma * (t != 0).float()
         return cf
 
+    def p_sample_coefficients(self, t):
+        """[len(t), 8] float32 coefficients of maua_p_sample_step: the float32 of the float64 tables at t, and t != 0."""
+        tt = torch.as_tensor(t).long().cpu().reshape(-1)
+        cf = torch.zeros((len(tt), 8), dtype=torch.float32)
+        cf[:, 0] = self._f32(self.sqrt_recip_alphas_cumprod, tt)
+        cf[:, 1] = self._f32(self.sqrt_recipm1_alphas_cumprod, tt)
+        cf[:, 2] = self._f32(self.posterior_mean_coef1, tt)
+        cf[:, 3] = self._f32(self.posterior_mean_coef2, tt)
+        cf[:, 4] = self._f32(self.posterior_log_variance_clipped, tt)
+        cf[:, 5] = self._f32(np.log(self.betas), tt)
+        cf[:, 6] = (tt != 0).float()
+        return cf
+
+    def plms_update_coefficients(self, t):
+        """[len(t), 8] float32 coefficients of maua_plms_update, evaluated like plms_sample evaluates them (float32 square roots of
+        the float32 alphas_cumprod_prev)."""
+        tt = torch.as_tensor(t).long().cpu().reshape(-1)
+        abp = self._f32(self.alphas_cumprod_prev, tt)
+        cf = torch.zeros((len(tt), 8), dtype=torch.float32)
+        cf[:, 0] = self._f32(self.sqrt_recip_alphas_cumprod, tt)
+        cf[:, 1] = self._f32(self.sqrt_recipm1_alphas_cumprod, tt)
+        cf[:, 2] = torch.sqrt(abp)
+        cf[:, 3] = torch.sqrt(1 - abp)
+        cf[:, 4] = (tt != 0).float()
+        return cf
+
     # -- gaussian_diffusion.py ---------------------------------------------------------------------------------
     def q_sample(self, x_start, t, noise=None):
         x = L.dev_tensor(x_start, torch.float32)
@@ -423,16 +449,7 @@ class SpacedDiffusion:
             raise NotImplementedError("p_sample needs the learned-range variance channels (learn_sigma)")
         grad = None if cond_fn is None else L.dev_tensor(cond_fn(x, mt), torch.float32)
         noise = torch.randn_like(x) if noise is None else L.dev_tensor(noise, torch.float32)
-        tt = torch.as_tensor(t).long().cpu().reshape(-1)
-        cf = torch.zeros((len(tt), 8), dtype=torch.float32)
-        cf[:, 0] = self._f32(self.sqrt_recip_alphas_cumprod, tt)
-        cf[:, 1] = self._f32(self.sqrt_recipm1_alphas_cumprod, tt)
-        cf[:, 2] = self._f32(self.posterior_mean_coef1, tt)
-        cf[:, 3] = self._f32(self.posterior_mean_coef2, tt)
-        cf[:, 4] = self._f32(self.posterior_log_variance_clipped, tt)
-        cf[:, 5] = self._f32(np.log(self.betas), tt)
-        cf[:, 6] = (tt != 0).float()
-        cf = L.dev_tensor(cf, torch.float32)
+        cf = L.dev_tensor(self.p_sample_coefficients(t), torch.float32)
         sample, pred = torch.empty_like(x), torch.empty_like(x)
         L.check(L.lib().maua_p_sample_step(L.ctx(x.device), L.ptr(x), L.ptr(out), L.ptr(grad), L.ptr(noise), L.ptr(cf), B, Cc,
                                            x[0, 0].numel(), L.ptr(sample), L.ptr(pred)))
@@ -450,15 +467,7 @@ class SpacedDiffusion:
         return eps, pred, pred_orig
 
     def _plms_update(self, x, t, eps_list, weights, divisor, pred):
-        tt = torch.as_tensor(t).long().cpu().reshape(-1)
-        abp = self._f32(self.alphas_cumprod_prev, tt)
-        cf = torch.zeros((len(tt), 8), dtype=torch.float32)
-        cf[:, 0] = self._f32(self.sqrt_recip_alphas_cumprod, tt)
-        cf[:, 1] = self._f32(self.sqrt_recipm1_alphas_cumprod, tt)
-        cf[:, 2] = torch.sqrt(abp)
-        cf[:, 3] = torch.sqrt(1 - abp)
-        cf[:, 4] = (tt != 0).float()
-        cf = L.dev_tensor(cf, torch.float32)
+        cf = L.dev_tensor(self.plms_update_coefficients(t), torch.float32)
         ptrs = (C.c_void_p * len(eps_list))(*[e.data_ptr() for e in eps_list])
         ws = (C.c_float * len(weights))(*weights)
         sample = torch.empty_like(x)

@@ -1,5 +1,5 @@
 """Guarded buffers and calls for the tests that drive the C ABI directly (tests/test_gpu_audio_kernels.py,
-tests/test_gpu_latent_kernels.py, tests/test_gpu_segment_kernels.py): G = 4096 guard elements on both sides of every buffer (NaN around
+tests/test_gpu_latent_kernels.py, tests/test_gpu_segment_kernels.py, tests/test_gpu_diffusion_kernels.py): G = 4096 guard elements on both sides of every buffer (NaN around
 inputs, a sentinel bit pattern in outputs), so that after a call the guards are intact, the body is fully written and no NaN leaked
 in.  A plain module, imported by name; it holds no test and no fixture."""
 import ctypes as C
@@ -12,8 +12,8 @@ from maua_amd import _lib as L
 
 DEV = "cuda"
 G = 4096                                            # guard elements on either side of every buffer
-SENT = {1: 0x5A, 4: 0x5A5A5A5A, 8: 0x5A5A5A5A5A5A5A5A}
-BITS = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+SENT = {1: 0x5A, 2: 0x5A5A, 4: 0x5A5A5A5A, 8: 0x5A5A5A5A5A5A5A5A}
+BITS = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 
 
 class Buf:
@@ -38,7 +38,8 @@ class Buf:
         return self.full.view(BITS[self.es])
 
     def get(self):
-        return self.full[G:G + self.n].cpu().numpy()
+        body = self.full[G:G + self.n]
+        return (body.float() if body.dtype == torch.bfloat16 else body).cpu().numpy()      # (numpy has no bfloat16: its float32 value)
 
     def check(self, what, nan_ok=False, written=None):
         b = self._bits()
