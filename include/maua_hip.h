@@ -205,10 +205,19 @@ int maua_synth_get_feature(maua_synth* net, int layer, int B, float* out_nchw);
  * (that mode keeps every layer's output in its own buffer; the styles and demodulation coefficients of that forward are still in
  * the layers' buffers).  noise / noise_batch_stride: what that forward was given.  g_img: device f32 [B,3,R,R] = d loss / d img;
  * g_ws: device f32 [B,num_ws,w_dim] = d loss / d ws (overwritten).  The walk goes from the last block to the first through the
- * layer gradients below; gradients to noise, biases and weights are not computed.  The gradient convolutions' weights are made
+ * layer gradients below; gradients to biases and weights are not computed (to the noise inputs: maua_synth_vjp_ex).  The gradient convolutions' weights are made
  * from the loaded ones on the first call: a network that only runs forwards allocates nothing for this.  Two calls give the same
  * bits.  No reference counterpart in code (the reference uses torch.autograd, sampling/langevin.py:100-127). */
 int maua_synth_vjp(maua_synth* net, const float* const* noise, const long* noise_batch_stride, int B, const float* g_img, float* g_ws);
+/* The same walk, and the gradient to the noise inputs.  g_noise: NULL (then exactly maua_synth_vjp: the same kernels, the same bits), or
+ * an array of num_layers device pointers, entry l = f32 gradient of layer l's noise map or NULL (not wanted: nothing is written).  With
+ * the layer's v = d u + noise strength + bias: g_noise[l][b][p] = strength sum_co g_v[b][p][co].  g_noise_batch_stride[l] (NULL: h w for
+ * every layer): h w = one map per sample; 0 = ONE map, the samples' gradients added in batch order (a shared input map, or the layer's
+ * noise_const).  The channel sum rides in the pass that forms g_v (32 channels per workgroup, a fixed tree), the groups and the batch
+ * are added in order by a second small kernel: no atomics, two calls give the same bits; g_ws has maua_synth_vjp's bits.  Refusals:
+ * maua_synth_vjp_check's, and overlapping samples of a g_noise entry. */
+int maua_synth_vjp_ex(maua_synth* net, const float* const* noise, const long* noise_batch_stride, int B, const float* g_img, float* g_ws,
+                      float* const* g_noise, const long* g_noise_batch_stride);
 /* host only: MAUA_OK if maua_synth_vjp would run; else MAUA_ERR and in maua_last_error() the cause - no kept forward of this batch
  * size; an option, a weight load or a resize after it; a resize or warp hook installed; an MAUA_F16 network; a forward that ran with
  * per-sample noise scales (maua_synth_set_noise_scale) */
@@ -1214,6 +1223,44 @@ int maua_philox_normal(maua_ctx* ctx, unsigned long long seed, unsigned long lon
 /* The benchmark clip's waveform on the device (0.3 sin(2 pi 220 t) + 0.2 (u - 0.5) [(2t mod 1) < 0.05] + 0.01 n; u / n =
  * streams 0 / 1 of `seed`): out device f32 [n].  No reference counterpart (synthetic input); host twin oracle/rng.py clip_audio. */
 int maua_philox_clip_audio(maua_ctx* ctx, unsigned long long seed, long n, double sample_rate, float* out);
+
+/* ---- latent-space projection (project.hip; maua_amd/projection.py drives it).  Restated from the published algorithm (Karras et al. 2020,
+ * "Analyzing and Improving the Image Quality of StyleGAN", appendix D): the reference's maua/parameterizations/stylegan.py is an empty file
+ * and the published projector.py is not among its files, so parity with that code is unpinned.  Every operation is rounded on its own (no
+ * fused multiply-add, IEEE division and square root) and every sum runs in ONE order: a range is cut into chunks of 4096 elements; in a
+ * chunk, thread t of 256 adds elements t, t + 256, ... in that order, the 256 sums fold as a[t] += a[t + s], s = 128, 64 .. 1, and the
+ * chunks are added in chunk order.  Reruns give the same bits; tests/projection_ref.py restates every entry in float32 to the bit.  All
+ * tensors device f32.  Every *_check is host only, needs no device and only checks pointers; ws: *_workspace_bytes() bytes, 256-byte aligned.
+ *
+ * maua_noise_reg: the noise regulariser of maps n [B][R][R], R a power of two in 4 .. 16384 (anything else is refused).  Per sample, n_0 = n;
+ * level k adds mean(n_k roll(n_k, 1, x))^2 + mean(n_k roll(n_k, 1, y))^2; after the level whose side is <= 8 it stops, else n_{k+1} =
+ * the 2 x 2 average of n_k ((a + b) + (c + d)) / 4 (maua_noise_reg_levels(R): 1 for 4 and 8, 2 for 16, 8 for 1024).  loss [B] (or NULL) =
+ * the levels in order, x then y.  grad [B][R][R] (or NULL): weight d loss / d n, written (accumulate 0) or added to what is there - the
+ * network's g_noise.  Closed form: level k gives 2 m_x / R_k^2 (left + right neighbour) + the same in y, plus a quarter of the coarser
+ * level's gradient at [i / 2][j / 2] (the pooling's adjoint), from the coarsest level down. */
+long maua_noise_reg_workspace_bytes(int B, int R);
+int maua_noise_reg_levels(int R);
+int maua_noise_reg_check(const float* n, int B, int R, const float* loss, const float* grad, const void* ws, long ws_bytes);
+int maua_noise_reg(maua_ctx* ctx, const float* n, int B, int R, float weight, float* loss, float* grad, int accumulate, void* ws,
+                   long ws_bytes);
+/* One Adam update (torch.optim.Adam without amsgrad or weight decay) of param [n] from grad [n] with the moments m, v [n]:
+ *   m = m + (1 - beta1) (g - m);  v = beta2 v + ((1 - beta2) g) g;  param = param - (step m) / (sqrt(v) inv_sqrt_bc2 + eps)
+ * step = lr / (1 - beta1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t) are the caller's, computed in double on the host. */
+int maua_adam_step_check(const float* param, const float* grad, const float* m, const float* v, long n, float beta1, float beta2, float eps);
+int maua_adam_step(maua_ctx* ctx, float* param, const float* grad, float* m, float* v, long n, float beta1, float beta2, float eps,
+                   float step, float inv_sqrt_bc2);
+/* n [maps][N] in place, per map: n -= mean(n); n *= 1 / sqrt(mean(n^2)).  A constant map becomes 0 x inf = NaN, as the published
+ * `buf -= buf.mean(); buf *= buf.square().mean().rsqrt()` makes it: not special-cased. */
+long maua_noise_renorm_workspace_bytes(int maps, long N);
+int maua_noise_renorm_check(const float* n, int maps, long N, const void* ws, long ws_bytes);
+int maua_noise_renorm(maua_ctx* ctx, float* n, int maps, long N, void* ws, long ws_bytes);
+/* ws [B][num_ws][w_dim] = w[b][r_in] + scale eps[b][r_in] (product, then sum); w and eps [B][w_rows][w_dim], w_rows = 1 (space w: r_in = 0)
+ * or num_ws (space w+: r_in = r); eps may be NULL (ws = w).  maua_latent_reduce: the adjoint for space w, g_w [B][w_dim] = sum_r
+ * g_ws[b][r], rows in order. */
+int maua_latent_expand_check(const float* w, int w_rows, const float* eps, const float* ws, int B, int num_ws, int w_dim);
+int maua_latent_expand(maua_ctx* ctx, const float* w, int w_rows, const float* eps, float scale, float* ws, int B, int num_ws, int w_dim);
+int maua_latent_reduce_check(const float* g_ws, const float* g_w, int B, int num_ws, int w_dim);
+int maua_latent_reduce(maua_ctx* ctx, const float* g_ws, float* g_w, int B, int num_ws, int w_dim);
 
 /* ---- neural cellular automaton (maua/nca/train.py:152-193, after znah's gitart_kunstformen_ca) ------------------------------------
  * One update of the f32 state x [B][chn][H][W]:  x += w2 . relu(w1 . perception(x) + b1) . mask

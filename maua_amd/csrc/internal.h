@@ -334,6 +334,9 @@ struct ModconvVjpArgs {
   void* g_x;            // d loss / d x [B][H][W][Ci] (T) or NULL (nobody wants it: the const input)
   int accumulate;       // g_x += instead of g_x =
   float* g_s;           // d loss / d s [B][Ci], through the modulation AND the demodulation coefficients
+  float* g_noise;       // d loss / d noise = strength sum_co g_v: [B][H up][W up], or one map summed over the batch (stride 0); or NULL
+  long g_noise_bstride;
+  float* npart;         // workspace of g_noise: modconv_vjp_noise_part_bytes()
   int B, H, W, Ci, Co, up;
   int act;              // MAUA_ACT_LINEAR / MAUA_ACT_LRELU
   float alpha, gain, clamp;
@@ -347,6 +350,7 @@ struct ModconvVjpArgs {
 };
 struct ModconvVjpWorkspace { size_t g_u, g_t, g_xm, part, g_d; };   // bytes
 ModconvVjpWorkspace modconv_vjp_workspace(int dtype, int B, int H, int W, int Ci, int Co, int up);
+size_t modconv_vjp_noise_part_bytes(int B, int H, int W, int Co, int up);   // per-group channel sums [B][Co / 32][H up][W up] f32
 int modconv_vjp_check(int dtype, const ModconvVjpArgs& a);   // host only: launch_modconv_vjp's refusals (everything but the workspaces)
 int launch_modconv_vjp(hipStream_t st, int dtype, const ModconvVjpArgs& a);
 // wg [t][ci][co] = W[co][ci][t] (up == 2 with flip: W[co][ci][8 - t]) from the float32 weights [Co][Ci][3][3]; wsq (optional) [Co][Ci]

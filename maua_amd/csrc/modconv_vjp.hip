@@ -28,12 +28,15 @@ namespace {
 int vjp_ppc(long P) { return (int)((std::max<long>(64, (P + 1023) / 1024) + 7) / 8 * 8); }
 int vjp_nchunk(long P) { return (int)((P + vjp_ppc(P) - 1) / vjp_ppc(P)); }
 
-// grid (chunks, Co / 32, B); thread = (pixel lane 0 .. 7, channel 0 .. 31)
-template <typename T>
+// grid (chunks, Co / 32, B); thread = (pixel lane 0 .. 7, channel 0 .. 31).  GN: also npart[b][group][p] = sum of g_v over the group's 32
+// channels (a pixel's channels are the 32 lanes of half a wave: five xor steps, the same tree every time), the gradient to the noise
+// before the sum over the groups (noise_grad_kernel)
+template <typename T, bool GN>
 __global__ __launch_bounds__(256) void act_vjp_kernel(const T* __restrict__ y, const T* __restrict__ g_y, const float* __restrict__ d,
                                                       const float* __restrict__ noise, long noise_bstride, float strength,
-                                                      const float* __restrict__ bias, T* __restrict__ g_u, float* __restrict__ part, int P,
-                                                      int Co, int ppc, int act, float alpha, float gain, float clamp) {
+                                                      const float* __restrict__ bias, T* __restrict__ g_u, float* __restrict__ part,
+                                                      float* __restrict__ npart, int P, int Co, int ppc, int act, float alpha, float gain,
+                                                      float clamp) {
   __shared__ float red[8][32];
   const int c = threadIdx.x & 31, pl = threadIdx.x >> 5;
   const int co = blockIdx.y * 32 + c, b = blockIdx.z, chunk = blockIdx.x;
@@ -44,18 +47,28 @@ __global__ __launch_bounds__(256) void act_vjp_kernel(const T* __restrict__ y, c
   const long base = (long)b * P * Co + co;
   const bool lrelu = act == MAUA_ACT_LRELU;
   float acc = 0.f;
-  for (int p = p0 + pl; p < p1; p += 8) {
-    const long e = base + (long)p * Co;
-    const float o = Elem<T>::load(y + e);
-    const bool neg = lrelu && !(o > 0.f);
-    float gv = Elem<T>::load(g_y + e) * gain * (neg ? alpha : 1.f);
-    if (clamp >= 0.f && !(fabsf(o) < clamp)) gv = 0.f;
-    if (d && gv != 0.f) {
-      float v = o / gain;
-      if (neg) v /= alpha;
-      acc += gv * ((v - (nz ? nz[p] * strength : 0.f) - bv) / dv);
+  for (int q = p0; q < p1; q += 8) {   // (every lane makes every trip: the channel sum below crosses lanes)
+    const int p = q + pl;
+    float gv = 0.f;
+    if (p < p1) {
+      const long e = base + (long)p * Co;
+      const float o = Elem<T>::load(y + e);
+      const bool neg = lrelu && !(o > 0.f);
+      gv = Elem<T>::load(g_y + e) * gain * (neg ? alpha : 1.f);
+      if (clamp >= 0.f && !(fabsf(o) < clamp)) gv = 0.f;
+      if (d && gv != 0.f) {
+        float v = o / gain;
+        if (neg) v /= alpha;
+        acc += gv * ((v - (nz ? nz[p] * strength : 0.f) - bv) / dv);
+      }
+      Elem<T>::store(g_u + e, gv * dv);
     }
-    Elem<T>::store(g_u + e, gv * dv);
+    if constexpr (GN) {
+      float t = gv;
+#pragma unroll
+      for (int m = 16; m >= 1; m >>= 1) t += __shfl_xor(t, m);
+      if (c == 0 && p < p1) npart[((long)b * gridDim.y + blockIdx.y) * P + p] = t;
+    }
   }
   red[pl][c] = acc;
   __syncthreads();
@@ -74,6 +87,22 @@ __global__ __launch_bounds__(256) void sum_chunks_kernel(const float* __restrict
   float t = 0.f;
   for (int k = 0; k < nchunk; k++) t += part[((long)b * nchunk + k) * C + c];
   out[(long)b * C + c] = t;
+}
+
+// g_noise[b][p] = strength * sum_g npart[b][g][p], the groups in order; nb == 1 with B > 1 (one shared map): the samples' sums added
+// in batch order before the product.  grid (cdiv(P, 256), nb)
+__global__ __launch_bounds__(256) void noise_grad_kernel(const float* __restrict__ npart, float* __restrict__ g_noise, long g_bstride, float strength,
+                                                         int P, int G, int B, int shared) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const int b0 = shared ? 0 : blockIdx.y, b1 = shared ? B : b0 + 1;
+  float t = 0.f;
+  for (int b = b0; b < b1; b++) {
+    float tb = npart[(long)b * G * P + p];
+    for (int g = 1; g < G; g++) tb += npart[((long)b * G + g) * P + p];
+    t = b == b0 ? tb : t + tb;
+  }
+  g_noise[(long)b0 * g_bstride + p] = strength * t;
 }
 
 // g_t[b][r][c][co] = sum_{a, e} f[a] f[e] g_u[b][r - a + 1][c - e + 1][co], r in [0, H2], c in [0, W2]; f = [1, 3, 3, 1] / 4
@@ -343,9 +372,18 @@ int launch_modconv_vjp_t(hipStream_t st, const ModconvVjpArgs& a) {
   const int Ho = a.H * a.up, Wo = a.W * a.up;
   const long Po = (long)Ho * Wo, Pi = (long)a.H * a.W;
   const int nco = vjp_nchunk(Po), nci = vjp_nchunk(Pi);
-  hipLaunchKernelGGL(act_vjp_kernel<T>, dim3(nco, a.Co / 32, a.B), dim3(256), 0, st, (const T*)a.y, (const T*)a.g_y, a.d, a.noise,
-                     a.noise_bstride, a.noise_strength, a.bias, (T*)a.g_u, a.d ? a.part : nullptr, (int)Po, a.Co, vjp_ppc(Po), a.act,
-                     a.alpha, a.gain, a.clamp);
+  if (a.g_noise) {
+    hipLaunchKernelGGL((act_vjp_kernel<T, true>), dim3(nco, a.Co / 32, a.B), dim3(256), 0, st, (const T*)a.y, (const T*)a.g_y, a.d, a.noise,
+                       a.noise_bstride, a.noise_strength, a.bias, (T*)a.g_u, a.d ? a.part : nullptr, a.npart, (int)Po, a.Co, vjp_ppc(Po),
+                       a.act, a.alpha, a.gain, a.clamp);
+    const int shared = a.g_noise_bstride == 0;
+    hipLaunchKernelGGL(noise_grad_kernel, dim3(cdiv((int)Po, 256), shared ? 1 : a.B), dim3(256), 0, st, a.npart, a.g_noise, a.g_noise_bstride,
+                       a.noise_strength, (int)Po, a.Co / 32, a.B, shared);
+  } else {
+    hipLaunchKernelGGL((act_vjp_kernel<T, false>), dim3(nco, a.Co / 32, a.B), dim3(256), 0, st, (const T*)a.y, (const T*)a.g_y, a.d, a.noise,
+                       a.noise_bstride, a.noise_strength, a.bias, (T*)a.g_u, a.d ? a.part : nullptr, nullptr, (int)Po, a.Co, vjp_ppc(Po),
+                       a.act, a.alpha, a.gain, a.clamp);
+  }
   if (a.d) hipLaunchKernelGGL(sum_chunks_kernel, dim3(cdiv(a.Co, 256), a.B), dim3(256), 0, st, a.part, a.g_d, nco, a.Co);
   const T* src = (const T*)a.g_u;
   int Hs = a.H, Ws = a.W, stp = 1, sg = -1, off = 1;
@@ -419,6 +457,8 @@ ModconvVjpWorkspace modconv_vjp_workspace(int dtype, int B, int H, int W, int Ci
   return w;
 }
 
+size_t modconv_vjp_noise_part_bytes(int B, int H, int W, int Co, int up) { return (size_t)B * (Co / 32) * H * up * W * up * 4; }
+
 int modconv_vjp_check(int dtype, const ModconvVjpArgs& a) {
   MAUA_REQUIRE(dtype == MAUA_F32 || dtype == MAUA_BF16, "maua_modconv_vjp: dtype must be MAUA_F32 or MAUA_BF16");
   MAUA_REQUIRE(a.B >= 0 && a.H > 0 && a.W > 0 && a.Ci > 0 && a.Co > 0, "maua_modconv_vjp: bad shape");
@@ -436,7 +476,9 @@ int modconv_vjp_check(int dtype, const ModconvVjpArgs& a) {
 
 int launch_modconv_vjp(hipStream_t st, int dtype, const ModconvVjpArgs& a) {
   if (int rc = modconv_vjp_check(dtype, a)) return rc;
-  MAUA_REQUIRE(a.wg && a.g_u && a.g_xm && a.part && (a.up == 1 || a.g_t) && (!a.d || (a.g_d && a.wsq)), "maua_modconv_vjp: NULL workspace");
+  MAUA_REQUIRE(a.wg && a.g_u && a.g_xm && a.part && (a.up == 1 || a.g_t) && (!a.d || (a.g_d && a.wsq)) && (!a.g_noise || a.npart),
+               "maua_modconv_vjp: NULL workspace");
+  MAUA_REQUIRE(!a.g_noise || a.g_noise_bstride == 0 || a.g_noise_bstride >= (long)a.H * a.up * a.W * a.up, "maua_modconv_vjp: samples of g_noise overlap");
   if (a.B == 0) return MAUA_OK;
   return dispatch_dtype<bf16_t, float>(dtype, "maua_modconv_vjp", [&](auto t) { return launch_modconv_vjp_t<decltype(t)>(st, a); });
 }

@@ -53,6 +53,8 @@ struct SynthVjpState {
   float* g_d = nullptr;
   float* g_s = nullptr;      // [B][max channels]
   float* g_wmod = nullptr;   // [B][3][max channels]
+  float* npart = nullptr;    // maua_synth_vjp_ex with g_noise: [B][max Co / 32 x pixels] per-group channel sums (allocated on first use)
+  int npart_bcap = 0;
 };
 void synth_vjp_release(SynthVjpState& v, bool weights_too, std::vector<ConvLayer>& convs);   // synth_vjp.hip
 

@@ -23,10 +23,10 @@ void synth_vjp_release(SynthVjpState& v, bool weights_too, std::vector<ConvLayer
     hipFree(v.gfeat[i]); v.gfeat[i] = nullptr;
     hipFree(v.gimg[i]); v.gimg[i] = nullptr;
   }
-  hipFree(v.g_u); hipFree(v.g_t); hipFree(v.g_xm); hipFree(v.part); hipFree(v.g_d); hipFree(v.g_s); hipFree(v.g_wmod);
+  hipFree(v.g_u); hipFree(v.g_t); hipFree(v.g_xm); hipFree(v.part); hipFree(v.g_d); hipFree(v.g_s); hipFree(v.g_wmod); hipFree(v.npart);
   v.g_u = v.g_t = nullptr;
-  v.g_xm = v.part = v.g_d = v.g_s = v.g_wmod = nullptr;
-  v.bcap = 0;
+  v.g_xm = v.part = v.g_d = v.g_s = v.g_wmod = v.npart = nullptr;
+  v.bcap = v.npart_bcap = 0;
   if (weights_too) {
     for (auto& c : convs) {
       hipFree(c.wg);
@@ -91,6 +91,21 @@ int ensure_vjp(maua_synth* n, int B) {
   return MAUA_OK;
 }
 
+// the per-group channel sums of the noise gradient: only a walk that was asked for g_noise allocates them
+int ensure_noise_part(maua_synth* n, int B) {
+  SynthVjpState& v = n->vjp;
+  if (B <= v.npart_bcap) return MAUA_OK;
+  MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
+  hipFree(v.npart);
+  v.npart = nullptr;
+  v.npart_bcap = 0;
+  size_t bytes = 0;
+  for (auto& c : n->convs) bytes = std::max(bytes, modconv_vjp_noise_part_bytes(B, c.ih, c.iw, c.Co, c.up));
+  MAUA_HIP_CHECK(hipMalloc((void**)&v.npart, bytes));
+  v.npart_bcap = B;
+  return MAUA_OK;
+}
+
 }  // namespace
 }  // namespace maua
 
@@ -99,9 +114,23 @@ using namespace maua;
 extern "C" int maua_synth_vjp_check(const maua_synth* net, int B) { return synth_vjp_check(net, B); }
 
 extern "C" int maua_synth_vjp(maua_synth* n, const float* const* noise, const long* noise_bstride, int B, const float* g_img, float* g_ws) {
+  return maua_synth_vjp_ex(n, noise, noise_bstride, B, g_img, g_ws, nullptr, nullptr);
+}
+
+extern "C" int maua_synth_vjp_ex(maua_synth* n, const float* const* noise, const long* noise_bstride, int B, const float* g_img, float* g_ws,
+                                 float* const* g_noise, const long* g_noise_bstride) {
   if (int rc = synth_vjp_check(n, B)) return rc;
   MAUA_REQUIRE(g_img && g_ws, "maua_synth_vjp: NULL argument");
+  bool want_noise = false;
+  for (size_t l = 0; g_noise && l < n->convs.size(); l++) {
+    if (!g_noise[l]) continue;
+    want_noise = true;
+    const long hw = (long)n->convs[l].oh * n->convs[l].ow;
+    MAUA_REQUIRE(!g_noise_bstride || g_noise_bstride[l] == 0 || g_noise_bstride[l] >= hw, "maua_synth_vjp_ex: samples of g_noise overlap");
+  }
   if (int rc = ensure_vjp(n, B)) return rc;
+  if (want_noise)
+    if (int rc = ensure_noise_part(n, B)) return rc;
   SynthVjpState& v = n->vjp;
   hipStream_t st = n->ctx->stream;
   MAUA_HIP_CHECK(hipMemsetAsync(g_ws, 0, (size_t)B * n->num_ws * n->w_dim * sizeof(float), st));
@@ -118,6 +147,9 @@ extern "C" int maua_synth_vjp(maua_synth* n, const float* const* noise, const lo
     a.noise_bstride = given ? (noise_bstride ? noise_bstride[l] : (long)c.oh * c.ow) : 0;
     a.noise_strength = (n->nv_compat & 2) ? c.noise_strength : 1.f;
     a.bias = c.bias; a.g_x = g_x; a.accumulate = 0; a.g_s = v.g_s;
+    if (g_noise && g_noise[l]) {   // (no stride array: one map per sample)
+      a.g_noise = g_noise[l]; a.g_noise_bstride = g_noise_bstride ? g_noise_bstride[l] : (long)c.oh * c.ow; a.npart = v.npart;
+    }
     a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = c.up;
     a.act = MAUA_ACT_LRELU; a.alpha = 0.2f; a.gain = std::sqrt(2.0f); a.clamp = 256.f;   // (synth.hip lrelu_epilogue)
     a.g_u = v.g_u; a.g_t = v.g_t; a.g_xm = v.g_xm; a.part = v.part; a.g_d = v.g_d;

@@ -439,10 +439,15 @@ class SynthesisNetwork(torch.nn.Module):
             return out
         return img if rgb8_out is None else rgb8_out
 
-    def vjp(self, g_img, noise=None):
+    def vjp(self, g_img, noise=None, noise_grad=False):
         """d loss / d ws [B, num_ws, w_dim] from ``g_img`` = d loss / d img [B, 3, R, R], for the last forward - which must have run
         with ``keep_features(True)``, at this batch size and with this ``noise`` (maua_synth_vjp: the walk back through every layer's
-        hand-written gradient kernels; 'skip' architecture, float32 or bfloat16 networks, no resize / warp hooks, no RawNoise)."""
+        hand-written gradient kernels; 'skip' architecture, float32 or bfloat16 networks, no resize / warp hooks, no RawNoise).
+
+        ``noise_grad``: True - also the gradient to every layer's noise input, returned as ``(g_ws, [g_noise_l])`` (maua_synth_vjp_ex).
+        g_noise_l has the shape of the map the layer read: [B, 1, h, w] for per-sample maps, [1, 1, h, w] (the samples' gradients added
+        in batch order) for one shared map or the layer's own noise_const.  A sequence instead of True chooses per layer: None / False
+        (not wanted: None comes back), True, or a float32 device tensor of that shape to be written."""
         net = self._handle()
         g_img = L.dev_tensor(g_img, torch.float32)
         B = g_img.shape[0]
@@ -453,9 +458,30 @@ class SynthesisNetwork(torch.nn.Module):
             raise NotImplementedError("un-normalised noise maps (RawNoise) are not differentiated: pass noise.normalised()")
         ptrs, strides, keep = self._noise_args(noise, B)
         g_ws = torch.empty((B, self.num_ws, self.w_dim), dtype=torch.float32, device=g_img.device)
-        L.check(L.lib().maua_synth_vjp(net, ptrs, strides, B, L.ptr(g_img), L.ptr(g_ws)))
+        if noise_grad is False or noise_grad is None:
+            L.check(L.lib().maua_synth_vjp(net, ptrs, strides, B, L.ptr(g_img), L.ptr(g_ws)))
+            del keep
+            return g_ws
+        n = self.num_layers
+        want = [True] * n if noise_grad is True else list(noise_grad) + [None] * (n - len(noise_grad))
+        g_ptrs, g_strides, g_noise = (C.c_void_p * n)(), (C.c_long * n)(), []
+        for l in range(n):
+            h, w = self.layer_size(l)
+            nb = B if strides is not None and strides[l] != 0 else 1
+            t = want[l]
+            if t is None or t is False:
+                g_ptrs[l], g_strides[l] = None, 0
+                g_noise.append(None)
+                continue
+            if t is True:
+                t = torch.empty((nb, 1, h, w), dtype=torch.float32, device=g_img.device)
+            elif not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (nb, 1, h, w)):
+                raise ValueError(f"noise_grad[{l}] must be a contiguous float32 device tensor [{nb}, 1, {h}, {w}]")
+            g_ptrs[l], g_strides[l] = t.data_ptr(), (0 if nb == 1 else h * w)
+            g_noise.append(t)
+        L.check(L.lib().maua_synth_vjp_ex(net, ptrs, strides, B, L.ptr(g_img), L.ptr(g_ws), g_ptrs, g_strides))
         del keep
-        return g_ws
+        return g_ws, g_noise
 
     def get_feature(self, layer, B):
         shp = self.layer_shapes()[layer]
