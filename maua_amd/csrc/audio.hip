@@ -639,12 +639,15 @@ using namespace maua;
 
 // The twiddle / window tables are tiny constants; they are computed on the host in double and cached per ctx.
 namespace {
-struct AudioTables {
+struct AudioTables {   // (views)
   float2* tw = nullptr;
   float* win = nullptr;
   float2* tw_big = nullptr;   // exp(-2 pi i k / GFFT), k < GFFT / 2: the general entry points above 2048 points
 };
 static thread_local std::vector<std::pair<maua_ctx*, AudioTables>> g_tables;
+// their owners, alive until the process exits: on the heap and never deleted, so that no destructor frees device memory after the
+// runtime has shut down
+static thread_local std::vector<DevBuf>* g_table_bufs = nullptr;
 
 int get_tables(maua_ctx* ctx, AudioTables& t) {
   for (auto& p : g_tables)
@@ -659,8 +662,10 @@ int get_tables(maua_ctx* ctx, AudioTables& t) {
     tw[k] = make_float2((float)cos(a), (float)sin(a));
   }
   for (int i = 0; i < NFFT; i++) win[i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * i / NFFT));  // periodic Hann
-  MAUA_HIP_CHECK(hipMalloc((void**)&t.tw, sizeof(float2) * tw.size()));
-  MAUA_HIP_CHECK(hipMalloc((void**)&t.win, sizeof(float) * win.size()));
+  DevBuf b_tw, b_win, b_big;   // (a failure below frees what was allocated)
+  if (int rc = b_tw.alloc(sizeof(float2) * tw.size())) return rc;
+  if (int rc = b_win.alloc(sizeof(float) * win.size())) return rc;
+  t.tw = b_tw.as<float2>(); t.win = b_win.as<float>();
   MAUA_HIP_CHECK(hipMemcpy(t.tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
   MAUA_HIP_CHECK(hipMemcpy(t.win, win.data(), sizeof(float) * win.size(), hipMemcpyHostToDevice));
   std::vector<float2> twb(GFFT / 2);
@@ -668,8 +673,11 @@ int get_tables(maua_ctx* ctx, AudioTables& t) {
     double a = -2.0 * M_PI * k / GFFT;
     twb[k] = make_float2((float)cos(a), (float)sin(a));
   }
-  MAUA_HIP_CHECK(hipMalloc((void**)&t.tw_big, sizeof(float2) * twb.size()));
+  if (int rc = b_big.alloc(sizeof(float2) * twb.size())) return rc;
+  t.tw_big = b_big.as<float2>();
   MAUA_HIP_CHECK(hipMemcpy(t.tw_big, twb.data(), sizeof(float2) * twb.size(), hipMemcpyHostToDevice));
+  if (!g_table_bufs) g_table_bufs = new std::vector<DevBuf>();
+  for (DevBuf* b : {&b_tw, &b_win, &b_big}) g_table_bufs->push_back(std::move(*b));
   g_tables.push_back({ctx, t});
   return MAUA_OK;
 }

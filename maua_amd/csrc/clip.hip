@@ -195,58 +195,45 @@ __global__ __launch_bounds__(256) void zero16_kernel(u32x4* __restrict__ p, long
 
 }  // namespace
 
-static void free_ws(maua_clip* n) {
-  for (void** p : {&n->patches, &n->pe, &n->tok, &n->x_last, &n->lno, &n->act, &n->dxa, &n->dxb, &n->dqkv, &n->dwide, &n->dtmp,
-                   (void**)&n->st_pre, (void**)&n->delta, (void**)&n->embed, (void**)&n->loss}) {
-    dfree(*p);
-    *p = nullptr;
-  }
-  for (auto& l : n->K)
-    for (void** p : {&l.x, &l.qkv, &l.ao, &l.xm, &l.h, (void**)&l.st1, (void**)&l.st2, (void**)&l.lse}) {
-      dfree(*p);
-      *p = nullptr;
-    }
-  n->cap = 0; n->keep = 0; n->kept_N = 0;
-  n->epoch++;
-}
-
 int ensure_ws(maua_clip* n, long N, int keep) {
   if (N <= n->cap && keep <= n->keep) return MAUA_OK;
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
   N = std::max(N, n->cap);
   keep = std::max(keep, n->keep);
-  free_ws(n);
+  n->cap = 0; n->keep = 0; n->kept_N = 0;
+  n->epoch++;   // (every piece moves)
   const size_t es = n->esize, w = n->width, M = (size_t)N * n->Tk, Mp = (size_t)N * n->G * n->G;
-  int rc = dalloc(&n->patches, Mp * n->kpp * es);
-  if (!rc) rc = dalloc(&n->pe, Mp * w * es);
-  if (!rc) rc = dalloc(&n->tok, M * w * es);
-  if (!rc) rc = dalloc(&n->x_last, M * w * es);
-  if (!rc) rc = dalloc(&n->lno, M * w * es);
-  if (!rc) rc = dalloc(&n->act, M * 4 * w * es);
-  if (!rc) rc = dalloc((void**)&n->st_pre, M * 2 * 4);
-  if (!rc) rc = dalloc((void**)&n->embed, (size_t)N * n->E * 4);
-  if (!rc) rc = dalloc((void**)&n->loss, (size_t)N * 4);
-  if (!rc && keep) {
-    rc = dalloc(&n->dxa, M * w * es);
-    if (!rc) rc = dalloc(&n->dxb, M * w * es);
-    if (!rc) rc = dalloc(&n->dqkv, M * 3 * w * es);
-    if (!rc) rc = dalloc(&n->dwide, std::max(M * 4 * w, Mp * n->kpp) * es);   // (d act [M][4 w], later d patches [Mp][kpp])
-    if (!rc) rc = dalloc(&n->dtmp, M * w * es);
-    if (!rc) rc = dalloc((void**)&n->delta, (size_t)N * n->heads * n->Tk * 4);
-  }
-  const int nl = keep ? n->layers : 1;
-  for (int i = 0; i < nl && !rc; i++) {
-    BlockActs& l = n->K[i];
-    rc = dalloc(&l.x, M * w * es);
-    if (!rc) rc = dalloc(&l.qkv, M * 3 * w * es);
-    if (!rc) rc = dalloc(&l.ao, M * w * es);
-    if (!rc) rc = dalloc(&l.xm, M * w * es);
-    if (!rc) rc = dalloc(&l.h, M * 4 * w * es);
-    if (!rc) rc = dalloc((void**)&l.st1, M * 2 * 4);
-    if (!rc) rc = dalloc((void**)&l.st2, M * 2 * 4);
-    if (!rc) rc = dalloc((void**)&l.lse, (size_t)N * n->heads * n->Tk * 4);
-  }
-  if (rc) { free_ws(n); return fail("maua_clip: out of device memory for the image tower's activations"); }
+  auto layout = [&](Scratch& s) {
+    auto take = [&](size_t elems) -> void* { return s.take<char>(elems * es); };
+    n->patches = take(Mp * n->kpp);
+    n->pe = take(Mp * w);
+    n->tok = take(M * w);
+    n->x_last = take(M * w);
+    n->lno = take(M * w);
+    n->act = take(M * 4 * w);
+    n->st_pre = s.take<float>(M * 2);
+    n->embed = s.take<float>((size_t)N * n->E);
+    n->loss = s.take<float>((size_t)N);
+    n->dxa = keep ? take(M * w) : nullptr;
+    n->dxb = keep ? take(M * w) : nullptr;
+    n->dqkv = keep ? take(M * 3 * w) : nullptr;
+    n->dwide = keep ? take(std::max(M * 4 * w, Mp * n->kpp)) : nullptr;   // (d act [M][4 w], later d patches [Mp][kpp])
+    n->dtmp = keep ? take(M * w) : nullptr;
+    n->delta = keep ? s.take<float>((size_t)N * n->heads * n->Tk) : nullptr;
+    for (int i = 0; i < n->layers; i++) {   // the kept activations: per layer, or one set for all
+      BlockActs& l = n->K[i];
+      const bool have = keep || i == 0;
+      l.x = have ? take(M * w) : nullptr;
+      l.qkv = have ? take(M * 3 * w) : nullptr;
+      l.ao = have ? take(M * w) : nullptr;
+      l.xm = have ? take(M * w) : nullptr;
+      l.h = have ? take(M * 4 * w) : nullptr;
+      l.st1 = have ? s.take<float>(M * 2) : nullptr;
+      l.st2 = have ? s.take<float>(M * 2) : nullptr;
+      l.lse = have ? s.take<float>((size_t)N * n->heads * n->Tk) : nullptr;
+    }
+  };
+  if (carve_into(n->ws, layout)) return fail("maua_clip: out of device memory for the image tower's activations");
   if (n->kpp != n->kp) {   // the pad columns of the patch rows: zero from here on (no writer touches them); a kernel, like zero_dx
     const long pieces = (long)(Mp * n->kpp * es / 16);
     hipLaunchKernelGGL(zero16_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, n->ctx->stream, (u32x4*)n->patches, pieces);
@@ -275,14 +262,14 @@ int run_forward(maua_clip* n, long N, bool keep) {
   const int w = n->width, Tk = n->Tk;
   const long M = N * Tk, Mp = N * n->G * n->G;
   // patch embedding (conv1, no bias) -> tokens -> ln_pre
-  if (int rc = block_gemm(r, n->patches, Mp, n->kpp, n->w_conv, w, nullptr, nullptr, n->pe)) return rc;
+  if (int rc = block_gemm(r, n->patches, Mp, n->kpp, n->w_conv.get(), w, nullptr, nullptr, n->pe)) return rc;
   const long total = M * (w / elems_per_piece(n->dtype));
   const dim3 tgrid((unsigned)((total + 255) / 256));
   dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip", [&](auto t) {
-    hipLaunchKernelGGL(tokens_kernel<decltype(t)>, tgrid, dim3(256), 0, r.st, (const decltype(t)*)n->pe, n->cls, n->pos, (decltype(t)*)n->tok, N, Tk, w);
+    hipLaunchKernelGGL(tokens_kernel<decltype(t)>, tgrid, dim3(256), 0, r.st, (const decltype(t)*)n->pe, n->cls.as<float>(), n->pos.as<float>(), (decltype(t)*)n->tok, N, Tk, w);
   });
   void* x = n->K[0].x;
-  launch_layer_norm(r.st, r.dtype, n->tok, n->lnpre_g, n->lnpre_b, x, n->st_pre, M, w);
+  launch_layer_norm(r.st, r.dtype, n->tok, n->lnpre_g.as<float>(), n->lnpre_b.as<float>(), x, n->st_pre, M, w);
   for (int i = 0; i < n->layers; i++) {
     // without kept activations the residual stream alternates between K[0].x and x_last, ending in x_last
     void* xn = i + 1 < n->layers ? (keep ? n->K[i + 1].x : (void*)((x == n->K[0].x) ? n->x_last : n->K[0].x)) : n->x_last;
@@ -296,8 +283,8 @@ int run_forward(maua_clip* n, long N, bool keep) {
 
 int run_head(maua_clip* n, long N, bool with_grad, const float* d_embed, int B, float coef, bool write_loss, const float* mult) {
   HeadArgs h{};
-  h.x = n->x_last; h.g = n->lnpost_g; h.b = n->lnpost_b; h.proj = n->proj; h.tgt = n->tgt; h.twt = n->twt;
-  h.sel = n->sel_B > 0 ? n->sel : nullptr;
+  h.x = n->x_last; h.g = n->lnpost_g.as<float>(); h.b = n->lnpost_b.as<float>(); h.proj = n->proj.as<float>(); h.tgt = n->tgt.as<float>(); h.twt = n->twt.as<float>();
+  h.sel = n->sel_B > 0 ? n->sel.as<int>() : nullptr;
   h.embed = n->embed; h.loss = write_loss ? n->loss : nullptr; h.d_embed = d_embed; h.dx = with_grad ? n->dxa : nullptr;
   h.Tk = n->Tk; h.w = n->width; h.E = n->E; h.P = n->P; h.B = B > 0 ? B : 1; h.coef = coef; h.mult = mult;
   const size_t smem = ((size_t)2 * n->width + 2 * n->E + std::max(n->P, 1) + 8) * 4;
@@ -315,8 +302,8 @@ int run_backward(maua_clip* n, long N) {
   for (int i = n->layers - 1; i >= 0; i--)
     if (int rc = block_backward(r, n->L[i], n->K[i], n->dxa, n->dxb, n->dqkv, n->dwide, n->dtmp, n->delta)) return rc;
   // ln_pre backwards (dropping the class token: its inputs are parameters), then the patch embedding's transpose
-  launch_layer_norm_vjp(r.st, r.dtype, n->tok, n->st_pre, n->lnpre_g, n->dxa, nullptr, n->dtmp, r.rows, n->width, n->Tk);
-  if (int rc = block_gemm(r, n->dtmp, N * n->G * n->G, n->width, n->w_conv_t, n->kpp, nullptr, nullptr, n->dwide)) return rc;
+  launch_layer_norm_vjp(r.st, r.dtype, n->tok, n->st_pre, n->lnpre_g.as<float>(), n->dxa, nullptr, n->dtmp, r.rows, n->width, n->Tk);
+  if (int rc = block_gemm(r, n->dtmp, N * n->G * n->G, n->width, n->w_conv_t.get(), n->kpp, nullptr, nullptr, n->dwide)) return rc;
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -363,12 +350,6 @@ int maua_clip_create(maua_ctx* ctx, int input_resolution, int patch_size, int wi
 void maua_clip_destroy(maua_clip* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  free_ws(n);
-  free_blocks(n->L);
-  for (void* p : {n->w_conv, n->w_conv_t, (void*)n->cls, (void*)n->pos, (void*)n->lnpre_g, (void*)n->lnpre_b, (void*)n->lnpost_g,
-                  (void*)n->lnpost_b, (void*)n->proj, (void*)n->tgt, (void*)n->twt, (void*)n->sel, n->cut_tables, (void*)n->cut_th,
-                  (void*)n->rects_dev, (void*)n->parts, (void*)n->aug_rects, n->aug_recs, (void*)n->aug_x1, (void*)n->aug_x2})
-    dfree(p);
   delete n;
 }
 

@@ -129,14 +129,14 @@ int clip_prepare_guide(maua_clip* n, int B, int H, int W, int cutn, int aug_side
   const size_t tb = cutouts_table_bytes(n_cut_group, n->res), thb = cutouts_th_bytes(n_cut_group, B, n->res, std::min(H, W));
   if (tb > n->cut_tables_bytes || thb > n->cut_th_bytes || !n->parts) {
     MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
-    dfree(n->cut_tables); dfree(n->cut_th);
-    n->cut_tables = nullptr; n->cut_th = nullptr;
-    n->cut_tables_bytes = std::max(tb, n->cut_tables_bytes); n->cut_th_bytes = std::max(thb, n->cut_th_bytes);
-    if (int rc = dalloc(&n->cut_tables, n->cut_tables_bytes)) return rc;
-    if (int rc = dalloc((void**)&n->cut_th, n->cut_th_bytes)) return rc;
-    if (!n->parts)
-      if (int rc = dalloc((void**)&n->parts, NPARTS * 8)) return rc;
-    n->epoch++;
+    const size_t ntb = std::max(tb, n->cut_tables_bytes), nthb = std::max(thb, n->cut_th_bytes);
+    n->cut_tables_bytes = n->cut_th_bytes = 0;
+    n->epoch++;   // (the pieces move)
+    auto layout = [&](Scratch& s) {
+      n->cut_tables = s.take<char>(ntb); n->cut_th = (float*)s.take<char>(nthb); n->parts = s.take<double>(NPARTS);
+    };
+    if (int rc = carve_into(n->cut_ws, layout)) return rc;
+    n->cut_tables_bytes = ntb; n->cut_th_bytes = nthb;
   }
   return MAUA_OK;
 }
@@ -188,29 +188,29 @@ static int clip_grad_group_aug(maua_clip* n, const float* img, int B, int H, int
   p.B = B; p.n_cut = n_cut; p.cs = n->res;
   if (!per_call) {
     const int S = std::min(H, W);
-    if (int rc = aug_forward_src(st, recs, n_cut, B, S, 0, img, H, W, 0.5f, 0.5f, n->aug_x1)) return rc;
-    if (int rc = aug_forward_out(st, MAUA_F32, recs, n_cut, B, S, 0, n->aug_x1, n->aug_x2, 0, zero3, one3)) return rc;
-    p.img = n->aug_x2; p.rects = slot_rects_dev; p.H = S; p.W = S; p.mul = 1.f; p.add = 0.f; p.img_stride = (long)B * 3 * S * S;
+    if (int rc = aug_forward_src(st, recs, n_cut, B, S, 0, img, H, W, 0.5f, 0.5f, n->aug_x1.as<float>())) return rc;
+    if (int rc = aug_forward_out(st, MAUA_F32, recs, n_cut, B, S, 0, n->aug_x1.as<float>(), n->aug_x2.as<float>(), 0, zero3, one3)) return rc;
+    p.img = n->aug_x2.as<float>(); p.rects = slot_rects_dev; p.H = S; p.W = S; p.mul = 1.f; p.add = 0.f; p.img_stride = (long)B * 3 * S * S;
     for (int c = 0; c < 3; c++) { p.mean[c] = CLIP_MEAN[c]; p.std[c] = CLIP_STD[c]; }
     p.patch = n->patch; p.patch_ld = n->kpp;
     if (int rc = launch_cutout_tables(st, p, n->cut_tables)) return rc;
     if (int rc = launch_cutouts_forward(st, n->dtype, p, n->cut_tables, n->patches)) return rc;
     if (int rc = tower_pass(n, N, B, coef, nullptr)) return rc;
-    if (int rc = launch_cutouts_vjp(st, n->dtype, p, n->cut_tables, n->dwide, n->cut_th, n->aug_x2, 0)) return rc;
-    if (int rc = aug_adjoint_out(st, MAUA_F32, recs, n_cut, B, S, n->aug_x2, 0, one3, n->aug_x1)) return rc;
-    return aug_adjoint_src(st, recs, n_cut, B, S, n->aug_x1, H, W, 0.5f, grad, accumulate);
+    if (int rc = launch_cutouts_vjp(st, n->dtype, p, n->cut_tables, n->dwide, n->cut_th, n->aug_x2.as<float>(), 0)) return rc;
+    if (int rc = aug_adjoint_out(st, MAUA_F32, recs, n_cut, B, S, n->aug_x2.as<float>(), 0, one3, n->aug_x1.as<float>())) return rc;
+    return aug_adjoint_src(st, recs, n_cut, B, S, n->aug_x1.as<float>(), H, W, 0.5f, grad, accumulate);
   }
   const int cs = n->res;
   p.img = img; p.rects = rects_dev; p.H = H; p.W = W; p.mul = 0.5f; p.add = 0.5f;
   for (int c = 0; c < 3; c++) { p.mean[c] = 0.f; p.std[c] = 1.f; }
   if (int rc = launch_cutout_tables(st, p, n->cut_tables)) return rc;
-  if (int rc = launch_cutouts_forward(st, MAUA_F32, p, n->cut_tables, n->aug_x2)) return rc;
-  if (int rc = aug_forward_src(st, recs, 1, (int)N, cs, noise_i0, n->aug_x2, cs, cs, 1.f, 0.f, n->aug_x1)) return rc;
-  if (int rc = aug_forward_out(st, n->dtype, recs, 1, (int)N, cs, noise_i0, n->aug_x1, n->patches, n->patch, CLIP_MEAN, CLIP_STD, n->kpp)) return rc;
+  if (int rc = launch_cutouts_forward(st, MAUA_F32, p, n->cut_tables, n->aug_x2.as<float>())) return rc;
+  if (int rc = aug_forward_src(st, recs, 1, (int)N, cs, noise_i0, n->aug_x2.as<float>(), cs, cs, 1.f, 0.f, n->aug_x1.as<float>())) return rc;
+  if (int rc = aug_forward_out(st, n->dtype, recs, 1, (int)N, cs, noise_i0, n->aug_x1.as<float>(), n->patches, n->patch, CLIP_MEAN, CLIP_STD, n->kpp)) return rc;
   if (int rc = tower_pass(n, N, B, coef, nullptr)) return rc;
-  if (int rc = aug_adjoint_out(st, n->dtype, recs, 1, (int)N, cs, n->dwide, n->patch, CLIP_STD, n->aug_x2, n->kpp)) return rc;
-  if (int rc = aug_adjoint_src(st, recs, 1, (int)N, cs, n->aug_x2, cs, cs, 1.f, n->aug_x1, 0)) return rc;
-  return launch_cutouts_vjp(st, MAUA_F32, p, n->cut_tables, n->aug_x1, n->cut_th, grad, accumulate);
+  if (int rc = aug_adjoint_out(st, n->dtype, recs, 1, (int)N, cs, n->dwide, n->patch, CLIP_STD, n->aug_x2.as<float>(), n->kpp)) return rc;
+  if (int rc = aug_adjoint_src(st, recs, 1, (int)N, cs, n->aug_x2.as<float>(), cs, cs, 1.f, n->aug_x1.as<float>(), 0)) return rc;
+  return launch_cutouts_vjp(st, MAUA_F32, p, n->cut_tables, n->aug_x1.as<float>(), n->cut_th, grad, accumulate);
 }
 
 // every rectangle (size | flags, top, left) lies inside the image; flags: the grey / mirror bits are allowed
@@ -242,28 +242,23 @@ int maua_clip_set_targets(maua_clip* n, const float* targets, const float* weigh
     const float nn = std::max((float)std::sqrt(ss), 1e-12f);
     for (int j = 0; j < n->E; j++) t[r * n->E + j] /= nn;
   }
-  if (S * P != n->S * n->P) {
-    dfree(n->tgt); dfree(n->twt);
-    n->tgt = nullptr; n->twt = nullptr;
-    if (int rc = dalloc((void**)&n->tgt, t.size() * 4)) return rc;
-    if (int rc = dalloc((void**)&n->twt, wv.size() * 4)) return rc;
+  if (t.size() * 4 != n->tgt.bytes() || wv.size() * 4 != n->twt.bytes()) {
     n->epoch++;
+    if (int rc = n->tgt.alloc(t.size() * 4)) return rc;
+    if (int rc = n->twt.alloc(wv.size() * 4)) return rc;
   }
-  MAUA_HIP_CHECK(hipMemcpy(n->tgt, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-  MAUA_HIP_CHECK(hipMemcpy(n->twt, wv.data(), wv.size() * 4, hipMemcpyHostToDevice));
+  MAUA_HIP_CHECK(hipMemcpy(n->tgt.as<float>(), t.data(), t.size() * 4, hipMemcpyHostToDevice));
+  MAUA_HIP_CHECK(hipMemcpy(n->twt.as<float>(), wv.data(), wv.size() * 4, hipMemcpyHostToDevice));
   n->S = S; n->P = P;
   n->sel_B = 0;
   if (sel) {
     MAUA_REQUIRE(B > 0, "maua_clip_set_targets: sel needs the batch size");
     for (int b = 0; b < B; b++) MAUA_REQUIRE(sel[b] >= 0 && sel[b] < S, "maua_clip_set_targets: sel out of range");
-    if (B > n->sel_cap) {
-      dfree(n->sel);
-      n->sel = nullptr;
-      if (int rc = dalloc((void**)&n->sel, (size_t)B * 4)) return rc;
-      n->sel_cap = B;
+    if ((size_t)B * 4 > n->sel.bytes()) {
       n->epoch++;
+      if (int rc = n->sel.alloc((size_t)B * 4)) return rc;
     }
-    MAUA_HIP_CHECK(hipMemcpy(n->sel, sel, (size_t)B * 4, hipMemcpyHostToDevice));
+    MAUA_HIP_CHECK(hipMemcpy(n->sel.as<int>(), sel, (size_t)B * 4, hipMemcpyHostToDevice));
     n->sel_B = B;
   }
   return MAUA_OK;
@@ -293,19 +288,16 @@ int maua_clip_guide_grad(maua_clip* n, const float* img, int B, int H, int W, co
     MAUA_REQUIRE(cutn_total >= cutn, "maua_clip_guide_grad: multiplicities are >= 1");
   }
   const size_t cnt = (size_t)batches * cutn * 4;   // 3 ints + 1 float per cutout
-  if (cnt > n->rects_cap) {
+  if (cnt * 4 > n->rects_dev.bytes()) {
     MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
-    dfree(n->rects_dev);
-    n->rects_dev = nullptr;
-    if (int rc = dalloc((void**)&n->rects_dev, cnt * 4)) return rc;
-    n->rects_cap = cnt;
+    if (int rc = n->rects_dev.alloc(cnt * 4)) return rc;
   }
-  float* mult_dev = mult ? (float*)(n->rects_dev + (size_t)batches * cutn * 3) : nullptr;
-  MAUA_HIP_CHECK(hipMemcpyAsync(n->rects_dev, rects, (size_t)batches * cutn * 12, hipMemcpyHostToDevice, n->ctx->stream));
+  float* mult_dev = mult ? (float*)(n->rects_dev.as<int>() + (size_t)batches * cutn * 3) : nullptr;
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->rects_dev.as<int>(), rects, (size_t)batches * cutn * 12, hipMemcpyHostToDevice, n->ctx->stream));
   if (mult) MAUA_HIP_CHECK(hipMemcpyAsync(mult_dev, mult, (size_t)batches * cutn * 4, hipMemcpyHostToDevice, n->ctx->stream));
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));   // (the caller's arrays may be temporaries)
   if (int rc = clip_prepare_guide(n, B, H, W, cutn)) return rc;
-  return clip_guide_grad(n, img, B, H, W, n->rects_dev, mult_dev, cutn, cutn_total, batches, scale, clamp_gradient, grad);
+  return clip_guide_grad(n, img, B, H, W, n->rects_dev.as<int>(), mult_dev, cutn, cutn_total, batches, scale, clamp_gradient, grad);
 }
 
 // CLIPGrads.forward with augmented "normal" (per_call 0) / "dango" (per_call 1) cutouts: maua_clip_guide_grad with, per cutout batch,
@@ -328,38 +320,26 @@ int maua_clip_guide_grad_aug(maua_clip* n, const float* img, int B, int H, int W
   const int S = per_call ? n->res : std::min(H, W);
   if (int rc = clip_prepare_guide(n, B, H, W, cutn, S)) return rc;
   const size_t xb = (size_t)n->grp * B * 3 * S * S * 4;
-  if ((size_t)total * 24 > n->aug_rects_cap || recs.size() > n->aug_recs_cap || xb > n->aug_x_bytes) {
+  if ((size_t)total * 24 > n->aug_rects.bytes() || recs.size() > n->aug_recs.bytes() || xb > n->aug_x1.bytes() || xb > n->aug_x2.bytes()) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if ((size_t)total * 24 > n->aug_rects_cap) {
-      dfree(n->aug_rects); n->aug_rects = nullptr;
-      if (int rc = dalloc((void**)&n->aug_rects, (size_t)total * 24)) return rc;
-      n->aug_rects_cap = (size_t)total * 24;
-    }
-    if (recs.size() > n->aug_recs_cap) {
-      dfree(n->aug_recs); n->aug_recs = nullptr;
-      if (int rc = dalloc(&n->aug_recs, recs.size())) return rc;
-      n->aug_recs_cap = recs.size();
-    }
-    if (xb > n->aug_x_bytes) {
-      dfree(n->aug_x1); dfree(n->aug_x2); n->aug_x1 = n->aug_x2 = nullptr;
-      if (int rc = dalloc((void**)&n->aug_x1, xb)) return rc;
-      if (int rc = dalloc((void**)&n->aug_x2, xb)) return rc;
-      n->aug_x_bytes = xb;
-    }
     n->epoch++;
+    if (int rc = n->aug_rects.reserve((size_t)total * 24)) return rc;
+    if (int rc = n->aug_recs.reserve(recs.size())) return rc;
+    if (int rc = n->aug_x1.reserve(xb)) return rc;
+    if (int rc = n->aug_x2.reserve(xb)) return rc;
   }
   std::vector<int> slot((size_t)total * 3);
   for (long i = 0; i < total; i++) { slot[3 * i] = rects[3 * i] & CUT_SIZE_MASK; slot[3 * i + 1] = 0; slot[3 * i + 2] = 0; }
-  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_rects, rects, (size_t)total * 12, hipMemcpyHostToDevice, st));
-  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_rects + 3 * total, slot.data(), (size_t)total * 12, hipMemcpyHostToDevice, st));
-  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_recs, recs.data(), recs.size(), hipMemcpyHostToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_rects.as<int>(), rects, (size_t)total * 12, hipMemcpyHostToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_rects.as<int>() + 3 * total, slot.data(), (size_t)total * 12, hipMemcpyHostToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->aug_recs.get(), recs.data(), recs.size(), hipMemcpyHostToDevice, st));
   MAUA_HIP_CHECK(hipStreamSynchronize(st));   // (the host vectors die with this call)
   const float coef = 1.f / ((float)cutn * (float)batches);
   const size_t rb = aug_record_bytes();
   return guide_groups(n, B, H, W, cutn, batches, scale, clamp_gradient, grad, [&](int k, int c0, int nc, int accumulate) {
     const long i0 = (long)k * cutn + c0;
-    const void* rp = (const char*)n->aug_recs + (per_call ? (size_t)k : (size_t)i0) * rb;
-    return clip_grad_group_aug(n, img, B, H, W, n->aug_rects + 3 * i0, n->aug_rects + 3 * (total + i0), rp, nc, per_call, c0 * B, coef, grad,
+    const void* rp = (const char*)n->aug_recs.get() + (per_call ? (size_t)k : (size_t)i0) * rb;
+    return clip_grad_group_aug(n, img, B, H, W, n->aug_rects.as<int>() + 3 * i0, n->aug_rects.as<int>() + 3 * (total + i0), rp, nc, per_call, c0 * B, coef, grad,
                                accumulate);
   });
 }

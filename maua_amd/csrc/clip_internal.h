@@ -52,10 +52,8 @@ constexpr int LN_MAXP = 8;   // LayerNorm's 16-byte pieces per lane: C <= 64 * 8
 
 // ------------------------------------------------------------------------------------------------ the residual block (transformer.hip)
 struct BlockWeights {   // *_t: the transposes, the image tower's way back (the text tower has none)
-  void *w_qkv = nullptr, *w_qkv_t = nullptr, *w_out = nullptr, *w_out_t = nullptr, *w_fc = nullptr, *w_fc_t = nullptr, *w_pr = nullptr,
-       *w_pr_t = nullptr;
-  float *b_qkv = nullptr, *b_out = nullptr, *b_fc = nullptr, *b_pr = nullptr, *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr,
-        *ln2_b = nullptr;
+  DevBuf w_qkv, w_qkv_t, w_out, w_out_t, w_fc, w_fc_t, w_pr, w_pr_t;        // tower dtype
+  DevBuf b_qkv, b_out, b_fc, b_pr, ln1_g, ln1_b, ln2_g, ln2_b;               // float
 };
 // what a block's forward writes on its way: kept per layer for the way back (image tower), or one set shared by the layers.  x is
 // the block's input as the way back reads it (the forward takes its input as an argument); st1 / st2 / lse may be NULL (not kept)
@@ -88,19 +86,13 @@ int block_forward(const BlockRun& r, const BlockWeights& l, const void* x, const
 int block_backward(const BlockRun& r, const BlockWeights& l, const BlockActs& k, void* dx, void* other, void* dqkv, void* dwide, void* dtmp,
                    float* delta);
 // host float matrix [R][C] -> device [R][C] in dtype (and optionally its transpose [C][R]); rows permuted by `perm` when given
-int upload_matrix(int dtype, size_t esize, const float* h, int R, int C, const int* perm, void** dev, void** dev_t);
-int upload_vec(const float* h, size_t count, const int* perm, float** dev);
+// (both allocate an empty `dev` and write into a held one)
+int upload_matrix(int dtype, size_t esize, const float* h, int R, int C, const int* perm, DevBuf* dev, DevBuf* dev_t);
+int upload_vec(const float* h, size_t count, const int* perm, DevBuf* dev);
 bool is_block_key(const std::string& s);   // "transformer.resblocks.<i>.<par>"
 int load_block(std::vector<BlockWeights>& L, int dtype, size_t esize, int width, int heads, const char* who, const std::string& s,
                const float* host, size_t count, bool with_t);
 bool blocks_loaded(const std::vector<BlockWeights>& L);
-void free_blocks(std::vector<BlockWeights>& L);
-
-inline int dalloc(void** p, size_t bytes) {
-  MAUA_HIP_CHECK(hipMalloc(p, bytes ? bytes : 16));
-  return MAUA_OK;
-}
-inline void dfree(void* p) { if (p) hipFree(p); }
 
 }  // namespace maua
 
@@ -114,12 +106,13 @@ struct maua_clip {
   // `patches` are zeroed by a kernel when the buffer is (re)allocated and no writer touches them afterwards; conv1.weight's pad
   // columns (and its transpose's pad rows) are zeros, so the backward GEMM writes zeros there and the readers stop at kp.
   int kpp;
-  void *w_conv = nullptr, *w_conv_t = nullptr;          // [w][kpp], [kpp][w]
-  float *cls = nullptr, *pos = nullptr, *lnpre_g = nullptr, *lnpre_b = nullptr, *lnpost_g = nullptr, *lnpost_b = nullptr, *proj = nullptr;
+  maua::DevBuf w_conv, w_conv_t;                               // [w][kpp], [kpp][w]
+  maua::DevBuf cls, pos, lnpre_g, lnpre_b, lnpost_g, lnpost_b, proj;   // float
   std::vector<maua::BlockWeights> L;
   std::vector<maua::BlockActs> K;   // kept by the forward for the way back: per layer (keep), else K[0] serves every layer
-  // workspaces for `cap` images
-  long cap = 0;
+  // workspaces for `cap` images: one set carved from ws by ensure_ws - the pieces below and every piece of K
+  maua::DevBuf ws;
+  long cap = 0;            // (cap, keep: what the set is placed for; set after it)
   int keep = 0;            // sized with the kept activations of a gradient pass
   void *patches = nullptr, *pe = nullptr, *tok = nullptr, *x_last = nullptr, *lno = nullptr, *act = nullptr;
   void *dxa = nullptr, *dxb = nullptr, *dqkv = nullptr, *dwide = nullptr, *dtmp = nullptr;
@@ -130,18 +123,20 @@ struct maua_clip {
   int grp = 0, grp_B = 0, grp_H = 0, grp_W = 0, grp_cutn = 0, grp_aug = 0;
   size_t ws_limit = 0;
   // targets
-  float *tgt = nullptr, *twt = nullptr;
+  maua::DevBuf tgt, twt;         // float [S][P][E], [S][P]
   int S = 0, P = 0;
-  int* sel = nullptr; int sel_cap = 0; int sel_B = 0;
-  // cutout scratch
-  void* cut_tables = nullptr; size_t cut_tables_bytes = 0;
+  maua::DevBuf sel;              // int: the target set of each sample
+  int sel_B = 0;           // samples it is set for (0: set 0 for everybody)
+  // cutout scratch: one set carved from cut_ws by clip_prepare_guide
+  maua::DevBuf cut_ws;
+  void* cut_tables = nullptr; size_t cut_tables_bytes = 0;   // (the sizes the pieces are placed for; set after the set)
   float* cut_th = nullptr; size_t cut_th_bytes = 0;
-  int* rects_dev = nullptr; size_t rects_cap = 0;   // + the multiplicities behind the rectangles (floats)
-  // augmented cutouts (cutout_augs.hip): rectangles + slot rectangles, records, and the two [group][B][3][S][S] buffers
-  int* aug_rects = nullptr; size_t aug_rects_cap = 0;
-  void* aug_recs = nullptr; size_t aug_recs_cap = 0;
-  float *aug_x1 = nullptr, *aug_x2 = nullptr; size_t aug_x_bytes = 0;
   double* parts = nullptr;
+  maua::DevBuf rects_dev;        // int: rectangles + the multiplicities behind them (floats)
+  // augmented cutouts (cutout_augs.hip): rectangles + slot rectangles, records, and the two [group][B][3][S][S] buffers
+  maua::DevBuf aug_rects;        // int
+  maua::DevBuf aug_recs;
+  maua::DevBuf aug_x1, aug_x2;   // float
   unsigned long long uid = 0, epoch = 0;   // identity of this tower / generation of its buffers (a captured graph holds pointers into
 };                                          // them: sampler.hip compares both before a replay)
 
@@ -151,10 +146,11 @@ struct maua_clip_text {
   int dtype;
   size_t esize;
   int ctx_len, vocab, width, layers, heads, E;
-  float *tok_emb = nullptr, *pos = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *proj = nullptr;   // f32 [vocab][w], [ctx][w], [w], [w], [w][E]
+  maua::DevBuf tok_emb, pos, lnf_g, lnf_b, proj;   // f32 [vocab][w], [ctx][w], [w], [w], [w][E]
   std::vector<maua::BlockWeights> L;   // (no transposes: no way back)
-  // workspaces for `cap` sequences (at least TEXT_MIN_ROWS rows), shared by the layers
-  long cap = 0;
+  // workspaces for `cap` sequences (at least TEXT_MIN_ROWS rows), shared by the layers: one set carved from ws
+  maua::DevBuf ws;
+  long cap = 0;            // (set after the set is placed)
   void *xa = nullptr, *xb = nullptr, *lno = nullptr, *act = nullptr;
   maua::BlockActs k;   // qkv, ao, xm, h (no input kept, no statistics)
 };

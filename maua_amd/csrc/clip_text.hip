@@ -73,19 +73,6 @@ __global__ __launch_bounds__(256) void text_head_kernel(const int* __restrict__ 
   }
 }
 
-// the workspaces in allocation order, and the columns of each in units of the width
-struct TextBuf { void** p; size_t cols; };
-std::vector<TextBuf> text_bufs(maua_clip_text* n) {
-  return {{&n->xa, 1}, {&n->xb, 1}, {&n->lno, 1}, {&n->k.qkv, 3}, {&n->k.ao, 1}, {&n->k.xm, 1}, {&n->k.h, 4}, {&n->act, 4}};
-}
-void free_text_ws(maua_clip_text* n) {
-  for (auto& b : text_bufs(n)) {
-    dfree(*b.p);
-    *b.p = nullptr;
-  }
-  n->cap = 0;
-}
-
 // The text tower's GEMMs run on ONE kernel for every batch size - gemm.hip's 128 x 128 register-staged kernel, never the LDS-direct
 // one (chosen by the row count) nor the small-M one - over at least TEXT_MIN_ROWS rows (the rows past N * ctx are workspace, zeroed
 // at allocation, never read back): a prompt's embedding then does not depend on what else is in the batch, so prompts embedded one by
@@ -104,13 +91,16 @@ long text_chunk(const maua_clip_text* n) {
 int ensure_text_ws(maua_clip_text* n, long N) {
   if (N <= n->cap) return MAUA_OK;
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
-  free_text_ws(n);
+  n->cap = 0;
   const size_t es = n->esize, M = (size_t)text_rows(n, N), w = n->width;
-  int rc = MAUA_OK;
-  for (auto& b : text_bufs(n))
-    if (!rc) rc = dalloc(b.p, M * b.cols * w * es);
-  if (rc) { free_text_ws(n); return fail("maua_clip_text: out of device memory for the text tower's activations"); }
-  for (auto& b : text_bufs(n)) MAUA_HIP_CHECK(hipMemset(*b.p, 0, M * b.cols * w * es));
+  auto layout = [&](Scratch& s) {
+    auto take = [&](size_t cols) -> void* { return s.take<char>(M * cols * w * es); };   // (columns in units of the width)
+    n->xa = take(1); n->xb = take(1); n->lno = take(1);
+    n->k.qkv = take(3); n->k.ao = take(1); n->k.xm = take(1); n->k.h = take(4);
+    n->act = take(4);
+  };
+  if (carve_into(n->ws, layout)) return fail("maua_clip_text: out of device memory for the text tower's activations");
+  MAUA_HIP_CHECK(hipMemset(n->ws.get(), 0, n->ws.bytes()));
   n->cap = N;
   return MAUA_OK;
 }
@@ -121,7 +111,7 @@ int text_forward(maua_clip_text* n, const int* tokens, long N, float* embeds) {
   const long total = r.rows * (w / elems_per_piece(n->dtype));
   const dim3 tgrid((unsigned)((total + 255) / 256));
   dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip_text", [&](auto t) {
-    hipLaunchKernelGGL(text_tokens_kernel<decltype(t)>, tgrid, dim3(256), 0, r.st, tokens, n->tok_emb, n->pos, (decltype(t)*)n->xa, N, Tk, w, n->vocab);
+    hipLaunchKernelGGL(text_tokens_kernel<decltype(t)>, tgrid, dim3(256), 0, r.st, tokens, n->tok_emb.as<float>(), n->pos.as<float>(), (decltype(t)*)n->xa, N, Tk, w, n->vocab);
   });
   void* x = n->xa;
   void* other = n->xb;
@@ -131,8 +121,8 @@ int text_forward(maua_clip_text* n, const int* tokens, long N, float* embeds) {
   }
   const size_t smem = ((size_t)w + 8) * 4;
   dispatch_dtype<bf16_t, float>(n->dtype, "maua_clip_text", [&](auto t) {
-    hipLaunchKernelGGL(text_head_kernel<decltype(t)>, dim3((unsigned)N), dim3(256), smem, r.st, tokens, (const decltype(t)*)x, n->lnf_g, n->lnf_b,
-                       n->proj, embeds, Tk, w, n->E);
+    hipLaunchKernelGGL(text_head_kernel<decltype(t)>, dim3((unsigned)N), dim3(256), smem, r.st, tokens, (const decltype(t)*)x, n->lnf_g.as<float>(), n->lnf_b.as<float>(),
+                       n->proj.as<float>(), embeds, Tk, w, n->E);
   });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
@@ -163,9 +153,6 @@ int maua_clip_text_create(maua_ctx* ctx, int context_length, int vocab_size, int
 void maua_clip_text_destroy(maua_clip_text* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  free_text_ws(n);
-  free_blocks(n->L);
-  for (void* p : {(void*)n->tok_emb, (void*)n->pos, (void*)n->lnf_g, (void*)n->lnf_b, (void*)n->proj}) dfree(p);
   delete n;
 }
 

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../include/maua_hip.h"
+#include "devbuf.h"
 #include "dtype.h"
 #include "scratch.h"
 
@@ -148,6 +149,9 @@ int fail(const std::string& msg);  // sets the thread-local error, returns MAUA_
     if (!(cond)) return ::maua::fail(std::string(msg));           \
   } while (0)
 
+// an owner's allocation failed inside entry point `who`: its message, with the entry point's name in front as before
+static inline int fail_in(const char* who) { return fail(std::string(who) + ": " + maua_last_error()); }
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // A row index that rides in gridDim.y or gridDim.z: one launch holds at most 65535 of them, so longer tensors are launched in
@@ -164,8 +168,7 @@ struct maua_ctx {
   int device;
   hipStream_t stream;
   // grow-only scratch arena for the operator-level entry points (layout conversion, prepared weights): carve_scratch (scratch.h)
-  void* scratch = nullptr;
-  size_t scratch_bytes = 0;
+  maua::DevBuf scratch;
   int dma_conv = 1;  // operator-level modconv: eligible shapes run the LDS-direct-load kernel (maua_ctx_set_option)
   int gemm_dma = 1;  // clip.hip (the image tower's BlockRun): large plain GEMMs on gemm_dma.hip (option "gemm_dma")
   int linear_dma = 0;  // maua_linear_nt: the same routing for operator-level callers (option "linear_dma")

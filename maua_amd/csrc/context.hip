@@ -9,16 +9,11 @@ int fail(const std::string& msg) {
   return MAUA_ERR;
 }
 int scratch_reserve(maua_ctx* ctx, size_t bytes, void** base) {
-  *base = ctx->scratch;
-  if (bytes <= ctx->scratch_bytes) return MAUA_OK;
-  MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (ctx->scratch) MAUA_HIP_CHECK(hipFree(ctx->scratch));
-  ctx->scratch = nullptr;
-  ctx->scratch_bytes = 0;
-  size_t want = bytes + bytes / 4;
-  MAUA_HIP_CHECK(hipMalloc(&ctx->scratch, want));
-  ctx->scratch_bytes = want;
-  *base = ctx->scratch;
+  if (bytes > ctx->scratch.bytes()) {
+    MAUA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (int rc = ctx->scratch.alloc(bytes + bytes / 4)) return rc;
+  }
+  *base = ctx->scratch.get();
   return MAUA_OK;
 }
 }  // namespace maua
@@ -88,10 +83,7 @@ int maua_ctx_clock_stamp(maua_ctx* ctx, unsigned long long* stamp_dev) {
 
 void maua_ctx_destroy(maua_ctx* ctx) {
   if (!ctx) return;
-  if (ctx->scratch) {
-    hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->scratch);
-  }
+  if (ctx->scratch) hipStreamSynchronize(ctx->stream);
   delete ctx;
 }
 

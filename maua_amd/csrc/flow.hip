@@ -568,8 +568,8 @@ int pyramid_levels(int H, int W) {
 using namespace maua;
 
 struct maua_farneback {
-  int device, max_h, max_w;
-  float* ws;
+  int device = 0, max_h = 0, max_w = 0;
+  DevBuf ws;   // float
   PolyTaps poly;
 };
 
@@ -658,12 +658,12 @@ int maua_farneback_create(maua_ctx* ctx, int max_h, int max_w, maua_farneback** 
   MAUA_REQUIRE(ctx && out, "maua_farneback_create: NULL argument");
   MAUA_REQUIRE(max_h >= 2 * FB_POLY_N + 1 && max_w >= 2 * FB_POLY_N + 1 && (long)max_h * max_w <= (1L << 26),
                "maua_farneback_create: the largest image must be between 15 x 15 and 2^26 pixels");
-  auto* h = new maua_farneback{ctx->device, max_h, max_w, nullptr, {}};
   MAUA_HIP_CHECK(hipSetDevice(ctx->device));
-  const hipError_t e = hipMalloc((void**)&h->ws, (size_t)FB_WS_FLOATS_PER_PIXEL * max_h * max_w * sizeof(float));
-  if (e != hipSuccess) {
+  auto* h = new maua_farneback();
+  h->device = ctx->device; h->max_h = max_h; h->max_w = max_w;
+  if (h->ws.alloc((size_t)FB_WS_FLOATS_PER_PIXEL * max_h * max_w * sizeof(float))) {
     delete h;
-    return fail(std::string("maua_farneback_create: ") + hipGetErrorString(e));
+    return fail_in("maua_farneback_create");
   }
   poly_setup(h->poly);
   *out = h;
@@ -672,7 +672,6 @@ int maua_farneback_create(maua_ctx* ctx, int max_h, int max_w, maua_farneback** 
 
 int maua_farneback_destroy(maua_farneback* h) {
   if (!h) return MAUA_OK;
-  hipFree(h->ws);
   delete h;
   return MAUA_OK;
 }
@@ -743,7 +742,7 @@ int maua_farneback_pair_ex(maua_farneback* fb, maua_ctx* ctx, const maua_farneba
   const int H = d->H, W = d->W;
   hipStream_t st = ctx->stream;
   const long n = (long)H * W;
-  float* p = fb->ws;
+  float* p = fb->ws.as<float>();
   float* gray = p;  p += 2 * n;
   float* tmp = p;   p += 2 * n;
   float* blur = p;  p += 2 * n;

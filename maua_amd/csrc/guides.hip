@@ -27,9 +27,9 @@ struct maua_guide {
   float scale = 1.f;
   int nbins = 255, sat = 1, per_sample = 0;
   // colour-match workspaces (grow-only)
-  unsigned long long* fix = nullptr;
-  float* gr = nullptr;
-  int cm_cap = 0;                     // samples the workspaces hold
+  DevBuf fix;                         // unsigned long long
+  DevBuf gr;                          // float
+  int cm_cap = 0;                     // samples the workspaces hold (set after them)
   unsigned long long cm_epoch = 0;
 };
 
@@ -43,11 +43,9 @@ int guide_prepare(maua_guide* g, int B, int H, int W) {
   if (g->kind != MAUA_GUIDE_COLORMATCH) return MAUA_OK;   // (the perceptors size their workspaces in their first eager evaluation)
   if (B <= g->cm_cap) return MAUA_OK;
   MAUA_HIP_CHECK(hipStreamSynchronize(g->ctx->stream));
-  if (g->fix) hipFree(g->fix);
-  if (g->gr) hipFree(g->gr);
-  g->fix = nullptr; g->gr = nullptr; g->cm_cap = 0; g->cm_epoch++;
-  MAUA_HIP_CHECK(hipMalloc((void**)&g->fix, colormatch_fix_bytes(B, g->nbins)));
-  MAUA_HIP_CHECK(hipMalloc((void**)&g->gr, (size_t)B * g->nbins * 4));
+  g->cm_cap = 0; g->cm_epoch++;
+  if (int rc = g->fix.alloc(colormatch_fix_bytes(B, g->nbins))) return rc;
+  if (int rc = g->gr.alloc((size_t)B * g->nbins * 4)) return rc;
   g->cm_cap = B;
   return MAUA_OK;
 }
@@ -62,7 +60,7 @@ int guide_eval(maua_guide* g, const float* img, int B, int H, int W, float* out)
                                  g->lins.data(), g->scale, out, nullptr);
     case MAUA_GUIDE_COLORMATCH:
       MAUA_REQUIRE(B <= g->cm_cap, "maua_guide: colour-match workspaces were prepared for a smaller batch");
-      return colormatch_grad_into(g->ctx->stream, img, B, H, W, g->nbins, g->sat, g->targets[0], g->per_sample, g->scale, g->fix, g->gr, out,
+      return colormatch_grad_into(g->ctx->stream, img, B, H, W, g->nbins, g->sat, g->targets[0], g->per_sample, g->scale, g->fix.as<unsigned long long>(), g->gr.as<float>(), out,
                                   nullptr);
   }
   return fail("maua_guide: unknown kind");
@@ -102,8 +100,6 @@ int maua_guide_create(maua_ctx* ctx, int kind, maua_vgg* vgg, const int* taps, i
 void maua_guide_destroy(maua_guide* g) {
   if (!g) return;
   hipStreamSynchronize(g->ctx->stream);
-  if (g->fix) hipFree(g->fix);
-  if (g->gr) hipFree(g->gr);
   delete g;
 }
 

@@ -793,6 +793,8 @@ int launch_upwalk_fused(hipStream_t stream, const HiresArgs& up, const HiresArgs
       if (best < 0 || cost < best) { best = cost; nseg = segs; seg_rows = rows; n_items = items; ipw = per; }
     }
   }
+  // (the one raw allocation outside devbuf.h, on purpose: a function-local static that lives until the process exits - an owner's
+  // destructor would free it after the runtime has shut down, which is worse than keeping these 128 bytes)
   static long long* dbg = nullptr;
   if (want_dbg && !dbg) { (void)hipMalloc((void**)&dbg, 16 * 8); (void)hipMemset(dbg, 0, 128); }
   hipLaunchKernelGGL(kern, dim3((n_items + ipw - 1) / ipw), dim3(512), smem, stream, A, seg_rows, nseg, strips, n_items,

@@ -315,10 +315,7 @@ int maua_nca_create(maua_ctx* ctx, int chn, int hidden, int dtype, maua_nca** ou
 
 int maua_nca_destroy(maua_nca* h) {
   if (!h) return MAUA_OK;
-  if (h->tmp) {
-    hipStreamSynchronize(h->ctx->stream);
-    hipFree(h->tmp);
-  }
+  if (h->tmp) hipStreamSynchronize(h->ctx->stream);
   delete h;
   return MAUA_OK;
 }
@@ -350,10 +347,10 @@ int maua_nca_step(maua_nca* h, const maua_nca_desc* d) {
     const long rows = (long)d->B * h->chn * d->H;
     const int ncols = a.whi - a.wlo;
     for (int s = 0; s < d->n_steps; s++) {
-      a.src = d->x; a.dst = h->tmp; a.t = d->step0 + (unsigned long long)s;
+      a.src = d->x; a.dst = h->tmp.as<float>(); a.t = d->step0 + (unsigned long long)s;
       a.u = d->u ? d->u + (long)s * d->B * plane : nullptr;
       launch(h, a);
-      hipLaunchKernelGGL(nca_copy_cols_kernel, dim3((unsigned)((rows * ncols + 255) / 256)), dim3(256), 0, st, h->tmp, d->x, rows, d->W,
+      hipLaunchKernelGGL(nca_copy_cols_kernel, dim3((unsigned)((rows * ncols + 255) / 256)), dim3(256), 0, st, h->tmp.as<float>(), d->x, rows, d->W,
                          d->col0 + a.wlo, ncols);
     }
   } else {
@@ -364,10 +361,10 @@ int maua_nca_step(maua_nca* h, const maua_nca_desc* d) {
     int launches = 0;
     for (int s = 0; s < d->n_steps; s += width(d->n_steps - s)) launches++;
     float* cur = d->x;
-    float* other = h->tmp;
+    float* other = h->tmp.as<float>();
     if (launches & 1) {
-      MAUA_HIP_CHECK(hipMemcpyAsync(h->tmp, d->x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
-      cur = h->tmp; other = d->x;
+      MAUA_HIP_CHECK(hipMemcpyAsync(h->tmp.as<float>(), d->x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+      cur = h->tmp.as<float>(); other = d->x;
     }
     for (int s = 0; s < d->n_steps;) {
       const int w = width(d->n_steps - s);

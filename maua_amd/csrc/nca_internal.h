@@ -8,8 +8,7 @@
 struct maua_nca {
   maua_ctx* ctx;
   int chn, hidden, dtype;
-  float* tmp = nullptr;   // grow-only: the step's second state buffer / the gradient's workspace
-  size_t tmp_bytes = 0;
+  maua::DevBuf tmp;   // float, grow-only: the step's second state buffer / the gradient's workspace
 };
 
 namespace maua {
@@ -57,15 +56,9 @@ static inline bool nca_sizes_ok(int chn, int hidden) {
 }
 
 static inline int nca_reserve(maua_nca* h, size_t bytes) {
-  if (bytes <= h->tmp_bytes) return MAUA_OK;
-  if (h->tmp) {
-    MAUA_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
-    MAUA_HIP_CHECK(hipFree(h->tmp));
-    h->tmp = nullptr; h->tmp_bytes = 0;
-  }
-  MAUA_HIP_CHECK(hipMalloc(&h->tmp, bytes));
-  h->tmp_bytes = bytes;
-  return MAUA_OK;
+  if (bytes <= h->tmp.bytes()) return MAUA_OK;
+  if (h->tmp) MAUA_HIP_CHECK(hipStreamSynchronize(h->ctx->stream));
+  return h->tmp.alloc(bytes);
 }
 
 }  // namespace maua

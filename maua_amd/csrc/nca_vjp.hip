@@ -299,7 +299,7 @@ int maua_nca_vjp(maua_nca* h, const maua_nca_desc* d, const float* states, const
     return MAUA_OK;
   }
   if (int rc = nca_reserve(h, g_bytes + gp_bytes + part_bytes)) return rc;
-  float* g_tmp = h->tmp;
+  float* g_tmp = h->tmp.as<float>();
   float* gp = g_tmp + n;
   float* partial = gp + 4 * n;
   VjpArgs a{};

@@ -41,8 +41,8 @@ struct POp {
   int conv = -1;
   int C = 0;           // output channels
   int shift = 0;       // output resolution = input >> shift
-  void* act = nullptr; // kept output of the last forward [B][h][w][C]
-  void* hg = nullptr;  // head gradient of a tap [B][h][w][C]
+  void* act = nullptr; // kept output of the last forward [B][h][w][C] (a piece of maua_vgg::ws)
+  void* hg = nullptr;  // head gradient of a tap [B][h][w][C] (a piece of maua_vgg::ws)
   bool hg_set = false;
 };
 
@@ -534,32 +534,18 @@ struct maua_vgg {
   float in_mul = 1.f, in_add = 0.f, mean[3] = {0, 0, 0}, istd[3] = {1, 1, 1};
   UnitStyles ones;                 // [bcap][512]
   int B = 0, H = 0, W = 0;         // shape of the kept forward (0: none)
-  size_t cap_key = 0;              // B * H * W the buffers were sized for
+  DevBuf fbuf;                     // float: gram partials / per-pixel values (grows on its own rule)
+  DevBuf ws;                       // the set ensure_ws carves, placed for (cap_key, loss_cap): every op's act and hg, and
+  size_t cap_key = 0;              // B * H * W the pieces were placed for
+  int loss_cap = 0;                // B they were placed for
   void *ga = nullptr, *gb = nullptr;
-  float* fbuf = nullptr;           // gram partials / per-pixel values
-  size_t fbuf_bytes = 0;
   float* gram = nullptr;           // [B][512][512]
   void* sym = nullptr;             // [B][512][512] network dtype
   float* loss_dev = nullptr;       // [B]
   float* part = nullptr;           // [B][STYLE_CHUNKS][2]
-  int loss_cap = 0;
 };
 
 namespace {
-
-void free_ws(maua_vgg* n) {
-  auto f = [](void*& p) { if (p) hipFree(p); p = nullptr; };
-  for (auto& o : n->ops) { f(o.act); f(o.hg); o.hg_set = false; }
-  f(n->ga); f(n->gb);
-  { void* p = n->fbuf; f(p); n->fbuf = nullptr; n->fbuf_bytes = 0; }
-  { void* p = n->gram; f(p); n->gram = nullptr; }
-  f(n->sym);
-  { void* p = n->loss_dev; f(p); n->loss_dev = nullptr; n->loss_cap = 0; }
-  { void* p = n->part; f(p); n->part = nullptr; }
-  n->cap_key = 0;
-  n->B = n->H = n->W = 0;
-  n->epoch++;
-}
 
 int max_c(const maua_vgg* n) {
   int m = 0;
@@ -572,20 +558,27 @@ int ensure_ws(maua_vgg* n, int B, int H, int W) {
   const size_t key = (size_t)B * H * W;
   if (key > n->cap_key || B > n->loss_cap) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    free_ws(n);
-    size_t widest = 0;
-    for (auto& o : n->ops) {
-      const size_t e = ((size_t)B * (H >> o.shift) * (W >> o.shift)) * o.C;
-      widest = std::max(widest, e);
-      if (hipMalloc(&o.act, e * n->esize) != hipSuccess) return fail("maua_vgg: out of device memory (activations)");
-      if (hipMalloc(&o.hg, e * n->esize) != hipSuccess) return fail("maua_vgg: out of device memory (head gradients)");
-    }
+    n->cap_key = 0; n->loss_cap = 0;
+    n->B = n->H = n->W = 0;
+    for (auto& o : n->ops) o.hg_set = false;
+    n->epoch++;   // (the pieces move even where the block does not)
     const int mc = max_c(n);
-    if (hipMalloc(&n->ga, widest * n->esize) != hipSuccess || hipMalloc(&n->gb, widest * n->esize) != hipSuccess ||
-        hipMalloc((void**)&n->gram, (size_t)B * mc * mc * 4) != hipSuccess ||
-        hipMalloc(&n->sym, (size_t)B * mc * mc * n->esize) != hipSuccess || hipMalloc((void**)&n->loss_dev, (size_t)B * 4) != hipSuccess ||
-        hipMalloc((void**)&n->part, (size_t)B * STYLE_CHUNKS * 2 * 4) != hipSuccess)
-      return fail("maua_vgg: out of device memory (workspaces)");
+    auto layout = [&](Scratch& s) {
+      size_t widest = 0;
+      for (auto& o : n->ops) {
+        const size_t e = ((size_t)B * (H >> o.shift) * (W >> o.shift)) * o.C;
+        widest = std::max(widest, e);
+        o.act = s.take<char>(e * n->esize);
+        o.hg = s.take<char>(e * n->esize);
+      }
+      n->ga = s.take<char>(widest * n->esize);
+      n->gb = s.take<char>(widest * n->esize);
+      n->gram = s.take<float>((size_t)B * mc * mc);
+      n->sym = s.take<char>((size_t)B * mc * mc * n->esize);
+      n->loss_dev = s.take<float>((size_t)B);
+      n->part = s.take<float>((size_t)B * STYLE_CHUNKS * 2);
+    };
+    if (carve_into(n->ws, layout)) return fail("maua_vgg: out of device memory (activations and workspaces)");
     n->cap_key = key;
     n->loss_cap = B;
   }
@@ -596,13 +589,10 @@ int ensure_ws(maua_vgg* n, int B, int H, int W) {
     const long hw = (long)(H >> o.shift) * (W >> o.shift);
     fb = std::max(fb, (size_t)B * ((hw + GRAM_PX - 1) / GRAM_PX) * o.C * o.C * 4);
   }
-  if (fb > n->fbuf_bytes) {
+  if (fb > n->fbuf.bytes()) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->fbuf) hipFree(n->fbuf);
-    n->fbuf = nullptr; n->fbuf_bytes = 0;
     n->epoch++;
-    if (hipMalloc((void**)&n->fbuf, fb) != hipSuccess) return fail("maua_vgg: out of device memory (workspaces)");
-    n->fbuf_bytes = fb;
+    if (n->fbuf.alloc(fb)) return fail("maua_vgg: out of device memory (workspaces)");
   }
   bool moved = false;
   const int rc = n->ones.ensure(st, B, 512, &moved);
@@ -614,8 +604,8 @@ int ensure_ws(maua_vgg* n, int B, int H, int W) {
 int run_conv(maua_vgg* n, const PlainConv& c, bool transposed, const void* x, void* y, int B, int h, int w) {
   ConvArgs a{};
   const int Ci = transposed ? c.Co : c.Ci, Co = transposed ? c.Ci : c.Co;
-  a.x = x; a.x_bstride = (long)h * w * Ci; a.w = transposed ? c.wt_t : c.wt; a.s = n->ones.p; a.d = nullptr;
-  a.noise = nullptr; a.bias = transposed ? c.zero_bias : c.bias; a.y = y;
+  a.x = x; a.x_bstride = (long)h * w * Ci; a.w = transposed ? c.wt_t.get() : c.wt.get(); a.s = n->ones.p(); a.d = nullptr;
+  a.noise = nullptr; a.bias = (transposed ? c.zero_bias : c.bias).as<float>(); a.y = y;
   a.B = B; a.H = h; a.W = w; a.Ci = Ci; a.Co = Co; a.up = 1;
   a.act = transposed ? MAUA_ACT_LINEAR : MAUA_ACT_LRELU; a.alpha = transposed ? 1.f : 0.f; a.gain = 1.f; a.clamp = -1.f;
   // bf16: the LDS-direct kernel where its tiles fit (8 x 32 pixels; 128 / 256-channel N tiles, or the 64-channel narrow form)
@@ -643,7 +633,7 @@ int forward_t(maua_vgg* n, const float* img, int B, int H, int W) {
   {
     const PlainConv& c = n->convs[0];
     const long total = (long)B * H * W * (c.Co / 16);
-    hipLaunchKernelGGL(vgg_conv0_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)27 * c.Co * 4, st, img, (const float*)c.wt, c.bias,
+    hipLaunchKernelGGL(vgg_conv0_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)27 * c.Co * 4, st, img, c.wt.as<float>(), c.bias.as<float>(),
                        (T*)n->ops[0].act, B, H, W, c.Co, n->pad0, n->in_mul, n->in_add, n->mean[0], n->mean[1], n->mean[2], n->istd[0],
                        n->istd[1], n->istd[2]);
     MAUA_HIP_CHECK(hipGetLastError());
@@ -685,11 +675,11 @@ int backward_t(maua_vgg* n, float* grad) {
       if (i == 0) {
         const long total = (long)B * H * W;
         if (c.Co == 64)
-          hipLaunchKernelGGL(vgg_conv0_vjp64_kernel<T>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, (const T*)gpre, (const float*)c.wt, grad, B, H, W,
+          hipLaunchKernelGGL(vgg_conv0_vjp64_kernel<T>, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, (const T*)gpre, c.wt.as<float>(), grad, B, H, W,
                              n->pad0, n->in_mul * n->istd[0], n->in_mul * n->istd[1], n->in_mul * n->istd[2]);
         else
           hipLaunchKernelGGL(vgg_conv0_vjp_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)27 * c.Co * 4, st, (const T*)gpre,
-                             (const float*)c.wt, grad, B, H, W, c.Co, n->pad0, n->in_mul * n->istd[0], n->in_mul * n->istd[1], n->in_mul * n->istd[2]);
+                             c.wt.as<float>(), grad, B, H, W, c.Co, n->pad0, n->in_mul * n->istd[0], n->in_mul * n->istd[1], n->in_mul * n->istd[2]);
         MAUA_HIP_CHECK(hipGetLastError());
       } else {
         T* gprev = (gpre == bufa) ? bufb : bufa;
@@ -714,12 +704,12 @@ int gram_t(maua_vgg* n, int op, float* G_out) {
   const POp& o = n->ops[op];
   const long hw = (long)(n->H >> o.shift) * (n->W >> o.shift);
   const int S = (int)((hw + GRAM_PX - 1) / GRAM_PX), C = o.C;
-  MAUA_REQUIRE((size_t)n->B * S * C * C * 4 <= n->fbuf_bytes, "maua_vgg: gram workspace too small");
+  MAUA_REQUIRE((size_t)n->B * S * C * C * 4 <= n->fbuf.bytes(), "maua_vgg: gram workspace too small");
   const int tiles = C / 64;
-  hipLaunchKernelGGL(gram_partial_kernel<T>, dim3(tiles * tiles, S, n->B), dim3(256), 0, st, (const T*)o.act, n->fbuf, hw, C, S);
+  hipLaunchKernelGGL(gram_partial_kernel<T>, dim3(tiles * tiles, S, n->B), dim3(256), 0, st, (const T*)o.act, n->fbuf.as<float>(), hw, C, S);
   MAUA_HIP_CHECK(hipGetLastError());
   const long CC = (long)C * C;
-  hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)((CC + 255) / 256), n->B), dim3(256), 0, st, (const float*)n->fbuf, G_out, CC, S);
+  hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)((CC + 255) / 256), n->B), dim3(256), 0, st, n->fbuf.as<float>(), G_out, CC, S);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
 }
@@ -782,9 +772,9 @@ int gram_mean_grad_t(maua_vgg* n, const float* img, int B, int H, int W, const i
     const int blocks = (int)((CC + 255) / 256);
     const float bhw = (float)B * (float)hw;
     hipLaunchKernelGGL(gram_mean_dsym_kernel<T>, dim3(blocks), dim3(256), 0, st, (const float*)n->gram, targets[k], C, B, 1.f / bhw,
-                       2.f / ((float)CC * bhw), (T*)n->sym, n->fbuf);   // (the Gram partials in fbuf are spent once gram_t has reduced them)
+                       2.f / ((float)CC * bhw), (T*)n->sym, n->fbuf.as<float>());   // (the Gram partials in fbuf are spent once gram_t has reduced them)
     MAUA_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(gram_mean_loss_kernel, dim3(1), dim3(256), 0, st, (const float*)n->fbuf, blocks, 1.f / (float)CC, n->loss_dev);
+    hipLaunchKernelGGL(gram_mean_loss_kernel, dim3(1), dim3(256), 0, st, n->fbuf.as<float>(), blocks, 1.f / (float)CC, n->loss_dev);
     MAUA_HIP_CHECK(hipGetLastError());
     {                                      // d L / d F_b = F_b Sym: [hw][C] x [C][C]^T, one operand for every image
       GemmArgs g{};
@@ -815,9 +805,9 @@ int lpips_grad_t(maua_vgg* n, const float* img, int B, int H, int W, const int* 
     const long hw = (long)(H >> o.shift) * (W >> o.shift);
     const long n_pix = (long)B * hw;
     hipLaunchKernelGGL(lpips_head_kernel<T>, dim3((unsigned)((n_pix + 3) / 4)), dim3(256), 0, st, (const T*)o.act, targets[k],
-                       t_bstride ? t_bstride[k] : 0L, lins[k], n->fbuf, (T*)o.hg, B, hw, o.C, scale / (float)hw);
+                       t_bstride ? t_bstride[k] : 0L, lins[k], n->fbuf.as<float>(), (T*)o.hg, B, hw, o.C, scale / (float)hw);
     MAUA_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(rows_sum_kernel, dim3(B), dim3(1024), 0, st, (const float*)n->fbuf, hw, 1.f / (float)hw, n->loss_dev);
+    hipLaunchKernelGGL(rows_sum_kernel, dim3(B), dim3(1024), 0, st, n->fbuf.as<float>(), hw, 1.f / (float)hw, n->loss_dev);
     MAUA_HIP_CHECK(hipGetLastError());
     o.hg_set = true;
   }
@@ -860,7 +850,7 @@ int maua_vgg_create(maua_ctx* ctx, int dtype, const int* plan, int n_ops, int re
       if (plan[i] % 64 != 0 || plan[i] > 512) { maua_vgg_destroy(n); return fail("maua_vgg_create: channels must be multiples of 64, at most 512"); }
       o.kind = 0; o.conv = (int)n->convs.size(); o.C = plan[i];
       PlainConv c; c.Ci = cin; c.Co = plan[i];
-      n->convs.push_back(c);
+      n->convs.push_back(std::move(c));
       cin = plan[i];
     } else {
       if (i > 0 && n->ops.back().kind == 1) { maua_vgg_destroy(n); return fail("maua_vgg_create: two pooling layers in a row"); }
@@ -880,9 +870,6 @@ int maua_vgg_create(maua_ctx* ctx, int dtype, const int* plan, int n_ops, int re
 void maua_vgg_destroy(maua_vgg* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  free_ws(n);
-  for (auto& c : n->convs) c.free();
-  n->ones.free();
   delete n;
 }
 
@@ -913,7 +900,7 @@ int maua_vgg_load(maua_vgg* n, int index, int what, const float* host, size_t co
     for (int o = 0; o < c.Co; o++)
       for (int i = 0; i < 3; i++)
         for (int k = 0; k < 9; k++) w0[((size_t)i * 9 + k) * c.Co + o] = host[((size_t)o * 3 + i) * 9 + k];
-    MAUA_HIP_CHECK(hipMemcpy(c.wt, w0.data(), w0.size() * 4, hipMemcpyHostToDevice));
+    MAUA_HIP_CHECK(hipMemcpy(c.wt.get(), w0.data(), w0.size() * 4, hipMemcpyHostToDevice));
     return MAUA_OK;
   }
   return c.load_weight(st, n->dtype, host, true);

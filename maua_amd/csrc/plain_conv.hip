@@ -7,32 +7,25 @@
 
 namespace maua {
 
-int DevTemp::alloc(size_t count) {
-  hipFree(p);
-  p = nullptr;
-  MAUA_HIP_CHECK(hipMalloc((void**)&p, count * 4));
-  return MAUA_OK;
-}
-
-int DevTemp::stage(const float* src, size_t count, hipMemcpyKind kind) {
-  if (int rc = alloc(count)) return rc;
-  MAUA_HIP_CHECK(hipMemcpy(p, src, count * 4, kind));
+int stage(DevBuf& tmp, const float* src, size_t count, hipMemcpyKind kind) {
+  if (int rc = tmp.alloc(count * 4)) return rc;
+  MAUA_HIP_CHECK(hipMemcpy(tmp.get(), src, count * 4, kind));
   return MAUA_OK;
 }
 
 int load_weight(hipStream_t st, int dtype, const float* host, int Co, int Ci, int k, int Cop, int Cip, void* wt, void* wt_t, bool split) {
   const size_t count = (size_t)Co * Ci * k * k;
   const size_t elems = prepped_weight_elems(k, 1, Cop, Cip), bytes = elems * elem_bytes(dtype);
-  DevTemp w, w_t;
-  if (int rc = w.stage(host, count)) return rc;
+  DevBuf w, w_t;
+  if (int rc = stage(w, host, count)) return rc;
   auto prep = [&]() -> int {
     MAUA_HIP_CHECK(hipMemsetAsync(wt, 0, bytes, st));   // (padded channels stay zero)
-    if (int rc = launch_prep_weights(st, dtype, w.p, wt, nullptr, Co, Ci, k, 1, 0, Cop, Cip)) return rc;
+    if (int rc = launch_prep_weights(st, dtype, w.as<float>(), wt, nullptr, Co, Ci, k, 1, 0, Cop, Cip)) return rc;
     if (wt_t) {
-      if (int rc = w_t.alloc(count)) return rc;
-      if (int rc = launch_transpose_flip(st, w.p, w_t.p, Co, Ci, k * k)) return rc;
+      if (int rc = w_t.alloc(count * 4)) return rc;
+      if (int rc = launch_transpose_flip(st, w.as<float>(), w_t.as<float>(), Co, Ci, k * k)) return rc;
       MAUA_HIP_CHECK(hipMemsetAsync(wt_t, 0, bytes, st));
-      if (int rc = launch_prep_weights(st, dtype, w_t.p, wt_t, nullptr, Ci, Co, k, 1, 0, Cip, Cop)) return rc;
+      if (int rc = launch_prep_weights(st, dtype, w_t.as<float>(), wt_t, nullptr, Ci, Co, k, 1, 0, Cip, Cop)) return rc;
     }
     if (split) {   // both copies in the form the matrix cores read
       if (int rc = launch_f32_split_inplace(st, wt, (long)elems)) return rc;
@@ -48,43 +41,29 @@ int load_weight(hipStream_t st, int dtype, const float* host, int Co, int Ci, in
 
 int PlainConv::alloc(int ci, int co, int cip, int cop, size_t es, bool transposed) {
   Ci = ci; Co = co; Cip = cip; Cop = cop; esize = es;
-  const size_t wb = (size_t)9 * Cop * Cip * esize;
-  MAUA_HIP_CHECK(hipMalloc(&wt, wb));
-  MAUA_HIP_CHECK(hipMemset(wt, 0, wb));
-  MAUA_HIP_CHECK(hipMalloc((void**)&bias, (size_t)Cop * 4));
-  MAUA_HIP_CHECK(hipMemset(bias, 0, (size_t)Cop * 4));
+  if (int rc = wt.alloc((size_t)9 * Cop * Cip * esize, true)) return rc;
+  if (int rc = bias.alloc((size_t)Cop * 4, true)) return rc;
   return transposed ? alloc_transposed() : MAUA_OK;
 }
 
 int PlainConv::alloc_transposed() {
-  const size_t wb = (size_t)9 * Cop * Cip * esize, zb = (size_t)std::max(Cip, Cop) * 4;
-  if (!wt_t) {
-    MAUA_HIP_CHECK(hipMalloc(&wt_t, wb));
-    MAUA_HIP_CHECK(hipMemset(wt_t, 0, wb));
-  }
-  if (!zero_bias) {
-    MAUA_HIP_CHECK(hipMalloc((void**)&zero_bias, zb));
-    MAUA_HIP_CHECK(hipMemset(zero_bias, 0, zb));
-  }
+  if (!wt_t)
+    if (int rc = wt_t.alloc((size_t)9 * Cop * Cip * esize, true)) return rc;
+  if (!zero_bias)
+    if (int rc = zero_bias.alloc((size_t)std::max(Cip, Cop) * 4, true)) return rc;
   return MAUA_OK;
-}
-
-void PlainConv::free() {
-  hipFree(wt); hipFree(wt_t); hipFree(bias); hipFree(zero_bias);
-  wt = wt_t = nullptr;
-  bias = zero_bias = nullptr;
 }
 
 int PlainConv::load_bias(hipStream_t st, const float* host) {
   MAUA_HIP_CHECK(hipStreamSynchronize(st));   // (a forward that reads the old values may still run)
-  MAUA_HIP_CHECK(hipMemcpy(bias, host, (size_t)Co * 4, hipMemcpyHostToDevice));
+  MAUA_HIP_CHECK(hipMemcpy(bias.get(), host, (size_t)Co * 4, hipMemcpyHostToDevice));
   return MAUA_OK;
 }
 
 int PlainConv::load_weight(hipStream_t st, int dtype, const float* host, bool transposed, bool split) {
   if (transposed)
     if (int rc = alloc_transposed()) return rc;
-  return maua::load_weight(st, dtype, host, Co, Ci, 3, Cop, Cip, wt, transposed ? wt_t : nullptr, split);
+  return maua::load_weight(st, dtype, host, Co, Ci, 3, Cop, Cip, wt.get(), transposed ? wt_t.get() : nullptr, split);
 }
 
 namespace {
@@ -106,18 +85,12 @@ int UnitStyles::ensure(hipStream_t st, int B, int C, bool* moved) {
   MAUA_HIP_CHECK(hipStreamSynchronize(st));
   const int nb = std::max(B, b), nc = std::max(C, c);
   if (moved) *moved = true;
-  free();
-  MAUA_HIP_CHECK(hipMalloc((void**)&p, (size_t)nb * nc * 4));
-  if (int rc = launch_fill_ones(st, p, (long)nb * nc)) return rc;
+  b = c = 0;
+  if (int rc = buf.alloc((size_t)nb * nc * 4)) return rc;
+  if (int rc = launch_fill_ones(st, p(), (long)nb * nc)) return rc;
   MAUA_HIP_CHECK(hipStreamSynchronize(st));
   b = nb; c = nc;
   return MAUA_OK;
-}
-
-void UnitStyles::free() {
-  hipFree(p);
-  p = nullptr;
-  b = c = 0;
 }
 
 }  // namespace maua

@@ -222,10 +222,6 @@ void maua_unet::SamplerState::release() {
     if (s) hipStreamDestroy(s);
   for (hipEvent_t e : {ev_fork, ev_join})
     if (e) hipEventDestroy(e);
-  // (g_x is the caller's tensor the graph was captured on)
-  for (void* p : {(void*)gd_buf, (void*)gd_tab, (void*)gd_flag, (void*)gd_rects, (void*)gd_gflag, (void*)g_out, (void*)g_pred, (void*)g_t,
-                  (void*)g_cf, (void*)emb_table})
-    if (p) hipFree(p);
   *this = SamplerState();
 }
 
@@ -331,11 +327,11 @@ static int prepare_sampler(maua_unet* n, int B, int H, int W, const float* model
   // per-step constants on the device: timesteps [n_steps][B], coefficients [n_steps][B][8]
   if (n->smp.g_steps < n_steps * B || !n->smp.g_t) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    for (float** p : {&n->smp.g_t, &n->smp.g_cf}) { if (*p) hipFree(*p); *p = nullptr; }
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.g_t, (size_t)n_steps * B * 4));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.g_cf, (size_t)n_steps * B * 8 * 4));
-    n->smp.g_steps = n_steps * B;
+    n->smp.g_steps = 0;
     drop_sampler_graphs(n);
+    if (int rc = n->smp.g_t.alloc((size_t)n_steps * B * 4)) return rc;
+    if (int rc = n->smp.g_cf.alloc((size_t)n_steps * B * 8 * 4)) return rc;
+    n->smp.g_steps = n_steps * B;
   }
   {
     std::vector<float> ht((size_t)n_steps * B), hc((size_t)n_steps * B * 8);
@@ -344,39 +340,36 @@ static int prepare_sampler(maua_unet* n, int B, int H, int W, const float* model
         ht[(size_t)s * B + b] = model_t[s];
         memcpy(&hc[((size_t)s * B + b) * 8], coef + (size_t)s * 8, 32);
       }
-    MAUA_HIP_CHECK(hipMemcpyAsync(n->smp.g_t, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
-    MAUA_HIP_CHECK(hipMemcpyAsync(n->smp.g_cf, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, st));
+    MAUA_HIP_CHECK(hipMemcpyAsync(n->smp.g_t.as<float>(), ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
+    MAUA_HIP_CHECK(hipMemcpyAsync(n->smp.g_cf.as<float>(), hc.data(), hc.size() * 4, hipMemcpyHostToDevice, st));
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
   }
   const size_t out_bytes = (size_t)B * n->out_ch * H * W * 4, pred_bytes = (size_t)B * chw * 4;
-  if (!n->smp.g_out || n->smp.out_cap < out_bytes + pred_bytes) {
+  if (!n->smp.g_out || !n->smp.g_pred || n->smp.g_out.bytes() + n->smp.g_pred.bytes() < out_bytes + pred_bytes) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    for (float** p : {&n->smp.g_out, &n->smp.g_pred}) { if (*p) hipFree(*p); *p = nullptr; }
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.g_out, out_bytes));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.g_pred, pred_bytes));
-    n->smp.out_cap = out_bytes + pred_bytes;
     drop_sampler_graphs(n);
+    if (int rc = n->smp.g_out.alloc(out_bytes)) return rc;
+    if (int rc = n->smp.g_pred.alloc(pred_bytes)) return rc;
   }
   // every step's timestep projections at once: the timesteps are known up front and shared by the samples, so the stacked
   // emb_layers GEMV (51 k x 1024 f32 weights at the 256^2 configuration) runs once per loop with n_steps rows instead of
   // once per step with B rows
   if (n->smp.emb_table_rows < (size_t)n_steps) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->smp.emb_table) hipFree(n->smp.emb_table);
-    n->smp.emb_table = nullptr; n->smp.emb_table_rows = 0;
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.emb_table, (size_t)n_steps * n->emb_total * 4));
-    n->smp.emb_table_rows = n_steps;
+    n->smp.emb_table_rows = 0;
     drop_sampler_graphs(n);
+    if (int rc = n->smp.emb_table.alloc((size_t)n_steps * n->emb_total * 4)) return rc;
+    n->smp.emb_table_rows = n_steps;
   }
   {
     const int E = n->emb_dim, mc = n->mc;
-    float *tt, *e0, *e1, *e2;
-    MAUA_HIP_CHECK(hipMalloc((void**)&tt, (size_t)n_steps * (1 + mc + 2 * E) * 4));
+    DevBuf tmp;
+    if (int rc = tmp.alloc((size_t)n_steps * (1 + mc + 2 * E) * 4)) return rc;
+    float *tt = tmp.as<float>(), *e0, *e1, *e2;
     e0 = tt + n_steps; e1 = e0 + (size_t)n_steps * mc; e2 = e1 + (size_t)n_steps * E;
     MAUA_HIP_CHECK(hipMemcpyAsync(tt, model_t, (size_t)n_steps * 4, hipMemcpyHostToDevice, st));
-    if (int rc = unet_emb_rows(n, st, tt, n_steps, e0, e1, e2, n->smp.emb_table)) return rc;
+    if (int rc = unet_emb_rows(n, st, tt, n_steps, e0, e1, e2, n->smp.emb_table.as<float>())) return rc;
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    hipFree(tt);
   }
   return MAUA_OK;
 }
@@ -396,24 +389,23 @@ int maua_ddim_sample_loop(maua_unet* n, float* x, int B, int H, int W, const flo
   if (int rc = prepare_sampler(n, B, H, W, model_t, coef, n_steps)) return rc;
   const size_t pred_bytes = (size_t)B * chw * 4;
   auto body = [&](int s) -> int {
-    n->emb_row = n->smp.emb_table + (size_t)s * n->emb_total;
-    int rc = maua_unet_forward(n, x, n->smp.g_t + (size_t)s * B, B, H, W, n->smp.g_out);
+    n->emb_row = n->smp.emb_table.as<float>() + (size_t)s * n->emb_total;
+    int rc = maua_unet_forward(n, x, n->smp.g_t.as<float>() + (size_t)s * B, B, H, W, n->smp.g_out.as<float>());
     n->emb_row = nullptr;
     if (rc) return rc;
-    return maua_ddim_step(n->ctx, x, n->smp.g_out, nullptr, nullptr, n->smp.g_cf + (size_t)s * B * 8, B, n->in_ch, n->out_ch,
-                          (long)H * W, x, n->smp.g_pred);
+    return maua_ddim_step(n->ctx, x, n->smp.g_out.as<float>(), nullptr, nullptr, n->smp.g_cf.as<float>() + (size_t)s * B * 8, B, n->in_ch, n->out_ch,
+                          (long)H * W, x, n->smp.g_pred.as<float>());
   };
   if (use_graph && !n->smp.graph_failed) {
     if (!n->smp.graph_exec || n->smp.graph_key != key || n->smp.g_x != x) {
       // one eager forward first: plans the arena, sets the kernels' attributes (nothing of that is capturable)
       // - on a scratch copy so that x is not advanced
       if (!unet_planned(n, B, H, W)) {
-        float* tmp;
-        MAUA_HIP_CHECK(hipMalloc((void**)&tmp, pred_bytes));
-        MAUA_HIP_CHECK(hipMemcpyAsync(tmp, x, pred_bytes, hipMemcpyDeviceToDevice, st));
-        int rc = maua_unet_forward(n, tmp, n->smp.g_t, B, H, W, n->smp.g_out);
+        DevBuf tmp;
+        if (int rc = tmp.alloc(pred_bytes)) return rc;
+        MAUA_HIP_CHECK(hipMemcpyAsync(tmp.get(), x, pred_bytes, hipMemcpyDeviceToDevice, st));
+        int rc = maua_unet_forward(n, tmp.as<float>(), n->smp.g_t.as<float>(), B, H, W, n->smp.g_out.as<float>());
         hipStreamSynchronize(st);
-        hipFree(tmp);
         if (rc) return rc;
       }
       auto step = [&](int s, hipStream_t main, hipStream_t) -> int {
@@ -433,7 +425,7 @@ int maua_ddim_sample_loop(maua_unet* n, float* x, int B, int H, int W, const flo
     for (int s = 0; s < n_steps; s++)
       if (int rc = body(s)) return rc;
   }
-  if (pred_xstart) MAUA_HIP_CHECK(hipMemcpyAsync(pred_xstart, n->smp.g_pred, pred_bytes, hipMemcpyDeviceToDevice, st));
+  if (pred_xstart) MAUA_HIP_CHECK(hipMemcpyAsync(pred_xstart, n->smp.g_pred.as<float>(), pred_bytes, hipMemcpyDeviceToDevice, st));
   return MAUA_OK;
 }
 
@@ -521,14 +513,13 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
   const size_t tb = (size_t)B * chw, tab = (size_t)n_steps * B * 7 + B;
   if (n->smp.gd_cap < 10 * tb || n->smp.gd_tab_cap < tab || !n->smp.gd_flag || n->smp.gd_flags < n_steps) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    for (void* p : {(void*)n->smp.gd_buf, (void*)n->smp.gd_tab, (void*)n->smp.gd_flag})
-      if (p) hipFree(p);
-    n->smp.gd_buf = nullptr; n->smp.gd_tab = nullptr; n->smp.gd_flag = nullptr; n->smp.gd_cap = n->smp.gd_tab_cap = 0;
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.gd_buf, 10 * tb * 4));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.gd_tab, tab * 4));
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.gd_flag, (size_t)n_steps * 4));
-    n->smp.gd_cap = 10 * tb; n->smp.gd_tab_cap = tab; n->smp.gd_flags = n_steps;
+    n->smp.gd_cap = n->smp.gd_tab_cap = 0; n->smp.gd_flags = 0;
     drop_sampler_graphs(n);
+    auto layout = [&](Scratch& s) {
+      n->smp.gd_buf = s.take<float>(10 * tb); n->smp.gd_tab = s.take<float>(tab); n->smp.gd_flag = s.take<int>((size_t)n_steps);
+    };
+    if (int rc = carve_into(n->smp.gd_ws, layout)) return rc;
+    n->smp.gd_cap = 10 * tb; n->smp.gd_tab_cap = tab; n->smp.gd_flags = n_steps;
   }
   float *bx = n->smp.gd_buf, *bv = bx + tb, *bp = bv + tb, *be = bp + tb, *bimg = be + tb, *bg = bimg + tb, *bjv = bg + tb,
         *bgrad = bjv + tb, *btgt = bgrad + tb, *bsub = btgt + tb;
@@ -558,7 +549,7 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
   auto guide_grad = [&](int s) -> int {
     int rc = MAUA_OK;
     if (clip)
-      rc = clip_guide_grad(clip, bimg, B, H, W, n->smp.gd_rects + (size_t)s * n->smp.gd_batches * n->smp.gd_cutn * 3,
+      rc = clip_guide_grad(clip, bimg, B, H, W, n->smp.gd_rects.as<int>() + (size_t)s * n->smp.gd_batches * n->smp.gd_cutn * 3,
                            n->smp.gd_mult ? n->smp.gd_mult + (size_t)s * n->smp.gd_batches * n->smp.gd_cutn : nullptr, n->smp.gd_cutn, n->smp.gd_cutn_total,
                            n->smp.gd_batches, n->smp.gd_clip_scale, n->smp.gd_clip_clamp, bg);
     else if (!guides)
@@ -566,7 +557,7 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
     // guided.py:258-266: img_grad += sub_grad per module, a module whose gradient holds a NaN skipped
     for (size_t k = 0; k < n->smp.gd_guides.size() && !rc; k++) {
       rc = guide_eval(n->smp.gd_guides[k], bimg, B, H, W, bsub);
-      if (!rc) rc = screened_accumulate(n->ctx->stream, bsub, bg, (long)tb, !clip && k == 0, n->smp.gd_gflag);
+      if (!rc) rc = screened_accumulate(n->ctx->stream, bsub, bg, (long)tb, !clip && k == 0, n->smp.gd_gflag.as<int>());
     }
     return rc;
   };
@@ -581,12 +572,12 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
   // speed "regular": no parallel branch (the gradient needs the forward it differentiates); everything on `main`
   auto step_regular = [&](int s, hipStream_t main) -> int {
     n->ctx->stream = main;
-    n->emb_row = n->smp.emb_table + (size_t)s * n->emb_total;
-    int rc = unet_forward(n, bx, n->smp.g_t + (size_t)s * B, B, H, W, n->smp.g_out, true);
+    n->emb_row = n->smp.emb_table.as<float>() + (size_t)s * n->emb_total;
+    int rc = unet_forward(n, bx, n->smp.g_t.as<float>() + (size_t)s * B, B, H, W, n->smp.g_out.as<float>(), true);
     if (!rc) {
       // pred_xstart = ra x - rm eps (gaussian_diffusion.py _predict_xstart_from_eps), img = sigma pred + (1 - sigma) x (:252)
       const long total = (long)B * chw;
-      hipLaunchKernelGGL(eps_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, main, n->smp.g_out, chw, (long)n->out_ch * H * W,
+      hipLaunchKernelGGL(eps_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, main, n->smp.g_out.as<float>(), chw, (long)n->out_ch * H * W,
                          total, be);
       if (hipGetLastError() != hipSuccess) rc = fail("maua_ddim_guided_loop: launch failed");
       if (!rc) rc = maua_axpby_rows(n->ctx, bx, be, t_pred + (size_t)s * B * 2, B, chw, bp);
@@ -597,8 +588,8 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
     n->emb_row = nullptr;
     if (!rc) rc = maua_axpby_rows(n->ctx, bg, bjv, t_grad + (size_t)s * B * 2, B, chw, bgrad);
     if (rc) return rc;
-    return maua_ddim_step(n->ctx, bx, n->smp.g_out, bgrad, nullptr, n->smp.g_cf + (size_t)s * B * 8, B, n->in_ch, n->out_ch, (long)H * W, bx,
-                          n->smp.g_pred);
+    return maua_ddim_step(n->ctx, bx, n->smp.g_out.as<float>(), bgrad, nullptr, n->smp.g_cf.as<float>() + (size_t)s * B * 8, B, n->in_ch, n->out_ch, (long)H * W, bx,
+                          n->smp.g_pred.as<float>());
   };
   auto step_on = [&](int s, hipStream_t main, hipStream_t side) -> int {
     if (regular) return step_regular(s, main);
@@ -608,8 +599,8 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
       MAUA_HIP_CHECK(hipStreamWaitEvent(side, n->smp.ev_fork, 0));
     }
     n->ctx->stream = main;
-    n->emb_row = n->smp.emb_table + (size_t)s * n->emb_total;
-    int rc = maua_unet_forward(n, bx, n->smp.g_t + (size_t)s * B, B, H, W, n->smp.g_out);
+    n->emb_row = n->smp.emb_table.as<float>() + (size_t)s * n->emb_total;
+    int rc = maua_unet_forward(n, bx, n->smp.g_t.as<float>() + (size_t)s * B, B, H, W, n->smp.g_out.as<float>());
     n->emb_row = nullptr;
     if (!rc) {
       n->ctx->stream = side;
@@ -625,8 +616,8 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
       if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) rc = fail("maua_ddim_guided_loop: joining the guidance branch failed");
     }
     if (rc) return rc;
-    return maua_ddim_step(n->ctx, bx, n->smp.g_out, bgrad, nullptr, n->smp.g_cf + (size_t)s * B * 8, B, n->in_ch, n->out_ch, (long)H * W, bx,
-                          n->smp.g_pred);
+    return maua_ddim_step(n->ctx, bx, n->smp.g_out.as<float>(), bgrad, nullptr, n->smp.g_cf.as<float>() + (size_t)s * B * 8, B, n->in_ch, n->out_ch, (long)H * W, bx,
+                          n->smp.g_pred.as<float>());
   };
   auto body = [&](int s) -> int {   // eager: on the caller's stream (+ the side stream)
     int rc = step_on(s, st, n->smp.gd_fork ? n->smp.side_stream : st);
@@ -680,7 +671,7 @@ int maua_ddim_guided_loop(maua_unet* n, maua_secondary* sec, float* x, int B, in
       if (int rc = body(s)) return rc;
   }
   MAUA_HIP_CHECK(hipMemcpyAsync(x, bx, tb * 4, hipMemcpyDeviceToDevice, st));
-  if (pred_xstart) MAUA_HIP_CHECK(hipMemcpyAsync(pred_xstart, n->smp.g_pred, tb * 4, hipMemcpyDeviceToDevice, st));
+  if (pred_xstart) MAUA_HIP_CHECK(hipMemcpyAsync(pred_xstart, n->smp.g_pred.as<float>(), tb * 4, hipMemcpyDeviceToDevice, st));
   return MAUA_OK;
 }
 
@@ -706,21 +697,18 @@ int maua_unet_set_clip_guide(maua_unet* n, maua_clip* clip, const int* rects, co
                    "maua_unet_set_clip_guide: every cutout batch must stand for the same number (>= cutn) of cutouts");
     }
   }
-  if (cnt > n->smp.gd_rects_cap) {
+  if (cnt * 4 > n->smp.gd_rects.bytes()) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    if (n->smp.gd_rects) hipFree(n->smp.gd_rects);
-    n->smp.gd_rects = nullptr; n->smp.gd_rects_cap = 0;
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.gd_rects, cnt * 4));
-    n->smp.gd_rects_cap = cnt;
     n->smp.gd_guide_gen++;
+    if (int rc = n->smp.gd_rects.alloc(cnt * 4)) return rc;
   }
-  float* mult_dev = mult ? (float*)(n->smp.gd_rects + per * 3) : nullptr;
+  float* mult_dev = mult ? (float*)(n->smp.gd_rects.as<int>() + per * 3) : nullptr;
   // (everything a captured loop bakes into its launches moves the generation; the rectangles themselves are data it reads)
   if (n->smp.gd_clip != clip || n->smp.gd_rect_steps != n_steps || n->smp.gd_cutn != cutn || n->smp.gd_batches != batches || n->smp.gd_clip_scale != scale ||
       n->smp.gd_clip_clamp != clamp_gradient || n->smp.gd_mult != mult_dev || n->smp.gd_cutn_total != cutn_total)
     n->smp.gd_guide_gen++;
   n->smp.gd_rects_host.assign(rects, rects + per * 3);
-  MAUA_HIP_CHECK(hipMemcpyAsync(n->smp.gd_rects, n->smp.gd_rects_host.data(), per * 12, hipMemcpyHostToDevice, st));
+  MAUA_HIP_CHECK(hipMemcpyAsync(n->smp.gd_rects.as<int>(), n->smp.gd_rects_host.data(), per * 12, hipMemcpyHostToDevice, st));
   if (mult) MAUA_HIP_CHECK(hipMemcpyAsync(mult_dev, mult, per * 4, hipMemcpyHostToDevice, st));
   MAUA_HIP_CHECK(hipStreamSynchronize(st));
   n->smp.gd_clip = clip; n->smp.gd_rect_steps = n_steps; n->smp.gd_cutn = cutn; n->smp.gd_batches = batches; n->smp.gd_clip_scale = scale;
@@ -739,7 +727,8 @@ int maua_unet_set_guides(maua_unet* n, maua_guide* const* guides, int n_guides) 
   if (uids != n->smp.gd_guide_uids) n->smp.gd_guide_gen++;   // (a captured loop bakes the list into its launches)
   n->smp.gd_guide_uids = uids;
   n->smp.gd_guides.assign(guides, guides + n_guides);
-  if (n_guides && !n->smp.gd_gflag) MAUA_HIP_CHECK(hipMalloc((void**)&n->smp.gd_gflag, 256));
+  if (n_guides && !n->smp.gd_gflag)
+    if (int rc = n->smp.gd_gflag.alloc(256)) return rc;
   return MAUA_OK;
 }
 

@@ -263,10 +263,11 @@ struct maua_secondary {
   int conv_dtype;
   size_t esize;
   PlainConv conv[NCONV];   // padded to 32 channels, each with its transposed copy
-  float* wemb = nullptr;   // [8] FourierFeatures weight
+  DevBuf wemb;             // float [8] FourierFeatures weight
   UnitStyles ones;         // [bcap][512]
-  // activations of the last forward (grow-only): see forward_t for the layout
-  size_t cap_px = 0;       // B * H * W
+  // activations of the last forward and the gradient workspaces: one set carved from ws (grow-only); see forward_t for the layout
+  DevBuf ws;
+  size_t cap_px = 0;       // B * H * W the pieces were placed for
   int B = 0, H = 0, W = 0; // shape of the last forward (0: none)
   void* in0 = nullptr;
   void* a[5] = {};         // first conv of each level: a[0] = c0 out, a[k] = c(2k) out
@@ -284,19 +285,6 @@ namespace {
 int level_ch_main(int k) { return k == 0 ? CS[0] : k == 1 ? CS[1] : k == 2 ? CS[2] : k == 3 ? CS[3] : CS[4]; }   // channels of up(main) at level k
 int level_ch_skip(int k) { return CS[k]; }                                                                      // ... of the skip s_k
 
-void free_ws(maua_secondary* n) {
-  auto f = [](void*& p) { if (p) hipFree(p); p = nullptr; };
-  f(n->in0); f(n->vbuf); f(n->ga); f(n->gb); f(n->gcat); f(n->gpool);
-  for (auto& p : n->a) f(p);
-  for (auto& p : n->cat) f(p);
-  for (auto& p : n->pool) f(p);
-  for (auto& p : n->bott) f(p);
-  for (auto& p : n->dec) f(p);
-  n->cap_px = 0;
-  n->B = n->H = n->W = 0;
-  n->epoch++;
-}
-
 // the 24 convolutions in execution order: channels in / out (guided.py:77-134)
 void conv_plan(int (&ci)[NCONV], int (&co)[NCONV]) {
   const int c0 = CS[0], c1 = CS[1], c2 = CS[2], c3 = CS[3], c4 = CS[4], c5 = CS[5];
@@ -311,32 +299,33 @@ int ensure_ws(maua_secondary* n, int B, int H, int W) {
   const size_t px = (size_t)B * H * W, es = n->esize;
   if (px > n->cap_px) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    free_ws(n);
-    auto al = [&](void*& p, size_t elems) -> int {
-      MAUA_HIP_CHECK(hipMalloc(&p, elems * es));
-      return MAUA_OK;
+    n->cap_px = 0;
+    n->B = n->H = n->W = 0;
+    n->epoch++;
+    auto layout = [&](Scratch& s) {
+      auto take = [&](size_t elems) -> void* { return s.take<char>(elems * es); };
+      n->in0 = take(px * 32);
+      n->vbuf = take(px * 32);
+      for (int k = 0; k < 5; k++) {
+        const size_t lp = px >> (2 * k);
+        n->a[k] = take(lp * CS[k]);
+        n->cat[k] = take(lp * (level_ch_main(k) + level_ch_skip(k)));
+        n->pool[k] = take((lp >> 2) * CS[k]);
+      }
+      const size_t l5 = px >> 10;
+      const int bc[4] = {CS[5], CS[5], CS[5], CS[4]};
+      for (int i = 0; i < 4; i++) n->bott[i] = take(l5 * bc[i]);
+      // decoder outputs: c14, c15 at level 4; c16, c17 at 3; c18, c19 at 2; c20, c21 at 1; c22 at 0
+      const int dc[9] = {CS[4], CS[3], CS[3], CS[2], CS[2], CS[1], CS[1], CS[0], CS[0]};
+      const int dl[9] = {4, 4, 3, 3, 2, 2, 1, 1, 0};
+      for (int i = 0; i < 9; i++) n->dec[i] = take((px >> (2 * dl[i])) * dc[i]);
+      // gradient workspaces: the widest tensors of the backward pass are the level-0 ones (128 channels)
+      n->ga = take(px * 128);
+      n->gb = take(px * 128);
+      n->gcat = take(px * 224);   // the concatenations' gradients of all five levels, back to back: 128 + 64 + 16 + 8 + 2 per level-0 pixel
+      n->gpool = take(px * 128 / 4);
     };
-    int rc = al(n->in0, px * 32);
-    if (!rc) rc = al(n->vbuf, px * 32);
-    for (int k = 0; k < 5 && !rc; k++) {
-      const size_t lp = px >> (2 * k);
-      rc = al(n->a[k], lp * CS[k]);
-      if (!rc) rc = al(n->cat[k], lp * (level_ch_main(k) + level_ch_skip(k)));
-      if (!rc) rc = al(n->pool[k], (lp >> 2) * CS[k]);
-    }
-    const size_t l5 = px >> 10;
-    const int bc[4] = {CS[5], CS[5], CS[5], CS[4]};
-    for (int i = 0; i < 4 && !rc; i++) rc = al(n->bott[i], l5 * bc[i]);
-    // decoder outputs: c14, c15 at level 4; c16, c17 at 3; c18, c19 at 2; c20, c21 at 1; c22 at 0
-    const int dc[9] = {CS[4], CS[3], CS[3], CS[2], CS[2], CS[1], CS[1], CS[0], CS[0]};
-    const int dl[9] = {4, 4, 3, 3, 2, 2, 1, 1, 0};
-    for (int i = 0; i < 9 && !rc; i++) rc = al(n->dec[i], (px >> (2 * dl[i])) * dc[i]);
-    // gradient workspaces: the widest tensors of the backward pass are the level-0 ones (128 channels)
-    if (!rc) rc = al(n->ga, px * 128);
-    if (!rc) rc = al(n->gb, px * 128);
-    if (!rc) rc = al(n->gcat, px * 224);   // the concatenations' gradients of all five levels, back to back: 128 + 64 + 16 + 8 + 2 per level-0 pixel
-    if (!rc) rc = al(n->gpool, px * 128 / 4);
-    if (rc) return rc;
+    if (int rc = carve_into(n->ws, layout)) return rc;
     n->cap_px = px;
   }
   bool moved = false;
@@ -351,8 +340,8 @@ int run_conv(maua_secondary* n, const PlainConv& c, bool transposed, const void*
              bool relu) {
   ConvArgs a{};
   const int Ci = transposed ? c.Cop : c.Cip, Co = transposed ? c.Cip : c.Cop;
-  a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = transposed ? c.wt_t : c.wt; a.s = n->ones.p; a.d = nullptr;
-  a.noise = nullptr; a.bias = transposed ? c.zero_bias : c.bias; a.y = y; a.y_pstride = yps; a.y_coff = ycoff; a.y_bstride = (long)h * w * yps;
+  a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = transposed ? c.wt_t.get() : c.wt.get(); a.s = n->ones.p(); a.d = nullptr;
+  a.noise = nullptr; a.bias = (transposed ? c.zero_bias : c.bias).as<float>(); a.y = y; a.y_pstride = yps; a.y_coff = ycoff; a.y_bstride = (long)h * w * yps;
   a.B = B; a.H = h; a.W = w; a.Ci = Ci; a.Co = Co; a.up = 1;
   a.act = relu ? MAUA_ACT_LRELU : MAUA_ACT_LINEAR; a.alpha = relu ? 0.f : 1.f; a.gain = 1.f; a.clamp = -1.f;
   return launch_modconv3x3(n->ctx->stream, n->conv_dtype, a);
@@ -423,7 +412,7 @@ int forward_t(maua_secondary* n, const float* x, const float* t, int B, int H, i
   if (int rc = ensure_ws<T>(n, B, H, W)) return rc;
   const long HW = (long)H * W;
   int rc;
-  if ((rc = launch_sec_input<T>(st, x, t, n->wemb, B, HW, (T*)n->in0))) return rc;
+  if ((rc = launch_sec_input<T>(st, x, t, n->wemb.as<float>(), B, HW, (T*)n->in0))) return rc;
   // encoder: level k's skip s_k lands in the upper channel slice of cat[k]
   const void* cur = n->in0;
   int cur_ps = 32;
@@ -563,11 +552,10 @@ int maua_secondary_create(maua_ctx* ctx, int dtype, maua_secondary** out) {
       maua_secondary_destroy(n);
       return fail("maua_secondary_create: out of device memory");
     }
-  if (hipMalloc((void**)&n->wemb, 32) != hipSuccess) {
+  if (n->wemb.alloc(32, true)) {
     maua_secondary_destroy(n);
     return fail("maua_secondary_create: out of device memory");
   }
-  hipMemset(n->wemb, 0, 32);
   *out = n;
   return MAUA_OK;
 }
@@ -575,10 +563,6 @@ int maua_secondary_create(maua_ctx* ctx, int dtype, maua_secondary** out) {
 void maua_secondary_destroy(maua_secondary* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  free_ws(n);
-  for (auto& c : n->conv) c.free();
-  if (n->wemb) hipFree(n->wemb);
-  n->ones.free();
   delete n;
 }
 
@@ -598,7 +582,7 @@ int maua_secondary_load(maua_secondary* n, int index, int what, const float* hos
   hipStream_t st = n->ctx->stream;
   if (what == 2) {
     MAUA_REQUIRE(count == 8, "maua_secondary_load: timestep_embed.weight has 8 values");
-    MAUA_HIP_CHECK(hipMemcpy(n->wemb, host, 32, hipMemcpyHostToDevice));
+    MAUA_HIP_CHECK(hipMemcpy(n->wemb.get(), host, 32, hipMemcpyHostToDevice));
     return MAUA_OK;
   }
   MAUA_REQUIRE(index >= 0 && index < NCONV, "maua_secondary_load: no such convolution");

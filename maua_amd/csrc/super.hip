@@ -120,9 +120,8 @@ struct maua_rrdbnet {
   int use_dma = 1;             // bf16 trunk convolutions on the LDS-direct kernel (MAUA_RRDB_DMA=0: the generic kernel)
   UnitStyles ones;             // [bcap][max Ci]
   // workspace (grow-only)
-  size_t cap_px = 0;           // B * H * W the buffers were sized for
-  void *in32 = nullptr, *feat0 = nullptr, *dense[3] = {nullptr, nullptr, nullptr}, *f1 = nullptr, *up1 = nullptr,
-       *f2 = nullptr, *up2 = nullptr, *f3 = nullptr, *f4 = nullptr, *f5 = nullptr;
+  size_t cap_px = 0;           // B * H * W the buffers were sized for (set after them)
+  DevBuf in32, feat0, dense[3], f1, up1, f2, up2, f3, f4, f5;   // (up1, up2, f5: allocated by the paths that need them)
 };
 
 static int alloc_conv(PlainConv& c, int Ci, int Co, size_t esize) {
@@ -133,19 +132,6 @@ static int alloc_conv(PlainConv& c, int Ci, int Co, size_t esize) {
   // (32 output channels: the narrow tile also takes an odd number of 32-channel chunks, so 96 / 160-channel layers are not padded)
   if (esize == 2 && Ci >= 64 && !(Cop == 32 && Ci >= 96)) Cip = (Ci + 63) / 64 * 64;
   return c.alloc(Ci, Co, Cip, Cop, esize, false);
-}
-
-// both up-scalers: the capacity goes first, so that a growth that fails half-way leaves "nothing allocated" behind it
-static void free_ws(size_t& cap_px, std::initializer_list<void**> ps) {
-  cap_px = 0;
-  for (void** p : ps) {
-    hipFree(*p);
-    *p = nullptr;
-  }
-}
-static void free_ws(maua_rrdbnet* n) {
-  free_ws(n->cap_px, {&n->in32, &n->feat0, &n->dense[0], &n->dense[1], &n->dense[2], &n->f1, &n->up1, &n->f2, &n->up2, &n->f3,
-                      &n->f4, &n->f5});
 }
 
 extern "C" {
@@ -185,10 +171,6 @@ int maua_rrdb_create(maua_ctx* ctx, int num_feat, int num_block, int num_grow_ch
 void maua_rrdb_destroy(maua_rrdbnet* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  free_ws(n);
-  for (PlainConv* c : {&n->conv_first, &n->conv_body, &n->conv_up1, &n->conv_up2, &n->conv_hr, &n->conv_last}) c->free();
-  for (auto& c : n->rdb) c.free();
-  n->ones.free();
   delete n;
 }
 
@@ -235,17 +217,19 @@ int forward_t(maua_rrdbnet* n, const float* img, int B, int H, int W, int do_cla
   const size_t px = (size_t)B * H * W;
   if (px > n->cap_px) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    free_ws(n);
-    MAUA_HIP_CHECK(hipMalloc(&n->in32, px * 32 * es));
-    MAUA_HIP_CHECK(hipMalloc(&n->feat0, px * F * es));
-    for (int i = 0; i < 3; i++) {
-      MAUA_HIP_CHECK(hipMalloc(&n->dense[i], px * D * es));
-      MAUA_HIP_CHECK(hipMemsetAsync(n->dense[i], 0, px * D * es, st));
+    n->cap_px = 0;
+    n->up1.free(); n->up2.free(); n->f5.free();
+    int rc = n->in32.alloc(px * 32 * es);
+    if (!rc) rc = n->feat0.alloc(px * F * es);
+    for (int i = 0; i < 3 && !rc; i++) {
+      rc = n->dense[i].alloc(px * D * es);
+      if (!rc) MAUA_HIP_CHECK(hipMemsetAsync(n->dense[i].get(), 0, px * D * es, st));
     }
-    MAUA_HIP_CHECK(hipMalloc(&n->f1, px * F * es));
-    MAUA_HIP_CHECK(hipMalloc(&n->f2, px * 4 * F * es));
-    MAUA_HIP_CHECK(hipMalloc(&n->f3, px * 16 * F * es));
-    MAUA_HIP_CHECK(hipMalloc(&n->f4, px * 16 * F * es));
+    if (!rc) rc = n->f1.alloc(px * F * es);
+    if (!rc) rc = n->f2.alloc(px * 4 * F * es);
+    if (!rc) rc = n->f3.alloc(px * 16 * F * es);
+    if (!rc) rc = n->f4.alloc(px * 16 * F * es);
+    if (rc) return rc;
     n->cap_px = px;
   }
   if (int rc = n->ones.ensure(st, B, D)) return rc;
@@ -254,8 +238,8 @@ int forward_t(maua_rrdbnet* n, const float* img, int B, int H, int W, int do_cla
   auto conv = [&](const PlainConv& c, const void* x, int xps, void* y, int yps, int ycoff, int h, int w, bool lrelu,
                   float gain, const void* res, int rps, const void* res2 = nullptr, int r2ps = 0, float res_gain = 1.f) -> int {
     ConvArgs a{};
-    a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = c.wt; a.s = n->ones.p; a.d = nullptr;
-    a.noise = nullptr; a.bias = c.bias; a.y = y; a.y_pstride = yps; a.y_coff = ycoff; a.y_bstride = (long)h * w * yps;
+    a.x = x; a.x_bstride = (long)h * w * xps; a.x_pstride = xps; a.w = c.wt.get(); a.s = n->ones.p(); a.d = nullptr;
+    a.noise = nullptr; a.bias = c.bias.as<float>(); a.y = y; a.y_pstride = yps; a.y_coff = ycoff; a.y_bstride = (long)h * w * yps;
     a.B = B; a.H = h; a.W = w; a.Ci = c.Cip; a.Co = c.Cop; a.up = 1;
     a.act = lrelu ? MAUA_ACT_LRELU : MAUA_ACT_LINEAR; a.alpha = 0.2f; a.gain = gain; a.clamp = -1.f;
     a.res = res; a.res_pstride = rps; a.res_bstride = (long)h * w * rps;
@@ -285,30 +269,30 @@ int forward_t(maua_rrdbnet* n, const float* img, int B, int H, int W, int do_cla
   const int oh = frames ? 4 * fh : 4 * H, ow = frames ? 4 * fw : 4 * W;   // the u8 frame's size (frames: the un-padded input's x4)
   if (frames) {
     const long total = (long)B * H * W;
-    hipLaunchKernelGGL(frames_u8_to_nhwc32_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, frames, (T*)n->in32, B, fh, fw,
+    hipLaunchKernelGGL(frames_u8_to_nhwc32_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, frames, (T*)n->in32.get(), B, fh, fw,
                        H, W);
     MAUA_HIP_CHECK(hipGetLastError());
   } else {
-    rc = launch_nchw_to_nhwc<float, T>(st, img, n->in32, B, 3, H * W, 32);
+    rc = launch_nchw_to_nhwc<float, T>(st, img, n->in32.get(), B, 3, H * W, 32);
   }
   if (rc) return rc;
-  if ((rc = conv(n->conv_first, n->in32, 32, n->feat0, F, 0, H, W, false, 1.f, nullptr, 0))) return rc;
+  if ((rc = conv(n->conv_first, n->in32.get(), 32, n->feat0.get(), F, 0, H, W, false, 1.f, nullptr, 0))) return rc;
   // the trunk: block input in channels [0, F) of dense[ia].  Three dense-block buffers rotate: a block's input stays untouched in
   // [0, F) of its buffer (the dense blocks only write the growth slices there) until the block's last conv5 adds it back, so
   // neither a saved copy of the input nor a separate "out * 0.2 + x" pass is needed - both ride on that conv5's epilogue.
   int ia = 0, ib = 1, ic = 2;
-  if ((rc = lincomb(n->dense[ia], D, 1.f, n->feat0, F, 0.f, nullptr, 0, (long)px, F))) return rc;
+  if ((rc = lincomb(n->dense[ia].get(), D, 1.f, n->feat0.get(), F, 0.f, nullptr, 0, (long)px, F))) return rc;
   for (int blk = 0; blk < n->num_block; blk++) {
     const int src[3] = {ia, ib, ic}, dst[3] = {ib, ic, ib};
     for (int r = 0; r < 3; r++) {
       const PlainConv* cs = &n->rdb[((size_t)blk * 3 + r) * 5];
-      char* db = (char*)n->dense[src[r]];
+      char* db = (char*)n->dense[src[r]].get();
       for (int k = 0; k < 4; k++)  // x_{k+1} = lrelu(conv_{k+1}(prefix)) -> its own channel slice of the same buffer
         if ((rc = conv(cs[k], db, D, db, D, F + k * G, H, W, true, 1.f, nullptr, 0))) return rc;
       // out = conv5(all) * 0.2 + x  -> the next dense block's input slice; the third one also: RRDB out = out * 0.2 + block input
       if (r < 2) {
-        if ((rc = conv(cs[4], db, D, n->dense[dst[r]], D, 0, H, W, false, 0.2f, db, D))) return rc;
-      } else if ((rc = conv(cs[4], db, D, n->dense[dst[r]], D, 0, H, W, false, 0.2f, db, D, n->dense[ia], D, 0.2f))) {
+        if ((rc = conv(cs[4], db, D, n->dense[dst[r]].get(), D, 0, H, W, false, 0.2f, db, D))) return rc;
+      } else if ((rc = conv(cs[4], db, D, n->dense[dst[r]].get(), D, 0, H, W, false, 0.2f, db, D, n->dense[ia].get(), D, 0.2f))) {
         return rc;
       }
     }
@@ -316,40 +300,42 @@ int forward_t(maua_rrdbnet* n, const float* img, int B, int H, int W, int do_cla
     ia = ib; ib = ic; ic = t;
   }
   // feat = feat0 + conv_body(trunk)
-  if ((rc = conv(n->conv_body, n->dense[ia], D, n->f1, F, 0, H, W, false, 1.f, n->feat0, F))) return rc;
+  if ((rc = conv(n->conv_body, n->dense[ia].get(), D, n->f1.get(), F, 0, H, W, false, 1.f, n->feat0.get(), F))) return rc;
   // conv_up(interpolate(x, 2, "nearest")): on the LDS-direct kernel the up-sampled tensor is never materialised (its halo loads
   // address the half-size source); otherwise one repetition pass in front of the generic kernel
-  auto conv_up = [&](const PlainConv& c, const void* src, void** tmp, void* dst, int h, int w) -> int {   // h, w: source size
+  auto conv_up = [&](const PlainConv& c, const void* src, DevBuf& tmp, void* dst, int h, int w) -> int {   // h, w: source size
     if (n->use_dma && dma_conv_narrow_supported(n->dtype, c.Cip, c.Cop, 2 * h, 2 * w)) {
       ConvArgs a{};
-      a.x = src; a.x_bstride = (long)h * w * F; a.x_pstride = F; a.x_up2 = 1; a.w = c.wt; a.s = n->ones.p; a.bias = c.bias;
+      a.x = src; a.x_bstride = (long)h * w * F; a.x_pstride = F; a.x_up2 = 1; a.w = c.wt.get(); a.s = n->ones.p(); a.bias = c.bias.as<float>();
       a.y = dst; a.y_pstride = F; a.y_bstride = (long)4 * h * w * F;
       a.B = B; a.H = 2 * h; a.W = 2 * w; a.Ci = c.Cip; a.Co = c.Cop; a.up = 1;
       a.act = MAUA_ACT_LRELU; a.alpha = 0.2f; a.gain = 1.f; a.clamp = -1.f;
       return launch_modconv_dma(st, a);
     }
     // (only this path needs the up-sampled tensor; sized like every other buffer, for the capacity in pixels)
-    if (!*tmp) MAUA_HIP_CHECK(hipMalloc(tmp, n->cap_px * (size_t)(4 * h * w / (H * W)) * F * es));
-    if (int r2 = up2(src, *tmp, h, w)) return r2;
-    return conv(c, *tmp, F, dst, F, 0, 2 * h, 2 * w, true, 1.f, nullptr, 0);
+    if (!tmp)
+      if (int r2 = tmp.alloc(n->cap_px * (size_t)(4 * h * w / (H * W)) * F * es)) return r2;
+    if (int r2 = up2(src, tmp.get(), h, w)) return r2;
+    return conv(c, tmp.get(), F, dst, F, 0, 2 * h, 2 * w, true, 1.f, nullptr, 0);
   };
-  if ((rc = conv_up(n->conv_up1, n->f1, &n->up1, n->f2, H, W))) return rc;
-  if ((rc = conv_up(n->conv_up2, n->f2, &n->up2, n->f3, 2 * H, 2 * W))) return rc;
-  if ((rc = conv(n->conv_hr, n->f3, F, n->f4, F, 0, 4 * H, 4 * W, true, 1.f, nullptr, 0))) return rc;
+  if ((rc = conv_up(n->conv_up1, n->f1.get(), n->up1, n->f2.get(), H, W))) return rc;
+  if ((rc = conv_up(n->conv_up2, n->f2.get(), n->up2, n->f3.get(), 2 * H, 2 * W))) return rc;
+  if ((rc = conv(n->conv_hr, n->f3.get(), F, n->f4.get(), F, 0, 4 * H, 4 * W, true, 1.f, nullptr, 0))) return rc;
   if (n->use_dma && n->conv_last.Cop == 32 && dma_conv_narrow_supported(n->dtype, n->conv_last.Cip, 32, 4 * H, 4 * W)) {
     // conv_last writes the image itself (clamp, f32 planes / u8 frame in its epilogue): no 32-channel tensor, no output pass
     const PlainConv& c = n->conv_last;
     ConvArgs a{};
-    a.x = n->f4; a.x_bstride = (long)16 * H * W * F; a.x_pstride = F; a.w = c.wt; a.s = n->ones.p; a.bias = c.bias;
+    a.x = n->f4.get(); a.x_bstride = (long)16 * H * W * F; a.x_pstride = F; a.w = c.wt.get(); a.s = n->ones.p(); a.bias = c.bias.as<float>();
     a.B = B; a.H = 4 * H; a.W = 4 * W; a.Ci = c.Cip; a.Co = 32; a.up = 1;
     a.act = MAUA_ACT_LINEAR; a.alpha = 0.2f; a.gain = 1.f; a.clamp = -1.f;
     a.img_f32 = out_f32; a.img_u8 = out_u8; a.img_clamp = do_clamp; a.img_h = oh; a.img_w = ow;
     return launch_modconv_dma(st, a);
   }
-  if (!n->f5) MAUA_HIP_CHECK(hipMalloc(&n->f5, n->cap_px * 16 * 32 * es));
-  if ((rc = conv(n->conv_last, n->f4, F, n->f5, 32, 0, 4 * H, 4 * W, false, 1.f, nullptr, 0))) return rc;
+  if (!n->f5)
+    if ((rc = n->f5.alloc(n->cap_px * 16 * 32 * es))) return rc;
+  if ((rc = conv(n->conv_last, n->f4.get(), F, n->f5.get(), 32, 0, 4 * H, 4 * W, false, 1.f, nullptr, 0))) return rc;
   const long opx = (long)B * 16 * H * W;
-  hipLaunchKernelGGL(rrdb_output_kernel<T>, dim3((unsigned)((opx + 255) / 256)), dim3(256), 0, st, (const T*)n->f5, 32,
+  hipLaunchKernelGGL(rrdb_output_kernel<T>, dim3((unsigned)((opx + 255) / 256)), dim3(256), 0, st, (const T*)n->f5.get(), 32,
                      (long)16 * H * W, B, do_clamp, out_f32, out_u8, 4 * W, oh, ow);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;
@@ -421,13 +407,11 @@ struct maua_srvgg {
   int num_feat, num_conv, upscale, dtype, act;  // act: 0 prelu, 1 relu, 2 leakyrelu(0.1)
   size_t esize;
   std::vector<PlainConv> convs;   // num_conv + 2
-  std::vector<float*> slopes;     // num_conv + 1 PReLU vectors [num_feat]
+  std::vector<DevBuf> slopes;     // num_conv + 1 PReLU vectors: float [num_feat]
   UnitStyles ones;
-  size_t cap_px = 0;
-  void *in32 = nullptr, *fa = nullptr, *fb = nullptr, *flast = nullptr;
+  size_t cap_px = 0;              // B * H * W the buffers were sized for (set after them)
+  DevBuf in32, fa, fb, flast;
 };
-
-static void free_ws(maua_srvgg* n) { free_ws(n->cap_px, {&n->in32, &n->fa, &n->fb, &n->flast}); }
 
 extern "C" {
 
@@ -444,12 +428,12 @@ int maua_srvgg_create(maua_ctx* ctx, int num_feat, int num_conv, int upscale, in
   int rc = alloc_conv(n->convs[0], 3, num_feat, n->esize);
   for (int i = 1; i <= num_conv && !rc; i++) rc = alloc_conv(n->convs[i], num_feat, num_feat, n->esize);
   if (!rc) rc = alloc_conv(n->convs[num_conv + 1], num_feat, 3 * upscale * upscale, n->esize);
-  n->slopes.assign((size_t)num_conv + 1, nullptr);
+  n->slopes.resize((size_t)num_conv + 1);
   for (auto& p : n->slopes) {
     if (rc) break;
-    if (hipMalloc((void**)&p, (size_t)num_feat * 4) != hipSuccess) { rc = fail("maua_srvgg_create: out of memory"); break; }
+    if (p.alloc((size_t)num_feat * 4)) { rc = fail("maua_srvgg_create: out of memory"); break; }
     std::vector<float> init((size_t)num_feat, 0.25f);   // nn.PReLU's default slope
-    hipMemcpy(p, init.data(), init.size() * 4, hipMemcpyHostToDevice);
+    hipMemcpy(p.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice);
   }
   if (rc) {
     maua_srvgg_destroy(n);
@@ -462,10 +446,6 @@ int maua_srvgg_create(maua_ctx* ctx, int num_feat, int num_conv, int upscale, in
 void maua_srvgg_destroy(maua_srvgg* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  free_ws(n);
-  for (auto& c : n->convs) c.free();
-  for (float* p : n->slopes) hipFree(p);
-  n->ones.free();
   delete n;
 }
 
@@ -480,7 +460,7 @@ int maua_srvgg_load(maua_srvgg* n, const char* name, const float* host, size_t c
   if (idx & 1) {  // activation module
     if (strcmp(par, "weight") || n->act != 0) return fail(std::string("maua_srvgg_load: unknown parameter name: ") + name);
     if (count != (size_t)n->num_feat) return fail(std::string("maua_srvgg_load: ") + name + ": wrong size");
-    MAUA_HIP_CHECK(hipMemcpy(n->slopes[idx / 2], host, count * 4, hipMemcpyHostToDevice));
+    MAUA_HIP_CHECK(hipMemcpy(n->slopes[idx / 2].get(), host, count * 4, hipMemcpyHostToDevice));
     return MAUA_OK;
   }
   PlainConv& c = n->convs[idx / 2];
@@ -505,34 +485,35 @@ int srvgg_forward_t(maua_srvgg* n, const float* img, int B, int H, int W, int do
   const int CL = n->convs.back().Cop;
   if (px > n->cap_px) {
     MAUA_HIP_CHECK(hipStreamSynchronize(st));
-    free_ws(n);
-    MAUA_HIP_CHECK(hipMalloc(&n->in32, px * 32 * es));
-    MAUA_HIP_CHECK(hipMalloc(&n->fa, px * F * es));
-    MAUA_HIP_CHECK(hipMalloc(&n->fb, px * F * es));
-    MAUA_HIP_CHECK(hipMalloc(&n->flast, px * CL * es));
+    n->cap_px = 0;
+    int rc = n->in32.alloc(px * 32 * es);
+    if (!rc) rc = n->fa.alloc(px * F * es);
+    if (!rc) rc = n->fb.alloc(px * F * es);
+    if (!rc) rc = n->flast.alloc(px * CL * es);
+    if (rc) return rc;
     n->cap_px = px;
   }
   if (int rc = n->ones.ensure(st, B, std::max(F, 32))) return rc;
   auto conv = [&](const PlainConv& c, const void* x, void* y, const float* slopes, bool activated) -> int {
     ConvArgs a{};
-    a.x = x; a.x_bstride = (long)H * W * c.Cip; a.w = c.wt; a.s = n->ones.p; a.bias = c.bias; a.y = y;
+    a.x = x; a.x_bstride = (long)H * W * c.Cip; a.w = c.wt.get(); a.s = n->ones.p(); a.bias = c.bias.as<float>(); a.y = y;
     a.B = B; a.H = H; a.W = W; a.Ci = c.Cip; a.Co = c.Cop; a.up = 1; a.gain = 1.f; a.clamp = -1.f; a.alpha = 0.1f;
     a.act = !activated ? MAUA_ACT_LINEAR : (n->act == 1 ? MAUA_ACT_RELU : MAUA_ACT_LRELU);
     a.prelu = activated && n->act == 0 ? slopes : nullptr;
     if (dma_conv_narrow_supported(n->dtype, c.Cip, c.Cop, H, W)) return launch_modconv_dma(st, a);
     return launch_modconv3x3(st, n->dtype, a);
   };
-  int rc = launch_nchw_to_nhwc<float, T>(st, img, n->in32, B, 3, H * W, 32);
+  int rc = launch_nchw_to_nhwc<float, T>(st, img, n->in32.get(), B, 3, H * W, 32);
   if (rc) return rc;
-  if ((rc = conv(n->convs[0], n->in32, n->fa, n->slopes[0], true))) return rc;
-  void *cur = n->fa, *nxt = n->fb;
+  if ((rc = conv(n->convs[0], n->in32.get(), n->fa.get(), n->slopes[0].as<float>(), true))) return rc;
+  void *cur = n->fa.get(), *nxt = n->fb.get();
   for (int i = 1; i <= n->num_conv; i++) {
-    if ((rc = conv(n->convs[i], cur, nxt, n->slopes[i], true))) return rc;
+    if ((rc = conv(n->convs[i], cur, nxt, n->slopes[i].as<float>(), true))) return rc;
     std::swap(cur, nxt);
   }
-  if ((rc = conv(n->convs[n->num_conv + 1], cur, n->flast, nullptr, false))) return rc;
+  if ((rc = conv(n->convs[n->num_conv + 1], cur, n->flast.get(), nullptr, false))) return rc;
   const long total = (long)B * H * W * n->upscale * n->upscale;
-  hipLaunchKernelGGL(srvgg_output_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const T*)n->flast, CL, img,
+  hipLaunchKernelGGL(srvgg_output_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const T*)n->flast.get(), CL, img,
                      B, H, W, n->upscale, do_clamp, out_f32, out_u8);
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;

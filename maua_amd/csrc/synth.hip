@@ -16,16 +16,6 @@
 
 using namespace maua;
 
-namespace {
-
-template <typename T>
-int dev_alloc(T** p, size_t n) {
-  MAUA_HIP_CHECK(hipMalloc((void**)p, n * sizeof(T)));
-  return MAUA_OK;
-}
-
-}  // namespace
-
 static void prof_mark(maua_synth* n) {
   if (!n->profile || n->ev_used >= (1u << 16)) return;
   if (n->ev_used == n->ev.size()) {
@@ -66,58 +56,47 @@ static void compute_dims(maua_synth* n) {
   n->out_h = h; n->out_w = w;
 }
 
-template <typename T>
-static void release(T*& p) {  // (hipFree(NULL) is a no-op)
-  hipFree(p);
-  p = nullptr;
-}
-
-static int free_workspace(maua_synth* n) {
-  for (auto& c : n->convs) {
-    release(c.s); release(c.d); release(c.feat);
-  }
-  for (auto& r : n->rgbs) {
-    release(r.s); release(r.wmod);
-  }
-  for (int i = 0; i < 2; i++) {
-    release(n->act[i]); release(n->img[i]); release(n->rgb_tmp[i]);
-  }
-  release(n->style_table_dev); release(n->tbuf); n->ones.free(); release(n->xm);
-  release(n->lowres_xm); release(n->lowres_ws); release(n->const_rs);
-  n->bcap = 0;
+static void free_workspace(maua_synth* n) {
+  n->wk = SynthWorkspace();
+  for (auto& c : n->convs) { c.s.free(); c.d.free(); c.feat.free(); }
+  for (auto& r : n->rgbs) { r.s.free(); r.wmod.free(); }
   n->kept_B = 0;   // (the kept features are gone)
-  return MAUA_OK;
 }
 
 static int ensure_workspace(maua_synth* n, int B) {
-  if (B <= n->bcap) return MAUA_OK;
+  SynthWorkspace& k = n->wk;
+  if (B <= k.bcap) return MAUA_OK;
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
   free_workspace(n);
   size_t max_act = 0;
   for (auto& c : n->convs) {
-    MAUA_HIP_CHECK(hipMalloc((void**)&c.s, (size_t)B * c.Ci * sizeof(float)));
-    MAUA_HIP_CHECK(hipMalloc((void**)&c.d, (size_t)B * c.Co * sizeof(float)));
+    if (int rc = c.s.alloc((size_t)B * c.Ci * sizeof(float))) return rc;
+    if (int rc = c.d.alloc((size_t)B * c.Co * sizeof(float))) return rc;
     size_t e = (size_t)c.fh * c.fw * c.Co;
     max_act = std::max(max_act, std::max(e, (size_t)c.oh * c.ow * c.Co));
-    if (n->keep_features) MAUA_HIP_CHECK(hipMalloc(&c.feat, (size_t)B * e * n->esize));
+    if (n->keep_features)
+      if (int rc = c.feat.alloc((size_t)B * e * n->esize)) return rc;
   }
   for (auto& r : n->rgbs) {
-    MAUA_HIP_CHECK(hipMalloc((void**)&r.s, (size_t)B * r.C * sizeof(float)));
-    MAUA_HIP_CHECK(hipMalloc((void**)&r.wmod, (size_t)B * 3 * r.C * sizeof(float)));
+    if (int rc = r.s.alloc((size_t)B * r.C * sizeof(float))) return rc;
+    if (int rc = r.wmod.alloc((size_t)B * 3 * r.C * sizeof(float))) return rc;
   }
   // (a resized / warped layer goes through scratch buffers, also when every layer keeps its own)
-  for (int i = 0; i < 2; i++) MAUA_HIP_CHECK(hipMalloc(&n->act[i], (size_t)B * max_act * n->esize));
+  for (int i = 0; i < 2; i++)
+    if (int rc = k.act[i].alloc((size_t)B * max_act * n->esize)) return rc;
   if (n->rs_layer == 0)
-    MAUA_HIP_CHECK(hipMalloc(&n->const_rs, (size_t)n->rs_th * n->rs_tw * n->convs[0].Ci * n->esize));
+    if (int rc = k.const_rs.alloc((size_t)n->rs_th * n->rs_tw * n->convs[0].Ci * n->esize)) return rc;
   if (n->rs_layer >= 1) {
     const ConvLayer& hc = n->convs[n->rs_layer - 1];
     const size_t px = std::max((size_t)hc.oh * hc.ow, (size_t)n->rs_th * n->rs_tw);
-    for (int i = 0; i < 2; i++) MAUA_HIP_CHECK(hipMalloc((void**)&n->rgb_tmp[i], (size_t)B * 3 * px * sizeof(float)));
+    for (int i = 0; i < 2; i++)
+      if (int rc = k.rgb_tmp[i].alloc((size_t)B * 3 * px * sizeof(float))) return rc;
   }
   size_t max_t = 0;
   for (auto& c : n->convs)
     if (c.up == 2) max_t = std::max(max_t, (size_t)(c.oh + 1) * (c.ow + 1) * c.Co);
-  if (max_t) MAUA_HIP_CHECK(hipMalloc(&n->tbuf, (size_t)B * max_t * n->esize));
+  if (max_t)
+    if (int rc = k.tbuf.alloc((size_t)B * max_t * n->esize)) return rc;
   size_t lx = 0, lw = 0;
   for (auto& c : n->convs)
     if (lowres_fits(n, c)) {
@@ -134,32 +113,35 @@ static int ensure_workspace(maua_synth* n, int B) {
       //  sized for any up-layer so that hooks / options can fall back to it)
       if (tconv_dma_fits(n, c)) xm_elems = std::max(xm_elems, (size_t)c.ih * c.iw * c.Ci);
     }
-    if (int rc = n->ones.ensure(n->ctx->stream, B, maxc)) return rc;
-    if (xm_elems) MAUA_HIP_CHECK(hipMalloc(&n->xm, (size_t)B * xm_elems * n->esize));
+    if (int rc = k.ones.ensure(n->ctx->stream, B, maxc)) return rc;
+    if (xm_elems)
+      if (int rc = k.xm.alloc((size_t)B * xm_elems * n->esize)) return rc;
   }
-  if (lx) MAUA_HIP_CHECK(hipMalloc(&n->lowres_xm, lx));
-  if (lw) MAUA_HIP_CHECK(hipMalloc((void**)&n->lowres_ws, lw));
+  if (lx)
+    if (int rc = k.lowres_xm.alloc(lx)) return rc;
+  if (lw)
+    if (int rc = k.lowres_ws.alloc(lw)) return rc;
   for (int i = 0; i < 2; i++)
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->img[i], (size_t)B * 3 * std::max(n->out_h * n->out_w, n->res * n->res) * sizeof(float)));
+    if (int rc = k.img[i].alloc((size_t)B * 3 * std::max(n->out_h * n->out_w, n->res * n->res) * sizeof(float))) return rc;
   // style table
   std::vector<StyleLayer> tab;
   for (auto& c : n->convs) {
     StyleLayer L{};
-    L.affine_w = c.affine_w; L.affine_b = c.affine_b; L.wsq = c.wsq; L.wrgb = nullptr;
-    L.s = c.s; L.d = c.d; L.wmod = nullptr; L.w_index = c.w_index;
+    L.affine_w = c.affine_w.as<float>(); L.affine_b = c.affine_b.as<float>(); L.wsq = c.wsq.as<float>(); L.wrgb = nullptr;
+    L.s = c.s.as<float>(); L.d = c.d.as<float>(); L.wmod = nullptr; L.w_index = c.w_index;
     L.Cin = c.Ci; L.Co = c.Co; L.Cs = c.Ci; L.Cd = c.Co; L.scale = 1.f;
     tab.push_back(L);
   }
   for (auto& r : n->rgbs) {
     StyleLayer L{};
-    L.affine_w = r.affine_w; L.affine_b = r.affine_b; L.wsq = nullptr; L.wrgb = r.wrgb;
-    L.s = r.s; L.d = nullptr; L.wmod = r.wmod; L.w_index = r.w_index;
+    L.affine_w = r.affine_w.as<float>(); L.affine_b = r.affine_b.as<float>(); L.wsq = nullptr; L.wrgb = r.wrgb.as<float>();
+    L.s = r.s.as<float>(); L.d = nullptr; L.wmod = r.wmod.as<float>(); L.w_index = r.w_index;
     L.Cin = r.C; L.Co = 3; L.Cs = r.C; L.Cd = 0; L.scale = 1.f / std::sqrt((float)r.C);
     tab.push_back(L);
   }
-  MAUA_HIP_CHECK(hipMalloc((void**)&n->style_table_dev, tab.size() * sizeof(StyleLayer)));
-  MAUA_HIP_CHECK(hipMemcpy(n->style_table_dev, tab.data(), tab.size() * sizeof(StyleLayer), hipMemcpyHostToDevice));
-  n->bcap = B;
+  if (int rc = k.style_table.alloc(tab.size() * sizeof(StyleLayer))) return rc;
+  MAUA_HIP_CHECK(hipMemcpy(k.style_table.get(), tab.data(), tab.size() * sizeof(StyleLayer), hipMemcpyHostToDevice));
+  k.bcap = B;
   return MAUA_OK;
 }
 
@@ -279,7 +261,7 @@ static Plan plan_forward(const maua_synth* n, bool want_u8, bool have_xm) {
         }
         // the 64 -> 32 up-layer: half the matrix work of the phase form; the last block as one walk when nothing else reads
         // its features (no hooks, no feature capture): they never reach HBM
-        if (s.route == Route::Hires && c.up == 2 && n->upwalk && c.wt_h &&
+        if (s.route == Route::Hires && c.up == 2 && n->upwalk && c.wt_h.get() &&
             upwalk_supported(n->dtype, c.Ci, c.Co, c.up, c.ih, c.iw)) {
           s.route = Route::Upwalk;
           if (n->upwalk >= 2 && last && nx && n->fuse_torgb && !rs_block && !next_replaced &&
@@ -346,42 +328,41 @@ int maua_synth_create(maua_ctx* ctx, int img_resolution, int w_dim, int channel_
       ConvLayer c{};
       c.block = i; c.which = 0; c.Ci = channels_for(r / 2, channel_base, channel_max); c.Co = co; c.res = r; c.up = 2;
       c.w_index = widx++;
-      n->convs.push_back(c);
+      n->convs.push_back(std::move(c));
     }
     ConvLayer c{};
     c.block = i; c.which = 1; c.Ci = co; c.Co = co; c.res = r; c.up = 1; c.w_index = widx++;
-    n->convs.push_back(c);
+    n->convs.push_back(std::move(c));
     RgbLayer g{};
     g.block = i; g.C = co; g.res = r; g.w_index = widx;  // toRGB shares the next block's first w (stylegan2.py:431-433)
-    n->rgbs.push_back(g);
+    n->rgbs.push_back(std::move(g));
   }
   compute_dims(n);
-  hipError_t e = hipSuccess;
-  auto A = [&](void** p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes);
-    if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+  auto alloc_params = [&]() -> int {   // all zeroed
+    for (auto& c : n->convs) {
+      if (int rc = c.affine_w.alloc((size_t)c.Ci * w_dim * 4, true)) return rc;
+      if (int rc = c.affine_b.alloc((size_t)c.Ci * 4, true)) return rc;
+      if (int rc = c.bias.alloc((size_t)c.Co * 4, true)) return rc;
+      if (int rc = c.noise_const.alloc((size_t)c.res * c.res * 4, true)) return rc;
+      if (int rc = c.wt.alloc(prepped_weight_elems(3, c.up, c.Co, c.Ci) * n->esize, true)) return rc;
+      if (c.up == 2)
+        if (int rc = c.wt_t.alloc(prepped_weight_elems(3, c.up, c.Co, c.Ci) * n->esize, true)) return rc;
+      // (the half-folded weights do not depend on the layer's size - it can change with a resize hook - only the routing does)
+      if (upwalk_supported(n->dtype, c.Ci, c.Co, c.up, 64, 64))
+        if (int rc = c.wt_h.alloc(upwalk_weight_elems(c.Co, c.Ci) * 2, true)) return rc;
+      if (int rc = c.wsq.alloc((size_t)c.Co * c.Ci * 4, true)) return rc;
+    }
+    for (auto& g : n->rgbs) {
+      if (int rc = g.affine_w.alloc((size_t)g.C * w_dim * 4, true)) return rc;
+      if (int rc = g.affine_b.alloc((size_t)g.C * 4, true)) return rc;
+      if (int rc = g.wrgb.alloc((size_t)3 * g.C * 4, true)) return rc;
+      if (int rc = g.bias.alloc(3 * 4, true)) return rc;
+    }
+    return n->const_x.alloc((size_t)16 * n->convs[0].Ci * n->esize, true);
   };
-  for (auto& c : n->convs) {
-    A((void**)&c.affine_w, (size_t)c.Ci * w_dim * 4);
-    A((void**)&c.affine_b, (size_t)c.Ci * 4);
-    A((void**)&c.bias, (size_t)c.Co * 4);
-    A((void**)&c.noise_const, (size_t)c.res * c.res * 4);
-    A(&c.wt, prepped_weight_elems(3, c.up, c.Co, c.Ci) * n->esize);
-    if (c.up == 2) A(&c.wt_t, prepped_weight_elems(3, c.up, c.Co, c.Ci) * n->esize);
-    // (the half-folded weights do not depend on the layer's size - it can change with a resize hook - only the routing does)
-    if (upwalk_supported(n->dtype, c.Ci, c.Co, c.up, 64, 64)) A(&c.wt_h, upwalk_weight_elems(c.Co, c.Ci) * 2);
-    A((void**)&c.wsq, (size_t)c.Co * c.Ci * 4);
-  }
-  for (auto& g : n->rgbs) {
-    A((void**)&g.affine_w, (size_t)g.C * w_dim * 4);
-    A((void**)&g.affine_b, (size_t)g.C * 4);
-    A((void**)&g.wrgb, (size_t)3 * g.C * 4);
-    A((void**)&g.bias, 3 * 4);
-  }
-  A(&n->const_x, (size_t)16 * n->convs[0].Ci * n->esize);
-  if (e != hipSuccess) {
+  if (alloc_params()) {
     maua_synth_destroy(n);
-    return fail(std::string("maua_synth_create: hipMalloc: ") + hipGetErrorString(e));
+    return fail_in("maua_synth_create");
   }
   upsample_fir16(n->fir);
   *out = n;
@@ -391,19 +372,7 @@ int maua_synth_create(maua_ctx* ctx, int img_resolution, int w_dim, int channel_
 void maua_synth_destroy(maua_synth* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
-  free_workspace(n);
-  synth_vjp_release(n->vjp, true, n->convs);
   for (auto e : n->ev) hipEventDestroy(e);
-  for (auto& c : n->convs) {
-    hipFree(c.affine_w); hipFree(c.affine_b); hipFree(c.bias); hipFree(c.noise_const); hipFree(c.wt); hipFree(c.wsq);
-    if (c.wt_t) hipFree(c.wt_t);
-    if (c.wt_h) hipFree(c.wt_h);
-  }
-  for (auto& g : n->rgbs) {
-    hipFree(g.affine_w); hipFree(g.affine_b); hipFree(g.wrgb); hipFree(g.bias);
-  }
-  hipFree(n->const_x);
-  if (n->rs_noise) hipFree(n->rs_noise);
   delete n;
 }
 
@@ -415,7 +384,8 @@ int maua_synth_set_resize(maua_synth* n, int layer, int mode, int target_h, int 
   MAUA_REQUIRE(n, "maua_synth_set_resize: net is NULL");
   MAUA_REQUIRE(layer >= -1 && layer <= (int)n->convs.size(), "maua_synth_set_resize: no such layer");
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
-  const std::vector<ConvLayer> before = n->convs;
+  std::vector<int> before;   // every layer's noise grid (oh, ow) as it is now
+  for (auto& c : n->convs) { before.push_back(c.oh); before.push_back(c.ow); }
   if (layer >= 0) {
     MAUA_REQUIRE(mode == 0 || mode == 1, "maua_synth_set_resize: mode must be 0 (stretch) or 1 (pad)");
     MAUA_REQUIRE(target_h >= 1 && target_w >= 1, "maua_synth_set_resize: empty target size");
@@ -440,13 +410,12 @@ int maua_synth_set_resize(maua_synth* n, int layer, int mode, int target_h, int 
   } else {
     n->rs_layer = -1;
   }
-  if (n->rs_noise) hipFree(n->rs_noise);
-  n->rs_noise = nullptr;
+  n->rs_noise.free();
   if (layer >= 0 && fill_noise_host) {
     const int C = layer == 0 ? n->convs[0].Ci : n->convs[layer - 1].Co;
     const size_t cnt = (size_t)C * target_h * target_w;
-    MAUA_HIP_CHECK(hipMalloc((void**)&n->rs_noise, cnt * sizeof(float)));
-    MAUA_HIP_CHECK(hipMemcpy(n->rs_noise, fill_noise_host, cnt * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = n->rs_noise.alloc(cnt * sizeof(float))) return rc;
+    MAUA_HIP_CHECK(hipMemcpy(n->rs_noise.get(), fill_noise_host, cnt * sizeof(float), hipMemcpyHostToDevice));
   }
   compute_dims(n);
   free_workspace(n);
@@ -454,12 +423,8 @@ int maua_synth_set_resize(maua_synth* n, int layer, int mode, int target_h, int 
   // layers whose grid changed get a zeroed noise_const of the new size (the caller uploads fresh noise, :141-150)
   for (size_t i = 0; i < n->convs.size(); i++) {
     ConvLayer& c = n->convs[i];
-    if (c.oh != before[i].oh || c.ow != before[i].ow) {
-      hipFree(c.noise_const);
-      c.noise_const = nullptr;
-      MAUA_HIP_CHECK(hipMalloc((void**)&c.noise_const, (size_t)c.oh * c.ow * sizeof(float)));
-      MAUA_HIP_CHECK(hipMemset(c.noise_const, 0, (size_t)c.oh * c.ow * sizeof(float)));
-    }
+    if (c.oh != before[2 * i] || c.ow != before[2 * i + 1])
+      if (int rc = c.noise_const.alloc((size_t)c.oh * c.ow * sizeof(float), true)) return rc;
   }
   return MAUA_OK;
 }
@@ -548,10 +513,10 @@ int maua_synth_load(maua_synth* n, const char* name, const float* host, size_t c
     if (blk != 0) return fail("maua_synth_load: only block 0 has a const input");
     int C = n->convs[0].Ci;
     if (count != (size_t)C * 16) return fail("maua_synth_load: bs.0.const: wrong size");
-    DevTemp tmp;
-    if (int rc = tmp.stage(host, count, g_load_kind)) return rc;
+    DevBuf tmp;
+    if (int rc = stage(tmp, host, count, g_load_kind)) return rc;
     int rc = dispatch_dtype<bf16_t, f16_t, float>(n->dtype, "maua_synth_load",
-                                                  [&](auto t) { return launch_nchw_to_nhwc<float, decltype(t)>(st, tmp.p, n->const_x, 1, C, 16, C); });
+                                                  [&](auto t) { return launch_nchw_to_nhwc<float, decltype(t)>(st, tmp.as<float>(), n->const_x.get(), 1, C, 16, C); });
     hipStreamSynchronize(st);
     return rc;
   }
@@ -560,10 +525,10 @@ int maua_synth_load(maua_synth* n, const char* name, const float* host, size_t c
   std::string mod = rest.substr(0, dot), par = rest.substr(dot + 1);
   if (mod == "torgb") {
     RgbLayer& g = n->rgbs[blk];
-    if (par == "weight") return upload(g.wrgb, host, count, (size_t)3 * g.C, name);
-    if (par == "bias") return upload(g.bias, host, count, 3, name);
-    if (par == "affine.weight") return upload(g.affine_w, host, count, (size_t)g.C * n->w_dim, name);
-    if (par == "affine.bias") return upload(g.affine_b, host, count, g.C, name);
+    if (par == "weight") return upload(g.wrgb.as<float>(), host, count, (size_t)3 * g.C, name);
+    if (par == "bias") return upload(g.bias.as<float>(), host, count, 3, name);
+    if (par == "affine.weight") return upload(g.affine_w.as<float>(), host, count, (size_t)g.C * n->w_dim, name);
+    if (par == "affine.bias") return upload(g.affine_b.as<float>(), host, count, g.C, name);
     return fail("maua_synth_load: unknown parameter name: " + s);
   }
   ConvLayer* c = nullptr;
@@ -571,10 +536,10 @@ int maua_synth_load(maua_synth* n, const char* name, const float* host, size_t c
     if (cc.block == blk && ((mod == "conv0" && cc.which == 0) || (mod == "conv1" && cc.which == 1))) c = &cc;
   if (!c) return fail("maua_synth_load: unknown parameter name: " + s);
   if (par == "resample_filter") return check_filter();
-  if (par == "bias") return upload(c->bias, host, count, c->Co, name);
-  if (par == "affine.weight") return upload(c->affine_w, host, count, (size_t)c->Ci * n->w_dim, name);
-  if (par == "affine.bias") return upload(c->affine_b, host, count, c->Ci, name);
-  if (par == "noise_const") return upload(c->noise_const, host, count, (size_t)c->oh * c->ow, name);
+  if (par == "bias") return upload(c->bias.as<float>(), host, count, c->Co, name);
+  if (par == "affine.weight") return upload(c->affine_w.as<float>(), host, count, (size_t)c->Ci * n->w_dim, name);
+  if (par == "affine.bias") return upload(c->affine_b.as<float>(), host, count, c->Ci, name);
+  if (par == "noise_const") return upload(c->noise_const.as<float>(), host, count, (size_t)c->oh * c->ow, name);
   if (par == "noise_strength") {
     if (count != 1) return fail("maua_synth_load: noise_strength is a scalar");
     c->noise_strength = host[0];
@@ -583,17 +548,17 @@ int maua_synth_load(maua_synth* n, const char* name, const float* host, size_t c
   if (par == "weight") {
     size_t expect = (size_t)c->Co * c->Ci * 9;
     if (count != expect) return fail("maua_synth_load: " + s + ": wrong size");
-    DevTemp tmp;
-    if (int rc = tmp.stage(host, count, g_load_kind)) return rc;
+    DevBuf tmp;
+    if (int rc = stage(tmp, host, count, g_load_kind)) return rc;
     // F16 networks: the reference's FP16 pre-normalisation of the weight (ops.py:161-163; every convolution of the synthesis
     // network demodulates) - the styles' half is applied per batch (launch_styles)
-    int rc = n->dtype == MAUA_F16 ? launch_f16_prenorm_weights(st, tmp.p, tmp.p, c->Co, c->Ci, 9) : MAUA_OK;
+    int rc = n->dtype == MAUA_F16 ? launch_f16_prenorm_weights(st, tmp.as<float>(), tmp.as<float>(), c->Co, c->Ci, 9) : MAUA_OK;
     if (!rc)
-      rc = launch_prep_weights(st, n->dtype, tmp.p, c->wt, c->wsq, c->Co, c->Ci, 3, c->up, (c->up == 2) ? (n->nv_compat & 1) : 0,
+      rc = launch_prep_weights(st, n->dtype, tmp.as<float>(), c->wt.get(), c->wsq.as<float>(), c->Co, c->Ci, 3, c->up, (c->up == 2) ? (n->nv_compat & 1) : 0,
                                c->Co, c->Ci);
     if (!rc && c->up == 2)
-      rc = launch_prep_tconv_weights(st, n->dtype, tmp.p, c->wt_t, c->Co, c->Ci, n->nv_compat & 1);
-    if (!rc && c->wt_h) rc = launch_prep_upwalk_weights(st, tmp.p, c->wt_h, c->Co, c->Ci, n->nv_compat & 1, n->dtype);
+      rc = launch_prep_tconv_weights(st, n->dtype, tmp.as<float>(), c->wt_t.get(), c->Co, c->Ci, n->nv_compat & 1);
+    if (!rc && c->wt_h.get()) rc = launch_prep_upwalk_weights(st, tmp.as<float>(), c->wt_h.get(), c->Co, c->Ci, n->nv_compat & 1, n->dtype);
     hipStreamSynchronize(st);
     return rc;
   }
@@ -628,7 +593,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
   if (B == 0) return MAUA_OK;
   if (int rc = ensure_workspace(n, B)) return rc;
   if (n->keep_features) n->kept_B = 0;   // (the kept features are being overwritten; set again when this forward is through)
-  const Plan plan = plan_forward(n, rgb8_out != nullptr, n->xm != nullptr);
+  const Plan plan = plan_forward(n, rgb8_out != nullptr, (bool)n->wk.xm);
   hipStream_t st = n->ctx->stream;
   const int ntab = (int)(n->convs.size() + n->rgbs.size());
   int max_c = 0;
@@ -637,28 +602,28 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
   // (two for the transposed-conv routes), toRGB per block, the u8 pack; a hook's launches land in the slot that follows
   if (n->profile) n->ev_fwd_start.push_back(n->ev_used);
   prof_mark(n);
-  if (int rc = launch_styles(st, n->style_table_dev, ntab, ws, n->num_ws, n->w_dim, B, max_c, n->dtype == MAUA_F16)) return rc;
+  if (int rc = launch_styles(st, n->wk.style_table.as<StyleLayer>(), ntab, ws, n->num_ws, n->w_dim, B, max_c, n->dtype == MAUA_F16)) return rc;
 
   prof_mark(n);
-  const void* x = n->const_x;
+  const void* x = n->const_x.get();
   long x_bstride = 0;
   int cur = 0;
   // the one feature-space resize (get_hook's resize(x, feat=True)): bicubic / pad + fill noise, NHWC
   auto resize_feat = [&](const void* src, long src_bstride, int nb, int H, int W, int C, void* dst) -> int {
     ResizeArgs r{};
     r.x = src; r.x_bstride = src_bstride; r.y = dst; r.B = nb; r.H = H; r.W = W; r.C = C; r.oh = n->rs_th; r.ow = n->rs_tw;
-    r.mode = n->rs_mode; r.pl = n->rs_pl; r.pt = n->rs_pt; r.how = n->rs_how; r.value = n->rs_value; r.noise = n->rs_noise;
+    r.mode = n->rs_mode; r.pl = n->rs_pl; r.pt = n->rs_pt; r.how = n->rs_how; r.value = n->rs_value; r.noise = n->rs_noise.as<float>();
     return launch_resize2d(st, n->dtype, true, r);
   };
   if (n->rs_layer == 0) {  // pre-hook on the first layer: its input (the learned const) is resized
-    if (int rc = resize_feat(n->const_x, 0, 1, 4, 4, n->convs[0].Ci, n->const_rs)) return rc;
-    x = n->const_rs;
+    if (int rc = resize_feat(n->const_x.get(), 0, 1, 4, 4, n->convs[0].Ci, n->wk.const_rs.get())) return rc;
+    x = n->wk.const_rs.get();
   }
   auto layer_noise = [&](size_t li) {
     const ConvLayer& c = n->convs[li];
     const bool given = noise && noise[li];
     NoiseOperands z;
-    z.noise = given ? noise[li] : c.noise_const;
+    z.noise = given ? noise[li] : c.noise_const.as<float>();
     z.bstride = given ? (noise_bstride ? noise_bstride[li] : (long)c.oh * c.ow) : 0;
     z.strength = (n->nv_compat & 2) ? c.noise_strength : 1.f;
     // (un-normalised Loop maps: the factor 1 / (rms + eps) of each sample rides on the noise strength; only with caller-supplied maps)
@@ -667,7 +632,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
   };
   auto layer_args = [&](auto a, size_t li, const void* in, void* out) {  // what every modulated 3x3 launch shares (ConvArgs / HiresArgs)
     const ConvLayer& c = n->convs[li];
-    return maua::layer_args(a, LayerOperands{in, c.wt, c.s, c.d, c.bias, out, B, c.ih, c.iw, c.Ci, c.Co, c.up}, layer_noise(li),
+    return maua::layer_args(a, LayerOperands{in, c.wt.get(), c.s.as<float>(), c.d.as<float>(), c.bias.as<float>(), out, B, c.ih, c.iw, c.Ci, c.Co, c.up}, layer_noise(li),
                             lrelu_epilogue());
   };
   auto pack_u8 = [&](HiresArgs& a) { pack_u8_args(a, rgb8_out, img_out == nullptr); };
@@ -677,16 +642,16 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
   for (int blk = 0; blk < n->nblocks; blk++) {
     const int nconv = blk == 0 ? 1 : 2;
     const RgbLayer& g = n->rgbs[blk];
-    float* rgb_out = (blk == n->nblocks - 1 && img_out) ? img_out : n->img[img_cur];
+    float* rgb_out = (blk == n->nblocks - 1 && img_out) ? img_out : n->wk.img[img_cur].as<float>();
     auto fuse_torgb = [&](auto& a) {  // the block's toRGB + skip in the epilogue (ConvArgs / HiresArgs)
-      fuse_torgb_args(a, g.wmod, g.bias, prev_img, rgb_out, 256.f, n->fir);
+      fuse_torgb_args(a, g.wmod.as<float>(), g.bias.as<float>(), prev_img, rgb_out, 256.f, n->fir);
     };
     for (int k = 0; k < nconv; k++, li++) {
       const ConvLayer& c = n->convs[li];
       const Step& s = plan.conv[li];
       const bool hooked = n->rs_layer == (int)li + 1;  // this layer's output is resized before anything reads it
-      void* y = n->keep_features && !hooked ? c.feat : n->act[cur];
-      const float* next_s = s.scale_next ? n->convs[li + 1].s : nullptr;
+      void* y = n->keep_features && !hooked ? c.feat.get() : n->wk.act[cur].get();
+      const float* next_s = s.scale_next ? n->convs[li + 1].s.as<float>() : nullptr;
       switch (s.route) {
         case Route::Lowres:
         case Route::Generic:
@@ -694,10 +659,10 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
           ConvArgs a = layer_args(ConvArgs{}, li, x, y);
           a.x_bstride = x_bstride;
           a.out_scale = next_s;
-          if (s.dual) a.y_scaled = n->xm;
+          if (s.dual) a.y_scaled = n->wk.xm.get();
           if (s.rgb) fuse_torgb(a);
           if (s.route == Route::DmaConv1) a.s = nullptr;  // (the input carries the styles)
-          if (int rc = s.route == Route::Lowres    ? launch_modconv_lowres(st, n->dtype, a, n->lowres_xm, n->lowres_ws)
+          if (int rc = s.route == Route::Lowres    ? launch_modconv_lowres(st, n->dtype, a, n->wk.lowres_xm.get(), n->wk.lowres_ws.as<float>())
                        : s.route == Route::Generic ? launch_modconv3x3(st, n->dtype, a)
                                                    : launch_modconv_dma(st, a, n->dtype))
             return rc;
@@ -709,7 +674,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
           HiresArgs a = layer_args(HiresArgs{}, li, x, s.skip_store ? nullptr : y);
           if (s.rgb) fuse_torgb(a);
           if (s.rgb8) pack_u8(a);
-          if (s.route != Route::Hires) a.w = c.wt_h;  // (the half-folded weights)
+          if (s.route != Route::Hires) a.w = c.wt_h.get();  // (the half-folded weights)
           if (s.route != Route::FusedWalk) {
             if (int rc = s.route == Route::Hires ? launch_modconv_hires(st, a, n->dtype) : launch_upwalk(st, a, n->dtype)) return rc;
             break;
@@ -725,15 +690,15 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
         case Route::TconvFir:
         case Route::TconvDma:
         case Route::Tconv2: {
-          ConvArgs a = tconv_args(x, x_bstride, c.wt_t, c.s, n->tbuf, B, c.ih, c.iw, c.Ci, c.Co);
-          UpfirArgs u = upfir_args(y, c.d, c.bias, next_s, B, c.ih, c.iw, c.Co, layer_noise(li), lrelu_epilogue());
+          ConvArgs a = tconv_args(x, x_bstride, c.wt_t.get(), c.s.as<float>(), n->wk.tbuf.get(), B, c.ih, c.iw, c.Ci, c.Co);
+          UpfirArgs u = upfir_args(y, c.d.as<float>(), c.bias.as<float>(), next_s, B, c.ih, c.iw, c.Co, layer_noise(li), lrelu_epilogue());
           if (s.src == Src::PremodPass)  // (the input is small: inputs up to 64^2 at 1024^2 networks)
-            if (int rc = launch_premod_nhwc(st, x, x_bstride, c.s, n->xm, B, (long)c.ih * c.iw, c.Ci, n->dtype)) return rc;
+            if (int rc = launch_premod_nhwc(st, x, x_bstride, c.s.as<float>(), n->wk.xm.get(), B, (long)c.ih * c.iw, c.Ci, n->dtype)) return rc;
           if (s.src == Src::PremodPass || s.src == Src::Xm) {
-            a.x = n->xm;
+            a.x = n->wk.xm.get();
             a.x_bstride = (long)c.ih * c.iw * c.Ci;
           }
-          if (reads_premod(s.route)) a.s = n->ones.p;
+          if (reads_premod(s.route)) a.s = n->wk.ones.p();
           if (s.route == Route::TconvFir) {  // the whole layer in one kernel: t never leaves LDS (bit-identical output)
             if (int rc = launch_tconv_fir(st, a, u, n->dtype, n->tconv_walk, 0)) return rc;
             prof_mark(n);  // (two profile slots like the two-launch path: the second measures ~0)
@@ -748,7 +713,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
             return rc;
           }
           prof_mark(n);  // (profile mode: this up-layer occupies two slots)
-          u.t = n->tbuf;
+          u.t = n->wk.tbuf.get();
           if (int rc = launch_upfir_epilogue(st, n->dtype, u)) return rc;
           break;
         }
@@ -758,7 +723,7 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
       x_bstride = (long)c.oh * c.ow * c.Co;
       cur ^= 1;
       if (hooked) {  // forward hook: resize(output, feat=True)
-        void* dst = n->keep_features ? c.feat : n->act[cur];
+        void* dst = n->keep_features ? c.feat.get() : n->wk.act[cur].get();
         if (int rc = resize_feat(x, x_bstride, B, c.oh, c.ow, c.Co, dst)) return rc;
         x = dst;
         x_bstride = (long)c.fh * c.fw * c.Co;
@@ -766,14 +731,14 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
       }
       for (int wsl = 0; wsl < 3; wsl++) {  // translate / zoom / rotate hooks on this layer (registered after the
         if (n->warp_layer[wsl] != (int)li + 1 || !n->warp_minv[wsl]) continue;  // resize hook, so they run after it)
-        void* dst = n->act[cur];
-        if (dst == x) dst = n->act[cur ^ 1];
+        void* dst = n->wk.act[cur].get();
+        if (dst == x) dst = n->wk.act[cur ^ 1].get();
         if (int rc = launch_warp_affine_nhwc(st, n->dtype, x, dst, n->warp_minv[wsl], B, c.fh, c.fw, c.Co)) return rc;
         if (n->keep_features) {  // the hook's output replaces the layer's
-          MAUA_HIP_CHECK(hipMemcpyAsync(c.feat, dst, (size_t)B * c.fh * c.fw * c.Co * n->esize, hipMemcpyDeviceToDevice, st));
+          MAUA_HIP_CHECK(hipMemcpyAsync(c.feat.get(), dst, (size_t)B * c.fh * c.fw * c.Co * n->esize, hipMemcpyDeviceToDevice, st));
         } else {
           x = dst;
-          cur = (dst == n->act[0]) ? 1 : 0;
+          cur = (dst == n->wk.act[0].get()) ? 1 : 0;
         }
       }
     }
@@ -783,22 +748,22 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
       // and the block's image is resized forward again (no fill noise on images)
       const bool hook = plan.rgb[blk] == RgbRoute::Hook;
       RgbArgs r{};
-      r.x = x; r.wmod = g.wmod; r.bias = g.bias; r.prev = hook ? nullptr : prev_img;
-      r.out = hook ? n->rgb_tmp[0] : rgb_out; r.B = B; r.H = g.h; r.W = g.w; r.C = g.C; r.clamp = 256.f;
+      r.x = x; r.wmod = g.wmod.as<float>(); r.bias = g.bias.as<float>(); r.prev = hook ? nullptr : prev_img;
+      r.out = hook ? n->wk.rgb_tmp[0].as<float>() : rgb_out; r.B = B; r.H = g.h; r.W = g.w; r.C = g.C; r.clamp = 256.f;
       memcpy(r.fir, n->fir, sizeof(r.fir));
       if (int rc = launch_torgb(st, n->dtype, r)) return rc;
       if (hook) {
         const ConvLayer& hc = n->convs[n->rs_layer - 1];
         const int nh = hc.oh, nw = hc.ow;  // native grid of the block
         ResizeArgs inv{};
-        inv.x = n->rgb_tmp[0]; inv.x_bstride = 3L * g.h * g.w; inv.y = n->rgb_tmp[1]; inv.B = B; inv.H = g.h; inv.W = g.w;
+        inv.x = n->wk.rgb_tmp[0].as<float>(); inv.x_bstride = 3L * g.h * g.w; inv.y = n->wk.rgb_tmp[1].as<float>(); inv.B = B; inv.H = g.h; inv.W = g.w;
         inv.C = 3; inv.oh = nh; inv.ow = nw; inv.mode = n->rs_mode; inv.pl = -n->rs_pl; inv.pt = -n->rs_pt;
         inv.how = MAUA_PAD_CONSTANT; inv.value = 0.f; inv.noise = nullptr;
         if (int rc = launch_resize2d(st, MAUA_F32, false, inv)) return rc;
-        const float* native = n->rgb_tmp[1];
+        const float* native = n->wk.rgb_tmp[1].as<float>();
         if (prev_img) {
-          if (int rc = launch_skip_add(st, n->rgb_tmp[1], prev_img, n->rgb_tmp[0], B, nh, nw, n->fir)) return rc;
-          native = n->rgb_tmp[0];
+          if (int rc = launch_skip_add(st, n->wk.rgb_tmp[1].as<float>(), prev_img, n->wk.rgb_tmp[0].as<float>(), B, nh, nw, n->fir)) return rc;
+          native = n->wk.rgb_tmp[0].as<float>();
         }
         ResizeArgs fwd{};
         fwd.x = native; fwd.x_bstride = 3L * nh * nw; fwd.y = rgb_out; fwd.B = B; fwd.H = nh; fwd.W = nw; fwd.C = 3;
@@ -827,8 +792,8 @@ int maua_synth_render_rgb8(maua_synth* n, const float* ws, const float* const* n
 // the plan of the next forward as plain ints (host only, no launch): what a test pins so that a threshold edit shows up as a diff
 int maua_synth_get_plan(maua_synth* n, int want_u8, int* conv_out, int capacity, int* rgb_out, int* pack, int* n_layers) {
   MAUA_REQUIRE(n && n_layers, "maua_synth_get_plan: NULL argument");
-  bool have_xm = n->xm != nullptr;
-  if (!n->bcap)   // no workspace yet: what ensure_workspace will decide
+  bool have_xm = (bool)n->wk.xm;
+  if (!n->wk.bcap)   // no workspace yet: what ensure_workspace will decide
     for (auto& c : n->convs) have_xm = have_xm || tconv_dma_fits(n, c);
   const Plan p = plan_forward(n, want_u8 != 0, have_xm);
   *n_layers = (int)p.conv.size();
@@ -882,11 +847,11 @@ int maua_synth_get_feature(maua_synth* n, int layer, int B, float* out_nchw) {
   MAUA_REQUIRE(n && out_nchw, "maua_synth_get_feature: NULL argument");
   MAUA_REQUIRE(n->keep_features, "maua_synth_get_feature: enable with maua_synth_set_option(net, \"keep_features\", 1)");
   MAUA_REQUIRE(layer >= 0 && layer < (int)n->convs.size(), "maua_synth_get_feature: no such layer");
-  MAUA_REQUIRE(B <= n->bcap, "maua_synth_get_feature: batch larger than the last forward");
+  MAUA_REQUIRE(B <= n->wk.bcap, "maua_synth_get_feature: batch larger than the last forward");
   ConvLayer& c = n->convs[layer];
   hipStream_t st = n->ctx->stream;
   return dispatch_dtype<bf16_t, f16_t, float>(n->dtype, "maua_synth_get_feature", [&](auto t) {
-    return launch_nhwc_to_nchw<decltype(t), float>(st, c.feat, out_nchw, B, c.Co, c.fh * c.fw, c.Co);
+    return launch_nhwc_to_nchw<decltype(t), float>(st, c.feat.get(), out_nchw, B, c.Co, c.fh * c.fw, c.Co);
   });
 }
 

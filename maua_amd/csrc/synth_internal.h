@@ -15,34 +15,34 @@ struct ConvLayer {
   int ih = 0, iw = 0;   // input grid of this launch
   int oh = 0, ow = 0;   // conv output grid (= where the noise is added)
   int fh = 0, fw = 0;   // grid handed to the next layer (differs from oh x ow only on the resized layer)
-  float* affine_w = nullptr;  // [Ci][w_dim]
-  float* affine_b = nullptr;  // [Ci]
-  float* bias = nullptr;      // [Co]
-  float* noise_const = nullptr;  // [res][res]
+  DevBuf affine_w;     // float [Ci][w_dim]
+  DevBuf affine_b;     // float [Ci]
+  DevBuf bias;         // float [Co]
+  DevBuf noise_const;  // float [oh][ow]
   float noise_strength = 0.f;    // loaded value (used under nv_compat bit1)
-  void* wt = nullptr;            // prepared weights (up-layers: 4 phase kernels, 9 taps each)
-  void* wt_t = nullptr;          // up-layers: transposed-conv class weights (minimal MACs; FIR done afterwards)
-  void* wt_h = nullptr;          // up-layers on the row-walk kernel: half-folded weights (modconv_upwalk.hip)
-  float* wsq = nullptr;          // [Co][Ci]
-  float* s = nullptr;            // [Bcap][Ci]
-  float* d = nullptr;            // [Bcap][Co]
-  void* feat = nullptr;          // keep_features buffer
-  void* wg = nullptr;            // input-gradient weights [9][Ci][Co] (synth_vjp.hip: made from wt / wt_t on the first gradient call)
+  DevBuf wt;           // prepared weights (up-layers: 4 phase kernels, 9 taps each)
+  DevBuf wt_t;         // up-layers: transposed-conv class weights (minimal MACs; FIR done afterwards)
+  DevBuf wt_h;         // up-layers on the row-walk kernel: half-folded weights (modconv_upwalk.hip)
+  DevBuf wsq;          // float [Co][Ci]
+  DevBuf s;            // float [Bcap][Ci]   (s, d, feat: the forward's workspace)
+  DevBuf d;            // float [Bcap][Co]
+  DevBuf feat;         // keep_features buffer
+  DevBuf wg;           // input-gradient weights [9][Ci][Co] (synth_vjp.hip: made from wt / wt_t on the first gradient call)
 };
 struct RgbLayer {
   int block, C, res, w_index;
   int h = 0, w = 0;     // grid toRGB runs on (the block's feature grid)
-  float* affine_w = nullptr;
-  float* affine_b = nullptr;
-  float* wrgb = nullptr;  // [3][C]
-  float* bias = nullptr;  // [3]
-  float* s = nullptr;     // [Bcap][C]
-  float* wmod = nullptr;  // [Bcap][3][C]
+  DevBuf affine_w, affine_b;   // float
+  DevBuf wrgb;   // float [3][C]
+  DevBuf bias;   // float [3]
+  DevBuf s;      // float [Bcap][C]      (s, wmod: the forward's workspace)
+  DevBuf wmod;   // float [Bcap][3][C]
 };
 
 // what maua_synth_vjp keeps between calls (synth_vjp.hip); nothing of it exists on a network that only runs forwards
 struct SynthVjpState {
   bool weights_ready = false;   // every ConvLayer.wg holds the weights now loaded
+  DevBuf ws;                    // one set for bcap samples, carved into the pieces below (ensure_vjp)
   int bcap = 0;
   void* gfeat[2] = {nullptr, nullptr};   // gradients of two neighbouring feature tensors (network dtype)
   float* gimg[2] = {nullptr, nullptr};   // gradient of the skip image at two neighbouring resolutions
@@ -53,10 +53,24 @@ struct SynthVjpState {
   float* g_d = nullptr;
   float* g_s = nullptr;      // [B][max channels]
   float* g_wmod = nullptr;   // [B][3][max channels]
-  float* npart = nullptr;    // maua_synth_vjp_ex with g_noise: [B][max Co / 32 x pixels] per-group channel sums (allocated on first use)
+  DevBuf npart;              // maua_synth_vjp_ex with g_noise: float [B][max Co / 32 x pixels] per-group channel sums (allocated on first use)
   int npart_bcap = 0;
 };
-void synth_vjp_release(SynthVjpState& v, bool weights_too, std::vector<ConvLayer>& convs);   // synth_vjp.hip
+
+// the forward's workspace for bcap samples, beside the layers' own s / d / feat / wmod: dropped as a whole when a grid or an option changes
+struct SynthWorkspace {
+  int bcap = 0;
+  DevBuf act[2];
+  DevBuf img[2];       // float
+  DevBuf rgb_tmp[2];   // float
+  DevBuf style_table;  // StyleLayer []
+  UnitStyles ones;     // [bcap][max channels] (kernels that take already-modulated input)
+  DevBuf xm;           // [bcap] pre-modulated copy of an up-layer's input when its producer could not scale it
+  DevBuf tbuf;         // [bcap] transposed-conv tensor of the largest up-layer
+  DevBuf lowres_xm;    // [bcap] modconv_lowres workspaces (premodulated input, split-K partial sums: float)
+  DevBuf lowres_ws;
+  DevBuf const_rs;     // resized const input (rs_layer == 0)
+};
 
 }  // namespace maua
 
@@ -67,7 +81,7 @@ struct maua_synth {
   size_t esize;
   std::vector<maua::ConvLayer> convs;
   std::vector<maua::RgbLayer> rgbs;
-  void* const_x = nullptr;  // NHWC [4][4][C0]
+  maua::DevBuf const_x;  // NHWC [4][4][C0]
   int keep_features = 0;
   int lowres = 1;      // <= 8x8 layers as one batch-wide split-K GEMM (option "lowres")
   int use_hires = 1;   // weights-in-registers kernels for the 512^2 / 1024^2 layers (bf16 / f16)
@@ -88,17 +102,10 @@ struct maua_synth {
   int dual_store = 1;  // ... whose toRGB is a separate pass (512 channels): plain + style-scaled output in one epilogue (no premod pass)
   int tconv_dma = 1;   // the up-layers' transposed conv on LDS-direct loads (main block; pre-modulated input) + the dedicated
                        // edge kernel for the last row / column (0: the register-staged transposed conv)
-  maua::UnitStyles ones;   // [Bcap][max channels] (kernels that take already-modulated input)
-  void* xm = nullptr;      // [Bcap] pre-modulated copy of an up-layer's input when its producer could not scale it
-  void* tbuf = nullptr;  // [Bcap] transposed-conv tensor of the largest up-layer
-  void* lowres_xm = nullptr;   // [Bcap] modconv_lowres workspaces (premodulated input, split-K partial sums)
-  float* lowres_ws = nullptr;
   // one feature-space resize (wrappers/stylegan2.py:104-151): rs_layer = -1 none, 0 = before layer 0, L = after layer L-1
   int rs_layer = -1, rs_mode = 0, rs_th = 0, rs_tw = 0, rs_pl = 0, rs_pr = 0, rs_pt = 0, rs_pb = 0, rs_how = 3;
   float rs_value = 0.f;
-  float* rs_noise = nullptr;   // [C][th][tw] fill noise or NULL
-  void* const_rs = nullptr;    // resized const input (rs_layer == 0)
-  float* rgb_tmp[2] = {nullptr, nullptr};
+  maua::DevBuf rs_noise;       // float [C][th][tw] fill noise, or empty
   int out_h = 0, out_w = 0;    // final image
   // geometric transform hooks (wrappers/stylegan2.py:153-194): up to 3 warps, applied in slot order after their layer
   int warp_layer[3] = {-1, -1, -1};
@@ -108,11 +115,7 @@ struct maua_synth {
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
   std::vector<size_t> ev_fwd_start;
-  // workspace
-  int bcap = 0;
-  void* act[2] = {nullptr, nullptr};
-  float* img[2] = {nullptr, nullptr};
-  maua::StyleLayer* style_table_dev = nullptr;
+  maua::SynthWorkspace wk;
   float fir[16];
   // the last forward that kept its features (maua_synth_vjp differentiates exactly that one): its batch (0 = none), whether it ran
   // with per-sample noise factors, and whether an option, a weight load or a resize came after it

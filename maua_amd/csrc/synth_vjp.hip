@@ -18,24 +18,6 @@
 
 namespace maua {
 
-void synth_vjp_release(SynthVjpState& v, bool weights_too, std::vector<ConvLayer>& convs) {
-  for (int i = 0; i < 2; i++) {
-    hipFree(v.gfeat[i]); v.gfeat[i] = nullptr;
-    hipFree(v.gimg[i]); v.gimg[i] = nullptr;
-  }
-  hipFree(v.g_u); hipFree(v.g_t); hipFree(v.g_xm); hipFree(v.part); hipFree(v.g_d); hipFree(v.g_s); hipFree(v.g_wmod); hipFree(v.npart);
-  v.g_u = v.g_t = nullptr;
-  v.g_xm = v.part = v.g_d = v.g_s = v.g_wmod = v.npart = nullptr;
-  v.bcap = v.npart_bcap = 0;
-  if (weights_too) {
-    for (auto& c : convs) {
-      hipFree(c.wg);
-      c.wg = nullptr;
-    }
-    v.weights_ready = false;
-  }
-}
-
 namespace {
 
 int synth_vjp_check(const maua_synth* n, int B) {
@@ -56,14 +38,15 @@ int ensure_vjp(maua_synth* n, int B) {
   hipStream_t st = n->ctx->stream;
   if (!v.weights_ready) {   // the forward's own (rounded, flipped) weights in the gradient convolution's layout
     for (auto& c : n->convs) {
-      if (!c.wg) MAUA_HIP_CHECK(hipMalloc(&c.wg, 9 * (size_t)c.Ci * c.Co * n->esize));
-      if (int rc = launch_vjp_weights_from_prepared(st, n->dtype, c.up == 2 ? c.wt_t : c.wt, c.wg, c.Co, c.Ci, c.up)) return rc;
+      if (!c.wg)
+        if (int rc = c.wg.alloc(9 * (size_t)c.Ci * c.Co * n->esize)) return rc;
+      if (int rc = launch_vjp_weights_from_prepared(st, n->dtype, (c.up == 2 ? c.wt_t : c.wt).get(), c.wg.get(), c.Co, c.Ci, c.up)) return rc;
     }
     v.weights_ready = true;
   }
   if (B <= v.bcap) return MAUA_OK;
   MAUA_HIP_CHECK(hipStreamSynchronize(st));
-  synth_vjp_release(v, false, n->convs);
+  v.bcap = 0;
   ModconvVjpWorkspace m{0, 0, 0, 0, 0};
   size_t feat = 0, rgb_part = 0;
   int maxc = 0;
@@ -76,17 +59,20 @@ int ensure_vjp(maua_synth* n, int B) {
   }
   for (auto& r : n->rgbs) rgb_part = std::max(rgb_part, torgb_vjp_part_bytes(B, r.h, r.w, r.C));
   m.part = std::max(m.part, rgb_part);
-  for (int i = 0; i < 2; i++) {
-    MAUA_HIP_CHECK(hipMalloc(&v.gfeat[i], feat));
-    MAUA_HIP_CHECK(hipMalloc((void**)&v.gimg[i], (size_t)B * 3 * std::max(1, n->out_h * n->out_w / 4) * sizeof(float)));
-  }
-  MAUA_HIP_CHECK(hipMalloc(&v.g_u, m.g_u));
-  if (m.g_t) MAUA_HIP_CHECK(hipMalloc(&v.g_t, m.g_t));
-  MAUA_HIP_CHECK(hipMalloc((void**)&v.g_xm, m.g_xm));
-  MAUA_HIP_CHECK(hipMalloc((void**)&v.part, m.part));
-  MAUA_HIP_CHECK(hipMalloc((void**)&v.g_d, m.g_d));
-  MAUA_HIP_CHECK(hipMalloc((void**)&v.g_s, (size_t)B * maxc * sizeof(float)));
-  MAUA_HIP_CHECK(hipMalloc((void**)&v.g_wmod, (size_t)B * 3 * maxc * sizeof(float)));
+  auto layout = [&](Scratch& s) {
+    for (int i = 0; i < 2; i++) {
+      v.gfeat[i] = s.take<char>(feat);
+      v.gimg[i] = s.take<float>((size_t)B * 3 * std::max(1, n->out_h * n->out_w / 4));
+    }
+    v.g_u = s.take<char>(m.g_u);
+    v.g_t = m.g_t ? s.take<char>(m.g_t) : nullptr;
+    v.g_xm = (float*)s.take<char>(m.g_xm);
+    v.part = (float*)s.take<char>(m.part);
+    v.g_d = (float*)s.take<char>(m.g_d);
+    v.g_s = s.take<float>((size_t)B * maxc);
+    v.g_wmod = s.take<float>((size_t)B * 3 * maxc);
+  };
+  if (int rc = carve_into(v.ws, layout)) return rc;
   v.bcap = B;
   return MAUA_OK;
 }
@@ -96,12 +82,10 @@ int ensure_noise_part(maua_synth* n, int B) {
   SynthVjpState& v = n->vjp;
   if (B <= v.npart_bcap) return MAUA_OK;
   MAUA_HIP_CHECK(hipStreamSynchronize(n->ctx->stream));
-  hipFree(v.npart);
-  v.npart = nullptr;
   v.npart_bcap = 0;
   size_t bytes = 0;
   for (auto& c : n->convs) bytes = std::max(bytes, modconv_vjp_noise_part_bytes(B, c.ih, c.iw, c.Co, c.up));
-  MAUA_HIP_CHECK(hipMalloc((void**)&v.npart, bytes));
+  if (int rc = v.npart.alloc(bytes)) return rc;
   v.npart_bcap = B;
   return MAUA_OK;
 }
@@ -142,29 +126,29 @@ extern "C" int maua_synth_vjp_ex(maua_synth* n, const float* const* noise, const
   auto conv_vjp = [&](const ConvLayer& c, size_t l, const void* x, long x_bstride, const void* g_y, void* g_x) -> int {
     const bool given = noise && noise[l];
     ModconvVjpArgs a{};
-    a.x = x; a.x_bstride = x_bstride; a.y = c.feat; a.g_y = g_y; a.wg = c.wg; a.wsq = c.wsq; a.s = c.s; a.d = c.d;
-    a.noise = given ? noise[l] : c.noise_const;
+    a.x = x; a.x_bstride = x_bstride; a.y = c.feat.get(); a.g_y = g_y; a.wg = c.wg.get(); a.wsq = c.wsq.as<float>(); a.s = c.s.as<float>(); a.d = c.d.as<float>();
+    a.noise = given ? noise[l] : c.noise_const.as<float>();
     a.noise_bstride = given ? (noise_bstride ? noise_bstride[l] : (long)c.oh * c.ow) : 0;
     a.noise_strength = (n->nv_compat & 2) ? c.noise_strength : 1.f;
-    a.bias = c.bias; a.g_x = g_x; a.accumulate = 0; a.g_s = v.g_s;
+    a.bias = c.bias.as<float>(); a.g_x = g_x; a.accumulate = 0; a.g_s = v.g_s;
     if (g_noise && g_noise[l]) {   // (no stride array: one map per sample)
-      a.g_noise = g_noise[l]; a.g_noise_bstride = g_noise_bstride ? g_noise_bstride[l] : (long)c.oh * c.ow; a.npart = v.npart;
+      a.g_noise = g_noise[l]; a.g_noise_bstride = g_noise_bstride ? g_noise_bstride[l] : (long)c.oh * c.ow; a.npart = v.npart.as<float>();
     }
     a.B = B; a.H = c.ih; a.W = c.iw; a.Ci = c.Ci; a.Co = c.Co; a.up = c.up;
     a.act = MAUA_ACT_LRELU; a.alpha = 0.2f; a.gain = std::sqrt(2.0f); a.clamp = 256.f;   // (synth.hip lrelu_epilogue)
     a.g_u = v.g_u; a.g_t = v.g_t; a.g_xm = v.g_xm; a.part = v.part; a.g_d = v.g_d;
     if (int rc = launch_modconv_vjp(st, n->dtype, a)) return rc;
-    return launch_affine_vjp(st, v.g_s, c.Ci, c.affine_w, wgain, g_ws, c.w_index, n->num_ws, n->w_dim, B, c.Ci);
+    return launch_affine_vjp(st, v.g_s, c.Ci, c.affine_w.as<float>(), wgain, g_ws, c.w_index, n->num_ws, n->w_dim, B, c.Ci);
   };
   for (int blk = n->nblocks - 1; blk >= 0; blk--) {
     const RgbLayer& g = n->rgbs[blk];
     const ConvLayer& c1 = n->convs[li - 1];
     RgbVjpArgs r{};
-    r.x = c1.feat; r.wmod = g.wmod; r.bias = g.bias; r.g_img = gi; r.g_x = v.gfeat[0]; r.accumulate = have_gx; r.g_wmod = v.g_wmod;
+    r.x = c1.feat.get(); r.wmod = g.wmod.as<float>(); r.bias = g.bias.as<float>(); r.g_img = gi; r.g_x = v.gfeat[0]; r.accumulate = have_gx; r.g_wmod = v.g_wmod;
     r.part = v.part; r.B = B; r.H = g.h; r.W = g.w; r.C = g.C; r.clamp = 256.f;
     if (int rc = launch_torgb_vjp(st, n->dtype, r)) return rc;
-    if (int rc = launch_rgb_styles_vjp(st, v.g_wmod, g.wrgb, v.g_s, B, g.C)) return rc;
-    if (int rc = launch_affine_vjp(st, v.g_s, g.C, g.affine_w, wgain / std::sqrt((float)g.C), g_ws, g.w_index, n->num_ws, n->w_dim, B, g.C))
+    if (int rc = launch_rgb_styles_vjp(st, v.g_wmod, g.wrgb.as<float>(), v.g_s, B, g.C)) return rc;
+    if (int rc = launch_affine_vjp(st, v.g_s, g.C, g.affine_w.as<float>(), wgain / std::sqrt((float)g.C), g_ws, g.w_index, n->num_ws, n->w_dim, B, g.C))
       return rc;
     if (blk > 0) {
       if (int rc = launch_skip_vjp(st, gi, v.gimg[img_cur], B, g.h / 2, g.w / 2)) return rc;
@@ -172,14 +156,14 @@ extern "C" int maua_synth_vjp_ex(maua_synth* n, const float* const* noise, const
       img_cur ^= 1;
     }
     if (blk == 0) {   // conv1 on the learned const input: only its styles want a gradient
-      if (int rc = conv_vjp(c1, li - 1, n->const_x, 0, v.gfeat[0], nullptr)) return rc;
+      if (int rc = conv_vjp(c1, li - 1, n->const_x.get(), 0, v.gfeat[0], nullptr)) return rc;
       li -= 1;
       break;
     }
     const ConvLayer& c0 = n->convs[li - 2];
-    if (int rc = conv_vjp(c1, li - 1, c0.feat, (long)c0.oh * c0.ow * c0.Co, v.gfeat[0], v.gfeat[1])) return rc;
+    if (int rc = conv_vjp(c1, li - 1, c0.feat.get(), (long)c0.oh * c0.ow * c0.Co, v.gfeat[0], v.gfeat[1])) return rc;
     const ConvLayer& pv = n->convs[li - 3];   // the previous block's conv1
-    if (int rc = conv_vjp(c0, li - 2, pv.feat, (long)pv.oh * pv.ow * pv.Co, v.gfeat[1], v.gfeat[0])) return rc;
+    if (int rc = conv_vjp(c0, li - 2, pv.feat.get(), (long)pv.oh * pv.ow * pv.Co, v.gfeat[1], v.gfeat[0])) return rc;
     have_gx = true;
     li -= 2;
   }

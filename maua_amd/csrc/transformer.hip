@@ -195,22 +195,22 @@ int block_forward(const BlockRun& r, const BlockWeights& l, const void* x, const
   const int w = r.width;
   const long M = r.gemm_rows;
   // x -> ln_1 -> in_proj -> attention -> out_proj (+ x) = xm
-  launch_layer_norm(r.st, r.dtype, x, l.ln1_g, l.ln1_b, lno, k.st1, r.rows, w);
-  if (int rc = block_gemm(r, lno, M, w, l.w_qkv, 3 * w, l.b_qkv, nullptr, k.qkv)) return rc;
+  launch_layer_norm(r.st, r.dtype, x, l.ln1_g.as<float>(), l.ln1_b.as<float>(), lno, k.st1, r.rows, w);
+  if (int rc = block_gemm(r, lno, M, w, l.w_qkv.get(), 3 * w, l.b_qkv.as<float>(), nullptr, k.qkv)) return rc;
   AttnArgs a{};
   a.qkv = k.qkv; a.out = k.ao; a.B = (int)r.N; a.T = r.Tk; a.heads = r.heads; a.D = w / r.heads; a.ld_qkv = 3 * w; a.ld_out = w;
   a.scale = 1.f / std::sqrt((float)a.D); a.lse = k.lse; a.causal = r.causal;
   if (int rc = launch_attention(r.st, r.dtype, a)) return rc;
-  if (int rc = block_gemm(r, k.ao, M, w, l.w_out, w, l.b_out, x, k.xm)) return rc;
+  if (int rc = block_gemm(r, k.ao, M, w, l.w_out.get(), w, l.b_out.as<float>(), x, k.xm)) return rc;
   // xm -> ln_2 -> c_fc -> QuickGELU -> c_proj (+ xm) = next x
-  launch_layer_norm(r.st, r.dtype, k.xm, l.ln2_g, l.ln2_b, lno, k.st2, r.rows, w);
+  launch_layer_norm(r.st, r.dtype, k.xm, l.ln2_g.as<float>(), l.ln2_b.as<float>(), lno, k.st2, r.rows, w);
   if (gemm_fuses(r, M, w, 4 * w)) {
-    if (int rc = block_gemm(r, lno, M, w, l.w_fc, 4 * w, l.b_fc, nullptr, k.h, 1, act)) return rc;
+    if (int rc = block_gemm(r, lno, M, w, l.w_fc.get(), 4 * w, l.b_fc.as<float>(), nullptr, k.h, 1, act)) return rc;
   } else {
-    if (int rc = block_gemm(r, lno, M, w, l.w_fc, 4 * w, l.b_fc, nullptr, k.h)) return rc;
+    if (int rc = block_gemm(r, lno, M, w, l.w_fc.get(), 4 * w, l.b_fc.as<float>(), nullptr, k.h)) return rc;
     launch_quick_gelu(r.st, r.dtype, k.h, act, r.rows * 4 * w);
   }
-  return block_gemm(r, act, M, 4 * w, l.w_pr, w, l.b_pr, k.xm, xn);
+  return block_gemm(r, act, M, 4 * w, l.w_pr.get(), w, l.b_pr.as<float>(), k.xm, xn);
 }
 
 int block_backward(const BlockRun& r, const BlockWeights& l, const BlockActs& k, void* dx, void* other, void* dqkv, void* dwide, void* dtmp,
@@ -219,33 +219,33 @@ int block_backward(const BlockRun& r, const BlockWeights& l, const BlockActs& k,
   const long M = r.gemm_rows;
   // MLP: d act = dx W_pr ; d h = d act * QuickGELU'(h) ; d ln2 = d h W_fc ; dxm = dx + LN2'(d ln2)
   if (gemm_fuses(r, M, w, 4 * w)) {
-    if (int rc = block_gemm(r, dx, M, w, l.w_pr_t, 4 * w, nullptr, nullptr, dwide, 2, nullptr, k.h)) return rc;
+    if (int rc = block_gemm(r, dx, M, w, l.w_pr_t.get(), 4 * w, nullptr, nullptr, dwide, 2, nullptr, k.h)) return rc;
   } else {
-    if (int rc = block_gemm(r, dx, M, w, l.w_pr_t, 4 * w, nullptr, nullptr, dwide)) return rc;
+    if (int rc = block_gemm(r, dx, M, w, l.w_pr_t.get(), 4 * w, nullptr, nullptr, dwide)) return rc;
     launch_quick_gelu_vjp(r.st, r.dtype, k.h, dwide, dwide, r.rows * 4 * w);
   }
-  if (int rc = block_gemm(r, dwide, M, 4 * w, l.w_fc_t, w, nullptr, nullptr, dtmp)) return rc;
-  launch_layer_norm_vjp(r.st, r.dtype, k.xm, k.st2, l.ln2_g, dtmp, dx, other, r.rows, w, 0);   // other = d xm
+  if (int rc = block_gemm(r, dwide, M, 4 * w, l.w_fc_t.get(), w, nullptr, nullptr, dtmp)) return rc;
+  launch_layer_norm_vjp(r.st, r.dtype, k.xm, k.st2, l.ln2_g.as<float>(), dtmp, dx, other, r.rows, w, 0);   // other = d xm
   // attention: d ao = dxm W_out ; d qkv = attention'(d ao) ; d ln1 = d qkv W_qkv ; d x = dxm + LN1'(d ln1)
-  if (int rc = block_gemm(r, other, M, w, l.w_out_t, w, nullptr, nullptr, dtmp)) return rc;
+  if (int rc = block_gemm(r, other, M, w, l.w_out_t.get(), w, nullptr, nullptr, dtmp)) return rc;
   AttnVjpArgs v{};
   v.qkv = k.qkv; v.out = k.ao; v.d_out = dtmp; v.lse = k.lse; v.d_qkv = dqkv; v.delta = delta;
   v.B = (int)r.N; v.T = r.Tk; v.heads = r.heads; v.D = w / r.heads; v.ld_qkv = 3 * w; v.ld_out = w; v.scale = 1.f / std::sqrt((float)v.D);
   if (int rc = launch_attention_vjp(r.st, r.dtype, v)) return rc;
-  if (int rc = block_gemm(r, dqkv, M, 3 * w, l.w_qkv_t, w, nullptr, nullptr, dtmp)) return rc;
-  launch_layer_norm_vjp(r.st, r.dtype, k.x, k.st1, l.ln1_g, dtmp, other, dx, r.rows, w, 0);
+  if (int rc = block_gemm(r, dqkv, M, 3 * w, l.w_qkv_t.get(), w, nullptr, nullptr, dtmp)) return rc;
+  launch_layer_norm_vjp(r.st, r.dtype, k.x, k.st1, l.ln1_g.as<float>(), dtmp, other, dx, r.rows, w, 0);
   return MAUA_OK;
 }
 
 // host float matrix [R][C] -> device T [R][C] (and optionally its transpose [C][R]); rows permuted by `perm` when given
-int upload_matrix(int dtype, size_t esize, const float* h, int R, int C, const int* perm, void** dev, void** dev_t) {
+int upload_matrix(int dtype, size_t esize, const float* h, int R, int C, const int* perm, DevBuf* dev, DevBuf* dev_t) {
   std::vector<float> a((size_t)R * C);
   for (int r = 0; r < R; r++) memcpy(&a[(size_t)r * C], h + (size_t)(perm ? perm[r] : r) * C, (size_t)C * 4);
-  auto put = [&](const std::vector<float>& src, void** d) -> int {
+  auto put = [&](const std::vector<float>& src, DevBuf* d) -> int {
     if (!*d)
-      if (int rc = dalloc(d, src.size() * esize)) return rc;
+      if (int rc = d->alloc(src.size() * esize)) return rc;
     if (dtype == MAUA_F32) {
-      MAUA_HIP_CHECK(hipMemcpy(*d, src.data(), src.size() * 4, hipMemcpyHostToDevice));
+      MAUA_HIP_CHECK(hipMemcpy(d->get(), src.data(), src.size() * 4, hipMemcpyHostToDevice));
     } else {
       std::vector<uint16_t> b(src.size());
       for (size_t i = 0; i < src.size(); i++) {   // round to nearest even
@@ -254,7 +254,7 @@ int upload_matrix(int dtype, size_t esize, const float* h, int R, int C, const i
         if ((u & 0x7f800000u) == 0x7f800000u) b[i] = (uint16_t)(u >> 16);
         else b[i] = (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
       }
-      MAUA_HIP_CHECK(hipMemcpy(*d, b.data(), b.size() * 2, hipMemcpyHostToDevice));
+      MAUA_HIP_CHECK(hipMemcpy(d->get(), b.data(), b.size() * 2, hipMemcpyHostToDevice));
     }
     return MAUA_OK;
   };
@@ -267,12 +267,12 @@ int upload_matrix(int dtype, size_t esize, const float* h, int R, int C, const i
   }
   return MAUA_OK;
 }
-int upload_vec(const float* h, size_t count, const int* perm, float** dev) {
+int upload_vec(const float* h, size_t count, const int* perm, DevBuf* dev) {
   std::vector<float> a(count);
   for (size_t i = 0; i < count; i++) a[i] = h[perm ? perm[i] : i];
   if (!*dev)
-    if (int rc = dalloc((void**)dev, count * 4)) return rc;
-  MAUA_HIP_CHECK(hipMemcpy(*dev, a.data(), count * 4, hipMemcpyHostToDevice));
+    if (int rc = dev->alloc(count * 4)) return rc;
+  MAUA_HIP_CHECK(hipMemcpy(dev->get(), a.data(), count * 4, hipMemcpyHostToDevice));
   return MAUA_OK;
 }
 
@@ -300,7 +300,7 @@ int load_block(std::vector<BlockWeights>& L, int dtype, size_t esize, int width,
   for (int h = 0; h < heads; h++)
     for (int part = 0; part < 3; part++)
       for (int d = 0; d < D; d++) perm[(h * 3 + part) * D + d] = part * w + h * D + d;
-  auto t = [&](void** p) { return with_t ? p : nullptr; };
+  auto t = [&](DevBuf* p) { return with_t ? p : nullptr; };
   if (par == "attn.in_proj_weight") { if (int rc = need((size_t)3 * w * w)) return rc; return upload_matrix(dtype, esize, host, 3 * w, w, perm.data(), &l.w_qkv, t(&l.w_qkv_t)); }
   if (par == "attn.in_proj_bias") { if (int rc = need((size_t)3 * w)) return rc; return upload_vec(host, 3 * w, perm.data(), &l.b_qkv); }
   if (par == "attn.out_proj.weight") { if (int rc = need((size_t)w * w)) return rc; return upload_matrix(dtype, esize, host, w, w, nullptr, &l.w_out, t(&l.w_out_t)); }
@@ -321,12 +321,6 @@ bool blocks_loaded(const std::vector<BlockWeights>& L) {
   for (auto& l : L)
     ok = ok && l.w_qkv && l.w_out && l.w_fc && l.w_pr && l.b_qkv && l.b_out && l.b_fc && l.b_pr && l.ln1_g && l.ln1_b && l.ln2_g && l.ln2_b;
   return ok;
-}
-void free_blocks(std::vector<BlockWeights>& L) {
-  for (auto& l : L)
-    for (void* p : {l.w_qkv, l.w_qkv_t, l.w_out, l.w_out_t, l.w_fc, l.w_fc_t, l.w_pr, l.w_pr_t, (void*)l.b_qkv, (void*)l.b_out, (void*)l.b_fc,
-                    (void*)l.b_pr, (void*)l.ln1_g, (void*)l.ln1_b, (void*)l.ln2_g, (void*)l.ln2_b})
-      dfree(p);
 }
 
 }  // namespace maua

@@ -98,17 +98,18 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restric
 namespace {
 
 template <typename P>
-int dev_alloc(maua_unet* n, P** p, size_t bytes, bool zero = true) {
-  MAUA_HIP_CHECK(hipMalloc((void**)p, bytes));
-  if (zero) MAUA_HIP_CHECK(hipMemset(*p, 0, bytes));
-  n->owned.push_back(*p);
+int own(maua_unet* n, P** p, size_t bytes, bool zero = true) {   // a parameter buffer of n->owned, handed out as *p
+  DevBuf b;
+  if (int rc = b.alloc(bytes, zero)) return rc;
+  *p = b.as<P>();
+  n->owned.push_back(std::move(b));
   return MAUA_OK;
 }
 
 int make_gn(maua_unet* n, UGN& g, int C, const std::string& name) {
   g.C = C;
-  if (int rc = dev_alloc(n, &g.gamma, (size_t)C * 4)) return rc;
-  if (int rc = dev_alloc(n, &g.beta, (size_t)C * 4)) return rc;
+  if (int rc = own(n, &g.gamma, (size_t)C * 4)) return rc;
+  if (int rc = own(n, &g.beta, (size_t)C * 4)) return rc;
   n->params[name + ".weight"] = PRef{P_GN_G, &g};
   n->params[name + ".bias"] = PRef{P_GN_B, &g};
   return MAUA_OK;
@@ -121,8 +122,8 @@ int make_conv(maua_unet* n, PlainConv& c, int Ci, int Co, const std::string& nam
 }
 int make_lin(maua_unet* n, ULin& l, int K, int N, const std::string& name) {
   l.K = K; l.N = N;
-  if (int rc = dev_alloc(n, &l.w, (size_t)N * K * n->esize)) return rc;
-  if (int rc = dev_alloc(n, &l.bias, (size_t)N * 4)) return rc;
+  if (int rc = own(n, &l.w, (size_t)N * K * n->esize)) return rc;
+  if (int rc = own(n, &l.bias, (size_t)N * 4)) return rc;
   n->params[name + ".weight"] = PRef{P_LIN_W, &l};
   n->params[name + ".bias"] = PRef{P_LIN_B, &l};
   return MAUA_OK;
@@ -229,13 +230,13 @@ int build_structure(maua_unet* n) {
   if ((rc = make_conv(n, n->conv_out, ch, n->out_ch, "out.2"))) return rc;
   // f32 timestep path
   const int E = n->emb_dim;
-  if ((rc = dev_alloc(n, &n->te0_w, (size_t)E * mc * 4))) return rc;
-  if ((rc = dev_alloc(n, &n->te0_b, (size_t)E * 4))) return rc;
-  if ((rc = dev_alloc(n, &n->te2_w, (size_t)E * E * 4))) return rc;
-  if ((rc = dev_alloc(n, &n->te2_b, (size_t)E * 4))) return rc;
-  if ((rc = dev_alloc(n, &n->embw, (size_t)n->emb_total * E * 4))) return rc;
-  if ((rc = dev_alloc(n, &n->embb, (size_t)n->emb_total * 4))) return rc;
-  if ((rc = dev_alloc(n, &n->freqs, (size_t)(mc / 2) * 4))) return rc;
+  if ((rc = own(n, &n->te0_w, (size_t)E * mc * 4))) return rc;
+  if ((rc = own(n, &n->te0_b, (size_t)E * 4))) return rc;
+  if ((rc = own(n, &n->te2_w, (size_t)E * E * 4))) return rc;
+  if ((rc = own(n, &n->te2_b, (size_t)E * 4))) return rc;
+  if ((rc = own(n, &n->embw, (size_t)n->emb_total * E * 4))) return rc;
+  if ((rc = own(n, &n->embb, (size_t)n->emb_total * 4))) return rc;
+  if ((rc = own(n, &n->freqs, (size_t)(mc / 2) * 4))) return rc;
   n->params["timestep_embedding.freqs"] = PRef{P_F32, nullptr, n->freqs, (size_t)(mc / 2)};
   n->params["time_embed.0.weight"] = PRef{P_F32, nullptr, n->te0_w, (size_t)E * mc};
   n->params["time_embed.0.bias"] = PRef{P_F32, nullptr, n->te0_b, (size_t)E};
@@ -311,6 +312,10 @@ struct Runner {
 
   // y = conv3x3(x) + bias (+ res); x, y, res dense NHWC [B][H][W][.]
   int conv(const PlainConv& c, const T* x, T* y, int H, int W, const T* res, float* psum = nullptr) {
+    return conv(ConvView{c.Cip, c.Cop, c.wt.get(), c.bias.as<float>()}, x, y, H, W, res, psum);
+  }
+  struct ConvView { int Cip, Cop; const void* wt; const float* bias; };   // the forward's weights, or the input gradient's
+  int conv(const ConvView& c, const T* x, T* y, int H, int W, const T* res, float* psum) {
     const size_t ws_need = gather_conv_supported(n->dtype, c.Cip, c.Cop, H, W) ? gather_conv_workspace(n->dtype, B, H, W, c.Cip, c.Cop) : 0;
     if (plan) {
       if (ws_need > gather_ws_bytes) gather_ws_bytes = ws_need;
@@ -332,7 +337,7 @@ struct Runner {
       return launch_modconv_dma(st, a);
     }
     if (r.kernel == 3) return launch_conv_gather(st, n->dtype, a, gather_ws);
-    a.s = n->ones.p;
+    a.s = n->ones.p();
     return launch_modconv3x3(st, n->dtype, a);
   }
 
@@ -530,9 +535,7 @@ struct Runner {
   // ------------------------------------------------------------------------------------------ input gradient (guided.py:250-272)
   // dx = conv3x3(dy) with the transposed, spatially flipped kernel (PlainConv.wt_t), no bias, optional residual
   int conv_t(const PlainConv& c, const T* dy, T* dx, int H, int W, const T* res) {
-    PlainConv v;
-    v.Ci = c.Co; v.Co = c.Ci; v.Cip = c.Cop; v.Cop = c.Cip; v.wt = c.wt_t; v.bias = c.zero_bias;
-    return conv(v, dy, dx, H, W, res);
+    return conv(ConvView{c.Cop, c.Cip, c.wt_t.get(), c.zero_bias.as<float>()}, dy, dx, H, W, res, nullptr);
   }
   // c [M][N] = a [M][K] w_t^T (+ res), w_t rows [n0, n0 + N) of a transposed linear weight [Kin][Nout]
   int gemm_t(const ULin& l, int n0, int N, const T* a, T* c, long M, const T* res) {
@@ -668,13 +671,10 @@ int run_forward(maua_unet* n, const float* x, const float* t, int B, int H, int 
     if (keep)
       if (int rc = pr.backward(ptape, nullptr, H, W, nullptr)) return rc;
     const size_t need = n->arena.peak + pr.gather_ws_bytes + (1 << 20);
-    if (need > n->arena.cap) {
+    if (need > n->arena.base.bytes()) {
       MAUA_HIP_CHECK(hipStreamSynchronize(st));
-      if (n->arena.base) hipFree(n->arena.base);
-      n->arena.base = nullptr; n->arena.cap = 0;
-      MAUA_HIP_CHECK(hipMalloc((void**)&n->arena.base, need));
-      n->arena.cap = need;
-      drop_sampler_graphs(n);   // (their pointers were into the old arena)
+      drop_sampler_graphs(n);   // (their pointers are into the old arena: gone whether or not the new one can be had)
+      if (int rc = n->arena.base.alloc(need)) return rc;
     }
     // a replan inside the same arena keeps the captured loops: each was captured under its own mode's plan (the graphs' keys hold
     // shape and mode), its offsets are baked in and stay inside [base, base + cap) - alternating an ordinary and a kept forward at
@@ -799,11 +799,6 @@ void maua_unet_destroy(maua_unet* n) {
   if (!n) return;
   hipStreamSynchronize(n->ctx->stream);
   n->smp.release();
-  for (void* p : n->owned) hipFree(p);
-  n->conv_in.free(); n->conv_out.free();
-  for (auto& r : n->res) { r.c1.free(); r.c2.free(); }
-  if (n->arena.base) hipFree(n->arena.base);
-  n->ones.free();
   delete n;
 }
 
@@ -883,7 +878,7 @@ int maua_unet_load(maua_unet* n, const char* name, const float* host, size_t cou
       ULin* l = (ULin*)p.obj;
       if (count != (size_t)l->N * l->K) return wrong();
       if (n->vjp && !l->w_t)
-        if (int rc = dev_alloc(n, &l->w_t, (size_t)l->N * l->K * n->esize)) return rc;
+        if (int rc = own(n, &l->w_t, (size_t)l->N * l->K * n->esize)) return rc;
       // a k = 1 "convolution": [N][K] rows, converted to the network dtype (and [K][N] for the input-gradient GEMM)
       return load_weight(st, n->dtype, host, l->N, l->K, 1, l->N, l->K, l->w, n->vjp ? l->w_t : nullptr, false);
     }

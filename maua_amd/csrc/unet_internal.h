@@ -37,14 +37,14 @@ struct TapeOp {
 };
 
 struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, top = 0, peak = 0;
+  DevBuf base;
+  size_t top = 0, peak = 0;
   bool plan = true;
   void* get(size_t bytes) {
     const size_t o = (top + 255) & ~(size_t)255;
     top = o + bytes;
     if (top > peak) peak = top;
-    return plan ? (void*)(uintptr_t)(o + 256) : (void*)(base + o);  // (planning: a non-NULL token, never dereferenced)
+    return plan ? (void*)(uintptr_t)(o + 256) : (void*)(base.as<char>() + o);  // (planning: a non-NULL token, never dereferenced)
   }
 };
 
@@ -70,7 +70,7 @@ struct maua_unet {
   int freqs_loaded = 0;
   int emb_total = 0;
   std::unordered_map<std::string, maua::PRef> params;
-  std::vector<void*> owned;
+  std::vector<maua::DevBuf> owned;   // the parameters behind the pointers of the records above
   maua::UnitStyles ones;   // [bcap][max_ch]
   int max_ch = 0;
   maua::Arena arena;
@@ -98,13 +98,14 @@ struct maua_unet {
     // sampler graph (maua_ddim_sample_loop)
     hipGraphExec_t graph_exec = nullptr;
     size_t graph_key = 0;
-    float* emb_table = nullptr;        // [n_steps][emb_total]: every step's emb_layers outputs, computed once per sampler loop
-    size_t emb_table_rows = 0;
+    maua::DevBuf emb_table;            // float [n_steps][emb_total]: every step's emb_layers outputs, computed once per sampler loop
+    size_t emb_table_rows = 0;         // (rows it holds; set after it)
     hipStream_t cap_stream = nullptr;  // capture happens on a private stream (the caller's may be the legacy NULL stream)
     int graph_failed = 0;              // capture / instantiation failed once: the loop runs eagerly from then on
-    float *g_x = nullptr, *g_out = nullptr, *g_pred = nullptr, *g_t = nullptr, *g_cf = nullptr;
-    int g_steps = 0;
-    size_t out_cap = 0;                // bytes behind g_out + g_pred
+    float* g_x = nullptr;              // the caller's tensor the graph was captured on
+    maua::DevBuf g_out, g_pred;        // float: the model's output, pred_xstart
+    maua::DevBuf g_t, g_cf;            // float [g_steps], [g_steps][8]: timesteps and DDIM coefficients per step and sample
+    int g_steps = 0;                   // (set after them)
     // guided sampler graph (maua_ddim_guided_loop): its own executable; the sample, the target and every per-step constant live in
     // library buffers, so one capture serves every call of a shape
     hipGraphExec_t gd_exec = nullptr;
@@ -113,22 +114,22 @@ struct maua_unet {
     // text-prompt guidance (maua_unet_set_clip_guide): CLIPGrads instead of the image-MSE module in the guided loop
     std::vector<maua_guide*> gd_guides;   // maua_unet_set_guides: grad modules evaluated (after CLIPGrads, if set) and summed per step
     std::vector<unsigned long long> gd_guide_uids, gd_guide_epochs;   // (epochs: as of the capture)
-    int* gd_gflag = nullptr;           // the NaN screen's flag of the guides' sum
+    maua::DevBuf gd_gflag;             // int: the NaN screen's flag of the guides' sum
     maua_clip* gd_clip = nullptr;
-    int* gd_rects = nullptr;           // device [n_steps][batches][cutn][3] (+ [n_steps][batches][cutn] float multiplicities behind them)
-    float* gd_mult = nullptr;          // NULL: every cutout counts once
+    maua::DevBuf gd_rects;             // int [n_steps][batches][cutn][3] (+ [n_steps][batches][cutn] float multiplicities behind them)
+    float* gd_mult = nullptr;          // those multiplicities (into gd_rects), or NULL: every cutout counts once
     int gd_last_graph = 0;             // the LAST guided loop replayed a captured graph (maua_unet_guided_graph_active)
     int gd_cutn_total = 0;
-    size_t gd_rects_cap = 0;
     std::vector<int> gd_rects_host;
     int gd_rect_steps = 0, gd_cutn = 0, gd_batches = 0;
     float gd_clip_scale = 1.f, gd_clip_clamp = 0.f;
     unsigned long long gd_clip_uid = 0, gd_clip_epoch = 0, gd_guide_gen = 0, gd_guide_gen_seen = 0;
     int gd_failed = 0;
+    maua::DevBuf gd_ws;                // one set, carved into the three pieces below; their counts are set after it is placed
     float* gd_buf = nullptr;           // x | v | pred | eps | img | g | jv | grad | target, B * C * H * W floats each
-    size_t gd_cap = 0;
+    size_t gd_cap = 0;                 // floats
     float* gd_tab = nullptr;           // cos_t [S][B] | (sigma, 1 - sigma) [S][B][2] | grad coefficients [S][B][2] | k [B]
-    size_t gd_tab_cap = 0;
+    size_t gd_tab_cap = 0;             // floats
     int* gd_flag = nullptr;            // [gd_flags] one NaN flag per step, zeroed before every loop (outside the graph)
     int gd_flags = 0;
     // the guidance branch of a step (secondary forward, grad module, secondary VJP) depends on x only: it runs BESIDE the UNet forward
@@ -136,7 +137,7 @@ struct maua_unet {
     int gd_fork = 1;
     hipStream_t side_stream = nullptr, cap_side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    void release();                    // both executables, the streams, the events and every buffer above
+    void release();                    // both executables, the streams and the events; the buffers free themselves
   } smp;
 };
 

@@ -343,14 +343,14 @@ int vfeat_check(int H, int W, int bins, int max_batch, const void* frames, int l
 using namespace maua;
 
 struct maua_vfeat {
-  int device, H, W, bins, max_batch, nblk;
-  char* ws;
-  float* part_mm;
-  unsigned long long* part_sum;
-  float* mm;
-  int* counts;
-  void* carry;
-  int carry_layout;   // -1: no carried frame
+  int device = 0, H = 0, W = 0, bins = 0, max_batch = 0, nblk = 0;
+  DevBuf ws;          // one set, carved at creation into the pieces below
+  float* part_mm = nullptr;
+  unsigned long long* part_sum = nullptr;
+  float* mm = nullptr;
+  int* counts = nullptr;
+  void* carry = nullptr;
+  int carry_layout = -1;   // -1: no carried frame
 };
 
 namespace {
@@ -374,7 +374,9 @@ int maua_vfeat_create(maua_ctx* ctx, int H, int W, int bins, int max_batch, maua
   if (vfeat_check(H, W, bins, max_batch, nullptr, MAUA_VFEAT_U8_HWC, 0, nullptr, nullptr, nullptr) != MAUA_OK) return MAUA_ERR;
   const long P = (long)H * W;
   const int nblk = (int)((P + VF_SPAN - 1) / VF_SPAN);
-  auto* h = new maua_vfeat{ctx->device, H, W, bins, max_batch, nblk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1};
+  MAUA_HIP_CHECK(hipSetDevice(ctx->device));
+  auto* h = new maua_vfeat();
+  h->device = ctx->device; h->H = H; h->W = W; h->bins = bins; h->max_batch = max_batch; h->nblk = nblk;
   auto layout = [&](Scratch& s) {
     h->part_mm = s.take<float>((size_t)max_batch * nblk * 12);
     h->part_sum = s.take<unsigned long long>((size_t)max_batch * nblk * 3);
@@ -382,21 +384,16 @@ int maua_vfeat_create(maua_ctx* ctx, int H, int W, int bins, int max_batch, maua
     h->counts = s.take<int>((size_t)max_batch * 6 * bins);
     h->carry = s.take<char>((size_t)P * 3 * sizeof(float));
   };
-  MAUA_HIP_CHECK(hipSetDevice(ctx->device));
-  const hipError_t e = hipMalloc((void**)&h->ws, scratch_bytes(layout));
-  if (e != hipSuccess) {
+  if (carve_into(h->ws, layout)) {
     delete h;
-    return fail(std::string("maua_vfeat_create: ") + hipGetErrorString(e));
+    return fail_in("maua_vfeat_create");
   }
-  Scratch place(h->ws);
-  layout(place);
   *out = h;
   return MAUA_OK;
 }
 
 int maua_vfeat_destroy(maua_vfeat* h) {
   if (!h) return MAUA_OK;
-  hipFree(h->ws);
   delete h;
   return MAUA_OK;
 }
