@@ -688,6 +688,26 @@ int maua_conv3x3_route(const maua_conv_desc* d, int dtype, int unet_route_option
  * tiles, its own choice of `variant`), 1 .. 3 = that kernel, refused (no launch, no fall-back) when it cannot take the shape or the
  * arguments */
 int maua_conv3x3_ex(maua_ctx* ctx, const maua_conv_desc* d, int dtype, int kernel);
+/* One operation of the ResNet backbone (csrc/resnet_conv.hip) with every argument in the caller's hand, for parity tests (no reference
+ * counterpart).  Tensors dense NHWC in `dtype` (MAUA_F32: exact f32 products, or MAUA_BF16; any other dtype is refused):
+ *   y[b][oh][ow][co] = act(sum_{r, s, ci} w[co][ci][r][s] x[b][oh stride - pad + r][ow stride - pad + s][ci] + bias[co] (+ res[b][oh][ow][co]))
+ * pixels outside the image count as zero; act = ReLU (relu != 0) or none, applied AFTER the residual; the residual is read in `dtype`, the
+ * sum is float32 and rounded once when stored.  Output size (H + 2 pad - k) / stride + 1.  (k, stride, pad) is one of (1, 1, 0),
+ * (1, 2, 0), (3, 1, 1), (3, 2, 1) with Ci and Co multiples of 64 - or (7, 2, 3) with Ci = 3, the stem: x is then the PLANAR float32 image
+ * [B][3][H][W] (no residual).  w: DEVICE float32 [Co][Ci][k][k], bias: DEVICE float32 [Co] or NULL; w is prepared into the context's
+ * scratch arena on every call.  The summation order is a function of the shape alone.  Anything else is refused: MAUA_ERR +
+ * maua_last_error(), no launch, no fall-back. */
+typedef struct maua_sconv_desc {
+  const void* x; const float* w; const float* bias; const void* res; void* y;
+  int B, H, W, Ci, Co, k, stride, pad, relu;
+} maua_sconv_desc;
+int maua_conv_strided_ex(maua_ctx* ctx, const maua_sconv_desc* d, int dtype);
+/* MaxPool2d(3, stride 2, padding 1) of NHWC x [B][H][W][C] -> y [B][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C]: taps outside the image are
+ * excluded (not zeros).  C % 8 == 0. */
+int maua_maxpool3x3s2(maua_ctx* ctx, const void* x, void* y, int B, int H, int W, int C, int dtype);
+/* AdaptiveAvgPool2d((1, 1)) + flatten of NHWC x -> out float32 [B][C]: the pixels summed in float32 in index order, then one multiply by
+ * 1 / (H W).  C % 8 == 0. */
+int maua_global_avgpool(maua_ctx* ctx, const void* x, float* out, int B, int H, int W, int C, int dtype);
 /* kernel-selection switches of the MODULATED 3x3 convolutions of the StyleGAN2 synthesis network, for parity tests (no reference
  * counterpart).  One layer as the network's forward describes it, on the route of the caller's choice:
  *   v = clamp(act(d[b][co] * conv(x[b] * s[b], w)[co] + noise[b][p] * noise_strength * noise_scale[b] + bias[co]) * gain)
@@ -989,6 +1009,30 @@ int maua_vgg_gram_mean_grad(maua_vgg* net, const float* img, int B, int H, int W
  * [B][hw][C] with target_bstride[k] = hw * C), lins: DEVICE pointers to the lin layers' weights [C]; dist optional device f32 [B] */
 int maua_vgg_lpips_grad(maua_vgg* net, const float* img, int B, int H, int W, const int* taps, int n_taps, const float* const* targets,
                         const long* target_bstride, const float* const* lins, float scale, float* grad, float* dist);
+
+/* ResNet bottleneck backbone (csrc/resnet.hip): the feature extractor of the GAN metrics' "SwAV" option
+ * (maua/GAN/metrics/extractors/swav.py ResNet(Bottleneck, layers): ConstantPad2d(1) + 7x7 stride-2 stem, MaxPool2d(3, 2, 1), four
+ * layers of bottleneck blocks - the stride on each block's 3x3 - global average pool; forward_backbone, no head).  BatchNorm never
+ * reaches the library: the caller folds it into each convolution's weight and bias.  layers: HOST int [4] blocks per layer (>= 1 each);
+ * width (a multiple of 64; 64 for ResNet-50): the stem's channels, the features are 32 * width wide.  dtype MAUA_F32 (exact products)
+ * or MAUA_BF16.  Convolutions are indexed in the state dict's order: conv1 (the stem), then per block conv1, conv2, conv3 and - in the
+ * first block of a layer - downsample.0.  maua_resnet_conv_shape reports Ci, Co, kernel size and stride of one (no device needed).
+ * maua_resnet_load: what 0 = weight, HOST float32 [Co][Ci][k][k], prepared once into the kernels' layout; 1 = bias, HOST float32 [Co].
+ * maua_resnet_forward: img device planar f32 [B][3][H][W] -> features device f32 [B][32 * width]; the activation workspace is laid out
+ * for (B, H, W) and laid out again when they change.  Every stage's output of the last forward is kept: maua_resnet_tap writes stage
+ * 0 stem, 1 max-pool, 2 .. 5 layer1 .. layer4 as planar float32 [B][C][h][w] (device), maua_resnet_tap_shape reports C, h, w. */
+typedef struct maua_resnet maua_resnet;
+int maua_resnet_create(maua_ctx* ctx, int dtype, const int* layers, int width, maua_resnet** out);
+void maua_resnet_destroy(maua_resnet* net);
+int maua_resnet_conv_count(maua_resnet* net);
+int maua_resnet_conv_shape(maua_resnet* net, int index, int* ci, int* co, int* k, int* stride);
+int maua_resnet_load(maua_resnet* net, int conv_index, int what /* 0 weight, 1 bias */, const float* host_data, size_t count);
+int maua_resnet_forward(maua_resnet* net, const float* img, int B, int H, int W, float* features);
+/* the same forward with HIP events between its stages; synchronises and writes HOST float [7] milliseconds: stem, max-pool,
+ * layer1 .. layer4, average pool (scripts/bench_swav.py) */
+int maua_resnet_forward_timed(maua_resnet* net, const float* img, int B, int H, int W, float* features, float* stage_ms);
+int maua_resnet_tap_shape(maua_resnet* net, int stage, int* C, int* h, int* w);
+int maua_resnet_tap(maua_resnet* net, int stage, float* out);
 
 /* grad modules as library objects, so that the guided loop can evaluate a LIST of them per step (guided.py:258-266 sums the modules'
  * gradients; get_diffusion_model hands the sampler up to four, maua/diffusion/image.py:92-97).  kind: MAUA_GUIDE_STYLE = VGGGrads

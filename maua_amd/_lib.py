@@ -226,6 +226,13 @@ class ConvDesc(C.Structure):
                 ("psum", C.c_void_p)]
 
 
+class SConvDesc(C.Structure):
+    """maua_sconv_desc (include/maua_hip.h): one convolution of the ResNet backbone for maua_conv_strided_ex; pointers as integers."""
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("res", C.c_void_p), ("y", C.c_void_p),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Ci", C.c_int), ("Co", C.c_int),
+                ("k", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("relu", C.c_int)]
+
+
 class ModconvDesc(C.Structure):
     """maua_modconv_desc (include/maua_hip.h): one modulated 3x3 layer for maua_modconv_route / maua_modconv_ex; pointers as integers."""
     _fields_ = [("x", C.c_void_p), ("x_bstride", C.c_long),

@@ -431,6 +431,29 @@ bool gemm256_shape_ok(const GemmArgs& g);
 bool gemm256_takes(const GemmArgs& g);
 int launch_gemm_dma(hipStream_t stream, const GemmArgs& g, int kernel);
 
+// ---- resnet_conv.hip: the convolutions of the ResNet backbones as one implicit GEMM, y = act(conv(x, w) + bias (+ res)) with the
+// ReLU AFTER the residual; (k, stride, pad) in {(1, 1, 0), (1, 2, 0), (3, 1, 1), (3, 2, 1)}, Ci and Co multiples of 64, any B, H, W.
+// stem: the 7 x 7 stride-2 convolution of the planar float32 image (zero border 3) instead.
+struct SConvArgs {
+  const void* x;        // NHWC [B][H][W][Ci] (T); stem: planar f32 [B][3][H][W]
+  const void* w;        // T [k * k][Co][Ci] (launch_prep_weights); stem: T [Co][kpad], k index = c * 49 + r * 7 + s (launch_prep_stem_weights)
+  const float* bias;    // [Co] or NULL
+  const void* res;      // NHWC [B][Ho][Wo][Co] (T) or NULL
+  void* y;              // NHWC [B][Ho][Wo][Co] (T), Ho = (H + 2 pad - k) / stride + 1
+  int B, H, W, Ci, Co, k, stride, pad;
+  int relu;
+  int stem, kpad;       // stem: kpad = stem_kpad(dtype), K = 147 padded to whole 128-byte chunks
+};
+int sconv_out(int n, int k, int stride, int pad);
+int stem_kpad(int dtype);
+int sconv_check(int dtype, const SConvArgs& a);   // host only: every refusal of launch_sconv (MAUA_ERR + last error)
+int sconv_route(const SConvArgs& a);              // host only: 1 the stem's 128 x 64 tile, 2 128 x 128, 3 64 x 64
+int launch_sconv(hipStream_t stream, int dtype, const SConvArgs& a);
+int launch_prep_stem_weights(hipStream_t stream, int dtype, const float* w /* [Co][147] */, void* wt, int Co);
+// MaxPool2d(3, 2, 1) (taps outside the image excluded) and the global average (f32 [B][C]) of NHWC tensors, C % 8 == 0
+int launch_maxpool3x3s2(hipStream_t stream, int dtype, const void* x, void* y, int B, int H, int W, int C);
+int launch_global_avgpool(hipStream_t stream, int dtype, const void* x, float* out, int B, int H, int W, int C);
+
 // ---- attention.hip: softmax(Q K^T / sqrt(D)) V per (sample, head); qkv [B][T][ld_qkv] with head-major [q | k | v] channel
 // layout (guided-diffusion's QKVAttentionLegacy), out [B][T][ld_out] with channel = head * D + d
 struct AttnArgs {

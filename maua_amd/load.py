@@ -368,6 +368,41 @@ class _NetworkUnpickler(__import__("pickle").Unpickler):
         return _PickledObject
 
 
+class _StateDictUnpickler(_NetworkUnpickler):
+    """The same allow-list for a file that should hold nothing but a state dict: a global the parent would replace by an inert stand-in
+    is refused by name instead - a plain checkpoint has no business naming one."""
+
+    def find_class(self, module, name):
+        found = super().find_class(module, name)
+        if found is _PickledObject or found is _persistent_obj:
+            raise ValueError(f"checkpoint names the global {module}.{name}: only tensors, arrays and plain containers are read")
+        return found
+
+
+def load_state_dict_file(path):
+    """A checkpoint that holds a state dict (optionally under "state_dict") -> {key: float32 CPU tensor}, executing nothing the file names.
+    A ``torch.save`` archive (zip or legacy) goes through torch's tensors-only loader - what ``_NetworkUnpickler`` itself hands embedded
+    storages to; a bare pickle stream through ``_StateDictUnpickler``.  Either refuses a file that names a foreign global (ValueError)."""
+    import pickle
+    import zipfile
+    with open(path, "rb") as f:
+        head = f.read(16)
+    legacy_magic = pickle.dumps(0x1950a86a20f9469cfc6c, protocol=2)[:-1]      # torch/serialization.py MAGIC_NUMBER as legacy files start
+    try:
+        if zipfile.is_zipfile(path) or head.startswith(legacy_magic[:len(head)]):
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+        else:
+            with open(path, "rb") as f:
+                sd = _StateDictUnpickler(f).load()
+    except pickle.UnpicklingError as e:
+        raise ValueError(f"{path}: refused: {e}") from None
+    if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
+        sd = sd["state_dict"]
+    if not isinstance(sd, dict) or not sd:
+        raise ValueError(f"{path}: not a state dict")
+    return {str(k): torch.as_tensor(v).detach().float().cpu() for k, v in sd.items() if isinstance(v, (torch.Tensor, np.ndarray))}
+
+
 def _module_state_dict(obj, prefix=""):
     """nn.Module.state_dict() over the raw __dict__ states of a pickled module tree."""
     sd = {}

@@ -5,8 +5,12 @@ generated ones.  Everything runs in float64 on the library's f64 matrix-core GEM
 load, float64 features are taken as they are.  Features are device tensors and stay there; only scalars come back.  There is no CPU path:
 without a device every function raises ``MauaHipError``.
 
-Not built (each raises ``NotImplementedError`` by name): ``symsqrtm`` (an SVD, unused by ``frechet_distance``) and the ``"SwAV"`` /
-``"Inception"`` extractors of ``compute`` (their ResNet-50 / Inception-v3 forwards are not part of this build).
+Extractors of ``compute``: a callable, a (module, size) pair, ``"CLIP:<tower>"`` and ``"SwAV:<checkpoint>"`` (``"SwAV-bf16:<checkpoint>"``
+in bfloat16) - the reference's SwAV ResNet-50 (maua_amd.resnet) with the weights read from a local file: they are not bundled, like CLIP's.
+
+Not built (each raises ``NotImplementedError`` by name): ``symsqrtm`` (an SVD, unused by ``frechet_distance``), the ``"Inception"`` extractor
+(its Inception-v3 forward is not part of this build; its checkpoint is a TorchScript archive) and the bare ``"SwAV"`` spelling, which
+would have to download its weights.
 """
 import ctypes as C
 import glob as _glob
@@ -22,7 +26,8 @@ from . import _lib as L
 MAX_NEAREST_K = 15
 SIZE = 224      # compute.py:22: what a folder's images are resized to when the extractor states no size of its own
 EXTENSIONS = {"bmp", "jpg", "jpeg", "pgm", "png", "ppm", "tif", "tiff", "webp", "npy"}
-UNBUILT_EXTRACTORS = {"SwAV": "its ResNet-50 forward (extractors/swav.py) is not part of this build",
+UNBUILT_EXTRACTORS = {"SwAV": "its weights (swav_800ep_pretrain.pth.tar) are not bundled and are never downloaded: name a local file as "
+                              "'SwAV:<checkpoint>' ('SwAV-bf16:<checkpoint>' in bfloat16)",
                       "Inception": "its Inception-v3 forward (extractors/inception.py) is not part of this build"}
 
 
@@ -343,18 +348,26 @@ class _ClipExtractor:
 
 def get_extractor(extractor, allow_random_init=False):
     """-> (callable batch [B, 3, size, size] in [0, 1] -> features [B, d], size or None, name).  A callable or a (module, size) pair is
-    taken as it is; ``"CLIP:<tower>"`` is one of maua_amd.clip's image towers; ``"SwAV"`` and ``"Inception"`` are not built."""
+    taken as it is; ``"CLIP:<tower>"`` is one of maua_amd.clip's image towers; ``"SwAV:<checkpoint>"`` is the reference's SwAV ResNet-50
+    with the weights of that local file (``"SwAV-bf16:<checkpoint>"``: in bfloat16; ``"SwAV:random"`` with ``allow_random_init``: the
+    reference's initialisation) - it takes the batch in [0, 1] as it is (compute.py:147) and reports under the name ``SwAV``; the bare
+    ``"SwAV"`` (nothing is downloaded) and ``"Inception"`` are not built."""
     if isinstance(extractor, (tuple, list)) and len(extractor) == 2 and callable(extractor[0]):
         return extractor[0], int(extractor[1]), getattr(extractor[0], "__name__", type(extractor[0]).__name__)
     if callable(extractor):
         return extractor, None, getattr(extractor, "__name__", type(extractor).__name__)
     if extractor in UNBUILT_EXTRACTORS:
         raise NotImplementedError(f"extractor {extractor!r} is not built: {UNBUILT_EXTRACTORS[extractor]}; pass a callable, a "
-                                  "(module, size) pair or 'CLIP:<tower>'")
+                                  "(module, size) pair, 'CLIP:<tower>' or 'SwAV:<checkpoint>'")
     if isinstance(extractor, str) and extractor.startswith("CLIP:"):
         ex = _ClipExtractor(extractor[len("CLIP:"):], allow_random_init)
         return ex, ex.size, extractor
-    raise ValueError(f"unknown extractor {extractor!r}: pass a callable, a (module, size) pair or 'CLIP:<tower>'")
+    if isinstance(extractor, str) and extractor.startswith(("SwAV:", "SwAV-bf16:")):
+        from .resnet import SwAV
+        spelling, _, checkpoint = extractor.partition(":")
+        dtype = torch.bfloat16 if spelling == "SwAV-bf16" else torch.float32
+        return SwAV(checkpoint, dtype=dtype, allow_random_init=allow_random_init), SIZE, "SwAV"
+    raise ValueError(f"unknown extractor {extractor!r}: pass a callable, a (module, size) pair, 'CLIP:<tower>' or 'SwAV:<checkpoint>'")
 
 
 @torch.inference_mode()
@@ -436,13 +449,13 @@ def parser():
     p.add_argument("--data_dir", type=str, required=True)
     p.add_argument("--checkpoint", type=str, required=True)
     p.add_argument("--n_samples", type=int, default=10_000)
-    p.add_argument("--extractor", type=str, default="SwAV", help="SwAV, Inception (neither is built) or CLIP:<tower>, e.g. CLIP:ViT-B/32")
+    p.add_argument("--extractor", type=str, default="SwAV", help="SwAV:<checkpoint> (SwAV-bf16:<checkpoint> in bfloat16), CLIP:<tower>, e.g. CLIP:ViT-B/32; bare SwAV and Inception are not built")
     p.add_argument("--metrics", type=str, nargs="+", default=["frechet", "kernel", "prdc"], choices=["frechet", "kernel", "prdc"])
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--num_workers", type=int, default=default_num_workers())
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--ignore_cache", action="store_true")
-    p.add_argument("--allow_random_init", action="store_true", help="a CLIP tower without weights gets CLIP's own initialisation")
+    p.add_argument("--allow_random_init", action="store_true", help="a CLIP tower without weights gets CLIP's own initialisation; SwAV:random the reference's")
     return p
 
 
