@@ -1255,6 +1255,47 @@ int maua_knn_radii(maua_ctx* ctx, const void* feats, int N, int d, int f64, int 
 int maua_prdc(maua_ctx* ctx, const void* real, int N, const void* fake, int M, int d, int f64, int nearest_k, void* ws, long ws_bytes,
               unsigned long long* counts, double* r_real, double* r_fake);
 
+/* ---- dense float64 SVD and symmetric eigendecomposition: one-sided Jacobi (csrc/svd_f64.hip) -----------------------------------------
+ * Serves maua/GAN/decomposition/sefa.py:7,25 (`torch.svd(weight).V` of the stacked style-affine weights) and GANSpace's PCA.  Hestenes'
+ * method in float64: pairs of columns of A are rotated until they are orthogonal; the rotations accumulate in V.  No vendor solver.
+ *   Order: the round-robin tournament on N = n rounded up to even.  A sweep is N - 1 rounds of N / 2 disjoint pairs; position 0 keeps
+ *   player 0, position k >= 1 of round r holds player 1 + (k - 1 + r) mod (N - 1), pair i is (position i, position N - 1 - i); a pair with
+ *   the padding index N - 1 of an odd n is skipped.  maua_jacobi_schedule (host only, no device): the pairs of one round in that order,
+ *   pairs [2 n_pairs] = p0, q0, p1, q1, ...
+ *   Pair (p, q): alpha = |a_p|^2, beta = |a_q|^2, gamma = a_p . a_q; left alone when alpha = 0, beta = 0 or |gamma| <= sqrt(m) eps
+ *   sqrt(alpha) sqrt(beta), eps = 2^-52 (LAPACK dgesvj's rule); else zeta = (beta - alpha) / (2 gamma), t = sign(zeta) / (|zeta| +
+ *   sqrt(1 + zeta^2)) (sign(0) = 1), c = 1 / sqrt(1 + t^2), s = c t; a_p <- c a_p - s a_q, a_q <- s a_p + c a_q, the same on v_p, v_q.
+ *   Stop: after the first sweep that rotated nothing - the host reads one integer per sweep; at most max_sweeps (1 .. 30, 0 = 30) sweeps.
+ *   When they run out the call returns MAUA_ERR AFTER writing the outputs of the last iterate, and sweeps / last_rotations say how far it got.
+ *   Finish: sigma_i = |a_i|, sorted descending (stable: ties keep the lower column first), u_i = a_i / sigma_i - a column with sigma_i = 0
+ *   gets u_i = 0, so U has orthonormal columns only over the nonzero singular values - and every (u_i, v_i) is flipped so that v_i's
+ *   largest-magnitude component (the lowest index on a tie) is positive: the output is a function of A alone.
+ *   Paths: 1 = one workgroup runs every round and sweep with A^T and V resident in LDS ((m + n) n doubles + 128 bytes within 159 KiB);
+ *   2 = one launch per round, one workgroup per pair, each column read from memory once per round (staged in LDS while 2 m doubles fit
+ *   128 KiB); 0 = path 1 where it fits, else 2.  All three dot products come from one function with one summation order, so both paths
+ *   and every rerun return the same bits.
+ * a [m][lda] row-major device f64, m >= n >= 1, n <= 4096, m <= 1048576; s [n], u [m][n] (want_u != 0; else not touched, may be NULL),
+ * v [n][n] row-major device f64 with A = u diag(s) v^T; sweeps, last_rotations: HOST ints (either may be NULL).  ws: *_workspace_bytes() bytes of
+ * device memory, 256-byte aligned (nothing is allocated).  Accuracy is norm-wise: |s - s_exact| = O(max(m, n) eps |A|), no relative
+ * claim for small singular values.  The *_check entries are host only, need no device, never dereference a pointer and state every refusal:
+ * n < 1, m < n, the size limits, lda < n, an unknown path, path 1 on a matrix beyond its limit, max_sweeps outside 0 .. 30, NULL arguments,
+ * a short or misaligned workspace. */
+int maua_jacobi_schedule(int n, int round, int* pairs, int* n_pairs);
+long maua_svd_f64_workspace_bytes(int m, int n);
+int maua_svd_f64_check(const double* a, int m, int n, long lda, int want_u, int path, int max_sweeps, const void* ws, long ws_bytes, const double* s,
+                       const double* u, const double* v);
+int maua_svd_f64(maua_ctx* ctx, const double* a, int m, int n, long lda, int want_u, int path, int max_sweeps, void* ws, long ws_bytes, double* s,
+                 double* u, double* v, int* sweeps, int* last_rotations);
+/* Symmetric S [n][lds] (only assumed, not checked): w [n] ascending and q [n][n] row-major, column i the eigenvector of w[i], as
+ * torch.linalg.eigh orders them, signs by the rule above.  The Jacobi above runs on S + c I, c = max_i sum_j |S_ij| (Gershgorin), which is
+ * positive semidefinite: its right singular vectors are S's eigenvectors and w = sigma - c.  (Without the shift a pair +lambda, -lambda
+ * of an indefinite S shares one singular value and the SVD mixes its two vectors.)  Eigenvalue accuracy is ABSOLUTE, O(n eps (|S| + c)),
+ * not relative: an eigenvalue far below |S| keeps few digits. */
+long maua_eigh_f64_workspace_bytes(int n);
+int maua_eigh_f64_check(const double* s, int n, long lds, int path, int max_sweeps, const void* ws, long ws_bytes, const double* w, const double* q);
+int maua_eigh_f64(maua_ctx* ctx, const double* s, int n, long lds, int path, int max_sweeps, void* ws, long ws_bytes, double* w, double* q, int* sweeps,
+                  int* last_rotations);
+
 /* ---- build-owned counter RNG: Philox4x32-10, identical on every device / rank and in the oracle twin (oracle/rng.py,
  * pinned to the published known-answer vectors).  No reference counterpart: the reference's random-init generator and noise planes
  * come from torch's host generator (inference/stylegan2.py:216-227, selfsupervised/noise.py:42-53); the benchmark's synthetic
@@ -1305,6 +1346,13 @@ int maua_latent_expand_check(const float* w, int w_rows, const float* eps, const
 int maua_latent_expand(maua_ctx* ctx, const float* w, int w_rows, const float* eps, float scale, float* ws, int B, int num_ws, int w_dim);
 int maua_latent_reduce_check(const float* g_ws, const float* g_w, int B, int num_ws, int w_dim);
 int maua_latent_reduce(maua_ctx* ctx, const float* g_ws, float* g_w, int B, int num_ws, int w_dim);
+/* Latent directions (csrc/latent.hip; the edit that follows sefa.py:7,25's factorisation): ws, out [T][num_ws][C], dirs [k][C], coeffs [T][k],
+ * device f32.  Rows ws_lo <= l < ws_hi: out[t][l] = ws[t][l] + sum_j coeffs[t][j] dirs[j], j ascending, every term one fmaf(coeff, dir, acc)
+ * starting from ws; every other row is copied.  An empty range or k = 0 copies ws.  out may not alias ws. */
+int maua_latent_add_directions_check(const float* ws, const float* dirs, const float* coeffs, int T, int num_ws, int C, int k, int ws_lo, int ws_hi,
+                                     const float* out);
+int maua_latent_add_directions(maua_ctx* ctx, const float* ws, const float* dirs, const float* coeffs, int T, int num_ws, int C, int k, int ws_lo,
+                               int ws_hi, float* out);
 
 /* ---- neural cellular automaton (maua/nca/train.py:152-193, after znah's gitart_kunstformen_ca) ------------------------------------
  * One update of the f32 state x [B][chn][H][W]:  x += w2 . relu(w1 . perception(x) + b1) . mask

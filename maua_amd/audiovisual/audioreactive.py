@@ -5,7 +5,7 @@ import torch
 from ..audio import (gaussian_filter as _gf_selfsup, harmonic as _harmonic, hpss, istft, melspectrogram, onset_strength,  # noqa
                      percussive as _percussive, rms as _rms, spectrogram, stft)
 from ..audio_io import load_audio as _load
-from ..latent import (copeerp, eerp, multi_weighted, select_modulo, single_weighted, slerp, slerp_loops,  # noqa
+from ..latent import (copeerp, direction_modulate, eerp, multi_weighted, select_modulo, single_weighted, slerp, slerp_loops,  # noqa
                       spline_loops, tempo_loops)
 from ..signal import (compress, expand, gaussian_filter, normalize, percentile, percentile_clip, resample,  # noqa
                       sosfilt)

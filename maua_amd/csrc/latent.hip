@@ -193,6 +193,29 @@ __global__ __launch_bounds__(256) void latent_merge_kernel(float* __restrict__ l
   lat[o] = v;
 }
 
+// latent directions: rows l0 <= l < l1 of every frame move along k direction vectors, out = ws + sum_j coeffs[t][j] dirs[j] - one fmaf per
+// term, j ascending, starting from ws; the other rows are copied.  V floats per thread (4: 16-byte accesses, C a multiple of 4).
+template <int V>
+__global__ __launch_bounds__(256) void add_directions_kernel(const float* __restrict__ ws, const float* __restrict__ dirs,
+                                                             const float* __restrict__ coeffs, int L, int C, int k, int l0, int l1,
+                                                             float* __restrict__ out, int row0) {
+  const int c = ((int)blockIdx.x * 256 + (int)threadIdx.x) * V;
+  if (c >= C) return;
+  const long row = (long)row0 + blockIdx.y;   // t * L + l
+  const int t = (int)(row / L), l = (int)(row % L);
+  typedef float vec_t __attribute__((ext_vector_type(V)));
+  vec_t acc = *(const vec_t*)(ws + row * C + c);
+  if (l >= l0 && l < l1) {
+    for (int j = 0; j < k; j++) {
+      const float w = coeffs[(long)t * k + j];
+      const vec_t d = *(const vec_t*)(dirs + (long)j * C + c);
+#pragma unroll
+      for (int v = 0; v < V; v++) acc[v] = fmaf(w, d[v], acc[v]);
+    }
+  }
+  *(vec_t*)(out + row * C + c) = acc;
+}
+
 }  // namespace maua
 
 using namespace maua;
@@ -352,6 +375,35 @@ int maua_latent_merge(maua_ctx* ctx, float* latents, const float* sequence, cons
   for_row_ranges(T, [&](int t0, int rows) {
     hipLaunchKernelGGL(latent_merge_kernel, dim3((unsigned)((span + 255) / 256), rows), dim3(256), 0, ctx->stream, latents,
                        sequence, mod, mode, L, D, l0, l1, t0);
+  });
+  MAUA_HIP_CHECK(hipGetLastError());
+  return MAUA_OK;
+}
+
+int maua_latent_add_directions_check(const float* ws, const float* dirs, const float* coeffs, int T, int num_ws, int C, int k, int ws_lo, int ws_hi,
+                                     const float* out) {
+  MAUA_REQUIRE(T >= 0 && num_ws > 0 && C > 0 && k >= 0, "maua_latent_add_directions: bad shape");
+  MAUA_REQUIRE((long)T * num_ws < (1L << 31) && (long)T * num_ws * C < (1L << 39), "maua_latent_add_directions: too many elements");
+  MAUA_REQUIRE(ws_lo >= 0 && ws_hi <= num_ws, "maua_latent_add_directions: layer range out of 0 .. num_ws");
+  MAUA_REQUIRE(T == 0 || (ws && out), "maua_latent_add_directions: NULL argument");
+  MAUA_REQUIRE(T == 0 || k == 0 || ws_hi <= ws_lo || (dirs && coeffs), "maua_latent_add_directions: NULL argument");
+  return MAUA_OK;
+}
+
+int maua_latent_add_directions(maua_ctx* ctx, const float* ws, const float* dirs, const float* coeffs, int T, int num_ws, int C, int k, int ws_lo,
+                               int ws_hi, float* out) {
+  MAUA_REQUIRE(ctx, "maua_latent_add_directions: ctx is NULL");
+  if (maua_latent_add_directions_check(ws, dirs, coeffs, T, num_ws, C, k, ws_lo, ws_hi, out) != MAUA_OK) return MAUA_ERR;
+  if (T == 0) return MAUA_OK;
+  if (ws_hi <= ws_lo) ws_lo = ws_hi = k = 0;   // an empty range: a copy
+  const bool vec = C % 4 == 0 && (((size_t)ws | (size_t)dirs | (size_t)out) & 15) == 0;
+  for_row_ranges((long)T * num_ws, [&](int row0, int rows) {
+    if (vec)
+      hipLaunchKernelGGL(add_directions_kernel<4>, dim3((unsigned)((C / 4 + 255) / 256), rows), dim3(256), 0, ctx->stream, ws, dirs, coeffs, num_ws, C,
+                         k, ws_lo, ws_hi, out, row0);
+    else
+      hipLaunchKernelGGL(add_directions_kernel<1>, dim3((unsigned)((C + 255) / 256), rows), dim3(256), 0, ctx->stream, ws, dirs, coeffs, num_ws, C, k,
+                         ws_lo, ws_hi, out, row0);
   });
   MAUA_HIP_CHECK(hipGetLastError());
   return MAUA_OK;

@@ -170,6 +170,20 @@ def latent_patch(rng, latents, palette, segmentations, features, tempo, fps, pat
     return merge(latents, sequence, merge_type, merge_depth, mod)
 
 
+def direction_modulate(latents, directions, envelopes, ws_layers=None):
+    """The audio-reactive hook of latent directions (maua_amd.decomposition; no reference counterpart): latents [T, num_ws, w_dim] moved
+    along ``directions`` (a ``Directions`` or a [k, w_dim] tensor) by the per-frame envelopes [T, k] (or [T] for one direction),
+    ``latents[t, l] + sum_j envelopes[t, j] directions[j]`` on rows ``ws_layers`` = (lo, hi) (a LAYER_SLICES name, or None: all rows)."""
+    from .decomposition import add_directions
+    vectors = getattr(directions, "vectors", directions)
+    env = A._f32(envelopes)
+    if env.dim() == 1:
+        env = env[:, None]
+    if isinstance(ws_layers, str):
+        ws_layers = (LAYER_SLICES[ws_layers][0], min(LAYER_SLICES[ws_layers][1], latents.shape[1]))
+    return add_directions(latents, vectors, env, ws_layers)
+
+
 def _eerp(a, b, t, mode):
     a, b, t = (A._f32(torch.as_tensor(v)) for v in (a, b, t))
     a, b, t = torch.broadcast_tensors(a, b, t)
